@@ -4,8 +4,12 @@ and BlobTree field Mvoxels/s on a 256^3 grid (BASELINE.json `metric`).
 
     python bench.py --gpus N --steps K --warmup W            (N = 1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (N > 1)
+    ... --dump-outputs DIR     after the timed steps: q, qvel, qaccel and the iteration count of the last step as DIR/<name>.npy
+    ... --full                 also the rest-state steps, kernel probes and roofline, field bench, BASELINE legs, CPU baseline,
+                               8M-tet leg and (N > 1) the sharded field and collective-library legs
 
-One JSON line on rank 0.  A "step" is one pass of the hot path: fb_fem_rebuild_elements (per-element rest state,
+One JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints `value` / `ms_per_step` of them;
+everything else it can measure is behind --full.  A "step" is one pass of the hot path: fb_fem_rebuild_elements (per-element rest state,
 the cutting path's K0 rebuild), corotational assembly of Keff/rhs and the PCG solve to the reference tolerance
 (eps 1e-6, max 10000), followed by the state update -- all inputs resident in HBM.  For N > 1 the SAME mesh is
 slab-decomposed over the ranks (strong scaling): one process per GPU, RCCL all-reduce for the PCG dots and
@@ -53,6 +57,24 @@ def workload_mesh(name, device=0):
     v, t = xyz.astype(np.float64), tets.astype(np.int32)
     ycut = np.sort(v[:, 1])[len(v) // 20]
     return v, t, fixed_vertices_to_dofs(np.nonzero(v[:, 1] <= ycut)[0])
+
+
+DUMP_MAX_VALUES = 1 << 20   # per array: 8 MiB of float64, so the few arrays of a dump stay far below 64 MB
+
+
+def dump_outputs(dirname, arrays):
+    """Writes {name: 1-D array} as dirname/<name>.npy in float64.  Arrays longer than DUMP_MAX_VALUES (the DOF vectors of the
+    largest meshes, all of one length) are replaced by one fixed, seeded sample of their positions, written as sample_index.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    pick = None
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64).ravel()
+        if len(a) > DUMP_MAX_VALUES:
+            if pick is None:
+                pick = np.sort(np.random.default_rng(0).choice(len(a), DUMP_MAX_VALUES, replace=False))
+                np.save(os.path.join(dirname, "sample_index.npy"), pick.astype(np.float64))
+            a = a[pick]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def cpu_baseline(mesh, cg_iterations, sample_iters=40):
@@ -575,7 +597,11 @@ def main():
     ap.add_argument("--precision", default="f32", choices=["f32", "f64"])
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-field", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also every measurement beside the timed steps (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the state after the last timed step as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -781,7 +807,8 @@ def main():
         # the same step of an UNSHARDED handle on rank 0's GPU (iteration count within max(3, 2 %), displacements within 2e-4
         # of max|q| -- the tolerance of the parity tests for two solves that both stop at a 1e-6 residual; the same check runs
         # under pytest at 8M tets: tests/test_sharded_gpu.py).  If a peer-to-peer form fails the check, the collective library
-        # takes over and is checked the same way; if that fails too the run aborts: a wrong solver is not timed.
+        # takes over and is checked the same way; if that fails too the run aborts: a wrong solver is not timed.  (Part of a plain
+        # run too: it decides which exchange form the timed steps use.)
         sharded_check = None
         if dist_mode and os.environ.get("FEMBRAIN_BENCH_NO_CHECK") != "1":
             def reference_step():
@@ -846,6 +873,18 @@ def main():
         (dt, iters, asm_s, solve_s), _ = stage("warm-up and timed steps", timed)
         dt = reduce_scalar(dt, "max")
 
+        if args.dump_outputs:
+            def dump():
+                state = g.get_q_state()
+                if dist_mode:   # every rank fills its owned range only
+                    state = [torch.from_numpy(a.copy()).to(tdev) for a in state]
+                    for a in state:
+                        dist.all_reduce(a, op=dist.ReduceOp.SUM)
+                    state = [a.cpu().numpy() for a in state]
+                if rank == 0:
+                    dump_outputs(args.dump_outputs, {"q": state[0], "qvel": state[1], "qaccel": state[2], "cg_iterations": [iters[-1]]})
+            stage("dump the outputs of the last timed step", dump)
+
         # The trajectory above continues a loaded dynamic simulation, so its iteration counts depend on --warmup / --steps.
         # Beside it: the same step from the SAME state every time (reset to rest before each timed step; only the step is timed).
         def fixed_state():
@@ -858,7 +897,7 @@ def main():
                 barrier()
                 tot += time.perf_counter() - ts
             return tot, its
-        fs, fs_why = stage("steps from the rest state", fixed_state, optional=True)
+        fs, fs_why = stage("steps from the rest state", fixed_state, optional=True) if args.full else (None, None)
         fixed_dt, fixed_iters = (reduce_scalar(fs[0], "max"), fs[1]) if fs else (None, None)
 
         def probes():
@@ -876,10 +915,13 @@ def main():
                 torch.cuda.synchronize()
                 resync_ms = (time.perf_counter() - ts) * 1e3
             return spmv_s, g.spmv_bytes(), asm_k_s, halo_s, sum_s, k0_s, resync_ms, persist, persist_s, g.iteration_bytes()
-        (spmv_s, spmv_bytes, asm_k_s, halo_s, sum_s, k0_s, resync_ms, persist, persist_s, iter_bytes), _ = stage("kernel probes", probes)
-        slots_total = int(fl.lib().fb_fem_device_plan_get(g.h, b"slot_coff", None, 0))   # SELL slots (64 block rows each) of this rank's matrix
+        if args.full:
+            (spmv_s, spmv_bytes, asm_k_s, halo_s, sum_s, k0_s, resync_ms, persist, persist_s, iter_bytes), _ = stage("kernel probes", probes)
+            slots_total = int(fl.lib().fb_fem_device_plan_get(g.h, b"slot_coff", None, 0))   # SELL slots (64 block rows each) of this rank's matrix
+        else:
+            persist = g.persist_info()
 
-        if rank == 0:
+        if rank == 0 and args.full:
             # HBM traffic of the dominant kernel from the PMC counters: taken from the committed profile only while the kernel
             # sources are still the ones that were profiled (tools/summarize_profiles.py records their hash), else null
             traffic, traffic_note = None, "no PMC profile of the current kernel sources under profiles/"
@@ -943,6 +985,7 @@ def main():
                             "persist_fallbacks": g.pcg_path()["fallbacks"], "persist_rearms": int(fl.lib().fb_fem_persist_rearms(g.h)), "spmv_kernel": spmv_roof}
             else:
                 roofline = dict(spmv_roof, bound="hbm", peak=HBM_PEAK_GBS, unit="GB/s", traffic=traffic, traffic_source=traffic_note)
+        if rank == 0:
             storage = "f64 arithmetic / f32 stored matrix" if args.precision == "f32" else "f64"
             _state["out"] = {
                 "metric": "FEM steps/sec (assemble+PCG) at 1M tets" if args.workload == "cube56" else "FEM steps/sec (assemble+PCG)", "value": args.steps / dt, "unit": "steps/s",
@@ -966,12 +1009,15 @@ def main():
                                    else "two launches per merged iteration (FB_PCG_MERGED)"),
                            "pcg_path_last_step": int(g.last.pcg_path), "persist_fallbacks": int(g.last.persist_fallbacks)},
                 "cg_iterations": [int(i) for i in iters], "cg_iterations_per_step": float(np.mean(iters)),
-                "value_note": "timed steps continue the loaded simulation after the warm-up steps (trajectory); value_at_fixed_state times the same "
-                              "step from the rest state every time",
-                "value_at_fixed_state": (args.steps / fixed_dt) if fixed_dt else None,
-                "cg_iterations_at_fixed_state": [int(i) for i in fixed_iters] if fixed_iters else fs_why,
+                "value_note": "timed steps continue the loaded simulation after the warm-up steps (trajectory); value_at_fixed_state (--full) "
+                              "times the same step from the rest state every time",
                 "assembly_ms_per_step": asm_s / args.steps * 1e3,
                 "solve_ms_per_step": solve_s / args.steps * 1e3, "us_per_cg_iteration": solve_s / max(sum(iters), 1) * 1e6,
+            }
+        if rank == 0 and args.full:
+            _state["out"].update({
+                "value_at_fixed_state": (args.steps / fixed_dt) if fixed_dt else None,
+                "cg_iterations_at_fixed_state": [int(i) for i in fixed_iters] if fixed_iters else fs_why,
                 "resync_ms": resync_ms,
                 # informational (north star: MFMA only for the batched 12x12 element contractions): forming every K0 = V B^T E B on the
                 # fp64 matrix cores; 2*(6*6*12 + 12*6*12) flop and 1152 B written per element.  The per-step path never forms K0.
@@ -984,7 +1030,7 @@ def main():
                 "assembly_kernels_us": asm_k_s * 1e6, "assembly_gbs": g.assembly_bytes() / asm_k_s / 1e9,
                 "roofline": roofline,
                 "cpu_baseline": None,
-            }
+            })
         out = _state["out"]
         mode_used = g.transport()
         sp_final = bool(dist_mode and g.sharded_persist())
@@ -996,17 +1042,17 @@ def main():
             g = None
         # (a sharded run keeps its handle for the collective-library leg, which runs LAST: after the field and the 8M-tet legs)
 
-        # ---- optional legs: each is entered and left by all ranks together; a failure is recorded, the headline survives ----
-        if dist_mode and world > 1 and not args.no_field:
+        # ---- optional legs (--full): each is entered and left by all ranks together; a failure is recorded, the headline survives ----
+        if args.full and dist_mode and world > 1 and not args.no_field:
             fs, why = stage("field grid dealt to the ranks", lambda: field_bench_sharded(device, rank, world, reduce_scalar), optional=True)
             if out is not None:
                 out.update(fs if fs else {"field_error": why})
-        if world == 1 and not args.no_field:
+        if args.full and world == 1 and not args.no_field:
             extra, why = stage("field bench", lambda: field_bench(device, cpu=not args.no_cpu_baseline), optional=True)
             if out is not None:
                 out.update(extra if extra else {"field_error": why})
         # BASELINE configs 1-2 and the numbering leg, one GPU only (driver-timed, never part of `value`)
-        if world == 1 and args.workload == "cube56" and os.environ.get("FEMBRAIN_BENCH_SKIP_LEGS") != "1":
+        if args.full and world == 1 and args.workload == "cube56" and os.environ.get("FEMBRAIN_BENCH_SKIP_LEGS") != "1":
             for key, wl in (("cube27", "cube27"), ("blob100k", "ventricle")):
                 leg, why = stage("leg: %s" % key, lambda wl=wl: small_leg(wl, device, prec, cpu=not args.no_cpu_baseline), optional=True)
                 if out is not None:
@@ -1023,7 +1069,7 @@ def main():
             leg, why = stage("leg: opt-in block-Jacobi", lambda: block_jacobi_leg(device, prec), optional=True)
             if out is not None:
                 out["cube56_block_jacobi_opt_in"] = leg if leg else {"error": why}
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
             _state["stage"] = "cpu baseline"
             try:
                 out["cpu_baseline"] = cpu_baseline((v, t, fixed), int(round(np.mean(iters))))
@@ -1033,7 +1079,7 @@ def main():
         # BASELINE config 5 in the same run: the 8M-tet cube (111^3 nodes) on the same ranks, 1 warm-up + 2 timed steps, so that
         # the N = 1, 2, 4, 8 runs of this script also give the 8M-tet strong-scaling series of the north star.  Reported
         # under "cube111"; never part of `value`.  Every stage of the leg is agreed on by all ranks.
-        if args.workload == "cube56" and os.environ.get("FEMBRAIN_BENCH_SKIP_8M") != "1":
+        if args.full and args.workload == "cube56" and os.environ.get("FEMBRAIN_BENCH_SKIP_8M") != "1":
             big, g8 = None, None
 
             steps8 = max(2, int(os.environ.get("FEMBRAIN_BENCH_8M_STEPS", "5")))
@@ -1148,7 +1194,7 @@ def main():
         # through the collective library (RCCL all-reduce of the three sums + ncclSend/ncclRecv of the halo rows; FB_XCH_COLLECTIVE), and the
         # same step in the form the timed steps used.  LAST of all legs (the 8M-tet scaling leg included) and under a watchdog of its own (90 s): a collective
         # that never returns costs this leg -- the line goes out without it, exit code 0 -- not the run.  FEMBRAIN_BENCH_TRY_RCCL=0 skips it.
-        if dist_mode and g is not None and os.environ.get("FEMBRAIN_BENCH_TRY_RCCL", "1") != "0":
+        if args.full and dist_mode and g is not None and os.environ.get("FEMBRAIN_BENCH_TRY_RCCL", "1") != "0":
             _state["soft_stage"] = "collective-library leg"
             def rest_step(mode, sp):
                 if sp_attached and g.persist_info()[0] != sp and not (sp and g.pcg_path()["fallbacks"]):

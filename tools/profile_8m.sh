@@ -4,7 +4,7 @@
 set -e
 R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
-ARGS="$R/bench.py --workload cube111 --steps 2 --warmup 1 --no-cpu-baseline --no-field"
+ARGS="$R/bench.py --workload cube111 --steps 2 --warmup 1 --no-cpu-baseline --no-field --full"
 export FEMBRAIN_BENCH_SKIP_8M=1
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof8_kt -o kt -- python3 $ARGS > $R/gpurun_out/prof8_kt.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $R/gpurun_out/prof8_fetch -o fetch -- python3 $ARGS > $R/gpurun_out/prof8_fetch.log 2>&1

@@ -7,7 +7,7 @@ export FEMBRAIN_BENCH_SKIP_8M=${FEMBRAIN_BENCH_SKIP_8M:-1}   # the 8M-tet leg ha
 export FEMBRAIN_BENCH_SKIP_LEGS=${FEMBRAIN_BENCH_SKIP_LEGS:-1} # (round 4) the cube27 / blob100k / scrambled legs: other handles' launches of the same kernels would mix into the per-launch sums
 R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
-ARGS="$R/bench.py --steps 5 --warmup 1 --no-cpu-baseline"
+ARGS="$R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --full"
 # (every pass writes the iteration count of each persistent launch, in launch order: the summaries divide per-launch figures by it)
 export FEMBRAIN_BENCH_LAUNCH_LOG=$R/gpurun_out/prof_kt_launches.json
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_kt -o kt -- python3 $ARGS > $R/gpurun_out/prof_kt.log 2>&1
