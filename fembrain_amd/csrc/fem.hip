@@ -157,6 +157,16 @@ struct fb_fem_s {
   int pipe_max_producers = 0;          // longest producer list (-1: some workgroup polls all)
   bool pipe_stats_pending = false;     // ... still on the device (pipe_stats: [0] longest list, [1] someone polls all)
   DevBuf<int> pipe_owner, pipe_stats;
+  // the LDS window of the one-row kernel (pcg_pipe_mirror.h; k_pipe_mirror_plan in setup_persist), empty: none (FEMBRAIN_PIPE_MIRROR=0, or
+  // another instantiation).  pipe_mir_stats: mirror layers, pool entries, fewest plain layers of a slice -- fetched when asked
+  DevBuf<int4> pipe_mir;
+  DevBuf<unsigned short> pipe_mir_addr;
+  DevBuf<int2> pipe_mir_wg;
+  DevBuf<int> pipe_mir_pool, pipe_mir_stats;
+  int pipe_mir_got[3] = {0, 0, 0};
+  int pipe_mir_klt = 0;                // the instantiation's unroll bound it was planned for
+  int pipe_mir_knob = -1;              // FEMBRAIN_PIPE_MIRROR as it was when the handle was made (-1: not read yet)
+  bool pipe_mir_pending = false;
   DevBuf<unsigned int> pipe_mask;
   long long persist_timeout_ticks = 0; // wall_clock64 ticks (100 MHz) a wait inside a persistent launch may last
   int persist_fallbacks = 0;           // solves that had to be repeated with the two-launch form
@@ -458,12 +468,51 @@ void read_persist_timeout(fb_fem_s* h) {
   h->persist_timeout_ticks = std::max(1LL, (long long)(ms * 1e5));  // 100 MHz
 }
 
+static bool pipe_klt7(const fb_fem_s* h);
+
+// The LDS window of the one-row (12, 6) / (12, 7) kernel (pcg_pipe_mirror.h): planned on the device for every (re)built plan, so a full
+// re-sync, both outcomes of a delta re-sync and a fresh node order all get the table of their own plan.  FEMBRAIN_PIPE_MIRROR=0 when the
+// handle is made: none.
+int setup_pipe_mirror(fb_fem_s* h) {
+  const FemPlan& P = h->plan;
+  hipStream_t s = h->stream;
+  if (h->pipe_mir_knob < 0) {  // (read once, at the handle's first plan: its re-syncs keep what it was made with)
+    const char* e = getenv("FEMBRAIN_PIPE_MIRROR");
+    h->pipe_mir_knob = e && atoi(e) == 0 ? 0 : 1;
+  }
+  const bool want = h->pipe_mir_knob != 0;
+  h->pipe_mir_pending = false;
+  h->pipe_mir_got[0] = h->pipe_mir_got[1] = h->pipe_mir_got[2] = 0;
+  if (!want || !h->persist || h->shard_persist || h->pipe_rows != 1 || h->pipe_wmax != 12 || h->pipe_tasks.p || h->pipe_xyz ||
+      h->prm.pcg_variant == FB_PCG_BLOCK_JACOBI || P.n_slices <= 0) {
+    h->pipe_mir.release(); h->pipe_mir_addr.release(); h->pipe_mir_wg.release(); h->pipe_mir_pool.release();
+    return FB_OK;
+  }
+  const int nb = h->persist_blocks;
+  const int klt = pipe_klt7(h) ? 7 : 6;
+  h->pipe_mir_klt = klt;
+  FB_TRY(h->pipe_mir.alloc((size_t)nb * kMirWaves));
+  FB_TRY(h->pipe_mir_addr.alloc((size_t)P.n_slices * kMirMax * 64));
+  FB_TRY(h->pipe_mir_wg.alloc((size_t)nb));
+  FB_TRY(h->pipe_mir_pool.alloc((size_t)nb * kMirPoolMax));
+  FB_TRY(h->pipe_mir_stats.alloc(3));
+  FB_HIP(hipMemsetAsync(h->pipe_mir_stats.p, 0, 2 * sizeof(int), s));
+  FB_HIP(hipMemsetAsync(h->pipe_mir_stats.p + 2, 0x7f, sizeof(int), s));  // (a minimum)
+  hipLaunchKernelGGL(k_pipe_mirror_plan, dim3(nb), dim3(64 * kMirWaves), 0, s, P.n_slices, P.n_owned, h->slice_off.p, h->colidx.p, h->pipe_wg_first.p, klt,
+                     h->c16 ? 1 : 0, h->pipe_mir.p, h->pipe_mir_addr.p, h->pipe_mir_pool.p, h->pipe_mir_wg.p, h->pipe_mir_stats.p);
+  FB_HIP(hipGetLastError());
+  h->pipe_mir_pending = true;
+  return FB_OK;
+}
+
 // Decides whether this handle solves inside persistent launches and allocates what they need (called for every (re)built plan).
 int setup_persist(fb_fem_s* h) {
   const FemPlan& P = h->plan;
   hipStream_t s = h->stream;
   ZeroBatch zb(s);  // (the clears of this set-up in one launch)
   h->persist = false;
+  h->pipe_mir.release(); h->pipe_mir_pending = false;  // (setup_pipe_mirror plans the window again where it applies)
+  h->pipe_mir_got[0] = h->pipe_mir_got[1] = h->pipe_mir_got[2] = 0;
   // Nothing of the previous plan's sharded persistent solver survives a rebuild: a re-sync to a mesh that is no longer
   // eligible must not leave attach_pipe_shard a stale "keep", stale send lists or a stale workgroup deal.  setup_persist_shard_local
   // is the only place that sets shard_persist again; a fresh plan also gets a fresh chance after a time-out.
@@ -765,7 +814,7 @@ int setup_persist(fb_fem_s* h) {
     const char* e = getenv("FEMBRAIN_PIPE_PLAIN_STORES");
     h->pipe_plain_local = e ? atoi(e) : (w <= 8 ? 1 : 0);
   }
-  return FB_OK;
+  return setup_pipe_mirror(h);
 }
 
 int upload_plan(fb_fem_s* h, const double* xyz_global, const float* xyz_device = nullptr, const double* xyz_device64 = nullptr) {
@@ -1356,6 +1405,9 @@ int launch_pipe(fb_fem_s* h, const double* b, int start, int n_iters, double eps
   pa.pstate = h->pipe_state.p;
   pa.tasks = h->pipe_tasks.p; pa.n_help = h->pipe_n_help;
   pa.wg_first = h->pipe_wg_first.p;
+  // the LDS window, where the instantiation launched below is the one it was planned for
+  const bool mir = h->pipe_mir.p && h->pipe_mir_klt == (pa.timing ? 6 : (pipe_klt7(h) ? 7 : 6));
+  pa.mirror = mir ? h->pipe_mir.p : nullptr; pa.mir_addr = h->pipe_mir_addr.p; pa.mir_wg = h->pipe_mir_wg.p; pa.mir_pool = h->pipe_mir_pool.p;
   // LDS: the sync buffers, then KLT slots of every slice; the request is the whole 160 KB of a CU, so exactly one workgroup lands on each
   const size_t lds = 160 * 1024;
   // one wavefront more than slices where the instantiation has room: it collects the sums while the others multiply
@@ -3304,6 +3356,19 @@ int fb_fem_pcg_path(fb_fem_t h, char* name, int name_len, int* persist_launches,
 
 int fb_fem_persist_rearms(fb_fem_t h) { return h ? h->persist_rearms : 0; }
 int fb_fem_persist_helpers(fb_fem_t h) { return h && h->persist ? h->pipe_help_tasks : 0; }
+int fb_fem_persist_mirror(fb_fem_t h, int* mirror_layers, int* pool_entries, int* plain_slots) {
+  if (!h) return fail(FB_EINVAL, "null FEM handle");
+  if (h->pipe_mir_pending) {
+    FB_TRY(h->pipe_mir_stats.download(h->pipe_mir_got, 3, h->stream));
+    h->pipe_mir_pending = false;
+  }
+  const bool on = h->persist && h->pipe_mir.p;
+  if (mirror_layers) *mirror_layers = on ? h->pipe_mir_got[0] : 0;
+  if (pool_entries) *pool_entries = on ? h->pipe_mir_got[1] : 0;
+  if (plain_slots) *plain_slots = on ? h->pipe_mir_got[2] : 0;
+  return on && h->pipe_mir_got[0] > 0 ? 1 : 0;
+}
+
 int fb_fem_persist_gather(fb_fem_t h, double* lines_planes, double* lines_records) {
   if (lines_planes) *lines_planes = h && h->persist ? h->pipe_gather_lines[0] : 0.0;
   if (lines_records) *lines_records = h && h->persist ? h->pipe_gather_lines[1] : 0.0;

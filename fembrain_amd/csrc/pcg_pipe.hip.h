@@ -31,6 +31,7 @@
 #pragma once
 #include "fem_kernels.h"
 #include "pcg_pipe_stream.hip.h"
+#include "pcg_pipe_mirror.h"
 
 namespace fb {
 
@@ -45,6 +46,9 @@ constexpr int pipe_slot_bytes(bool c16) { return c16 ? 9 * 256 + 128 : 10 * 256;
 constexpr int pipe_lds_slots(bool c16) { return c16 ? 65 : 62; }
 static_assert(sizeof(double) * kPipeSyncDoubles + (size_t)pipe_lds_slots(false) * pipe_slot_bytes(false) <= 160 * 1024, "LDS budget of k_pcg_pipe");
 static_assert(sizeof(double) * kPipeSyncDoubles + (size_t)pipe_lds_slots(true) * pipe_slot_bytes(true) <= 160 * 1024, "LDS budget of k_pcg_pipe<c16>");
+static_assert(mir_slot_bytes(true) == pipe_slot_bytes(true) && mir_slot_bytes(false) == pipe_slot_bytes(false) && mir_lds_slots(true) == pipe_lds_slots(true) &&
+              mir_lds_slots(false) == pipe_lds_slots(false) && kMirWaves == kPipeMaxWaves, "the LDS window's planner sees the kernel's LDS");
+static_assert(pipe_lds_slots(true) * pipe_slot_bytes(true) / 4 < 65536 && pipe_lds_slots(false) * pipe_slot_bytes(false) / 4 < 65536, "16-bit LDS word addresses of the mirror layers");
 
 struct PipeArgs {
   unsigned long long* post;   // [2][n_blocks][4] granules: (hi, lo) of gamma, delta, each | sequence << 32
@@ -78,6 +82,14 @@ struct PipeArgs {
   const int* wg_first;        // the deal of the slices to the workgroups balanced by slots (pipe_deal), or nullptr: equal numbers of slices
   const int4* tasks;          // [n_blocks][kPipeTaskStride]
   int n_help;                 // most helpers of any workgroup (0: none; LDS for their partial sums is set aside when > 0)
+  // The LDS window (pcg_pipe_mirror.h, k_pipe_mirror_plan; the (12, 6) and (12, 7) instantiations only), nullptr: the first slots of every slice
+  // are its resident ones.  mirror[b][wv] = (a | m << 8 | p << 16, first wavefront-slot of the plain layers, byte offset of the mirror table);
+  // mir_addr[slice][kMirMax][64] LDS word addresses of the blocks the mirror layers read transposed; the pool: mir_wg[b] = (first LDS word,
+  // entries), mir_pool[b][kMirPoolMax] the index in `vals` of each entry's block.
+  const int4* mirror;
+  const unsigned short* mir_addr;
+  const int2* mir_wg;
+  const int* mir_pool;
 };
 constexpr int kPipeTaskStride = 16;
 constexpr int kPipeMaxHelpers = 8;   // per workgroup
@@ -217,6 +229,90 @@ __global__ __launch_bounds__(kBlock) void k_wg_producers(int n_slices, int nb, c
   atomicMax(&stats[0], n);
 }
 
+// The LDS window of every workgroup (pcg_pipe_mirror.h), a workgroup of the plan per persistent workgroup, a wavefront per slice:
+// wave_out[b][w] = (a | m << 8 | p << 16, first wavefront-slot of the plain layers, byte offset of the mirror table, 0); addr_out[slice][k][64] = the
+// LDS word address of mirror layer k's block to read transposed (the partner's plain block or a pool entry); pool_src[b][e] = the index in `vals` of
+// the lane's own block that pool entry e holds; wg_out[b] = (pool's first LDS word, entries); stats += (mirror layers, pool entries), min= plain layers.
+// A workgroup whose window would not keep more slots on chip than the plain share gets the plain kernel's layout (no mirrors, no pool).
+__global__ __launch_bounds__(64 * kMirWaves) void k_pipe_mirror_plan(int n_slices, int n_owned, const int* __restrict__ slice_off, const int* __restrict__ colidx,
+                                                                   const int* __restrict__ wg_first, int klt, int c16i, int4* __restrict__ wave_out,
+                                                                   unsigned short* __restrict__ addr_out, int* __restrict__ pool_src, int2* __restrict__ wg_out,
+                                                                   int* __restrict__ stats) {
+  const bool c16 = c16i != 0;
+  __shared__ MirWave mw[kMirWaves];
+  __shared__ int cnt[kMirWaves];
+  __shared__ int ok;
+  const int b = blockIdx.x, nb = gridDim.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int first, count;
+  pipe_deal(wg_first, n_slices, nb, b, &first, &count);
+  count = min(count, kMirWaves);
+  const int lo = first * 64, hi = min((first + count) * 64, n_owned);
+  if (w < count) {  // the diagonal slot most lanes have, and the layers below it whose columns are lower rows of this workgroup
+    const int sl = first + w, width = slice_off[sl + 1] - slice_off[sl];
+    const int dk = mir_lane_diag(slice_off, colidx, sl, lane, n_owned);
+    int d = -1, best = 0;
+    for (int k = 0; k < width; k++) {
+      const int c = __popcll(__ballot(dk == k));
+      if (c > best) { best = c; d = k; }
+    }
+    int m = 0;
+    if (d >= 0)
+      for (; m < kMirMax && d - 1 - m >= 0; m++)
+        if (__popcll(__ballot(mir_lane_lower(slice_off, colidx, sl, d - 1 - m, lane, lo, hi))) < kMirLanes) break;
+    if (lane == 0) { mw[w].d = d; mw[w].m = m; mw[w].width = width; }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) ok = count > 0 && mir_wg_layout(mw, count, klt, c16, 0, false) ? 1 : 0;
+  __syncthreads();
+  // the lanes without a resident partner block, twice: with the least plain share; then with the plain layers the pool leaves room for (more
+  // partner slots resident: never more lanes)
+  for (int pass = 0; pass < 2; pass++) {
+    if (ok && w < count) {
+      int e = 0;
+      for (int k = 0; k < mw[w].m; k++) e += __popcll(__ballot(mir_lane_addr(slice_off, colidx, first, mw, w, k, lane, lo, hi, c16) < 0));
+      if (lane == 0) cnt[w] = e;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && ok) {
+      int E = 0;
+      for (int v = 0; v < count; v++) E += cnt[v];
+      if (pass == 0) ok = E <= kMirPoolMax && mir_wg_layout(mw, count, klt, c16, E, true) ? 1 : 0;
+      else ok = mir_wg_gains(mw, count, klt, c16) ? 1 : 0;
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    if (!ok) mir_wg_plain(mw, count, klt, c16);
+    int E = 0, layers = 0, fewest = 1 << 30;
+    for (int v = 0; v < count; v++) {
+      const int e = ok ? cnt[v] : 0;
+      cnt[v] = E;  // (exclusive prefix: the first pool entry of slice v)
+      E += e; layers += mw[v].m; fewest = min(fewest, mw[v].p);
+    }
+    wg_out[b] = make_int2(mir_pool_at(mw, count, c16) / 4, E);
+    atomicAdd(&stats[0], layers); atomicAdd(&stats[1], E);
+    if (count > 0) atomicMin(&stats[2], fewest);
+  }
+  __syncthreads();
+  if (w < count) {
+    const int sl = first + w, pool_at = mir_pool_at(mw, count, c16) / 4;
+    int e = cnt[w];
+    for (int k = 0; k < mw[w].m; k++) {
+      int addr = mir_lane_addr(slice_off, colidx, first, mw, w, k, lane, lo, hi, c16);
+      const unsigned long long miss = __ballot(addr < 0);
+      if (addr < 0) {
+        const int idx = e + __popcll(miss & ((1ULL << lane) - 1ULL));
+        pool_src[(size_t)b * kMirPoolMax + idx] = (slice_off[sl] + mw[w].a + k) * 9 * 64 + lane;
+        addr = pool_at + (idx >> 6) * 9 * 64 + (idx & 63);
+      }
+      e += __popcll(miss);
+      addr_out[((size_t)sl * kMirMax + k) * 64 + lane] = (unsigned short)addr;
+    }
+  }
+  if (w < kMirWaves && lane == 0)
+    wave_out[(size_t)b * kMirWaves + w] = w < count ? make_int4(mw[w].a | mw[w].m << 8 | mw[w].p << 16, mw[w].at, mw[w].tab, 0) : make_int4(0, 0, 0, 0);
+}
+
 // One wavefront's share of the collection of all workgroups' posted sums of sequence number `sums`: lane `l0` of `stride` takes workgroups
 // l0, l0 + stride, ...; adds their two values to t0s / t1s in that order (the callers fix the order of the rest).  Bounded by the wall clock.
 __device__ __forceinline__ void pipe_collect_posts(const PipeArgs& pa, unsigned int sums, int nb, int lane, int stride, int l0, long long t0, long long t_limit, bool& failed,
@@ -344,6 +440,10 @@ __global__ __launch_bounds__(64 * WMAX) void k_pcg_pipe(SellView sv, const MT* _
   // (HELP: how many and where is the plan's decision, PipeArgs::tasks -- a slice of 27 slots among slices of 15 keeps 17 of them here, so
   // that every wavefront of the workgroup streams about the same number: an iteration ends with the slowest wavefront)
   int klt_w, lres_at;
+  // the LDS window (PipeArgs::mirror, pcg_pipe_mirror.h): slots [mir_a, mir_a + mir_m) are read from LDS as the transposes of other rows'
+  // blocks, [kp, kp + klt_w) are the plain resident ones, the rest is streamed.  Without a window: kp = 0, the first klt_w slots.
+  constexpr bool kMir = !HELP && !SHARD && !BJ && !XYZ && WMAX == 12 && (KLT == 6 || KLT == 7);
+  int mir_a = 0, mir_m = 0, mir_tab = 0;
   if constexpr (HELP) {
     const int4 tk = pa.tasks[(size_t)blockIdx.x * kPipeTaskStride + wv];
     klt_w = __builtin_amdgcn_readfirstlane(live ? tk.x : 0);
@@ -353,8 +453,19 @@ __global__ __launch_bounds__(64 * WMAX) void k_pcg_pipe(SellView sv, const MT* _
     const int lbase = min(KLT, kSlots / max(count, 1)), lrem = lbase < KLT ? min(count, kSlots - lbase * count) : 0;  // workgroup-uniform
     klt_w = __builtin_amdgcn_readfirstlane(live ? lbase + (wv < lrem ? 1 : 0) : 0);
     lres_at = wv * lbase + min(wv, lrem);
+    if constexpr (kMir) {
+      if (pa.mirror) {
+        const int4 mt = live ? pa.mirror[(size_t)blockIdx.x * kPipeMaxWaves + wv] : make_int4(0, 0, 0, 0);
+        klt_w = __builtin_amdgcn_readfirstlane((mt.x >> 16) & 0xff);
+        lres_at = __builtin_amdgcn_readfirstlane(mt.y);
+        mir_a = __builtin_amdgcn_readfirstlane(mt.x & 0xff);
+        mir_m = __builtin_amdgcn_readfirstlane((mt.x >> 8) & 0xff);
+        mir_tab = __builtin_amdgcn_readfirstlane(mt.z);
+      }
+    }
   }
-  const int KL = min(klt_w, width);
+  const int kp = mir_a + mir_m, k_after = kp + klt_w;  // first plain slot, first slot streamed after the window
+  const int KL = min(klt_w, width - kp);
   // this wavefront's part: C16 [klt_w][9][64] value words, then [klt_w][64] column differences (halfwords); else [klt_w][10][64] words, the tenth the column
   constexpr int kValWords = C16 ? 9 : 10;
   char* lwave = (char*)(lds + kPipeSyncDoubles) + (size_t)lres_at * pipe_slot_bytes(C16);
@@ -366,11 +477,32 @@ __global__ __launch_bounds__(64 * WMAX) void k_pcg_pipe(SellView sv, const MT* _
   };
   if (sizeof(MT) == 4) {
     for (int k = 0; k < KL; k++) {
-      const MT* vk = v + (size_t)k * 9 * 64;
+      const MT* vk = v + (size_t)(kp + k) * 9 * 64;
 #pragma unroll
       for (int j = 0; j < 9; j++) lres[(k * kValWords + j) * 64] = __float_as_uint((float)vk[j * 64]);
-      if constexpr (C16) lcd[k * 64] = cd[(size_t)k * 64];
-      else lres[(k * 10 + 9) * 64] = (unsigned int)ci[(size_t)k * 64];
+      if constexpr (C16) lcd[k * 64] = cd[(size_t)(kp + k) * 64];
+      else lres[(k * 10 + 9) * 64] = (unsigned int)ci[(size_t)(kp + k) * 64];
+    }
+  }
+  if constexpr (kMir) {
+    if (pa.mirror) {
+      // the mirror tables: per lane and layer the column and the LDS word of the block to read transposed
+      unsigned int* lmt = (unsigned int*)((char*)(lds + kPipeSyncDoubles) + mir_tab) + lane;
+      const unsigned short* ma = pa.mir_addr + (size_t)(live ? sl : 0) * kMirMax * 64 + lane;
+      for (int k = 0; k < mir_m; k++) {
+        const unsigned int addr = ma[k * 64];
+        if constexpr (C16) lmt[k * 64] = addr << 16 | (unsigned short)cd[(size_t)(mir_a + k) * 64];
+        else { lmt[k * 96] = (unsigned int)ci[(size_t)(mir_a + k) * 64]; ((unsigned short*)(lmt - lane + k * 96 + 64))[lane] = (unsigned short)addr; }
+      }
+      // the pool: blocks whose transposes are not resident elsewhere, stored transposed (value 3a + b of the block at word (3b + a) x 64)
+      const int2 pw = pa.mir_wg[blockIdx.x];
+      unsigned int* lmat = (unsigned int*)(lds + kPipeSyncDoubles);
+      for (int e = threadIdx.x; e < pw.y; e += blockDim.x) {
+        const MT* src = vals + pa.mir_pool[(size_t)blockIdx.x * kMirPoolMax + e];
+        unsigned int* pe = lmat + pw.x + (e >> 6) * 9 * 64 + (e & 63);
+#pragma unroll
+        for (int j = 0; j < 9; j++) pe[(3 * (j % 3) + j / 3) * 64] = __float_as_uint((float)src[j * 64]);
+      }
     }
   }
   // this wavefront's task (helpers, see PipeArgs): the owner of a slice streams its slots up to own_k1 and adds the partial sums of the
@@ -449,13 +581,13 @@ __global__ __launch_bounds__(64 * WMAX) void k_pcg_pipe(SellView sv, const MT* _
     __syncthreads();
     lap(0);  // publish, drained
     if (post_sums) sums++;
-    if (wv != 0 && live && pa.prefetch_slots > 0 && own_k1 > klt_w) {
+    if (wv != 0 && live && pa.prefetch_slots > 0 && (mir_a > 0 || own_k1 > k_after)) {
       // idle until wavefront 0 has seen the neighbours' flags: the first streamed slots' values go to L2 meanwhile (measured at 1M
       // tets, us per iteration with 0 / 2 / 3 / 4 slots: 17.15 / 16.25 / 16.1 / 16.05; the same during the drain of the publish
-      // stores instead delays the flag and loses: 16.85)
-      int so_k = so + klt_w;
+      // stores instead delays the flag and loses: 16.85).  With an LDS window: those of the first streamed part, [0, mir_a).
+      int so_k = so + (mir_a > 0 ? 0 : k_after);
       asm volatile("" : "+s"(so_k));  // (opaque, as for the streamed loop below)
-      pipe_prefetch_values(min(pa.prefetch_slots, own_k1 - klt_w), ((unsigned int)so_k * 9u * 64u + (unsigned int)lane) * (unsigned int)sizeof(float), vals);
+      pipe_prefetch_values(min(pa.prefetch_slots, mir_a > 0 ? mir_a : own_k1 - k_after), ((unsigned int)so_k * 9u * 64u + (unsigned int)lane) * (unsigned int)sizeof(float), vals);
     }
     if constexpr (SHARD) {
       if (spare) shard_service_product(sa, BL, pa, pub, pl, nb, lane, send_mask, t_limit, bc, failed);
@@ -527,6 +659,31 @@ __global__ __launch_bounds__(64 * WMAX) void k_pcg_pipe(SellView sv, const MT* _
       y2 = l02 * vin[0] + l12 * vin[1] + l22 * vin[2];
     }
     if (live) {
+      if constexpr (kMir) {
+        // the LDS window in slot order: the slots in front of it streamed, then the mirror layers (the same mul / mul / add / mul / add / add
+        // per row as everywhere: the sum of a row runs over the same slots in the same order with the same values as without a window)
+        if (mir_a > 0) {
+          int so_k = so;
+          asm volatile("" : "+s"(so_k));  // (opaque, as below)
+          pipe_stream_slots<C16, XYZ>(mir_a, ((unsigned int)so_k * 9u * 64u + (unsigned int)lane) * (unsigned int)sizeof(float),
+                                      ((unsigned int)so_k * 64u + (unsigned int)lane) * (unsigned int)(C16 ? sizeof(short) : sizeof(int)), vals,
+                                      C16 ? (const void*)sv.coldelta : (const void*)sv.colidx, pl, pl + xs, pl + 2 * xs, row, y0, y1, y2);
+        }
+        const unsigned int* lmt = (const unsigned int*)((const char*)(lds + kPipeSyncDoubles) + mir_tab) + lane;
+        const unsigned int* lmat = (const unsigned int*)(lds + kPipeSyncDoubles);
+#pragma unroll
+        for (int k = 0; k < kMirMax; k++) if (k < mir_m) {
+          unsigned int addr, col;
+          if constexpr (C16) { const unsigned int wd = lmt[k * 64]; addr = wd >> 16; col = (unsigned int)(row + (int)(short)(wd & 0xffffu)); }
+          else { col = lmt[k * 96]; addr = ((const unsigned short*)(lmt - lane + k * 96 + 64))[lane]; }
+          const unsigned int* pk = lmat + addr;  // the block (col, row): value 3a + b of this row's block is its value 3b + a
+          const double* xp = pl + cs * (size_t)col;
+          const double x0 = xp[0], x1 = xp[xs], x2 = xp[2 * xs];
+          y0 += (double)__uint_as_float(pk[0 * 64]) * x0 + (double)__uint_as_float(pk[3 * 64]) * x1 + (double)__uint_as_float(pk[6 * 64]) * x2;
+          y1 += (double)__uint_as_float(pk[1 * 64]) * x0 + (double)__uint_as_float(pk[4 * 64]) * x1 + (double)__uint_as_float(pk[7 * 64]) * x2;
+          y2 += (double)__uint_as_float(pk[2 * 64]) * x0 + (double)__uint_as_float(pk[5 * 64]) * x1 + (double)__uint_as_float(pk[8 * 64]) * x2;
+        }
+      }
       if (sizeof(MT) == 4 && KLT >= 16) {
         // whole slices in LDS, five wavefronts per CU: registers to spare, so ALL gathers of the product are in flight before the first
         // multiplication (the loop below waits for each slot's three gathers in turn: 5.5 us for the slowest wavefronts at 105k tets, whose
@@ -577,9 +734,9 @@ __global__ __launch_bounds__(64 * WMAX) void k_pcg_pipe(SellView sv, const MT* _
         }
       }
       // the streamed slots: hand-pipelined loads (pcg_pipe_stream.hip.h); those from own_k1 on are a helper's
-      const int n_str = own_k1 - klt_w;
+      const int n_str = own_k1 - k_after;
       if (n_str > 0) {
-        int so_k = so + klt_w;
+        int so_k = so + k_after;
         asm volatile("" : "+s"(so_k));  // opaque: keeps the two offsets below from being hoisted out of the solver loop into live registers
         pipe_stream_slots<C16, XYZ>(n_str, ((unsigned int)so_k * 9u * 64u + (unsigned int)lane) * (unsigned int)sizeof(float),
                                ((unsigned int)so_k * 64u + (unsigned int)lane) * (unsigned int)(C16 ? sizeof(short) : sizeof(int)), vals,

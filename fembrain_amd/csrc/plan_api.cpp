@@ -7,6 +7,7 @@
 #include "../../include/fembrain_hip_testing.h"
 #include "fem_plan.h"
 #include "renumber.h"
+#include "pcg_pipe_mirror.h"
 
 namespace fb {
 int fail(int code, const char* fmt, ...);
@@ -88,6 +89,65 @@ int fb_plan_shard_vote(int n_nodes, int n_tets, const int* tets, int n_ranks, in
   unsigned long long sum = 0;
   int splits_sum = 0;
   fb::shard_neighbour_count(n_nodes, n_tets, tets, n_ranks, rank, node_splits, &out[0], &sum, &splits_sum, &out[1], &out[2]);
+  return FB_OK;
+}
+
+// Host model of k_pipe_mirror_plan (fem.hip / pcg_pipe.hip.h) over the plan's SELL layout, the slices dealt in equal numbers to nb workgroups
+// as pipe_slices does: the same functions of pcg_pipe_mirror.h, the wavefront-wide counts as loops over the 64 lanes.  out[0] = mirror layers,
+// out[1] = pool entries, out[2] = fewest plain layers of a slice, out[3] = workgroups that keep mirrors.
+int fb_plan_mirror_model(fb_plan_t p, int nb, int c16, int klt, int out[4]) {
+  if (!p || !out || nb < 8 || (nb & 7) || (klt != 6 && klt != 7)) return fb::fail(FB_EINVAL, "bad argument");
+  const fb::FemPlan& P = p->plan;
+  const int* so = P.slice_off.data();
+  const int* ci = P.colidx.data();
+  out[0] = out[1] = out[3] = 0;
+  out[2] = 1 << 30;
+  for (int b = 0; b < nb; b++) {
+    // (pipe_slices, pcg_pipe.hip.h)
+    const int xcd = b & 7, j = b >> 3, per = nb >> 3, chunk = (P.n_slices + 7) >> 3, lo_s = xcd * chunk;
+    int len = P.n_slices - lo_s;
+    len = len < 0 ? 0 : (len > chunk ? chunk : len);
+    const int base = len / per, rem = len - base * per;
+    const int first = lo_s + j * base + (j < rem ? j : rem);
+    const int count = std::min(base + (j < rem ? 1 : 0), fb::kMirWaves);
+    if (count <= 0) continue;
+    const int lo = first * 64, hi = std::min((first + count) * 64, P.n_owned);
+    fb::MirWave mw[fb::kMirWaves];
+    for (int w = 0; w < count; w++) {
+      const int sl = first + w, width = so[sl + 1] - so[sl];
+      int hist[256] = {0};
+      for (int l = 0; l < 64; l++) {
+        const int dk = fb::mir_lane_diag(so, ci, sl, l, P.n_owned);
+        if (dk >= 0 && dk < 256) hist[dk]++;
+      }
+      int d = -1, best = 0;
+      for (int k = 0; k < width && k < 256; k++)
+        if (hist[k] > best) { best = hist[k]; d = k; }
+      int m = 0;
+      if (d >= 0)
+        for (; m < fb::kMirMax && d - 1 - m >= 0; m++) {
+          int n = 0;
+          for (int l = 0; l < 64; l++) n += fb::mir_lane_lower(so, ci, sl, d - 1 - m, l, lo, hi) ? 1 : 0;
+          if (n < fb::kMirLanes) break;
+        }
+      mw[w].d = d; mw[w].m = m; mw[w].width = width;
+    }
+    auto misses = [&]() {
+      int e = 0;
+      for (int w = 0; w < count; w++)
+        for (int k = 0; k < mw[w].m; k++)
+          for (int l = 0; l < 64; l++) e += fb::mir_lane_addr(so, ci, first, mw, w, k, l, lo, hi, c16 != 0) < 0 ? 1 : 0;
+      return e;
+    };
+    bool ok = fb::mir_wg_layout(mw, count, klt, c16 != 0, 0, false);
+    int E = ok ? misses() : 0;
+    ok = ok && E <= fb::kMirPoolMax && fb::mir_wg_layout(mw, count, klt, c16 != 0, E, true);
+    if (ok) { E = misses(); ok = fb::mir_wg_gains(mw, count, klt, c16 != 0); }
+    if (!ok) { fb::mir_wg_plain(mw, count, klt, c16 != 0); E = 0; }
+    for (int w = 0; w < count; w++) { out[0] += mw[w].m; out[2] = std::min(out[2], mw[w].p); }
+    out[1] += E;
+    out[3] += ok ? 1 : 0;
+  }
   return FB_OK;
 }
 

@@ -311,6 +311,14 @@ class FemIntegrator:
         on = self._L.fb_fem_persist_gather(self.h, C.byref(a), C.byref(b))
         return bool(on), a.value, b.value
 
+    def persist_mirror(self):
+        """(some layer mirrored?, mirror layers over all slices, pool entries, fewest plain LDS slots of a slice) -- fb_fem_persist_mirror"""
+        m, p, k = C.c_int(0), C.c_int(0), C.c_int(0)
+        on = self._L.fb_fem_persist_mirror(self.h, C.byref(m), C.byref(p), C.byref(k))
+        if on < 0:
+            _l.check(on)
+        return bool(on == 1), m.value, p.value, k.value
+
     def pcg_path(self):
         """What ran: dict(path = FB_PCG_PATH_* of the last solve, kernel = the persistent instantiation this handle launches or '',
         launches, fallbacks, max_producers)"""

@@ -356,6 +356,13 @@ int fb_fem_persist_helpers(fb_fem_t h);
  * load touches 4 lines), unstructured ones ~80 / ~44 (node by node: 606k-tet Delaunay probe 18.9 -> 16.2 us per PCG iteration).  0 / 0 where
  * it was not measured (handles outside the one-row persistent kernel's range).  FEMBRAIN_PIPE_XYZ=0/1 overrides. */
 int fb_fem_persist_gather(fb_fem_t h, double* lines_planes, double* lines_records);
+/* The LDS window of the one-row persistent kernel (k_pcg_pipe (12, 6) / (12, 7), 9-12 slices per CU): per slice a contiguous run of slots is
+ * kept in LDS, and its layers whose blocks have a lower row of the same workgroup as column are not stored again but read as the transposes of
+ * those rows' resident blocks (A = A^T bitwise; the iterates do not change by a bit).  mirror_layers = such layers over all slices,
+ * pool_entries = blocks kept transposed in the workgroups' pools (lanes of those layers whose partner block is not resident), plain_slots =
+ * fewest plainly stored slots of any slice (never fewer than fb_fem_persist_info's lds_slots).  Returns 1 if some layer is mirrored, else 0
+ * (0 / 0 / 0: no window -- other instantiations, FEMBRAIN_PIPE_MIRROR=0).  Any pointer may be NULL. */
+int fb_fem_persist_mirror(fb_fem_t h, int* mirror_layers, int* pool_entries, int* plain_slots);
 /* average device seconds of ONE persistent launch that starts a solve of the current system and is cut after n_iters
  * iterations (tolerance out of reach), HIP events on the handle's stream around the launch; the difference of two lengths
  * prices an iteration without the launch's fixed cost */

@@ -23,6 +23,11 @@ int fb_plan_info(fb_plan_t p, int info[12]);
  *        slot_coff, slot_ccnt, contrib (uint32 bits), dofmask (one int per DOF) */
 int fb_plan_get(fb_plan_t p, const char* name, int* out, size_t capacity);
 
+/* Host model of the persistent solver's LDS window planner (fembrain_amd/csrc/pcg_pipe_mirror.h, k_pipe_mirror_plan) over this plan, its slices
+ * dealt in equal numbers to nb workgroups: out[0] = mirror layers over all slices, out[1] = pool entries, out[2] = fewest plain layers of a
+ * slice, out[3] = workgroups that keep mirrors.  c16: 16-bit column words; klt: the instantiation's bound (6 or 7). */
+int fb_plan_mirror_model(fb_plan_t p, int nb, int c16, int klt, int out[4]);
+
 /* Host restatement of the handle's internal node order (fembrain_amd/csrc/renumber.h: slab order of the rest positions): the caller id of
  * every internal id, and the widest element (largest id difference inside a tet) in the caller's and in that order */
 int fb_plan_slab_order(int n_nodes, const double* xyz, int n_tets, const int* tets, int* old_of_new, int* span_caller, int* span_internal);
