@@ -53,6 +53,9 @@ struct MeshDelta {
 // uploads the change (host arrays already validated), marks the elements, scans the new ids.  Does not synchronise.
 int delta_upload(hipStream_t s, int n_tets_old, int n_removed, const int* removed, int n_changed, const int* changed_ids, const int* changed_nodes, int n_added,
                  const int* added, int n_new_nodes, const double* new_xyz, MeshDelta& D, PlanWorkspace& W);
+// the same from device arrays (fb_fem_cut: valid by construction, no element changed in place)
+int delta_upload_device(hipStream_t s, int n_tets_old, int n_removed, const int* removed, int n_added, const int4* added, int n_new_nodes, const double* new_xyz,
+                        MeshDelta& D, PlanWorkspace& W);
 // changed_nodes / added: node ids through `map` (caller id -> internal id)
 int delta_relabel_nodes(hipStream_t s, MeshDelta& D, int n_nodes, const int* map);
 // the new element list: kept elements in their order (node ids through imap, nullptr = as they are), changed ones with their new nodes, added ones behind

@@ -546,6 +546,8 @@ __global__ __launch_bounds__(kB) void k_delta_new_pairs(int n_changed, int n_add
 
 }  // namespace
 
+static int delta_mark(hipStream_t s, int n_tets_old, MeshDelta& D, PlanWorkspace& W);
+
 int delta_upload(hipStream_t s, int n_tets_old, int n_removed, const int* removed, int n_changed, const int* changed_ids, const int* changed_nodes, int n_added,
                  const int* added, int n_new_nodes, const double* new_xyz, MeshDelta& D, PlanWorkspace& W) {
   D.n_tets_old = n_tets_old; D.n_removed = n_removed; D.n_changed = n_changed; D.n_added = n_added; D.n_new_nodes = n_new_nodes;
@@ -563,6 +565,29 @@ int delta_upload(hipStream_t s, int n_tets_old, int n_removed, const int* remove
   D.changed_nodes = reinterpret_cast<int4*>(D.ints.p + o_cn); D.added = reinterpret_cast<int4*>(D.ints.p + o_add);
   FB_TRY(D.new_xyz.reserve((size_t)std::max(1, 3 * n_new_nodes)));
   if (n_new_nodes) FB_HIP(hipMemcpyAsync(D.new_xyz.p, new_xyz, sizeof(double) * 3 * (size_t)n_new_nodes, hipMemcpyHostToDevice, s));
+  return delta_mark(s, n_tets_old, D, W);
+}
+
+int delta_upload_device(hipStream_t s, int n_tets_old, int n_removed, const int* removed, int n_added, const int4* added, int n_new_nodes, const double* new_xyz,
+                        MeshDelta& D, PlanWorkspace& W) {
+  D.n_tets_old = n_tets_old; D.n_removed = n_removed; D.n_changed = 0; D.n_added = n_added; D.n_new_nodes = n_new_nodes;
+  D.n_kept = n_tets_old - n_removed;
+  D.mapped = false;
+  const int o_chg = pad4(n_removed), o_add = o_chg, total = o_add + 4 * n_added + 4;
+  FB_TRY(D.ints.reserve((size_t)total));
+  FB_HIP(hipMemsetAsync(D.ints.p, 0, sizeof(int) * (size_t)total, s));
+  if (n_removed) FB_HIP(hipMemcpyAsync(D.ints.p, removed, sizeof(int) * (size_t)n_removed, hipMemcpyDeviceToDevice, s));
+  if (n_added) FB_HIP(hipMemcpyAsync(D.ints.p + o_add, added, sizeof(int4) * (size_t)n_added, hipMemcpyDeviceToDevice, s));
+  D.removed = D.ints.p; D.changed_ids = D.ints.p + o_chg;
+  D.changed_nodes = reinterpret_cast<int4*>(D.ints.p + o_add); D.added = reinterpret_cast<int4*>(D.ints.p + o_add);
+  FB_TRY(D.new_xyz.reserve((size_t)std::max(1, 3 * n_new_nodes)));
+  if (n_new_nodes) FB_HIP(hipMemcpyAsync(D.new_xyz.p, new_xyz, sizeof(double) * 3 * (size_t)n_new_nodes, hipMemcpyDeviceToDevice, s));
+  return delta_mark(s, n_tets_old, D, W);
+}
+
+// the element states and the new element ids of an uploaded change
+static int delta_mark(hipStream_t s, int n_tets_old, MeshDelta& D, PlanWorkspace& W) {
+  const int n_removed = D.n_removed, n_changed = D.n_changed;
   FB_TRY(D.estate.reserve((size_t)n_tets_old + 1));
   FB_HIP(hipMemsetAsync(D.estate.p, 0, (size_t)n_tets_old + 1, s));
   if (n_removed + n_changed) {

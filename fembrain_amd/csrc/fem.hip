@@ -15,6 +15,7 @@
 #include "plan_device.h"
 #include "renumber.h"
 #include "delta.h"
+#include "subdivide.h"
 
 using namespace fb;
 
@@ -50,6 +51,9 @@ struct fb_fem_s {
   DevBuf<int> halo_base;   // c16 == 2: lowest halo column of every slice
   PlanWorkspace plan_ws;  // the device plan builder's temporaries, kept for the next re-sync
   MeshDelta delta;        // fb_fem_resync_delta: the change on the device and its scratch
+  CutWork cut;            // fb_fem_cut: the last cut's codes, edges, pieces and new nodes (fb_fem_read_cut)
+  DevBuf<double> carry;   // fb_fem_cut, FB_CUT_CARRY: the state in the caller's order across the re-sync
+  std::vector<int> fixed_caller;  // the constrained DOFs in the caller's numbering (unsharded): what fb_fem_cut keeps
   DevBuf<int4> tets_next, tets_caller;   // (the element list being built; swapped with `tets`)
   DevBuf<double> x0_next;
   DevBuf<int> map_next_a, map_next_b;
@@ -1991,6 +1995,7 @@ int build(fb_fem_s* h, int n_nodes, const double* xyz, int n_tets, const int* te
           int rank, const int* splits, const DeviceTetMesh* dm = nullptr) {
   drop_graph(h);  // the buffers it refers to are about to be replaced
   SlackScope slack(handle_slack(h, n_nodes, n_tets));
+  if (n_ranks == 1 && fixed != h->fixed_caller.data()) h->fixed_caller.assign(fixed, fixed + n_fixed);
   if (h->prm.matrix_precision == FB_MATRIX_AUTO) h->f64 = auto_matrix_f64(h, n_nodes, n_ranks);
   h->last_resync_path = FB_RESYNC_FULL;
   h->csr_ready = false;
@@ -2617,8 +2622,9 @@ int resync_delta_rebuild(fb_fem_s* h, int n_old, int n_new, int n_fixed, const i
   return FB_OK;
 }
 
+// device_src: removed / added / new_xyz are device arrays (fb_fem_cut; no element changed in place)
 int resync_delta(fb_fem_s* h, int n_removed, const int* removed, int n_changed, const int* changed_ids, const int* changed_nodes, int n_added, const int* added,
-                 int n_new_nodes, const double* new_xyz, int n_fixed, const int* fixed) {
+                 int n_new_nodes, const double* new_xyz, int n_fixed, const int* fixed, bool device_src = false) {
   static const bool timing = getenv("FEMBRAIN_TIMING") != nullptr;
   const auto t0 = std::chrono::steady_clock::now();
   auto lap = [&](const char* what) {
@@ -2630,7 +2636,11 @@ int resync_delta(fb_fem_s* h, int n_removed, const int* removed, int n_changed, 
   const int n_old = h->plan.n_global, nt_old = h->plan.n_tets, n_new = n_old + n_new_nodes;
   SlackScope slack(handle_slack(h, n_new, nt_old - n_removed + n_added));
   drop_graph(h);
-  FB_TRY(delta_upload(s, nt_old, n_removed, removed, n_changed, changed_ids, changed_nodes, n_added, added, n_new_nodes, new_xyz, D, W));
+  if (fixed != h->fixed_caller.data()) h->fixed_caller.assign(fixed, fixed + n_fixed);
+  if (device_src)
+    FB_TRY(delta_upload_device(s, nt_old, n_removed, removed, n_added, reinterpret_cast<const int4*>(added), n_new_nodes, new_xyz, D, W));
+  else
+    FB_TRY(delta_upload(s, nt_old, n_removed, removed, n_changed, changed_ids, changed_nodes, n_added, added, n_new_nodes, new_xyz, D, W));
   const int nt_new = D.n_tets_new();
   lap("change uploaded");
   const char* env = getenv("FEMBRAIN_RESYNC_DELTA");
@@ -2787,6 +2797,140 @@ int fb_fem_resync_delta(fb_fem_t h, int n_removed, const int* removed, int n_cha
 }
 
 int fb_fem_resync_path(fb_fem_t h) { return h ? h->last_resync_path : FB_RESYNC_FULL; }
+
+// ---- fb_fem_cut (subdivide.h) ----
+int fb_fem_cut(fb_fem_t h, int n_strip_points, const double* strip_xyz, int mode, int modify, fb_cut_result* out) {
+  CHECK_HANDLE(h);
+  if (out) memset(out, 0, sizeof(*out));
+  if (h->plan.n_ranks > 1 || !h->device_plan) return fail(FB_EINVAL, "fb_fem_cut is for unsharded handles whose plan was built on the device");
+  if (mode != FB_CUT_BAKE && mode != FB_CUT_CARRY) return fail(FB_EINVAL, "cut mode %d: FB_CUT_BAKE or FB_CUT_CARRY", mode);
+  std::vector<double> quads;
+  FB_TRY(cut_quads(n_strip_points, strip_xyz, quads));
+  hipStream_t s = h->stream;
+  CutWork& C = h->cut;
+  C.valid = false;
+  C.mode = mode;
+  C.n_quads = (int)(quads.size() / 12);
+  C.n_cut = C.n_a = C.n_b = C.n_unhandled = C.n_edges = C.n_added = 0;
+  C.min_ratio = 0.0;
+  C.unhandled_ids.clear();
+  C.unhandled_codes.clear();
+  bool delta = false;
+  int status = FB_CUT_NOTHING;
+  const int n_old = h->plan.n_global, nt_old = h->plan.n_tets;
+  const int* caller_of = h->ren.active ? h->ren.d_old_of_new.p : nullptr;
+  const int* internal_of = h->ren.active ? h->ren.d_new_of_old.p : nullptr;
+  if (C.n_quads) {
+    FB_TRY(C.quads.alloc(quads.size()));
+    FB_HIP(hipMemcpyAsync(C.quads.p, quads.data(), sizeof(double) * quads.size(), hipMemcpyHostToDevice, s));
+    FB_TRY(cut_classify(s, C, nt_old, h->tets.p, caller_of, h->x0.p, h->q.p, h->plan_ws));
+    if (C.n_unhandled) {
+      status = FB_CUT_UNHANDLED;
+      FB_TRY(cut_read_unhandled(s, C, h->plan_ws));
+    } else if (C.n_cut) {
+      FB_TRY(cut_emit(s, C, n_old, h->tets.p, caller_of, internal_of, h->x0.p, h->q.p, h->plan_ws));
+      delta = true;
+      status = modify ? FB_CUT_DONE : FB_CUT_DRY;
+      if ((long long)n_old + 2LL * C.n_edges >= (1LL << 31) - 2 || (long long)nt_old - C.n_cut + C.n_added >= (1LL << 28)) return fail(FB_EINVAL, "mesh too large after the cut");
+      // a split point on a node (t = 0 or |edge|) would leave a flat piece, which the rest state refuses after the point of no return
+      if (modify && !(C.min_ratio > 0.0)) return fail(FB_EINVAL, "the cut would leave a piece without volume (smallest piece / parent volume %g)", C.min_ratio);
+    }
+  }
+  C.valid = true;
+  C.n_nodes = n_old;
+  if (out) {
+    out->status = status;
+    out->n_quads = C.n_quads;
+    out->n_case_a = C.n_a; out->n_case_b = C.n_b; out->n_unhandled = C.n_unhandled;
+    if (delta) {
+      out->n_cut_edges = C.n_edges;
+      out->n_removed = C.n_cut; out->n_added = C.n_added; out->n_new_nodes = 2 * C.n_edges;
+      out->min_volume_ratio = C.min_ratio;
+    }
+  }
+  if (status != FB_CUT_DONE) return FB_OK;
+  // ---- the point of no return ----
+  const int n_new = n_old + 2 * C.n_edges;
+  const bool newmark = h->prm.integrator == FB_INTEGRATOR_NEWMARK;
+  const int n_vec = newmark ? 3 : 2;
+  const size_t len = (size_t)3 * n_new;
+  h->poisoned = true;
+  h->system_valid = false;
+  if (mode == FB_CUT_CARRY) {  // the state in the caller's order, new nodes interpolated
+    FB_TRY(h->carry.reserve(len * n_vec));
+    const DevBuf<double>* src[3] = {&h->q, &h->qvel, &h->qacc};
+    for (int v = 0; v < n_vec; v++) {
+      double* dst = h->carry.p + len * v;
+      if (h->ren.active) FB_TRY(gather_nodes(s, n_old, 3, src[v]->p, h->ren.d_new_of_old.p, dst));
+      else FB_HIP(hipMemcpyAsync(dst, src[v]->p, sizeof(double) * 3 * (size_t)n_old, hipMemcpyDeviceToDevice, s));
+      FB_TRY(cut_interpolate(s, C, n_old, dst));
+    }
+  } else {
+    FB_TRY(cut_bake(s, 3LL * n_old, h->x0.p, h->q.p));  // the deformed shape is the new rest shape (Deformable.cpp:144-147)
+  }
+  const std::vector<int> fixed = h->fixed_caller;
+  FB_TRY(resync_delta(h, C.n_cut, C.cut_tets.p, 0, nullptr, nullptr, C.n_added, reinterpret_cast<const int*>(C.added.p), 2 * C.n_edges, C.new_xyz.p, (int)fixed.size(),
+                      fixed.data(), true));
+  if (mode == FB_CUT_CARRY) {
+    DevBuf<double>* dst[3] = {&h->q, &h->qvel, &h->qacc};
+    for (int v = 0; v < n_vec; v++) {
+      const double* src = h->carry.p + len * v;
+      if (h->ren.active) FB_TRY(gather_nodes(s, n_new, 3, src, h->ren.d_old_of_new.p, dst[v]->p));
+      else FB_HIP(hipMemcpyAsync(dst[v]->p, src, sizeof(double) * len, hipMemcpyDeviceToDevice, s));
+    }
+  }
+  FB_HIP(hipStreamSynchronize(s));
+  h->poisoned = false;
+  return FB_OK;
+}
+
+int fb_fem_read_cut(fb_fem_t h, int* removed, int* added_tets, double* new_xyz, int* edge_nodes, double* edge_frac, int* unhandled_ids, int* unhandled_codes) {
+  CHECK_HANDLE(h);
+  const CutWork& C = h->cut;
+  if (!C.valid) return fail(FB_EINVAL, "no fb_fem_cut has run on this handle");
+  hipStream_t s = h->stream;
+  const bool delta = C.n_cut > 0 && C.n_unhandled == 0;
+  if (delta) {
+    if (removed) FB_TRY(C.cut_tets.download(removed, (size_t)C.n_cut, s));
+    if (added_tets) FB_TRY(C.added.download(reinterpret_cast<int4*>(added_tets), (size_t)C.n_added, s));
+    if (new_xyz) FB_TRY(C.new_xyz.download(new_xyz, (size_t)6 * C.n_edges, s));
+    if (edge_nodes || edge_frac) {
+      std::vector<unsigned long long> keys((size_t)C.n_edges);
+      std::vector<double> frac((size_t)C.n_edges);
+      FB_TRY(C.ukeys.download(keys.data(), keys.size(), s));
+      FB_TRY(C.frac.download(frac.data(), frac.size(), s));
+      for (int k = 0; k < C.n_edges; k++)
+        for (int c = 0; c < 2; c++) {
+          if (edge_nodes) { edge_nodes[4 * k + 2 * c] = (int)(keys[k] >> 32); edge_nodes[4 * k + 2 * c + 1] = (int)(keys[k] & 0xffffffffu); }
+          if (edge_frac) edge_frac[2 * k + c] = frac[k];
+        }
+    }
+  }
+  for (size_t k = 0; k < C.unhandled_ids.size(); k++) {
+    if (unhandled_ids) unhandled_ids[k] = C.unhandled_ids[k];
+    if (unhandled_codes) unhandled_codes[k] = C.unhandled_codes[k];
+  }
+  return FB_OK;
+}
+
+int fb_fem_read_mesh(fb_fem_t h, double* rest_xyz, int* tets) {
+  CHECK_HANDLE(h);
+  if (h->plan.n_ranks > 1) return fail(FB_EINVAL, "fb_fem_read_mesh is for unsharded handles");
+  hipStream_t s = h->stream;
+  const int n = h->plan.n_global, nt = h->plan.n_tets;
+  if (rest_xyz) FB_TRY(download_owned(h, h->x0, rest_xyz));
+  if (tets) {
+    if (h->ren.active) {
+      FB_TRY(h->tets_caller.alloc((size_t)nt));
+      FB_HIP(hipMemcpyAsync(h->tets_caller.p, h->tets.p, sizeof(int4) * (size_t)nt, hipMemcpyDeviceToDevice, s));
+      FB_TRY(relabel_tets(s, nt, h->tets_caller.p, n, h->ren.d_old_of_new.p));
+      FB_TRY(h->tets_caller.download(reinterpret_cast<int4*>(tets), (size_t)nt, s));
+    } else {
+      FB_TRY(h->tets.download(reinterpret_cast<int4*>(tets), (size_t)nt, s));
+    }
+  }
+  return FB_OK;
+}
 
 int fb_fem_rebuild_elements(fb_fem_t h) {
   CHECK_HANDLE(h);
@@ -3022,6 +3166,7 @@ int fb_fem_set_constrained_dofs(fb_fem_t h, int n_fixed_dofs, const int* fixed_d
   if (h->device_plan && h->plan.n_ranks == 1) {
     FB_TRY(device_constraint_masks(h->stream, h->plan.n_global, n_fixed_dofs, fixed_dofs, h->ren.active ? h->ren.d_new_of_old.p : nullptr, h->fixed_stage, h->dofmask, h->nodemask));
     h->plan.n_fixed_owned = n_fixed_dofs;
+    h->fixed_caller.assign(fixed_dofs, fixed_dofs + n_fixed_dofs);
   } else if (!h->l2c.empty()) {  // a renumbered shard: the list in internal ids, ascending again
     const int r = 3 * h->plan.n_global;
     for (int i = 0; i < n_fixed_dofs; i++) {

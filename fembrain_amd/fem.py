@@ -179,6 +179,46 @@ class FemIntegrator:
         self.r = 3 * self.n_nodes
         self.node_lo, self.node_hi = 0, self.n_nodes
 
+    def cut(self, strip, mode="bake", modify=True, track=True):
+        """CuttableMesh::cut + Deformable::syncForceModel in one device call (fb_fem_cut): ``strip`` is the blade's swept quad strip
+        ((2m, 3) points, quad i = points 2i .. 2i+3).  mode "bake" (FemBrain: the deformed shape becomes the rest shape, state reset) or
+        "carry" (rest shape and state kept, new nodes interpolated).  Returns (info, delta): info a dict of the fb_cut_result fields,
+        delta the change in ``meshgen.apply_delta``'s terms (removed, changed_ids, changed_nodes, added, new_xyz) plus per new node
+        its cut edge (edge_nodes, lo and hi caller ids) and fraction (edge_frac), and the first unhandled element ids / codes.  The
+        delta is empty unless the status is FB_CUT_DONE or FB_CUT_DRY.  With track, ``self.verts`` / ``self.tets`` follow the cut."""
+        modes = {"bake": _l.FB_CUT_BAKE, "carry": _l.FB_CUT_CARRY}
+        if mode not in modes:
+            raise ValueError("mode is 'bake' or 'carry', not %r" % (mode,))
+        pts = np.ascontiguousarray(strip, dtype=np.float64).reshape(-1)
+        if pts.size % 3:
+            raise ValueError("strip points are xyz triples")
+        res = _l.CutResult()
+        _l.check(self._L.fb_fem_cut(self.h, pts.size // 3, _l.dptr(pts), modes[mode], 1 if modify else 0, C.byref(res)))
+        info = {name: getattr(res, name) for name, _ in _l.CutResult._fields_}
+        nr, na, nn = res.n_removed, res.n_added, res.n_new_nodes
+        nu = min(res.n_unhandled, _l.FB_CUT_UNHANDLED_IDS)
+        removed, added = np.zeros(nr, np.int32), np.zeros((na, 4), np.int32)
+        new_xyz, edge_nodes, edge_frac = np.zeros((nn, 3)), np.zeros((nn, 2), np.int32), np.zeros(nn)
+        uid, ucode = np.zeros(nu, np.int32), np.zeros(nu, np.int32)
+        _l.check(self._L.fb_fem_read_cut(self.h, _l.iptr(removed), _l.iptr(added), _l.dptr(new_xyz), _l.iptr(edge_nodes), _l.dptr(edge_frac),
+                                         _l.iptr(uid), _l.iptr(ucode)))
+        delta = dict(removed=removed, changed_ids=np.zeros(0, np.int32), changed_nodes=np.zeros((0, 4), np.int32), added=added, new_xyz=new_xyz,
+                     edge_nodes=edge_nodes, edge_frac=edge_frac, unhandled_ids=uid, unhandled_codes=ucode)
+        if res.status == _l.FB_CUT_DONE:
+            self.n_nodes = int(self._L.fb_fem_num_nodes(self.h))
+            self.r = 3 * self.n_nodes
+            self.node_lo, self.node_hi = 0, self.n_nodes
+            if track:
+                self.verts, self.tets = self.read_mesh()
+        return info, delta
+
+    def read_mesh(self):
+        """(rest positions (n, 3), elements (m, 4)) as the device holds them, in the caller's numbering (fb_fem_read_mesh)"""
+        n, m = int(self._L.fb_fem_num_nodes(self.h)), int(self._L.fb_fem_num_tets(self.h))
+        xyz, tets = np.zeros((n, 3)), np.zeros((m, 4), np.int32)
+        _l.check(self._L.fb_fem_read_mesh(self.h, _l.dptr(xyz), _l.iptr(tets)))
+        return xyz, tets
+
     def resync_path(self):
         """FB_RESYNC_* of the handle's last (re-)build"""
         return int(self._L.fb_fem_resync_path(self.h))

@@ -20,6 +20,9 @@ FB_SPMV_AUTO, FB_SPMV_ROWS, FB_SPMV_SPLIT = 0, 1, 2
 FB_INTEGRATOR_VOLUME_CONSERVING, FB_INTEGRATOR_NEWMARK = 0, 1
 FB_RENUMBER_AUTO, FB_RENUMBER_ON, FB_RENUMBER_OFF = 0, 1, -1
 FB_RESYNC_FULL, FB_RESYNC_DELTA_MERGED, FB_RESYNC_DELTA_REBUILT = 0, 1, 2
+FB_CUT_BAKE, FB_CUT_CARRY = 0, 1
+FB_CUT_NOTHING, FB_CUT_DONE, FB_CUT_UNHANDLED, FB_CUT_DRY = 0, 1, 2, 3
+FB_CUT_UNHANDLED_IDS = 64  # unhandled element ids fb_fem_read_cut returns at most (subdivide.h kCutUnhandledIds)
 
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
@@ -46,6 +49,11 @@ class StepInfo(C.Structure):
     _fields_ = [("cg_iterations", C.c_int), ("converged", C.c_int), ("assembly_seconds", C.c_double),
                 ("solve_seconds", C.c_double), ("rho0", C.c_double), ("rho", C.c_double), ("pcg_path", C.c_int),
                 ("persist_fallbacks", C.c_int), ("newton_iterations", C.c_int)]
+
+
+class CutResult(C.Structure):
+    _fields_ = [("status", C.c_int), ("n_quads", C.c_int), ("n_cut_edges", C.c_int), ("n_case_a", C.c_int), ("n_case_b", C.c_int),
+                ("n_unhandled", C.c_int), ("n_removed", C.c_int), ("n_added", C.c_int), ("n_new_nodes", C.c_int), ("min_volume_ratio", C.c_double)]
 
 
 class PolyCounts(C.Structure):
@@ -110,6 +118,9 @@ def lib():
         "fb_fem_resync_sharded": (C.c_int, [vp, C.c_int, _dp, C.c_int, _ip, C.c_int, _ip, _ip]),
         "fb_fem_resync_delta": (C.c_int, [vp, C.c_int, _ip, C.c_int, _ip, _ip, C.c_int, _ip, C.c_int, _dp, C.c_int, _ip]),
         "fb_fem_resync_path": (C.c_int, [vp]),
+        "fb_fem_cut": (C.c_int, [vp, C.c_int, _dp, C.c_int, C.c_int, C.POINTER(CutResult)]),
+        "fb_fem_read_cut": (C.c_int, [vp, _ip, _ip, _dp, _ip, _dp, _ip, _ip]),
+        "fb_fem_read_mesh": (C.c_int, [vp, _dp, _ip]),
         "fb_fem_rebuild_elements": (C.c_int, [vp]),
         "fb_fem_set_external_forces": (C.c_int, [vp, _dp]),
         "fb_fem_add_external_forces": (C.c_int, [vp, _dp]),

@@ -16,6 +16,15 @@
 
 #include "../fembrain_hip.h"
 
+// CuttableMesh::cut return codes (src/deformable/CuttableMesh.h:24-28)
+#ifndef CUT_ERR_INVALID_INPUT_ARG
+#define CUT_ERR_INVALID_INPUT_ARG -1
+#define CUT_ERR_NO_INTERSECTION -2
+#define CUT_ERR_UNHANDLED_CUT_STATE -3
+#define CUT_ERR_UNABLE_TO_CUT_EDGE -4
+#define CUT_ERR_USER_CANCELLED_CUT -5
+#endif
+
 namespace PS {
 namespace FEM {
 
@@ -136,6 +145,18 @@ class HipIntegrator {
     mass_.clear(); bptr_.clear(); bcol_.clear();
     check(fb_fem_resync_delta(h_, nRemoved, removed, nChanged, changedIds, changedNodes, nAdded, added, nNewVertices, newRest, nFixed, fixed));
     r_ = 3 * fb_fem_num_nodes(h_);
+  }
+  // fb_fem_cut: the blade's swept quad strip (nPoints xyz) cuts the mesh on the device and the handle re-syncs; `out` says what happened
+  void Cut(int nPoints, const double* strip, int mode, bool modify, fb_cut_result* out) {
+    check(fb_fem_cut(h_, nPoints, strip, mode, modify ? 1 : 0, out));
+    if (out->status == FB_CUT_DONE) { mass_.clear(); bptr_.clear(); bcol_.clear(); }
+    r_ = 3 * fb_fem_num_nodes(h_);
+  }
+  // the device-resident mesh in the caller's numbering
+  void ReadMesh(std::vector<double>& rest, std::vector<int>& elements) {
+    rest.resize(3 * (size_t)fb_fem_num_nodes(h_));
+    elements.resize(4 * (size_t)fb_fem_num_tets(h_));
+    check(fb_fem_read_mesh(h_, rest.data(), elements.data()));
   }
   fb_fem_t handle() const { return h_; }
   static void check(int rc) {
@@ -301,6 +322,30 @@ class Deformable {
     m_bptr.clear(); m_bcol.clear();
     m_restVolume = -1.0;
     return true;
+  }
+  // CuttableMesh::cut(segments, quadstrips, modifyMesh) (CuttableMesh.cpp:283-505) + cutCompleted's syncForceModel (main.cpp:614-617) in
+  // one device call (fb_fem_cut, FB_CUT_BAKE: the deformed shape becomes the rest shape).  Returns the number of subdivided cells, 0 when
+  // nothing was cut, or CUT_ERR_INVALID_INPUT_ARG / CUT_ERR_UNHANDLED_CUT_STATE / CUT_ERR_USER_CANCELLED_CUT as the reference does.
+  // segments: the blade's path, used by the reference's cut-node detection only, which FemBrain leaves off -- accepted and ignored.
+  // The host copy of the mesh is read back after the device call has returned (the rule syncForceModelDelta keeps).
+  int cut(const std::vector<vec3d>& segments, const std::vector<vec3d>& quadstrips, bool modifyMesh) {
+    if (segments.size() < 2) return CUT_ERR_INVALID_INPUT_ARG;
+    if (quadstrips.size() < 4 || quadstrips.size() % 2 != 0) return CUT_ERR_INVALID_INPUT_ARG;
+    if (!m_lpIntegrator) syncForceModel();
+    std::vector<double> strip;
+    strip.reserve(3 * quadstrips.size());
+    for (size_t i = 0; i < quadstrips.size(); i++) { strip.push_back(quadstrips[i].x); strip.push_back(quadstrips[i].y); strip.push_back(quadstrips[i].z); }
+    fb_cut_result r;
+    m_lpIntegrator->Cut((int)quadstrips.size(), strip.data(), FB_CUT_BAKE, modifyMesh, &r);
+    if (r.status == FB_CUT_NOTHING) return 0;
+    if (r.status == FB_CUT_UNHANDLED) return CUT_ERR_UNHANDLED_CUT_STATE;
+    if (r.status == FB_CUT_DRY) return CUT_ERR_USER_CANCELLED_CUT;
+    m_lpIntegrator->ReadMesh(m_rest, m_elements);
+    m_dof = (U32)m_rest.size();
+    m_q.assign(m_dof, 0.0); m_qVel.assign(m_dof, 0.0); m_arrExtForces.assign(m_dof, 0.0);
+    m_bptr.clear(); m_bcol.clear();
+    m_restVolume = -1.0;
+    return r.n_removed;
   }
   void setMesh(int numVertices, const double* rest, int numElements, const int* elements) {
     m_rest.assign(rest, rest + 3 * (size_t)numVertices);
@@ -470,6 +515,7 @@ class Deformable {
   U32 countNodes() const { return (U32)(m_rest.size() / 3); }
   U32 countCells() const { return (U32)(m_elements.size() / 4); }
   const std::vector<int>& cells() const { return m_elements; }
+  HipIntegrator* getIntegrator() const { return m_lpIntegrator; }
   std::vector<double> currentPositions() {
     if (m_lpIntegrator) m_lpIntegrator->GetqState(m_q.data(), nullptr, nullptr);
     std::vector<double> p(m_rest);

@@ -214,6 +214,46 @@ int fb_fem_resync_delta(fb_fem_t h, int n_removed, const int* removed, int n_cha
                         int n_added, const int* added_tets, int n_new_nodes, const double* new_xyz, int n_fixed_dofs, const int* fixed_dofs);
 int fb_fem_resync_path(fb_fem_t h);
 
+/* The cut itself: CuttableMesh::cut(segments, quadstrips, modifyMesh) (CuttableMesh.cpp:283-505) + cutCompleted's
+ * Deformable::syncForceModel (main.cpp:614-617) in one call, on the device (fembrain_amd/csrc/subdivide.h).  strip_xyz: the blade's
+ * swept quad strip, n_strip_points >= 4 and even, quad i = points 2i .. 2i+3 (degenerate quads skipped, CuttableMesh.cpp:154-164).
+ * Every mesh edge an odd number of quads cross (fp64 IntersectSegmentTriangle against the current positions rest + q) is split in two
+ * coincident nodes; every element on a cut edge is subdivided (case A: 4 pieces, case B: 6).  Any other cut pattern refuses the whole
+ * cut and changes nothing (FB_CUT_UNHANDLED, CUT_ERR_UNHANDLED_CUT_STATE), as does modify == 0 (FB_CUT_DRY, CUT_ERR_USER_CANCELLED_CUT)
+ * and a strip that cuts nothing (FB_CUT_NOTHING).  Otherwise the change -- cut elements removed keeping the order of the rest, pieces
+ * and new nodes appended: fb_fem_resync_delta's contract, fed from device memory -- is applied (FB_CUT_DONE).  Where this differs from
+ * the reference (edge orientation lo -> hi, node ids, prism diagonals): DESIGN.md section 7.
+ *   FB_CUT_BAKE   (FemBrain: syncForceModel rebuilds from the deformed positions) the rest shape becomes x0 + q, new nodes at the split
+ *                 point, state reset
+ *   FB_CUT_CARRY  the rest shape is kept, a new node's rest position is at the edge fraction f = t / |current edge| of its rest edge; q,
+ *                 qvel, qaccel of old nodes carried over, new nodes interpolated at f
+ * Constrained DOFs stay the handle's own (new nodes are free).  Unsharded handles with a device-built plan only (FB_EINVAL otherwise);
+ * a failure after the change began leaves the handle unusable until a full fb_fem_resync, as fb_fem_resync_delta does. */
+#define FB_CUT_BAKE 0
+#define FB_CUT_CARRY 1
+#define FB_CUT_NOTHING 0    /* no edge cut: nothing changed */
+#define FB_CUT_DONE 1       /* the mesh was cut and the handle re-synced */
+#define FB_CUT_UNHANDLED 2  /* a cut element is neither case A nor case B: nothing changed */
+#define FB_CUT_DRY 3        /* modify == 0: the cut was worked out (fb_fem_read_cut) but nothing changed */
+typedef struct fb_cut_result {
+  int status;             /* FB_CUT_* */
+  int n_quads;            /* usable quads of the strip */
+  int n_cut_edges;        /* unique cut edges (0 unless status is DONE or DRY) */
+  int n_case_a, n_case_b; /* cut elements of case A / B */
+  int n_unhandled;        /* cut elements of neither case */
+  int n_removed, n_added, n_new_nodes;  /* the delta (0 unless DONE or DRY) */
+  double min_volume_ratio;  /* smallest piece volume / parent volume in the new rest shape (0 unless DONE or DRY) */
+} fb_cut_result;
+int fb_fem_cut(fb_fem_t h, int n_strip_points, const double* strip_xyz, int mode, int modify, fb_cut_result* out);
+/* The last fb_fem_cut's change in fb_fem_resync_delta's form (also after a dry run): removed[n_removed], added_tets[4 n_added],
+ * new_xyz[3 n_new_nodes] (rest positions); per new node the cut edge it lies on (edge_nodes[2 n_new_nodes]: lo, hi caller ids) and
+ * its fraction from lo (edge_frac[n_new_nodes]); the first min(n_unhandled, 64) unhandled element ids (ascending) and their 6-bit edge
+ * codes (bit e: local edge (0,1) (0,2) (0,3) (1,2) (1,3) (2,3)).  Any pointer may be NULL.  FB_EINVAL when no cut has run. */
+int fb_fem_read_cut(fb_fem_t h, int* removed, int* added_tets, double* new_xyz, int* edge_nodes, double* edge_frac, int* unhandled_ids, int* unhandled_codes);
+/* The device-resident mesh in the caller's numbering: rest_xyz[3 fb_fem_num_nodes], tets[4 fb_fem_num_tets] (either may be NULL).
+ * Unsharded handles only. */
+int fb_fem_read_mesh(fb_fem_t h, double* rest_xyz, int* tets);
+
 
 /* Per-element rest-state rebuild on the device (M^-1 rows / volume, corotationalLinearFEM.cpp:66-90 and
  * tetMesh.cpp:184-188) -- the per-step "K0 rebuild" of BASELINE config 4. */
