@@ -2223,8 +2223,10 @@ int create_common(fb_fem_t* out, int n_nodes, const double* xyz, int n_tets, con
   if (dm && dm->device != params->device) return fail(FB_EINVAL, "the polygonizer lives on device %d, the FEM handle is asked for device %d", dm->device, params->device);
   if (n_fixed < 0 || (n_fixed > 0 && !fixed)) return fail(FB_EINVAL, "bad constrained DOF list");
   if (params->integrator != FB_INTEGRATOR_VOLUME_CONSERVING && params->integrator != FB_INTEGRATOR_NEWMARK) return fail(FB_EINVAL, "unknown integrator %d", params->integrator);
-  if (!(params->timestep > 0) || !(params->E > 0) || !(params->rho > 0) || !(params->nu > -1.0 && params->nu < 0.5))
-    return fail(FB_EINVAL, "bad material / timestep parameters");
+  if (!(params->timestep > 0) || !(params->E > 0) || !(params->rho > 0) || !(params->nu > -1.0 && params->nu < 0.5) ||
+      !std::isfinite(params->timestep) || !std::isfinite(params->E) || !std::isfinite(params->rho) ||
+      !std::isfinite(params->damping_mass) || !std::isfinite(params->damping_stiffness))
+    return fail(FB_EINVAL, "bad material / timestep / damping parameters");
   if (params->pcg_variant != FB_PCG_MERGED && params->pcg_variant != FB_PCG_REFERENCE && params->pcg_variant != FB_PCG_PERSISTENT &&
       params->pcg_variant != FB_PCG_BLOCK_JACOBI)
     return fail(FB_EINVAL, "unknown pcg_variant %d", params->pcg_variant);
@@ -3128,7 +3130,7 @@ int fb_fem_reset(fb_fem_t h) {
 
 int fb_fem_set_timestep(fb_fem_t h, double timestep) {
   CHECK_HANDLE(h);
-  if (!(timestep > 0)) return fail(FB_EINVAL, "timestep must be positive");
+  if (!(timestep > 0) || !std::isfinite(timestep)) return fail(FB_EINVAL, "timestep must be positive and finite");
   h->prm.timestep = timestep;
   h->system_valid = false;
   return FB_OK;
@@ -3136,6 +3138,8 @@ int fb_fem_set_timestep(fb_fem_t h, double timestep) {
 
 int fb_fem_set_damping(fb_fem_t h, double damping_mass, double damping_stiffness) {
   CHECK_HANDLE(h);
+  // (finite negative coefficients stay accepted, as the reference accepts them; a NaN or an infinity would poison s_m / s_k)
+  if (!std::isfinite(damping_mass) || !std::isfinite(damping_stiffness)) return fail(FB_EINVAL, "damping coefficients must be finite");
   h->prm.damping_mass = damping_mass; h->prm.damping_stiffness = damping_stiffness;
   h->system_valid = false;
   return FB_OK;

@@ -19,6 +19,10 @@ at test time.
                   56^3 / 58^3 truth cubes (998,250 / 1,111,158 tets): iteration count, norms, q and qvel at 2,000 seeded DOFs
   fem_{tumor,dumbel,dumbelclose,eggshell,implicit_sphere}.npz   (round 3, `python make_fem_golden.py round3`) the remaining tet meshes the
                   reference ships as polygonizer output: mesh, q after 2 steps under the reference load and under -10, iteration counts
+  fem_cube5_params.npz   (`python make_fem_golden.py params`) the 5^3 cube at four parameter sets of tests/fem_params.py (soft_damped,
+                  near_incomp, auxetic, tiny_step): Keff applied to a seeded vector w and its diagonal, rhs from the live state of
+                  fem_params.live_state, iteration counts and q / qvel after three steps under fem_params.load; and the Newmark step with
+                  (beta, gamma) = (0.4, 0.6) at soft_damped: (Newton, PCG) counts and q / qvel / qaccel after three steps
   fem_beam3.npz   data/models/beam3/beam3_tet.veg (208 nodes / 450 tets, Vega's own sample) with beam3.bou clamps:
                   mesh, the reference's consistent mass matrix file beam3_tet.mass (a known answer shipped by the
                   reference), and q after 3 steps with -10 per y-DOF
@@ -223,6 +227,43 @@ def shipped_tet_mesh(name, rel):
     print("%s:" % name, v.shape, t.shape, "fixed", len(fixed_vertices), "iters", ia_, ib_, "|q|", np.abs(qa[-1]).max(), np.abs(qb[-1]).max())
 
 
+def cube5_params():
+    sys.path.insert(0, os.path.join(HERE, ".."))
+    import scipy.sparse as sp
+    import fem_params as fp
+    n = 5
+    v, t = truth_cube(n, n, n, 0.1)
+    fixed = fixed_vertices_to_dofs(cube_fixed_plane_i0(n, n))
+    names = ["soft_damped", "near_incomp", "auxetic", "tiny_step"]
+    w = np.random.default_rng(13).normal(size=3 * len(v))
+    w[fixed] = 0
+    out = dict(n=n, names=np.array(names), w=w)
+    for name in names:
+        r = RefFem(v, t, **fp.material(name))
+        r.integrator(fixed, **fp.integrator(name))
+        r.set_state(*fp.live_state(r.r, fixed))
+        r.set_external_forces(fp.load(name, r.r))
+        _, keff, rhs, _ = r.step(want=True)
+        ia, ja = r.csr()
+        A = sp.csr_matrix((keff, ja, ia), shape=(r.r, r.r))
+        out[name + "_keff_w"], out[name + "_keff_diag"], out[name + "_rhs"] = A @ w, A.diagonal(), rhs
+        r.set_state(np.zeros(r.r), np.zeros(r.r))
+        out[name + "_its"] = np.array([r.step() for _ in range(3)])
+        out[name + "_q3"], out[name + "_v3"] = r.get_state()
+        print("cube5 %s: iterations" % name, out[name + "_its"])
+    r = RefFem(v, t, **fp.material("soft_damped"))
+    r.integrator(fixed, **fp.integrator("soft_damped"))
+    its = []
+    for _ in range(3):
+        r.set_external_forces(fp.load("soft_damped", r.r))
+        its.append(r.newmark_step(0.4, 0.6, max_newton=1))
+    out["newmark_pair"], out["newmark_its"] = np.array([0.4, 0.6]), np.array(its)
+    out["newmark_q3"], out["newmark_v3"] = r.get_state()
+    out["newmark_a3"] = r.get_accel()
+    print("cube5 soft_damped newmark (0.4, 0.6): (newton, pcg)", its)
+    np.savez_compressed(os.path.join(HERE, "fem_cube5_params.npz"), **out)
+
+
 def cube_big(n):
     """Round 3: the FIRST step from rest of the n^3-node truth cube under the reference load (plane i = 0 clamped, -10000 per y-DOF,
     CG eps 1e-6) by the reference build -- 56^3 = BASELINE config 4 (998,250 tets), 58^3 = the largest cube of 12 slices per CU:
@@ -262,6 +303,8 @@ if __name__ == "__main__":
         shipped_meshes()
     elif len(sys.argv) > 1 and sys.argv[1] == "peanut":
         peanut()
+    elif len(sys.argv) > 1 and sys.argv[1] == "params":
+        cube5_params()   # added later: leaves the other files as they are
     else:
         cube5()
         cube5_linear()

@@ -508,3 +508,24 @@ def test_unstructured_mesh_generator_gives_positive_elements_and_uneven_valences
     assert val.max() >= 2 * np.median(val)
     v2, t2, f2 = delaunay_jittered(10)
     assert np.array_equal(v, v2) and np.array_equal(t, t2) and np.array_equal(f, f2)
+
+
+@pytest.mark.parametrize("field,bad", [("E", 0.0), ("E", -1e7), ("E", float("nan")), ("E", float("inf")),
+                                       ("nu", -1.0), ("nu", 0.5), ("nu", 0.7), ("nu", float("nan")),
+                                       ("rho", 0.0), ("rho", -1000.0), ("rho", float("nan")), ("rho", float("inf")),
+                                       ("timestep", 0.0), ("timestep", -0.01), ("timestep", float("nan")), ("timestep", float("inf")),
+                                       ("damping_mass", float("nan")), ("damping_mass", float("inf")),
+                                       ("damping_stiffness", float("nan")), ("damping_stiffness", -float("inf"))])
+def test_fem_create_refuses_bad_parameters_before_the_device(field, bad):
+    """fb_fem_create checks the material, the time step and the damping before it looks for a device: E, rho, h > 0 and finite, nu in
+    (-1, 0.5), c_M and c_K finite (finite negative damping is accepted, as the reference accepts it).  A NaN fails every one of these
+    tests; FB_EINVAL on a machine with or without a GPU, and no handle."""
+    L = fl.lib()
+    v, t = truth_cube(3, 3, 3)
+    p = fl.FemParams()
+    L.fb_fem_default_params(C.byref(p))
+    setattr(p, field, bad)
+    h = C.c_void_p()
+    tt = np.ascontiguousarray(t, np.int32).reshape(-1)
+    rc = L.fb_fem_create(C.byref(h), len(v), fl.dptr(np.ascontiguousarray(v, np.float64)), len(t), fl.iptr(tt), 0, None, C.byref(p))
+    assert rc == fl.FB_EINVAL and not h.value, (field, bad, rc)

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+import fem_params as fp
 from fembrain_amd.meshgen import cube_fixed_plane_i0, fixed_vertices_to_dofs, truth_cube
 from oracle import pyoracle
 from oracle.pyoracle import OrcFem
@@ -242,3 +243,114 @@ def test_peanut_veg_steps_against_reference_build():
             q, _ = o.get_state()
             assert abs(it - int(g["it_" + key][k])) <= max(3, 0.02 * int(g["it_" + key][k]))
             assert np.abs(q - g["q_" + key][k]).max() <= 5e-6 * np.abs(g["q_" + key][k]).max()
+
+
+# --- away from the default parameters (tests/fem_params.py) ------------------------------------------------------------------------------
+
+def _param_mesh(mesh):
+    if mesh == "cube5":
+        v, t = truth_cube(5, 5, 5, 0.1)
+        return v, t, fixed_vertices_to_dofs(cube_fixed_plane_i0(5, 5))
+    g = np.load(os.path.join(GOLD, "fem_beam3.npz"))
+    return g["verts"], g["tets"], fixed_vertices_to_dofs(g["fixed_vertices"])
+
+
+def _rel(a, b):
+    return np.abs(np.asarray(a) - np.asarray(b)).max() / np.abs(np.asarray(b)).max()
+
+
+@pytest.mark.skipif(not pyoracle.have_ref(), reason="oracle/_ref (reference build) not present")
+@pytest.mark.parametrize("mesh", ["cube5", "beam3"])
+@pytest.mark.parametrize("name", fp.NAMES)
+def test_oracle_matches_the_reference_build_at_every_parameter_set(mesh, name):
+    """OrcFem against RefFem (the reference's own CorotationalLinearFEM, GenerateMassMatrix, SparseMatrix, CGSolver) at each set of
+    tests/fem_params.py: f and K at a seeded displacement, the mass on the pattern (rho), Keff and rhs of a backward-Euler step from a
+    live state (h, c_M, c_K, lambda < 0 or >> mu), and q, qdot after three steps.  Same arithmetic in both up to summation order: 1e-12
+    on the matrices; both solves stop at the reference's 1e-6 residual, iteration counts within max(2, 5 %) (the long solves of near_incomp
+    and of beam3 part on summation order alone: 386 against 400 at stiff_long on beam3)."""
+    from oracle.pyoracle import RefFem
+    v, t, fixed = _param_mesh(mesh)
+    o, r = OrcFem(v, t, **fp.material(name)), RefFem(v, t, **fp.material(name))
+    ia, ja = o.csr()
+    ria, rja = r.csr()
+    assert np.array_equal(ia, ria) and np.array_equal(ja, rja)
+    u = np.random.default_rng(11).normal(size=o.r) * 0.003
+    (fo, Ko), (fr, Kr) = o.assemble(u), r.assemble(u)
+    assert _rel(fo, fr) <= 1e-12 and _rel(Ko, Kr) <= 1e-12
+    M = sp.csr_matrix((o.mass_on_pattern(), ja, ia), shape=(o.r, o.r))
+    mia, mja, ma = r.mass_csr()
+    Mr = sp.csr_matrix((ma, mja, mia), shape=(o.r, o.r))
+    assert abs(M - Mr).max() <= 1e-15 * abs(Mr).max()
+    for x in (o, r):
+        x.integrator(fixed, **fp.integrator(name))
+        x.set_state(*fp.live_state(x.r, fixed))
+        x.set_external_forces(fp.load(name, x.r))
+    (io, ko, bo, _), (ir, kr, br, _) = o.step(want=True), r.step(want=True)
+    assert _rel(ko, kr) <= 1e-12 and _rel(bo, br) <= 1e-12 and abs(io - ir) <= max(2, 0.05 * abs(ir)), (io, ir)
+    for x in (o, r):
+        x.set_state(np.zeros(x.r), np.zeros(x.r))
+    for k in range(3):
+        io, ir = o.step(), r.step()
+        assert abs(io - ir) <= max(2, 0.05 * abs(ir)), (k, io, ir)
+        (qo, vo), (qr, vr) = o.get_state(), r.get_state()
+        assert _rel(qo, qr) <= 2e-6 and _rel(vo, vr) <= 2e-5, (k, _rel(qo, qr), _rel(vo, vr))
+
+
+@pytest.mark.skipif(not pyoracle.have_ref(), reason="oracle/_ref (reference build) not present")
+@pytest.mark.parametrize("mesh", ["cube5", "beam3"])
+@pytest.mark.parametrize("name", fp.NAMES)
+def test_oracle_newmark_matches_the_reference_build_off_the_control_pair(mesh, name):
+    """ImplicitNewmarkSparse::DoTimestep, oracle against the reference build, for every (beta, gamma) of tests/fem_params.py -- the two
+    with gamma != 2 beta make a6 = (1 - gamma / 2 beta) h, a3 and a5 live -- with 1 and 3 Newton iterations: q, qdot, qddot after three
+    steps, the same Newton counts and PCG totals within max(2 per solve, 5 %) (two solves that both stop at 1e-6, as in
+    test_newmark_step_against_reference_golden)"""
+    from oracle.pyoracle import RefFem
+    v, t, fixed = _param_mesh(mesh)
+    for beta, gamma in fp.NEWMARK:
+        for mx in (1, 3):
+            o, r = OrcFem(v, t, **fp.material(name)), RefFem(v, t, **fp.material(name))
+            for x in (o, r):
+                x.integrator(fixed, **fp.integrator(name))
+            f = fp.load(name, o.r)
+            for k in range(3):
+                for x in (o, r):
+                    x.set_external_forces(f)
+                (no, po), (nr, pr) = o.newmark_step(beta, gamma, max_newton=mx), r.newmark_step(beta, gamma, max_newton=mx)
+                assert no == nr and abs(po - pr) <= max(2 * mx, 0.05 * pr), (beta, gamma, mx, k, po, pr)
+                (qo, vo), (qr, vr) = o.get_state(), r.get_state()
+                for a, b, tol in ((qo, qr, 5e-6), (vo, vr, 5e-5), (o.get_accel(), r.get_accel(), 5e-5)):
+                    assert _rel(a, b) <= tol, (beta, gamma, mx, k, _rel(a, b))
+
+
+def test_parameter_golden_is_the_oracle_at_those_parameters():
+    """tests/golden/fem_cube5_params.npz (make_fem_golden.py params: the reference build's vectors at four sets of tests/fem_params.py)
+    through the oracle: Keff applied to a seeded vector, its diagonal, rhs from a live state, q / qdot after three steps; the Newmark
+    step with (beta, gamma) = (0.4, 0.6) at soft_damped; the step tolerances of the live comparisons above.  The same file pins the
+    device in tests/test_fem_params_gpu.py."""
+    g = np.load(os.path.join(GOLD, "fem_cube5_params.npz"))
+    v, t, fixed = _param_mesh("cube5")
+    ia, ja = OrcFem(v, t).csr()
+    for name in [str(s) for s in g["names"]]:
+        o = OrcFem(v, t, **fp.material(name))
+        o.integrator(fixed, **fp.integrator(name))
+        o.set_state(*fp.live_state(o.r, fixed))
+        o.set_external_forces(fp.load(name, o.r))
+        _, keff, rhs, _ = o.step(want=True)
+        A = sp.csr_matrix((keff, ja, ia), shape=(o.r, o.r))
+        assert _rel(A @ g["w"], g[name + "_keff_w"]) <= 1e-12 and _rel(A.diagonal(), g[name + "_keff_diag"]) <= 1e-12
+        assert _rel(rhs, g[name + "_rhs"]) <= 1e-12
+        o.set_state(np.zeros(o.r), np.zeros(o.r))
+        for k in range(3):
+            it = o.step()
+            assert abs(it - int(g[name + "_its"][k])) <= max(2, 0.05 * it), (name, k, it)
+        q, qv = o.get_state()
+        assert _rel(q, g[name + "_q3"]) <= 2e-6 and _rel(qv, g[name + "_v3"]) <= 2e-5, name
+    beta, gamma = g["newmark_pair"]
+    o = OrcFem(v, t, **fp.material("soft_damped"))
+    o.integrator(fixed, **fp.integrator("soft_damped"))
+    for k in range(3):
+        o.set_external_forces(fp.load("soft_damped", o.r))
+        newton, pcg = o.newmark_step(beta, gamma, max_newton=1)
+        assert newton == g["newmark_its"][k][0] and abs(pcg - g["newmark_its"][k][1]) <= 2, (k, pcg)
+    q, qv = o.get_state()
+    assert _rel(q, g["newmark_q3"]) <= 5e-6 and _rel(qv, g["newmark_v3"]) <= 5e-5 and _rel(o.get_accel(), g["newmark_a3"]) <= 5e-5
