@@ -1,5 +1,6 @@
 // C-ABI of the FEM hot path (include/fembrain_hip.h): handle life cycle, the per-step driver and the
 // inspection entry points.  Kernels live in fem_device.hip.h, the host-side plan in fem_plan.cpp.
+#include <cfloat>
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -2815,6 +2816,7 @@ int fb_fem_cut(fb_fem_t h, int n_strip_points, const double* strip_xyz, int mode
   C.n_quads = (int)(quads.size() / 12);
   C.n_cut = C.n_a = C.n_b = C.n_unhandled = C.n_edges = C.n_added = 0;
   C.min_ratio = 0.0;
+  C.min_volume = 0.0;
   C.unhandled_ids.clear();
   C.unhandled_codes.clear();
   bool delta = false;
@@ -2836,6 +2838,13 @@ int fb_fem_cut(fb_fem_t h, int n_strip_points, const double* strip_xyz, int mode
       if ((long long)n_old + 2LL * C.n_edges >= (1LL << 31) - 2 || (long long)nt_old - C.n_cut + C.n_added >= (1LL << 28)) return fail(FB_EINVAL, "mesh too large after the cut");
       // a split point on a node (t = 0 or |edge|) would leave a flat piece, which the rest state refuses after the point of no return
       if (modify && !(C.min_ratio > 0.0)) return fail(FB_EINVAL, "the cut would leave a piece without volume (smallest piece / parent volume %g)", C.min_ratio);
+      // ... and so would a piece the records cannot hold: every handle keeps the rest volumes as floats (volf, and the element records of fp32
+      // storage, which FB_MATRIX_AUTO may choose at any later re-sync).  Below FLT_MIN a float loses bits and from 1.4e-45 down it is zero: the
+      // piece then weighs and resists nothing, and a node that lies in such pieces only gets an empty row.  k_tet_rest itself is fp64 and would
+      // accept the piece (its determinant is not zero), so this is checked here, before anything changes.
+      if (modify && !((float)C.min_volume >= FLT_MIN))
+        return fail(FB_EINVAL, "the cut would leave a piece of volume %g, which the fp32 element records cannot hold (below %g; smallest piece / parent volume %g)",
+                    C.min_volume, (double)FLT_MIN, C.min_ratio);
     }
   }
   C.valid = true;

@@ -31,6 +31,7 @@ struct CutWork {
   int n_tets = 0, n_nodes = 0, mode = FB_CUT_BAKE, n_quads = 0;
   int n_cut = 0, n_a = 0, n_b = 0, n_unhandled = 0, n_edges = 0, n_added = 0;
   double min_ratio = 0.0;
+  double min_volume = 0.0;                  // smallest piece volume in the new rest shape
   bool valid = false;                       // the read-back describes the last fb_fem_cut of the handle
   std::vector<int> unhandled_ids, unhandled_codes;
   DevBuf<double> quads;                     // usable quads, 12 doubles each (q0 q1 q2 q3)

@@ -247,6 +247,7 @@ __device__ __forceinline__ double det3(D3 a, D3 b, D3 c) { return dot3(a, cross3
 struct PieceOut {
   int4* out;
   double* ratio;
+  double* vol;
   double parent_vol;
   const double* x0;
   const double* new_xyz;
@@ -267,7 +268,9 @@ __device__ void emit_piece(const PieceCtx& c, const PieceOut& o, int slot, int t
   const int4 id = {tok_id(c, t0), tok_id(c, t1), tok_id(c, t2), tok_id(c, t3)};
   o.out[slot] = id;
   const D3 p0 = rest_of(o, c, id.x);
-  o.ratio[slot] = det3(sub3(rest_of(o, c, id.y), p0), sub3(rest_of(o, c, id.z), p0), sub3(rest_of(o, c, id.w), p0)) / o.parent_vol;
+  const double det = det3(sub3(rest_of(o, c, id.y), p0), sub3(rest_of(o, c, id.z), p0), sub3(rest_of(o, c, id.w), p0));
+  o.ratio[slot] = det / o.parent_vol;
+  o.vol[slot] = fabs(det) * (1.0 / 6);
 }
 // prism v0 v1 v2 | v3 v4 v5 (vi - v(i+3) lateral edges) into 3 tets by the lowest-global-id rule
 __device__ void emit_prism(const PieceCtx& c, const PieceOut& o, int slot, const int v[6]) {
@@ -296,13 +299,13 @@ __global__ __launch_bounds__(kB) void k_cut_pieces(int n_cut, const int* __restr
                                                    const int* __restrict__ internal_of, const double* __restrict__ x0, const double* __restrict__ q, int carry,
                                                    const unsigned char* __restrict__ code, const int* __restrict__ piece_off, int n_nodes, int n_edges,
                                                    const unsigned long long* __restrict__ ukeys, const double* __restrict__ new_xyz, int4* __restrict__ out,
-                                                   double* __restrict__ ratio) {
+                                                   double* __restrict__ ratio, int n_ratio) {
   const int j = blockIdx.x * kB + threadIdx.x;
   if (j >= n_cut) return;
   const int id = cut_tets[j];
   const TetView v = tet_view(tets[id], caller_of);
   const PieceCtx c = {&v, n_nodes, n_edges, ukeys};
-  PieceOut o = {out, ratio, 0.0, x0, new_xyz, internal_of, carry, q};
+  PieceOut o = {out, ratio, ratio + n_ratio, 0.0, x0, new_xyz, internal_of, carry, q};
   {
     D3 p[4];
     for (int k = 0; k < 4; k++) p[k] = rest_of(o, c, v.g[k]);
@@ -450,12 +453,12 @@ int cut_emit(hipStream_t s, CutWork& C, int n_nodes, const int4* tets, const int
   FB_TRY(C.frac.reserve((size_t)std::max(1, C.n_edges)));
   FB_TRY(C.new_xyz.reserve((size_t)std::max(1, 6 * C.n_edges)));
   FB_TRY(C.added.reserve((size_t)std::max(1, C.n_added)));
-  FB_TRY(C.ratio.reserve((size_t)std::max(1, C.n_added) + 1));
+  FB_TRY(C.ratio.reserve(2 * ((size_t)std::max(1, C.n_added) + 1)));  // ratios, their minimum, absolute volumes, their minimum
   const int carry = C.mode == FB_CUT_CARRY ? 1 : 0;
   hipLaunchKernelGGL(k_cut_nodes, grid_for(C.n_edges), dim3(kB), 0, s, C.n_edges, C.ukeys.p, C.ut.p, internal_of, x0, q, carry, C.frac.p, C.new_xyz.p);
   FB_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_cut_pieces, grid_for(m), dim3(kB), 0, s, m, C.cut_tets.p, tets, caller_of, internal_of, x0, q, carry, C.code.p, C.piece_off.p, n_nodes, C.n_edges,
-                     C.ukeys.p, C.new_xyz.p, C.added.p, C.ratio.p);
+                     C.ukeys.p, C.new_xyz.p, C.added.p, C.ratio.p, C.n_added + 1);
   FB_HIP(hipGetLastError());
   // the smallest piece-to-parent volume ratio (read back with the result)
   double* out = C.ratio.p + C.n_added;
@@ -464,6 +467,11 @@ int cut_emit(hipStream_t s, CutWork& C, int n_nodes, const int4* tets, const int
   FB_TRY(W.temp.reserve(std::max<size_t>(b4, 16)));
   FB_HIP(rocprim::reduce(W.temp.p, b4, C.ratio.p, out, 1e300, (size_t)C.n_added, rocprim::minimum<double>(), s));
   FB_HIP(hipMemcpyAsync(&C.min_ratio, out, sizeof(double), hipMemcpyDeviceToHost, s));
+  // ... and the smallest piece volume itself: what the fp32 records have to hold (fb_fem_cut refuses a cut they cannot)
+  const double* vol = C.ratio.p + C.n_added + 1;
+  double* vout = C.ratio.p + 2 * (size_t)C.n_added + 1;
+  FB_HIP(rocprim::reduce(W.temp.p, b4, vol, vout, 1e300, (size_t)C.n_added, rocprim::minimum<double>(), s));
+  FB_HIP(hipMemcpyAsync(&C.min_volume, vout, sizeof(double), hipMemcpyDeviceToHost, s));
   FB_HIP(hipStreamSynchronize(s));
   return FB_OK;
 }

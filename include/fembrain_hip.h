@@ -227,6 +227,17 @@ int fb_fem_resync_path(fb_fem_t h);
  *                 point, state reset
  *   FB_CUT_CARRY  the rest shape is kept, a new node's rest position is at the edge fraction f = t / |current edge| of its rest edge; q,
  *                 qvel, qaccel of old nodes carried over, new nodes interpolated at f
+ * State and forces after FB_CUT_DONE, on the merged and on the rebuilt re-sync path alike: BAKE leaves q, qvel and qaccel zero on every
+ * node; CARRY leaves them as described; in either mode the external forces are ZERO afterwards (the vector is made anew for the new node
+ * count) -- call fb_fem_set_external_forces / fb_fem_set_uniform_force again before the next step.
+ * Refused with FB_EINVAL before anything changes (modify != 0; a dry run still reports the cut and its min_volume_ratio):
+ *   - a piece without volume (min_volume_ratio <= 0: a split point on a node);
+ *   - a piece whose volume, as a float, is below FLT_MIN (1.18e-38).  Every handle keeps the rest volumes as floats and fp32 matrix
+ *     storage keeps the element records so; below FLT_MIN a float loses bits, below 1.4e-45 it is zero, and a node that lies in such
+ *     pieces only would get an empty row.  (k_tet_rest works in fp64 and would accept the piece.)  The limit is on the volume the records
+ *     hold, not on the ratio: a piece 1e-15 of a parent of volume 1/6 is cut.
+ * A cut that is made gives the handle of the cut mesh -- what a handle created from fb_fem_read_mesh's arrays is, slivers included: thin
+ * pieces cost PCG iterations (FB_ESOLVER at cg_max_iter, state unchanged), they do not harm the handle.
  * Constrained DOFs stay the handle's own (new nodes are free).  Unsharded handles with a device-built plan only (FB_EINVAL otherwise);
  * a failure after the change began leaves the handle unusable until a full fb_fem_resync, as fb_fem_resync_delta does. */
 #define FB_CUT_BAKE 0

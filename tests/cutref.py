@@ -55,9 +55,9 @@ def _cross(a, b):
 def segments(plo, phi):
     d = phi - plo
     ln = np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2])
-    with np.errstate(divide="ignore", invalid="ignore"):
+    with np.errstate(divide="ignore", invalid="ignore"):  # (a zero-length edge, e.g. between unwelded twins: 0 * inf, not taken)
         inv = 1.0 / ln
-    rd = np.where((ln != 0.0)[:, None], d * inv[:, None], d)
+        rd = np.where((ln != 0.0)[:, None], d * inv[:, None], d)
     return rd, ln
 
 
