@@ -17,6 +17,7 @@
 #include "renumber.h"
 #include "delta.h"
 #include "subdivide.h"
+#include "surface.h"
 
 using namespace fb;
 
@@ -54,6 +55,7 @@ struct fb_fem_s {
   MeshDelta delta;        // fb_fem_resync_delta: the change on the device and its scratch
   CutWork cut;            // fb_fem_cut: the last cut's codes, edges, pieces and new nodes (fb_fem_read_cut)
   DevBuf<double> carry;   // fb_fem_cut, FB_CUT_CARRY: the state in the caller's order across the re-sync
+  SurfaceWork surf;       // fb_fem_surface: the boundary of the current mesh (surface.h); empty until somebody asks
   std::vector<int> fixed_caller;  // the constrained DOFs in the caller's numbering (unsharded): what fb_fem_cut keeps
   DevBuf<int4> tets_next, tets_caller;   // (the element list being built; swapped with `tets`)
   DevBuf<double> x0_next;
@@ -1995,6 +1997,7 @@ int rest_state_checked(fb_fem_s* h) {
 int build(fb_fem_s* h, int n_nodes, const double* xyz, int n_tets, const int* tets, int n_fixed, const int* fixed, int n_ranks,
           int rank, const int* splits, const DeviceTetMesh* dm = nullptr) {
   drop_graph(h);  // the buffers it refers to are about to be replaced
+  h->surf.valid = false;  // a new mesh generation (fb_fem_surface)
   SlackScope slack(handle_slack(h, n_nodes, n_tets));
   if (n_ranks == 1 && fixed != h->fixed_caller.data()) h->fixed_caller.assign(fixed, fixed + n_fixed);
   if (h->prm.matrix_precision == FB_MATRIX_AUTO) h->f64 = auto_matrix_f64(h, n_nodes, n_ranks);
@@ -2639,6 +2642,7 @@ int resync_delta(fb_fem_s* h, int n_removed, const int* removed, int n_changed, 
   const int n_old = h->plan.n_global, nt_old = h->plan.n_tets, n_new = n_old + n_new_nodes;
   SlackScope slack(handle_slack(h, n_new, nt_old - n_removed + n_added));
   drop_graph(h);
+  h->surf.valid = false;  // a new mesh generation (fb_fem_surface)
   if (fixed != h->fixed_caller.data()) h->fixed_caller.assign(fixed, fixed + n_fixed);
   if (device_src)
     FB_TRY(delta_upload_device(s, nt_old, n_removed, removed, n_added, reinterpret_cast<const int4*>(added), n_new_nodes, new_xyz, D, W));
@@ -2941,6 +2945,85 @@ int fb_fem_read_mesh(fb_fem_t h, double* rest_xyz, int* tets) {
     }
   }
   return FB_OK;
+}
+
+// ---- fb_fem_surface (surface.h) ----
+namespace {
+int surface_ready(fb_fem_s* h, bool force) {
+  if (h->plan.n_ranks > 1) return fail(FB_EINVAL, "fb_fem_surface is for unsharded handles");
+  if (h->surf.valid && !force) return FB_OK;
+  SlackScope slack(handle_slack(h, h->plan.n_global, h->plan.n_tets));
+  const char* wk = getenv("FEMBRAIN_SURFACE_WIDE_KEYS");  // read at every build, like FEMBRAIN_PLAN_KEYS64
+  return surface_build(h->stream, h->surf, h->plan.n_global, h->plan.n_tets, h->tets.p, h->x0.p, h->ren.active ? h->ren.d_old_of_new.p : nullptr,
+                       h->ren.active ? h->ren.d_new_of_old.p : nullptr, wk && atoi(wk) != 0, h->plan_ws);
+}
+void surface_fill(const SurfaceWork& S, const float* box, fb_fem_surface_info* out) {
+  if (!out) return;
+  out->n_faces = S.n_faces; out->n_vertices = S.n_vertices; out->n_builds = S.n_builds;
+  for (int k = 0; k < 3; k++) { out->aabb_lo[k] = box[k]; out->aabb_hi[k] = box[3 + k]; }
+}
+}  // namespace
+
+int fb_fem_surface(fb_fem_t h, fb_fem_surface_info* out) {
+  CHECK_HANDLE(h);
+  FB_TRY(surface_ready(h, false));
+  surface_fill(h->surf, h->surf.rest_box, out);
+  return FB_OK;
+}
+
+int fb_fem_read_surface(fb_fem_t h, int* faces, int* vertex_ids, int* face_tets) {
+  CHECK_HANDLE(h);
+  FB_TRY(surface_ready(h, false));
+  const SurfaceWork& S = h->surf;
+  if (faces) FB_TRY(S.faces.download(faces, (size_t)3 * S.n_faces, h->stream));
+  if (vertex_ids) FB_TRY(S.vertex_ids.download(vertex_ids, (size_t)S.n_vertices, h->stream));
+  if (face_tets) FB_TRY(S.face_tets.download(face_tets, (size_t)S.n_faces, h->stream));
+  return FB_OK;
+}
+
+int fb_fem_surface_update(fb_fem_t h, float* xyz, float* normals, fb_fem_surface_info* out) {
+  CHECK_HANDLE(h);
+  FB_TRY(surface_ready(h, false));
+  SurfaceWork& S = h->surf;
+  const size_t nv = (size_t)S.n_vertices;
+  const float zero[6] = {0, 0, 0, 0, 0, 0};
+  if (!nv) { surface_fill(S, zero, out); return FB_OK; }
+  FB_TRY(surface_update(h->stream, S, h->x0.p, h->q.p, true));
+  if (xyz) memcpy(xyz, S.host.data(), sizeof(float) * 3 * nv);
+  if (normals) memcpy(normals, S.host.data() + 3 * nv, sizeof(float) * 3 * nv);
+  surface_fill(S, S.host.data() + 6 * nv, out);
+  return FB_OK;
+}
+
+int fb_fem_time_surface(fb_fem_t h, int reps, double* seconds_build, double* seconds_update) {
+  CHECK_HANDLE(h);
+  if (reps < 1) return fail(FB_EINVAL, "reps must be positive");
+  FB_TRY(surface_ready(h, false));  // warm: the buffers exist
+  hipEvent_t e0, e1;
+  FB_HIP(hipEventCreate(&e0));
+  FB_HIP(hipEventCreate(&e1));
+  int rc = FB_OK;
+  auto median = [](std::vector<double>& v) { std::sort(v.begin(), v.end()); return v[v.size() / 2]; };
+  for (int what = 0; what < 2 && rc == FB_OK; what++) {
+    double* dst = what == 0 ? seconds_build : seconds_update;
+    if (!dst) continue;
+    std::vector<double> t;
+    for (int r = 0; r < reps && rc == FB_OK; r++) {
+      if (hipEventRecord(e0, h->stream) != hipSuccess) { rc = fail(FB_EDEVICE, "hipEventRecord failed"); break; }
+      rc = what == 0 ? surface_ready(h, true) : surface_update(h->stream, h->surf, h->x0.p, h->q.p, true);
+      if (rc != FB_OK) break;
+      float ms = 0;
+      if (hipEventRecord(e1, h->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) {
+        rc = fail(FB_EDEVICE, "timing events failed");
+        break;
+      }
+      t.push_back(ms * 1e-3);
+    }
+    if (rc == FB_OK) *dst = median(t);
+  }
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  return rc;
 }
 
 int fb_fem_rebuild_elements(fb_fem_t h) {

@@ -219,6 +219,32 @@ class FemIntegrator:
         _l.check(self._L.fb_fem_read_mesh(self.h, _l.dptr(xyz), _l.iptr(tets)))
         return xyz, tets
 
+    def surface(self):
+        """The boundary triangles of the mesh the device holds (fb_fem_surface; SurfaceMesh::setupFromTetMesh): dict of faces (F, 3) and
+        face_tets (F,) in the caller's numbering, vertex_ids (V,) the ascending ids of the nodes on the surface, n_builds, and aabb
+        (2, 3) of the surface's rest positions.  Built on the device, and again only after the mesh has changed."""
+        info = _l.SurfaceInfo()
+        _l.check(self._L.fb_fem_surface(self.h, C.byref(info)))
+        faces, vids, ft = np.zeros((info.n_faces, 3), np.int32), np.zeros(info.n_vertices, np.int32), np.zeros(info.n_faces, np.int32)
+        _l.check(self._L.fb_fem_read_surface(self.h, _l.iptr(faces), _l.iptr(vids), _l.iptr(ft)))
+        return dict(faces=faces, vertex_ids=vids, face_tets=ft, n_builds=int(info.n_builds),
+                    aabb=np.array([list(info.aabb_lo), list(info.aabb_hi)], np.float32))
+
+    def surface_update(self):
+        """(xyz (V, 3) float32, normals (V, 3) float32, aabb (2, 3) float32) of the surface vertices at the current state, in
+        ``surface()['vertex_ids']`` order (fb_fem_surface_update; SurfaceMesh::applyDisplacements, VolMeshRender::sync)"""
+        info = _l.SurfaceInfo()
+        _l.check(self._L.fb_fem_surface(self.h, C.byref(info)))
+        xyz, nrm = np.zeros((info.n_vertices, 3), np.float32), np.zeros((info.n_vertices, 3), np.float32)
+        _l.check(self._L.fb_fem_surface_update(self.h, _l.fptr(xyz), _l.fptr(nrm), C.byref(info)))
+        return xyz, nrm, np.array([list(info.aabb_lo), list(info.aabb_hi)], np.float32)
+
+    def time_surface(self, reps=20):
+        """(seconds per build, seconds per update): medians of ``reps`` HIP-event timings each (fb_fem_time_surface)"""
+        b, u = C.c_double(0), C.c_double(0)
+        _l.check(self._L.fb_fem_time_surface(self.h, reps, C.byref(b), C.byref(u)))
+        return b.value, u.value
+
     def resync_path(self):
         """FB_RESYNC_* of the handle's last (re-)build"""
         return int(self._L.fb_fem_resync_path(self.h))
@@ -501,6 +527,10 @@ class Deformable:
 
     def get_solver_time(self):
         return self.integrator.get_system_solve_time()
+
+    def surface_mesh(self, update=False):
+        """What the host draws: ``FemIntegrator.surface()``, or with ``update`` ``FemIntegrator.surface_update()``"""
+        return self.integrator.surface_update() if update else self.integrator.surface()
 
     def reset_deformations(self):
         self.integrator.reset_to_rest()

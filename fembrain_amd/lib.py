@@ -56,6 +56,10 @@ class CutResult(C.Structure):
                 ("n_unhandled", C.c_int), ("n_removed", C.c_int), ("n_added", C.c_int), ("n_new_nodes", C.c_int), ("min_volume_ratio", C.c_double)]
 
 
+class SurfaceInfo(C.Structure):
+    _fields_ = [("n_faces", C.c_int), ("n_vertices", C.c_int), ("n_builds", C.c_int), ("aabb_lo", C.c_float * 3), ("aabb_hi", C.c_float * 3)]
+
+
 class PolyCounts(C.Structure):
     _fields_ = [("grid", C.c_int * 3), ("n_points", C.c_int), ("n_cells", C.c_int), ("n_crossed_edges", C.c_int),
                 ("n_surface_cells", C.c_int), ("n_included_cells", C.c_int),
@@ -121,6 +125,10 @@ def lib():
         "fb_fem_cut": (C.c_int, [vp, C.c_int, _dp, C.c_int, C.c_int, C.POINTER(CutResult)]),
         "fb_fem_read_cut": (C.c_int, [vp, _ip, _ip, _dp, _ip, _dp, _ip, _ip]),
         "fb_fem_read_mesh": (C.c_int, [vp, _dp, _ip]),
+        "fb_fem_surface": (C.c_int, [vp, C.POINTER(SurfaceInfo)]),
+        "fb_fem_read_surface": (C.c_int, [vp, _ip, _ip, _ip]),
+        "fb_fem_surface_update": (C.c_int, [vp, _fp, _fp, C.POINTER(SurfaceInfo)]),
+        "fb_fem_time_surface": (C.c_int, [vp, C.c_int, _dp, _dp]),
         "fb_fem_rebuild_elements": (C.c_int, [vp]),
         "fb_fem_set_external_forces": (C.c_int, [vp, _dp]),
         "fb_fem_add_external_forces": (C.c_int, [vp, _dp]),

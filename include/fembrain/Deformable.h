@@ -7,6 +7,7 @@
 //                                vegafem/integrator/integratorBase.h:107-205, integratorBaseSparse.h:45-84)
 //   PS::FEM::Deformable     <-> class Deformable (reference src/deformable/Deformable.h:63-235): same method names,
 //                               argument meaning and callback type; timestep() follows Deformable.cpp:318-420.
+//   PS::FEM::SurfaceMesh    <-> class SurfaceMesh (SurfaceMesh.h, included at the end of this file): what the host draws.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -235,6 +236,8 @@ class HipCGSolver {
   HipIntegrator* in_;
 };
 
+class SurfaceMesh;
+
 class Deformable {
  public:
   Deformable(int numVertices, const double* restPositions, int numElements, const int* elements,
@@ -244,7 +247,10 @@ class Deformable {
     init();
     syncForceModel();
   }
-  ~Deformable() { delete m_lpIntegrator; }
+  ~Deformable();  // (SurfaceMesh.h)
+  // What the host draws (the reference's Deformable IS an SGMesh; its surface is getSurfMesh()): the boundary triangles of the mesh the
+  // device holds, built and kept current there (SurfaceMesh.h).  Owned by the Deformable, created at the first call.
+  SurfaceMesh* surfaceMesh();
 
   // Deformable::timestep (Deformable.cpp:318-420)
   void timestep() {
@@ -282,6 +288,7 @@ class Deformable {
     m_q.assign(m_dof, 0.0); m_qVel.assign(m_dof, 0.0); m_arrExtForces.assign(m_dof, 0.0);
     m_bptr.clear(); m_bcol.clear();
     m_restVolume = -1.0;
+    surfaceChanged();
     return true;
   }
   // The same after a cut that the host can describe (CuttableMesh::cut erases the cut cells -- VolMesh.cpp:630 -- appends their pieces
@@ -321,6 +328,7 @@ class Deformable {
     m_q.assign(m_dof, 0.0); m_qVel.assign(m_dof, 0.0); m_arrExtForces.assign(m_dof, 0.0);
     m_bptr.clear(); m_bcol.clear();
     m_restVolume = -1.0;
+    surfaceChanged();
     return true;
   }
   // CuttableMesh::cut(segments, quadstrips, modifyMesh) (CuttableMesh.cpp:283-505) + cutCompleted's syncForceModel (main.cpp:614-617) in
@@ -345,6 +353,7 @@ class Deformable {
     m_q.assign(m_dof, 0.0); m_qVel.assign(m_dof, 0.0); m_arrExtForces.assign(m_dof, 0.0);
     m_bptr.clear(); m_bcol.clear();
     m_restVolume = -1.0;
+    surfaceChanged();
     return r.n_removed;
   }
   void setMesh(int numVertices, const double* rest, int numElements, const int* elements) {
@@ -529,6 +538,7 @@ class Deformable {
   }
 
  private:
+  void surfaceChanged();  // the surface mesh, if there is one, re-reads its topology at the next access (SurfaceMesh.h)
   double volumeOf(const std::vector<double>& q, double* arrStore = nullptr, U32 count = 0) const {
     const U32 m = (U32)(m_elements.size() / 4);
     const bool store = arrStore != nullptr && count == m;
@@ -550,7 +560,7 @@ class Deformable {
     m_dampingMassCoeff = 0.0; m_dampingStiffnessCoeff = 0.01; m_timeStep = 0.0333; m_ctTimeStep = 0;
     m_hapticForceNeighorhoodSize = 5;  // DEFAULT_FORCE_NEIGHBORHOOD_SIZE, Deformable.h:41
     m_bApplyGravity = true;  // left uninitialised by the reference's init(); true is what its .sim files set
-    m_lpIntegrator = nullptr; m_hasFloor = false; m_floorY = 0.0; m_dof = 0; m_restVolume = -1.0;
+    m_lpIntegrator = nullptr; m_lpSurface = nullptr; m_hasFloor = false; m_floorY = 0.0; m_dof = 0; m_restVolume = -1.0;
   }
   std::vector<double> m_rest;
   std::vector<int> m_elements;
@@ -558,6 +568,7 @@ class Deformable {
   std::vector<vec3d> m_vHapticForces;
   std::vector<double> m_q, m_qVel, m_arrExtForces;
   HipIntegrator* m_lpIntegrator;
+  SurfaceMesh* m_lpSurface;
   FOnApplyDeformations m_fOnDeform;
   U32 m_dof, m_ctCollided, m_ctTimeStep;
   int m_idxPulledVertex, m_device, m_hapticForceNeighorhoodSize;
@@ -568,3 +579,5 @@ class Deformable {
 
 }  // namespace FEM
 }  // namespace PS
+
+#include "SurfaceMesh.h"  // class SurfaceMesh and the members of Deformable that need it

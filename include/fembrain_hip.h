@@ -265,6 +265,42 @@ int fb_fem_read_cut(fb_fem_t h, int* removed, int* added_tets, double* new_xyz, 
  * Unsharded handles only. */
 int fb_fem_read_mesh(fb_fem_t h, double* rest_xyz, int* tets);
 
+/* ---- The surface of the simulated (and cut) mesh, on the device ----
+ * What a host draws a deformable through in the reference: the boundary triangles of the tet mesh
+ * (SurfaceMesh::setupFromTetMesh, src/deformable/SurfaceMesh.cpp:141-213), their current positions and box
+ * (applyDisplacements + updateAABB, :338-373) and a normal per node (VolMeshRender::sync, src/deformable/VolMeshRender.cpp:74-112).
+ * Unsharded handles only (where fb_fem_read_mesh works), device- or host-built plan alike.  A handle that never asks allocates and
+ * launches nothing.
+ *
+ * Faces (SurfaceMesh.cpp:155-207): for every element in element order det = (v1-v0).((v2-v0)x(v3-v0)) on the fp64 rest positions;
+ * det >= 0 gives the local faces (1,2,3) (2,0,3) (3,0,1) (1,0,2), otherwise (3,2,1) (3,0,2) (1,0,3) (2,0,1) (:180-190).  A face whose
+ * sorted vertex triple occurs an odd number of times survives with the vertex order of its LAST occurrence (what insert / erase /
+ * insert on the reference's std::set leaves, :168-178), and the faces are listed in ascending order of the sorted triple (:200-207).
+ * Node ids are the CALLER's, also on a renumbered handle.  face_tets (not in the reference): the element of that last occurrence.
+ * vertex_ids: the ascending caller ids of the nodes some face uses -- the reference keeps every tet vertex in the surface mesh
+ * (:147-148); faces index node ids as its m_faces do, and vertex_ids is the compact list a vertex buffer is filled from.
+ *
+ * The handle counts mesh generations: creation, fb_fem_resync, fb_fem_resync_delta and a fb_fem_cut that returns FB_CUT_DONE make the
+ * topology stale; a step, a state change and a cut that changes nothing do not.  fb_fem_surface builds only when stale (n_builds counts
+ * the builds of this handle) and fills the box from the rest positions; fb_fem_surface_update builds first if it must. */
+typedef struct fb_fem_surface_info {
+  int n_faces, n_vertices, n_builds;
+  float aabb_lo[3], aabb_hi[3];
+} fb_fem_surface_info;
+int fb_fem_surface(fb_fem_t h, fb_fem_surface_info* out);
+/* faces[3 n_faces], vertex_ids[n_vertices], face_tets[n_faces] of the current topology (built first if stale); any pointer may be NULL */
+int fb_fem_read_surface(fb_fem_t h, int* faces, int* vertex_ids, int* face_tets);
+/* The current state of the surface vertices, in vertex_ids' order: xyz[3 n_vertices] = (float)(x0 + q) (fp64 add, one rounding;
+ * SurfaceMesh.cpp:338-352), normals[3 n_vertices] = (float) of the normalised fp64 sum, in ascending face order, of the fp64 unit
+ * normals (p1-p0)x(p2-p0)/|..| of the node's faces at the current positions (VolMeshRender.cpp:74-112; a sum of length 0 gives
+ * (0,0,0), a face without area adds nothing).  The reference's flip towards the camera (VolMeshRender.cpp:83-91) is not reproduced:
+ * the faces are wound outward already.  out->aabb_lo/hi: min / max of xyz (SurfaceMesh.cpp:354-373).  Pointers may be NULL.  One copy
+ * of 24 n_vertices + 24 bytes leaves the device. */
+int fb_fem_surface_update(fb_fem_t h, float* xyz, float* normals, fb_fem_surface_info* out);
+/* Device time of `reps` forced builds and of `reps` updates (HIP events on the handle's stream around each; the medians).  Either
+ * pointer may be NULL.  The build's figure includes its two host waits. */
+int fb_fem_time_surface(fb_fem_t h, int reps, double* seconds_build, double* seconds_update);
+
 
 /* Per-element rest-state rebuild on the device (M^-1 rows / volume, corotationalLinearFEM.cpp:66-90 and
  * tetMesh.cpp:184-188) -- the per-step "K0 rebuild" of BASELINE config 4. */
