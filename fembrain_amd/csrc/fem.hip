@@ -7,195 +7,15 @@
 
 #include <chrono>
 
-#include "comm.h"
-#include "common.h"
 #include "fem_device.hip.h"
-#include "fem_plan.h"
-#include "pcg_pipe.hip.h"
-#include "pcg_pipe2.hip.h"
-#include "plan_device.h"
-#include "renumber.h"
-#include "delta.h"
-#include "subdivide.h"
-#include "surface.h"
+#include "fem_handle.h"
 
 using namespace fb;
-
-struct fb_fem_s {
-  fb_fem_params prm;
-  hipStream_t stream = nullptr;
-  hipStream_t side = nullptr;          // the slot-major assembly of the few slices too wide for the element-major kernel runs beside it (launch_rows)
-  hipEvent_t ev_side[2] = {nullptr, nullptr};
-  fb_comm_s* comm = nullptr;  // not owned
-  P2P* p2p = nullptr;         // direct peer mailboxes for halo refresh and dots (comm.h); null = collective library
-  int xch_mode = FB_XCH_COLLECTIVE;     // how the exchanges of a sharded handle run (fb_fem_set_exchange_mode)
-  DevBuf<int> send_off_dev, halo_off_dev;
-  DevBuf<unsigned char> slice_halo;
-  FemPlan plan;
-  double lambda = 0, mu = 0;
-  int grid = 8;
-  bool f64 = false;
-  // mesh
-  DevBuf<int4> tets;
-  DevBuf<double> x0, rest, fe;
-  DevBuf<char> rec;  // MT[16] per tet
-  DevBuf<char> kcorr;  // exact tangent (warp = 2): MT[144] per tet, the rotation-derivative terms of the element stiffness
-  // Newmark (ImplicitNewmarkSparse): acceleration and the state at the start of the step
-  DevBuf<double> qacc, q1, qvel1, qacc1;
-  double nm_beta = 0.25, nm_gamma = 0.5, nm_eps = 1e-6;
-  int nm_max_newton = 1;
-  bool pcg_warm = false;  // the next solve starts from the x left by the previous one (Newmark), not from 0
-  // matrix
-  DevBuf<int> slice_off, colidx, slot_coff, slot_ccnt, send_local;
-  DevBuf<uint32_t> contrib;
-  DevBuf<short> coldelta;  // 16-bit column words (device-built plans); c16 says whether the SpMV may use them and in which form:
-  int c16 = 0;             // 0 no, 1 column - row (unsharded), 2 the halo form of a shard (plan_device.hip k_plan_sell)
-  DevBuf<int> halo_base;   // c16 == 2: lowest halo column of every slice
-  PlanWorkspace plan_ws;  // the device plan builder's temporaries, kept for the next re-sync
-  MeshDelta delta;        // fb_fem_resync_delta: the change on the device and its scratch
-  CutWork cut;            // fb_fem_cut: the last cut's codes, edges, pieces and new nodes (fb_fem_read_cut)
-  DevBuf<double> carry;   // fb_fem_cut, FB_CUT_CARRY: the state in the caller's order across the re-sync
-  SurfaceWork surf;       // fb_fem_surface: the boundary of the current mesh (surface.h); empty until somebody asks
-  std::vector<int> fixed_caller;  // the constrained DOFs in the caller's numbering (unsharded): what fb_fem_cut keeps
-  DevBuf<int4> tets_next, tets_caller;   // (the element list being built; swapped with `tets`)
-  DevBuf<double> x0_next;
-  DevBuf<int> map_next_a, map_next_b;
-  int last_resync_path = FB_RESYNC_FULL;
-  int ren_nodes_at_build = 0;  // nodes when the internal order was last built from scratch
-  DevBuf<int> flat_flag;
-  DevBuf<int> inc_off;               // element-major assembly (k_assemble_tets): incidence lists per slice, see fem_device.hip.h
-  DevBuf<uint32_t> inc, inc_slot;
-  bool asm_tets = false;             // the assembly kernel in use
-  int asm_lds = 0, asm_grid = 0, asm_max_width = 0;
-  DevBuf<int> pipe_wg_first;         // persistent solver: the deal of the slices to the workgroups balanced by slots (pipe_deal), empty: equal numbers
-  std::vector<int> pipe_wg_first_host;
-  DevBuf<int4> pipe_tasks;           // persistent solver: per workgroup and wavefront its share of the slices (helpers, pcg_pipe.hip.h PipeArgs)
-  int pipe_help_waves = 0;           // wavefronts launched beyond slices + service wavefront, for the helpers (0: none)
-  DevBuf<unsigned long long> pipe_lines;  // k_gather_lines' three sums
-  bool pipe_xyz = false;             // the published vector node by node instead of in planes (irregular meshes; k_pcg_pipe<..., XYZ>)
-  int pipe_lines_nodes = 0;          // nodes of the plan the counts below were taken on
-  double pipe_gather_lines[2] = {0, 0};  // cache lines a slot's gathers touch on average: three planes | 24-byte records (k_gather_lines; 0: not measured)
-  int pipe_n_help = 0, pipe_help_tasks = 0;  // most helper tasks of a workgroup; all of them
-  int asm_wide = 0;                  // slices wider than the element-major kernel takes (kIncMaxWidth slots): k_assemble_wide assembles those
-  int asm_wide_slots = 0, asm_wide_grid = 0;  // the widest of them; workgroups of k_assemble_wide (each with a scratch area of asm_wide_slots slots)
-  DevBuf<int> wide_list;             // their slice numbers
-  DevBuf<double> res_all;            // Newmark, several Newton iterations: the residual of every DOF (AsmOut::res_all)
-  DevBuf<double> wide_scratch;
-  bool asm_staged = false;           // k_assemble_tets_st (records staged in LDS, mass entries precomputed) instead of k_assemble_tets
-  int asm_lds_st = 0, asm_grid_st = 0;
-  bool mass_valid = false;           // h->mblk holds the mass entries of the current rest data (k_mass_blocks)
-  // locality renumbering behind the ABI (renumber.h): the handle works in its own node order, ids are mapped on the way in and out
-  Renumbering ren;
-  DevBuf<double> xyz_in;               // the caller-order rest positions the order was derived from
-  DevBuf<double> io;                   // staging of a caller-order vector on its way to / from the internal order
-  bool x0_ready = false;               // build_plan_on_device has put the (permuted) rest positions in place already
-  bool masks_ready = false;            // ... and the constraint masks (device_constraint_masks)
-  std::vector<int> l2c;                // a renumbered SHARDED handle: caller id of every local node (owned, then halo); empty otherwise
-  unsigned long long order_sum = 0;    // ... and a checksum of the order, compared across the ranks
-  int n_cu_device = 256;               // CUs of the device (FB_MATRIX_AUTO's size rule; setup_persist asks the device itself)
-  bool shard_auto_on = false;          // FB_RENUMBER_AUTO on a sharded handle: the ranks voted for the internal order (vote_shard_order)
-  int shard_vote_neighbours = 0;       // most neighbour ranks any rank would have had under the caller's numbering (what the vote saw)
-  DevBuf<int> fixed_stage;
-  std::vector<int> c_bptr, c_bcol, c_src;  // the pattern in the caller's numbering and the internal block behind each of its blocks (inspection entry points)
-  bool caller_pattern = false;
-  std::vector<double> x0_stage;  // host staging of the rest positions in local numbering (kept: a re-sync does not fault fresh pages)
-  DevBuf<int> d_bptr, d_bcol, d_blk_slot;  // device-built plan only: pattern and slot table, fetched when an inspection entry point asks
-  DevBuf<unsigned int> d_ucnt;             // ... and the pairs of every block (unsharded): with the three above and the contribution table, what fb_fem_resync_delta updates
-  bool span_stale = false;                 // ren.span_after / mean_after are to be measured again (fb_fem_renumbering)
-  bool csr_ready = false;                  // the four describe the current plan
-  bool device_plan = false, host_pattern = true;
-  DevBuf<uint8_t> dofmask;
-  DevBuf<uint8_t> nodemask;  // the three dofmask bytes of a node as bits 0..2 (one gather per column in the assembly)
-  DevBuf<char> vals;  // MT[n_slots][9][64]
-  DevBuf<char> dlo;   // MT[n_slices][9][64]: low part of every row's diagonal block
-  DevBuf<double> mblk;
-  DevBuf<float> volf;                // rest volumes as the fp32 records hold them (k_tet_rest -> k_mass_blocks)
-  DevBuf<double> invblk;  // FB_PCG_BLOCK_JACOBI: inverse 3x3 diagonal block per row
-  // vectors (3*n_local each)
-  DevBuf<double> q, qvel, fext, fint, rhs, x, r, d, Ad, invdiag, tmp, sendbuf;
-  DevBuf<double> part_a, part_b, part_c, scal;
-  DevBuf<CGState> st;
-  DevBuf<int> counter;
-  CGState* st_host = nullptr;  // pinned, 2 slots
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr}, ev_batch[2] = {nullptr, nullptr};
-  bool system_valid = false;
-  bool poisoned = false;  // a re-sync failed half way: the buffers no longer belong to one mesh; only a successful re-sync (or destroy) is accepted
-  double last_assembly_s = 0, last_solve_s = 0;
-  // one batch of 30 PCG iterations (29 merged + the exact-residual one) captured once and replayed: the launch sequence
-  // and every kernel argument repeat from batch to batch, and on meshes of ~100k tets the host's launch rate, not the
-  // device, would otherwise bound the iteration time
-  int split = 0;       // wavefronts per slice of the SpMV on small / mid-size meshes (k_spmv_split): 0 (row kernel), 2 or 4
-  int sgrid = 8;       // blocks (= partial sums) of the SpMV launches; equals grid unless split
-  bool spmv_nt = false;  // stream the matrix values non-temporally (systems larger than the Infinity Cache, see k_spmv)
-  int vgrid = 8;       // blocks of the merged vector pass: one 16-byte pair per thread
-  hipGraphExec_t batch_graph = nullptr;
-  const double* graph_rhs = nullptr;
-  bool use_graph = true;
-  bool literal_now = false, graph_literal = false;  // this solve runs the literal two-reduction sequence (tolerance below kPersistMinEps); what the captured batch runs
-  // persistent solver (pcg_pipe.hip.h): one workgroup per CU, `persist_waves` wavefronts = slices each, the whole solve in one launch
-  bool persist = false;
-  int persist_blocks = 0, persist_waves = 0;
-  DevBuf<long long> persist_timing;    // FEMBRAIN_PERSIST_TIMING=1 (development aid)
-  DevBuf<unsigned long long> pipe_post;
-  DevBuf<unsigned int> pipe_flags;     // [blocks padded to 4] flags, [+4] the error word, [+8..9] the two sequence numbers
-  DevBuf<int> pipe_prod, pipe_prod_count, pipe_prod_xcd;
-  DevBuf<unsigned int> pipe_xcc;        // per workgroup: the XCC id it announced in the current launch (k_pcg_pipe: plain-store publish)
-  int pipe_plain_local = 0;            // interior workgroups publish with plain stores (FEMBRAIN_PIPE_PLAIN_STORES)
-  DevBuf<double> pipe_planes, pipe_z, pipe_s, pipe_state;
-  int pipe_klt = 0, pipe_wmax = 0;
-  // sharded persistent solver (pcg_shard_box.hip.h; opt-in FEMBRAIN_SHARDED_PERSIST=1, unmeasured on multi-GPU hardware)
-  bool shard_persist = false;
-  bool persist_broken = false;  // a launch timed out: the handle runs the two-launch iteration until it is re-armed (below) or re-synced
-  // Re-arming: one co-tenant burst must not cost a 1M-tet host 40 % of its speed for the life of the handle.  After
-  // `rearm_after` clean two-launch solves an unsharded handle tries the persistent launch again; every further time-out doubles the
-  // wait (32, 64, 128, ... solves; FEMBRAIN_PERSIST_REARM=n sets the first, 0 = never).  A sharded handle re-arms at a re-sync only
-  // (the ranks must switch together).
-  int rearm_after = 32, clean_solves = 0, persist_rearms = 0;
-  char* sbox = nullptr;                // my box (fine-grained, mapped by the peers)
-  void* sbox_opened[kP2PMaxRanks] = {nullptr};
-  long long sbox_halo_cap = 0;
-  DevBuf<char*> sbox_peers;
-  DevBuf<int> sh_peer_seg, sh_halo_off, sh_row_send_off, sh_row_send_rank, sh_row_send_pos, sh_n_senders, sh_proxy_wg, sh_wg_duty;
-  DevBuf<int2> sh_wg_range;
-  int sh_n_proxy = 1, sh_relief = 0;
-  DevBuf<unsigned int> sh_wg_send_mask;
-  int pipe_flag_extra = 0;             // flag slots after the workgroups' (the proxies' flags of a sharded handle)
-  int pipe_rows = 1;                   // rows per lane: 1 = k_pcg_pipe (up to 12 slices per CU), 2 = k_pcg_pipe2 (13..24)
-  int pipe_max_producers = 0;          // longest producer list (-1: some workgroup polls all)
-  bool pipe_stats_pending = false;     // ... still on the device (pipe_stats: [0] longest list, [1] someone polls all)
-  DevBuf<int> pipe_owner, pipe_stats;
-  // the LDS window of the one-row kernel (pcg_pipe_mirror.h; k_pipe_mirror_plan in setup_persist), empty: none (FEMBRAIN_PIPE_MIRROR=0, or
-  // another instantiation).  pipe_mir_stats: mirror layers, pool entries, fewest plain layers of a slice -- fetched when asked
-  DevBuf<int4> pipe_mir;
-  DevBuf<unsigned short> pipe_mir_addr;
-  DevBuf<int2> pipe_mir_wg;
-  DevBuf<int> pipe_mir_pool, pipe_mir_stats;
-  int pipe_mir_got[3] = {0, 0, 0};
-  int pipe_mir_klt = 0;                // the instantiation's unroll bound it was planned for
-  int pipe_mir_knob = -1;              // FEMBRAIN_PIPE_MIRROR as it was when the handle was made (-1: not read yet)
-  bool pipe_mir_pending = false;
-  DevBuf<unsigned int> pipe_mask;
-  long long persist_timeout_ticks = 0; // wall_clock64 ticks (100 MHz) a wait inside a persistent launch may last
-  int persist_fallbacks = 0;           // solves that had to be repeated with the two-launch form
-  int persist_launches = 0;            // persistent launches made by this handle
-  int last_pcg_path = 0;               // FB_PCG_PATH_* of the last solve
-  int cu_limit = 0;                    // > 0: the stream is confined to this many CUs (FEMBRAIN_CU_MASK)
-  hipEvent_t ev_p[2] = {nullptr, nullptr};  // around every persistent launch
-  double persist_seconds = 0;          // device seconds of all persistent launches of this handle (HIP events on its stream)
-  long long persist_iterations = 0;    // PCG iterations they ran
-};
 
 namespace {
 
 size_t mt_size(const fb_fem_s* h) { return h->f64 ? sizeof(double) : sizeof(float); }
 
-SellView sell_view(const fb_fem_s* h) {
-  SellView sv;
-  sv.slice_off = h->slice_off.p; sv.colidx = h->colidx.p; sv.n_slices = h->plan.n_slices; sv.n_owned = h->plan.n_owned;
-  sv.coldelta = h->c16 ? h->coldelta.p : nullptr;
-  sv.halo_base = h->c16 == 2 ? h->halo_base.p : nullptr;
-  return sv;
-}
 
 // one wavefront per slice: does any of its columns lie in the halo?
 __global__ __launch_bounds__(kBlock) void k_slice_halo(int n_slices, int n_owned, const int* __restrict__ slice_off, const int* __restrict__ colidx,
@@ -216,7 +36,6 @@ __global__ __launch_bounds__(kBlock) void k_widen_positions(long long n, const f
 // FB_RENUMBER_* of this handle: fb_fem_params.renumber unless FEMBRAIN_RENUMBER=0/1 says otherwise; a sharded handle renumbers on request only
 // Zero fills of a (re-)build, batched: about twenty buffers are cleared, and a fill per buffer costs 4-5 us of launch each however
 // small it is.  add() notes them (4-byte granularity), flush() clears up to kZeroMax per launch.
-constexpr int kZeroMax = 24;
 struct ZeroList { unsigned int* p[kZeroMax]; unsigned long long end[kZeroMax]; unsigned int tail_words[kZeroMax]; int n; };  // end: running total of 16-byte chunks
 __global__ __launch_bounds__(kBlock) void k_zero_many(ZeroList z, unsigned long long total_chunks) {
   for (unsigned long long c = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; c < total_chunks; c += (unsigned long long)gridDim.x * kBlock) {
@@ -230,38 +49,36 @@ __global__ __launch_bounds__(kBlock) void k_zero_many(ZeroList z, unsigned long 
     }
   }
 }
-struct ZeroBatch {
+}  // namespace
+namespace fb {
+void ZeroBatch::add(void* ptr, size_t bytes) {
+  if (!ptr || !bytes || rc != FB_OK) return;
+  if (bytes & 3) {  // (not a whole number of words: the runtime's fill)
+    if (hipMemsetAsync(ptr, 0, bytes, s) != hipSuccess) rc = fail(FB_EDEVICE, "hipMemsetAsync failed");
+    return;
+  }
+  if (n == kZeroMax) flush();
+  const unsigned long long chunks = (bytes + 15) / 16, before = n ? end[n - 1] : 0ULL;
+  p[n] = static_cast<unsigned int*>(ptr);
+  end[n] = before + chunks;
+  tail_words[n] = (unsigned int)((bytes & 15) / 4);
+  n++;
+}
+int ZeroBatch::flush() {
+  if (rc != FB_OK) return rc;
+  if (n == 0) return FB_OK;
   ZeroList z;
-  hipStream_t s;
-  int rc = FB_OK;
-  explicit ZeroBatch(hipStream_t stream) : s(stream) { z.n = 0; }
-  // p: 16-byte aligned (the start of an allocation); bytes: a multiple of 4 (else the runtime's fill takes it)
-  void add(void* p, size_t bytes) {
-    if (!p || !bytes || rc != FB_OK) return;
-    if (bytes & 3) {  // (not a whole number of words: the runtime's fill)
-      if (hipMemsetAsync(p, 0, bytes, s) != hipSuccess) rc = fail(FB_EDEVICE, "hipMemsetAsync failed");
-      return;
-    }
-    if (z.n == kZeroMax) flush();
-    const unsigned long long chunks = (bytes + 15) / 16, before = z.n ? z.end[z.n - 1] : 0ULL;
-    z.p[z.n] = static_cast<unsigned int*>(p);
-    z.end[z.n] = before + chunks;
-    z.tail_words[z.n] = (unsigned int)((bytes & 15) / 4);
-    z.n++;
-  }
-  template <typename T>
-  void add(DevBuf<T>& b) { add(b.p, b.n * sizeof(T)); }
-  int flush() {
-    if (rc != FB_OK) return rc;
-    if (z.n == 0) return FB_OK;
-    const unsigned long long total = z.end[z.n - 1];
-    const unsigned int blocks = (unsigned int)std::min<unsigned long long>((total + kBlock - 1) / kBlock, 256ULL * 16);
-    hipLaunchKernelGGL(k_zero_many, dim3(blocks), dim3(kBlock), 0, s, z, total);
-    if (hipGetLastError() != hipSuccess) rc = fail(FB_EDEVICE, "k_zero_many failed to launch");
-    z.n = 0;
-    return rc;
-  }
-};
+  memcpy(z.p, p, sizeof p); memcpy(z.end, end, sizeof end); memcpy(z.tail_words, tail_words, sizeof tail_words);
+  z.n = n;
+  const unsigned long long total = end[n - 1];
+  const unsigned int blocks = (unsigned int)std::min<unsigned long long>((total + kBlock - 1) / kBlock, 256ULL * 16);
+  hipLaunchKernelGGL(k_zero_many, dim3(blocks), dim3(kBlock), 0, s, z, total);
+  if (hipGetLastError() != hipSuccess) rc = fail(FB_EDEVICE, "k_zero_many failed to launch");
+  n = 0;
+  return rc;
+}
+}  // namespace fb
+namespace {
 
 // slack of this handle's allocations (common.h): a quarter for a mesh that will be cut, or what reserve_nodes / reserve_elements ask for
 int handle_slack(const fb_fem_s* h, int n_nodes, int n_tets) {
@@ -270,17 +87,6 @@ int handle_slack(const fb_fem_s* h, int n_nodes, int n_tets) {
   if (h->prm.reserve_nodes > n_nodes && n_nodes > 0) f = std::max(f, (double)h->prm.reserve_nodes / n_nodes - 1.0);
   if (h->prm.reserve_elements > n_tets && n_tets > 0) f = std::max(f, (double)h->prm.reserve_elements / n_tets - 1.0);
   return std::max(2, std::min(32, (int)std::ceil(f * 16.0)));
-}
-
-// FB_MATRIX_AUTO: fp32 values from 2 slices per CU on (setup_persist's `w`, the persistent solver's range) and where the persistent solver is
-// asked for by name; fp64 below (include/fembrain_hip.h).  A shard decides by the WHOLE mesh, so that the sharded and the unsharded handle
-// of one mesh store the same values; the sharded persistent solver, asked for through the environment, needs fp32 as the unsharded one does.
-bool auto_matrix_f64(const fb_fem_s* h, int n_nodes, int n_ranks) {
-  const int cus = h->cu_limit > 0 ? std::min(h->cu_limit, h->n_cu_device) : h->n_cu_device;
-  const int nb = std::min(kPipeMaxBlocks, (cus / 8) * 8);
-  const int w = nb >= 8 ? ceil_div(ceil_div(ceil_div(n_nodes, 64), 8), nb / 8) : 0;
-  const bool shard_persist_asked = n_ranks > 1 && getenv("FEMBRAIN_SHARDED_PERSIST") && atoi(getenv("FEMBRAIN_SHARDED_PERSIST")) != 0;
-  return h->prm.pcg_variant != FB_PCG_PERSISTENT && !shard_persist_asked && w < 2;
 }
 
 constexpr int kFreshOrderPercent = 2;
@@ -304,524 +110,6 @@ int upload_masks(fb_fem_s* h) {
   std::vector<uint8_t> nm((size_t)P.n_local);
   for (int l = 0; l < P.n_local; l++) nm[l] = (uint8_t)((P.dofmask[3 * (size_t)l] ? 1 : 0) | (P.dofmask[3 * (size_t)l + 1] ? 2 : 0) | (P.dofmask[3 * (size_t)l + 2] ? 4 : 0));
   return h->nodemask.upload(nm, h->stream);
-}
-
-void release_shard_persist(fb_fem_s* h) {
-  for (auto& o : h->sbox_opened) { if (o) (void)hipIpcCloseMemHandle(o); o = nullptr; }
-  if (h->sbox) (void)hipFree(h->sbox);
-  h->sbox = nullptr;
-  h->shard_persist = false;
-}
-
-// The rank-local half of the sharded persistent solver's set-up (pcg_shard_box.hip.h): planes over owned + halo columns, per-row send
-// lists, producer lists with the proxies' flags.  The collective half (boxes, sender counts) is attach_pipe_shard.
-int setup_persist_shard_local(fb_fem_s* h, int nb, int w) {
-  const FemPlan& P = h->plan;
-  hipStream_t s = h->stream;
-  const int R = P.n_ranks;
-  if (R > kP2PMaxRanks) return FB_OK;
-  FB_TRY(h->sh_halo_off.upload(P.halo_off, s));
-  // per slice: its owned column range and the ranks whose halo rows it gathers
-  DevBuf<int4> range;
-  FB_TRY(range.alloc((size_t)std::max(1, P.n_slices)));
-  hipLaunchKernelGGL(k_slice_colrange_shard, dim3(ceil_div(std::max(1, P.n_slices), kWavesPerBlock)), dim3(kBlock), 0, s, P.n_slices, P.n_owned, R, h->slice_off.p,
-                     h->colidx.p, h->sh_halo_off.p, range.p);
-  FB_HIP(hipGetLastError());
-  std::vector<int4> rg((size_t)std::max(1, P.n_slices));
-  FB_TRY(range.download(rg.data(), rg.size(), s));
-  // slice -> workgroup.  A workgroup whose slices gather halo rows gets its input later than the others by the length of the
-  // cross-rank chain (drain -> counter -> proxy copy -> flag; ~4.5 us between two processes on one MI355X) EVERY iteration, and the
-  // whole grid ends up at its pace.  So it is dealt fewer slices ("relief", FEMBRAIN_SHARD_RELIEF=n, default 35 % of the
-  // slices per CU): its shorter product absorbs the wait.
-  const int relief_env = getenv("FEMBRAIN_SHARD_RELIEF") ? atoi(getenv("FEMBRAIN_SHARD_RELIEF")) : -1;
-  std::vector<int2> wg_range((size_t)nb, make_int2(0, 0));   // first slice and slice count of every workgroup
-  // Default (profiles/r04_remote_delay.json: two and four ranks on CU shares of one GPU, remote signals delayed by 0 / 1 / 2 / 5 us): relief
-  // pays where FEW workgroups gather halo rows -- 1M tets on two ranks, 2 of 28 planes per rank: 18.5 against 20.6 us per iteration, and
-  // still 21.4 against 22.8 with 2 us added per hop -- and costs where many do: on four ranks (14 planes per rank, the geometry of the
-  // 8M-tet mesh on eight GPUs) the even deal runs 20.4 against 23.5.  So: 35 % of the slices per CU while at most a twelfth of the slices
-  // gather halo rows, none beyond.
-  int halo_slices = 0;
-  for (int sl = 0; sl < P.n_slices; sl++) halo_slices += rg[sl].z != 0 ? 1 : 0;
-  const int relief_default = 12 * halo_slices <= P.n_slices ? std::max(0, (w * 35 + 50) / 100) : 0;
-  int Q = w, relief = std::min(w - 1, relief_env >= 0 ? relief_env : relief_default);
-  for (;; relief--) {
-    Q = 0;
-    if (relief <= 0 || (nb & 7)) {  // the even deal of the unsharded kernel
-      relief = 0;
-      for (int b = 0; b < nb; b++) {
-        int first, count;
-        pipe_slices(P.n_slices, nb, b, &first, &count);
-        wg_range[b] = make_int2(first, count);
-        Q = std::max(Q, count);
-      }
-      break;
-    }
-    // a slice that gathers halo rows weighs w / (w - relief) slices; equal weight per workgroup, contiguous, and in pipe_slices'
-    // order: the workgroups of XCD b & 7 (round-robin dispatch) hold a contiguous eighth
-    const double rho = (double)w / (double)(w - relief);
-    double W = 0;
-    for (int sl = 0; sl < P.n_slices; sl++) W += rg[sl].z != 0 ? rho : 1.0;
-    std::vector<int> start((size_t)nb + 1, P.n_slices);
-    double acc = 0;
-    int pos = 0;
-    for (int sl = 0; sl < P.n_slices; sl++) {
-      while (pos < nb && acc >= W * pos / nb - 1e-9) start[pos++] = sl;   // position pos starts at the first slice at or past its share
-      acc += rg[sl].z != 0 ? rho : 1.0;
-    }
-    const int per = nb >> 3;
-    for (int p2 = 0; p2 < nb; p2++) {
-      const int b = (p2 % per) * 8 + p2 / per;
-      wg_range[b] = make_int2(start[p2], start[p2 + 1] - start[p2]);
-      Q = std::max(Q, start[p2 + 1] - start[p2]);
-    }
-    if (Q <= 2 * (kPipeMaxWaves - 1)) break;
-  }
-  w = Q;
-  h->pipe_rows = w < kPipeMaxWaves ? 1 : 2;   // 12..22 slices per CU: two rows per lane (k_pcg_pipe2_shard)
-  h->pipe_wmax = h->pipe_rows == 2 ? 12 : (w < 8 ? 8 : 12);   // (one wavefront more than slices / slice pairs: the spare one serves the proxies and the sums)
-  h->pipe_klt = h->pipe_rows == 2 ? std::min(kPipe2Klt, pipe2_lds_slots(w, false) / std::max(w, 1)) : std::min(h->pipe_wmax == 8 ? 8 : 6, pipe_lds_slots(false) / std::max(w, 1));  // (a shard's columns are 32-bit)
-  h->persist_blocks = nb; h->persist_waves = w;
-  h->sh_relief = relief;
-  h->pipe_flag_extra = kP2PMaxRanks * kShardProxies;
-  FB_TRY(h->sh_wg_range.upload(wg_range, s));
-  FB_TRY(h->pipe_post.alloc((size_t)2 * nb * 4));
-  FB_TRY(h->pipe_post.zero(s));
-  FB_TRY(h->pipe_flags.alloc((size_t)nb + h->pipe_flag_extra + 16));
-  FB_TRY(h->pipe_flags.zero(s));
-  const size_t n_pad = (size_t)ceil_div(P.n_local, 64) * 64, nv = (size_t)3 * P.n_local + 2;
-  FB_TRY(h->pipe_planes.alloc(2 * 3 * n_pad));
-  FB_TRY(h->pipe_planes.zero(s));
-  FB_TRY(h->pipe_z.alloc(nv));
-  FB_TRY(h->pipe_s.alloc(nv));
-  FB_TRY(h->pipe_state.alloc(2));
-  FB_TRY(h->pipe_state.zero(s));
-  h->persist_timing.release();
-  std::vector<int> owner((size_t)P.n_slices, 0);
-  for (int b = 0; b < nb; b++)
-    for (int k = 0; k < wg_range[b].y; k++) owner[wg_range[b].x + k] = b;
-  // per-row send lists and per-workgroup destination masks from the plan's send lists (ascending owned ids per destination: the
-  // position of a row in that list is its position in the destination's halo segment of this rank)
-  std::vector<int> row_off((size_t)P.n_owned + 1, 0);
-  for (int q = 0; q < R; q++)
-    for (int k = P.send_off[q]; k < P.send_off[q + 1]; k++) row_off[(size_t)P.send_local[k] + 1]++;
-  for (int a = 0; a < P.n_owned; a++) row_off[(size_t)a + 1] += row_off[a];
-  std::vector<int> row_rank((size_t)std::max(1, row_off[P.n_owned])), row_pos(row_rank.size()), fill(row_off.begin(), row_off.end() - 1);
-  std::vector<unsigned int> wg_mask((size_t)nb, 0u);
-  for (int q = 0; q < R; q++)
-    for (int k = P.send_off[q]; k < P.send_off[q + 1]; k++) {
-      const int a = P.send_local[k];
-      row_rank[fill[a]] = q; row_pos[fill[a]] = k - P.send_off[q]; fill[a]++;
-      wg_mask[owner[a >> 6]] |= 1u << q;
-    }
-  FB_TRY(h->sh_row_send_off.upload(row_off, s));
-  FB_TRY(h->sh_row_send_rank.upload(row_rank, s));
-  FB_TRY(h->sh_row_send_pos.upload(row_pos, s));
-  FB_TRY(h->sh_wg_send_mask.upload(wg_mask, s));
-  // proxies: up to kShardProxies per rank I have halo nodes of, dealt to the workgroups from the last one downwards
-  int n_src = 0;
-  for (int q = 0; q < R; q++) n_src += P.halo_off[q + 1] > P.halo_off[q];
-  const int K = std::max(1, std::min(kShardProxies, nb * kShardDuties / std::max(1, n_src)));
-  h->sh_n_proxy = K;
-  std::vector<int> proxy((size_t)R * K, -1), duty((size_t)nb * kShardDuties, -1), n_duty((size_t)nb, 0);
-  for (int q = 0, idx = 0; q < R; q++)
-    for (int k = 0; k < K; k++) {
-      int lo, hi;
-      shard_proxy_rows(P.halo_off[q], P.halo_off[q + 1], K, k, &lo, &hi);
-      if (hi <= lo) continue;
-      const int b = nb - 1 - (idx++ % nb);   // (idx < nb * kShardDuties by the choice of K)
-      proxy[(size_t)q * K + k] = b;
-      duty[(size_t)b * kShardDuties + n_duty[b]++] = q * K + k;
-    }
-  FB_TRY(h->sh_proxy_wg.upload(proxy, s));
-  FB_TRY(h->sh_wg_duty.upload(duty, s));
-  // producer lists: local workgroups from the owned column range of every slice, proxies from the ranks its halo columns belong to
-  std::vector<int> prod((size_t)nb * kPipeMaxProducers, -1), cnt((size_t)nb, 0), far((size_t)nb, 1);
-  std::vector<char> mark((size_t)nb + (size_t)R * K);
-  h->pipe_max_producers = 0;
-  h->pipe_stats_pending = false;
-  for (int b = 0; b < nb; b++) {
-    std::fill(mark.begin(), mark.end(), 0);
-    int n = 0;
-    for (int sl0 = wg_range[b].x; sl0 < wg_range[b].x + wg_range[b].y; sl0++) {
-      const int4 r = rg[sl0];
-      for (int sl = r.x >> 6; r.y >= r.x && sl <= (r.y >> 6) && sl < P.n_slices; sl++) {
-        const int o = owner[sl];
-        if (o != b && !mark[o]) { mark[o] = 1; n++; }
-      }
-      for (int q = 0; q < R; q++)
-        if ((unsigned int)r.z >> q & 1u)
-          for (int kk = 0; kk < K; kk++)   // (all proxies of a rank this slice gathers halo rows of)
-            if (proxy[(size_t)q * K + kk] >= 0 && !mark[nb + q * K + kk]) { mark[nb + q * K + kk] = 1; n++; }
-    }
-    if (n > kPipeMaxProducers) { cnt[b] = -1; h->pipe_max_producers = -1; continue; }
-    cnt[b] = n;
-    if (h->pipe_max_producers >= 0) h->pipe_max_producers = std::max(h->pipe_max_producers, n);
-    for (int o = 0, k = 0; o < nb + R * K; o++) if (mark[o]) prod[(size_t)b * kPipeMaxProducers + k++] = o;
-  }
-  FB_TRY(h->pipe_prod.upload(prod, s));
-  FB_TRY(h->pipe_prod_count.upload(cnt, s));
-  FB_TRY(h->pipe_prod_xcd.upload(far, s));
-  h->pipe_plain_local = 0;
-  h->shard_persist = true;  // (confirmed or withdrawn by attach_pipe_shard, collectively)
-  return FB_OK;
-}
-
-// how long a wait inside a persistent launch may last before the launch gives up (read when a plan is built and when the solver is re-armed)
-void read_persist_timeout(fb_fem_s* h) {
-  const char* t = getenv("FEMBRAIN_PERSIST_TIMEOUT_MS");
-  // default 50 ms: a whole 1M-tet solve is ~25 ms, one wait is microseconds.  A sharded handle also waits for the OTHER RANKS' launches
-  // to begin, and those are separated by host jitter (first launch: code object load): 2 s there
-  const double ms = t ? atof(t) : (h->plan.n_ranks > 1 ? 2000.0 : 50.0);
-  h->persist_timeout_ticks = std::max(1LL, (long long)(ms * 1e5));  // 100 MHz
-}
-
-static bool pipe_klt7(const fb_fem_s* h);
-
-// The LDS window of the one-row (12, 6) / (12, 7) kernel (pcg_pipe_mirror.h): planned on the device for every (re)built plan, so a full
-// re-sync, both outcomes of a delta re-sync and a fresh node order all get the table of their own plan.  FEMBRAIN_PIPE_MIRROR=0 when the
-// handle is made: none.
-int setup_pipe_mirror(fb_fem_s* h) {
-  const FemPlan& P = h->plan;
-  hipStream_t s = h->stream;
-  if (h->pipe_mir_knob < 0) {  // (read once, at the handle's first plan: its re-syncs keep what it was made with)
-    const char* e = getenv("FEMBRAIN_PIPE_MIRROR");
-    h->pipe_mir_knob = e && atoi(e) == 0 ? 0 : 1;
-  }
-  const bool want = h->pipe_mir_knob != 0;
-  h->pipe_mir_pending = false;
-  h->pipe_mir_got[0] = h->pipe_mir_got[1] = h->pipe_mir_got[2] = 0;
-  if (!want || !h->persist || h->shard_persist || h->pipe_rows != 1 || h->pipe_wmax != 12 || h->pipe_tasks.p || h->pipe_xyz ||
-      h->prm.pcg_variant == FB_PCG_BLOCK_JACOBI || P.n_slices <= 0) {
-    h->pipe_mir.release(); h->pipe_mir_addr.release(); h->pipe_mir_wg.release(); h->pipe_mir_pool.release();
-    return FB_OK;
-  }
-  const int nb = h->persist_blocks;
-  const int klt = pipe_klt7(h) ? 7 : 6;
-  h->pipe_mir_klt = klt;
-  FB_TRY(h->pipe_mir.alloc((size_t)nb * kMirWaves));
-  FB_TRY(h->pipe_mir_addr.alloc((size_t)P.n_slices * kMirMax * 64));
-  FB_TRY(h->pipe_mir_wg.alloc((size_t)nb));
-  FB_TRY(h->pipe_mir_pool.alloc((size_t)nb * kMirPoolMax));
-  FB_TRY(h->pipe_mir_stats.alloc(3));
-  FB_HIP(hipMemsetAsync(h->pipe_mir_stats.p, 0, 2 * sizeof(int), s));
-  FB_HIP(hipMemsetAsync(h->pipe_mir_stats.p + 2, 0x7f, sizeof(int), s));  // (a minimum)
-  hipLaunchKernelGGL(k_pipe_mirror_plan, dim3(nb), dim3(64 * kMirWaves), 0, s, P.n_slices, P.n_owned, h->slice_off.p, h->colidx.p, h->pipe_wg_first.p, klt,
-                     h->c16 ? 1 : 0, h->pipe_mir.p, h->pipe_mir_addr.p, h->pipe_mir_pool.p, h->pipe_mir_wg.p, h->pipe_mir_stats.p);
-  FB_HIP(hipGetLastError());
-  h->pipe_mir_pending = true;
-  return FB_OK;
-}
-
-// Decides whether this handle solves inside persistent launches and allocates what they need (called for every (re)built plan).
-int setup_persist(fb_fem_s* h) {
-  const FemPlan& P = h->plan;
-  hipStream_t s = h->stream;
-  ZeroBatch zb(s);  // (the clears of this set-up in one launch)
-  h->persist = false;
-  h->pipe_mir.release(); h->pipe_mir_pending = false;  // (setup_pipe_mirror plans the window again where it applies)
-  h->pipe_mir_got[0] = h->pipe_mir_got[1] = h->pipe_mir_got[2] = 0;
-  // Nothing of the previous plan's sharded persistent solver survives a rebuild: a re-sync to a mesh that is no longer
-  // eligible must not leave attach_pipe_shard a stale "keep", stale send lists or a stale workgroup deal.  setup_persist_shard_local
-  // is the only place that sets shard_persist again; a fresh plan also gets a fresh chance after a time-out.
-  h->shard_persist = false;
-  h->persist_broken = false;
-  h->pipe_stats_pending = false;
-  h->clean_solves = 0;
-  h->rearm_after = getenv("FEMBRAIN_PERSIST_REARM") ? std::max(0, atoi(getenv("FEMBRAIN_PERSIST_REARM"))) : 32;
-  h->sh_halo_off.release(); h->sh_row_send_off.release(); h->sh_row_send_rank.release(); h->sh_row_send_pos.release(); h->sh_proxy_wg.release();
-  h->sh_wg_duty.release(); h->sh_wg_range.release(); h->sh_wg_send_mask.release();
-  hipDeviceProp_t prop;
-  FB_HIP(hipGetDeviceProperties(&prop, h->prm.device));
-  const int nb = std::min(kPipeMaxBlocks, ((h->cu_limit > 0 ? std::min(h->cu_limit, prop.multiProcessorCount) : prop.multiProcessorCount) / 8) * 8);
-  const char* e = getenv("FEMBRAIN_PCG_PERSIST");
-  int w = nb >= 8 ? ceil_div(ceil_div(P.n_slices, 8), nb / 8) : 0;
-  // The deal of the slices to the workgroups.  Equal NUMBERS of slices per workgroup (pipe_slices) is equal work only where the slices are
-  // alike; on a mesh with hull nodes of 40-60 neighbours the workgroups of the hull stream 2.5 x the slots of the others and every
-  // iteration waits for them (606k-tet Delaunay probe: product 18 us there, 7.5 on average).  Where the fullest workgroup of the equal
-  // deal has a quarter more slots than the average, the slices of every XCD's share are dealt to its workgroups by SLOTS instead
-  // (contiguous runs still, at most 12 -- or 24 where the two-row kernel is the mesh's anyway -- slices each).  FEMBRAIN_PIPE_BALANCE=0/1.
-  h->pipe_wg_first_host.clear();
-  h->pipe_wg_first.release();
-  if (P.n_ranks == 1 && nb >= 8 && w >= 1 && w <= 2 * kPipeMaxWaves && !P.slice_off.empty()) {
-    const int per = nb / 8, chunk = ceil_div(P.n_slices, 8), cap = w <= kPipeMaxWaves ? kPipeMaxWaves : 2 * kPipeMaxWaves;
-    long long total = 0, worst = 0;
-    for (int b = 0; b < nb; b++) {
-      int first, count;
-      pipe_slices(P.n_slices, nb, b, &first, &count);
-      const long long sl = count > 0 ? P.slice_off[first + count] - P.slice_off[first] : 0;
-      total += sl;
-      worst = std::max(worst, sl);
-    }
-    const char* eb = getenv("FEMBRAIN_PIPE_BALANCE");
-    // (a fullest workgroup a quarter above the average -- or 15 % above it on a mesh whose widest slice is half again as wide as the mean:
-    // the 56^3 cube after one cut, 200 slots against 171, 20.2 -> 19.3 us per iteration.  Forced on a uniform mesh the deal by slots is
-    // SLOWER, 16.4 against 15.6 at 1M tets: some workgroups then hold 12 slices and a smaller LDS share each.)
-    int widest = 0;
-    for (int sl = 0; sl < P.n_slices; sl++) widest = std::max(widest, P.slice_off[sl + 1] - P.slice_off[sl]);
-    const bool uneven = P.n_slices > 0 && (long long)widest * 2 * P.n_slices >= 3 * (long long)P.slice_off[P.n_slices];
-    // (uneven WIDTHS only: on a small uniform mesh the fullest workgroup is a quarter above the average because it holds 2 slices where others
-    // hold 1, which no deal changes -- and dealt by slots such a mesh was 2-5 % slower: 27^3 cube 8.65 -> 8.86 us per iteration, ventricle.blob 8.28 -> 8.62)
-    const bool want = eb ? atoi(eb) != 0 : (uneven && (worst * nb * 4 > total * 5 || (w <= kPipeMaxWaves && worst * nb * 100 > total * 115)));  // (the two-row kernel at 13 slices per CU: 28.7 with the equal deal, 29.9 by slots)
-    if (want) {
-      std::vector<int> tab((size_t)2 * nb + 2, 0);
-      int most = 0;
-      for (int x = 0; x < 8; x++) {
-        const int lo = std::min(x * chunk, P.n_slices), hi = std::min((x + 1) * chunk, P.n_slices);
-        int at = lo;
-        for (int j = 0; j < per; j++) {
-          const int b = x + 8 * j, left = per - j;
-          const long long rest = P.slice_off[hi] - P.slice_off[at];
-          const double target = (double)rest / left;
-          int n = 0;
-          long long cum = 0;
-          // at least what the workgroups behind cannot take, then slices while the run stays closer to its share than without the next one
-          const int must = std::max(0, (hi - at) - (left - 1) * cap);
-          while (at + n < hi && n < cap) {
-            const long long wd = P.slice_off[at + n + 1] - P.slice_off[at + n];
-            if (n >= must && left > 1 && (double)cum + 0.5 * (double)wd > target) break;
-            cum += wd;
-            n++;
-          }
-          tab[b] = at;
-          tab[(size_t)nb + 1 + b] = n;
-          at += n;
-          most = std::max(most, n);
-        }
-      }
-      tab[nb] = P.n_slices;
-      h->pipe_wg_first_host = tab;
-      FB_TRY(h->pipe_wg_first.upload(tab, s));
-      if (getenv("FEMBRAIN_TIMING")) fprintf(stderr, "[fembrain] persistent solver: slices dealt by slots (fullest workgroup of the equal deal: %lld slots, average %.1f); up to %d slices per workgroup\n", worst, (double)total / nb, most);
-      w = std::max(1, most);
-    }
-  }
-  read_persist_timeout(h);
-  const bool explicit_p = h->prm.pcg_variant == FB_PCG_PERSISTENT;
-  const bool shard_opt = P.n_ranks > 1 && getenv("FEMBRAIN_SHARDED_PERSIST") && atoi(getenv("FEMBRAIN_SHARDED_PERSIST")) != 0;
-  if (explicit_p && P.n_ranks > 1 && !shard_opt) return fail(FB_EINVAL, "FB_PCG_PERSISTENT on a sharded handle needs FEMBRAIN_SHARDED_PERSIST=1 (unmeasured on multi-GPU hardware)");
-  if (explicit_p && h->f64) return fail(FB_EINVAL, "FB_PCG_PERSISTENT needs FB_MATRIX_F32 storage (part of the matrix is kept in LDS as fp32 words)");
-  if (explicit_p && (nb < 8 || w < 1 || w > 2 * kPipeMaxWaves))
-    return fail(FB_EINVAL, "FB_PCG_PERSISTENT needs at most %d slices per CU, this mesh has %d on %d CUs", 2 * kPipeMaxWaves, w, nb);
-  // asked for explicitly (parameter or FEMBRAIN_PCG_PERSIST=1), or by default where it was measured faster than the
-  // two-launch iteration: fp32 storage, up to 12 slices per CU
-  // (a sharded handle: opt-in, one row per lane, and a spare wavefront per workgroup for the proxies and the sums)
-  const bool eligible = !h->f64 && nb >= 8 && w >= 1 && (P.n_ranks == 1 ? w <= 2 * kPipeMaxWaves : (shard_opt && w <= 2 * (kPipeMaxWaves - 1)));  // (sharded: the spare wavefront leaves 11 for slices, two rows per lane from 12 slices on)
-  // (us per iteration, two-launch vs persistent, on MI355X: 7.83 / 7.87 at 125 slices = 1 per CU, 8.74 / 8.74 at 308 and 8.98 / 8.64 at 466
-  // = 2 per CU, 10.9 / 8.8 at 614 = 3 per CU, 14.0 / 10.3 at 792, 15.8 / 8.9 at 1,000, 27.4 / 15.75 at 2,744 = 1M tets)
-  const int min_w = getenv("FEMBRAIN_PERSIST_MIN_WAVES") ? atoi(getenv("FEMBRAIN_PERSIST_MIN_WAVES")) : 2;
-  // FB_PCG_BLOCK_JACOBI (opt-in, outside parity): the one-row persistent kernel with the block preconditioner, same rule
-  const bool bj = h->prm.pcg_variant == FB_PCG_BLOCK_JACOBI;
-  const bool rows2_forced = getenv("FEMBRAIN_PERSIST_ROWS") && atoi(getenv("FEMBRAIN_PERSIST_ROWS")) == 2;
-  const bool by_default = (h->prm.pcg_variant == FB_PCG_MERGED || bj) && w >= min_w;
-  const bool want_p = e ? atoi(e) != 0 && (h->prm.pcg_variant == FB_PCG_MERGED || explicit_p || bj) : (explicit_p || by_default);
-  if (!want_p || !eligible) return FB_OK;
-  if (bj && (w > kPipeMaxWaves || rows2_forced || P.n_ranks > 1)) return FB_OK;  // (no two-row form with the block preconditioner)
-  if (P.n_ranks > 1) return setup_persist_shard_local(h, nb, w);
-  h->persist = true; h->persist_blocks = nb; h->persist_waves = w;
-  // pipelined whole-solve kernel
-  // up to 12 slices per CU: one row per lane (k_pcg_pipe); 13..24: two (k_pcg_pipe2, no LDS-resident slots).  FEMBRAIN_PERSIST_ROWS=2
-  // forces the two-row kernel on a smaller system (tests).
-  h->pipe_rows = w > kPipeMaxWaves || rows2_forced ? 2 : 1;
-  // Up to 4 slices per CU (BASELINE config 2: 105k tets = 2 per CU) k_pcg_pipe<..,5,16> keeps the WHOLE slice in LDS -- 16 slots each where
-  // (8, 8) keeps 8 of ~15 and streams the rest from L2 in every product.  Built, tested, measured -- and NOT the
-  // default: 9.24 / 9.50 / 9.63 us per iteration at 27^3 / 33^3 / 37^3 against 8.82 / 9.06 / 9.58 with (8, 8).  The phase table says why
-  // (profiles/r05_small_mesh_phase_table.txt): the product is 2.2 of the 8.9 us, the other 6.6 are the hand-offs between the CUs (drain of
-  // the publish stores 1.0, flag + neighbour wait + acquire 3.2, sweep of the sums 2.0, recurrences 0.5), which no residency shortens.
-  // FEMBRAIN_PIPE_SMALL=1 selects it.
-  const bool small = h->pipe_rows == 1 && w <= 4 && !bj && P.n_ranks == 1 && getenv("FEMBRAIN_PIPE_SMALL") && atoi(getenv("FEMBRAIN_PIPE_SMALL")) != 0;
-  h->pipe_wmax = h->pipe_rows == 2 ? 12 : (small ? 5 : (w <= 8 ? 8 : 12));
-  // slots of every slice resident in LDS at least: the CU's 62 / 65 (16-bit columns) wavefront-slots dealt to the slices of a workgroup (k_pcg_pipe), at most 16 / 8 / 6
-  const int lds_all = pipe_lds_slots(h->c16 != 0), lds_help = pipe_help_slots(h->c16 != 0);
-  h->pipe_klt = h->pipe_rows == 2 ? std::min(kPipe2Klt, pipe2_lds_slots(w, h->c16 != 0) / std::max(w, 1)) : std::min(small ? 16 : (w <= 8 ? 8 : 6), lds_all / std::max(w, 1));
-  // Helpers for very wide slices (unsharded, one row per lane, Jacobi): the widest slice at least half again as wide as the average and
-  // wider than 24 slots.  A workgroup's wavefronts without a slice of their own -- those its neighbours' fuller deal leaves idle, and
-  // the ones launched for the purpose: the 12-wavefront instantiation then serves fewer than 9 slices per CU too -- take the upper halves of
-  // the longest streams, longest first, until none is left or no stream is longer than 2 x 8 slots.  FEMBRAIN_PIPE_HELPERS=0/1 overrides.
-  h->pipe_tasks.release();
-  h->pipe_help_waves = 0; h->pipe_n_help = 0; h->pipe_help_tasks = 0;
-  if (!bj && !small && P.n_ranks == 1 && !P.slice_off.empty()) {  // (one row per lane: helpers and layout; two rows per lane: the layout)
-    int mx = 0;
-    long long tot = 0;
-    for (int sl = 0; sl < P.n_slices; sl++) { const int wd = P.slice_off[sl + 1] - P.slice_off[sl]; mx = std::max(mx, wd); tot += wd; }
-    const double mean = P.n_slices ? (double)tot / P.n_slices : 0.0;
-    const char* eh = getenv("FEMBRAIN_PIPE_HELPERS");
-    const bool want_h = h->pipe_rows == 1 && (eh ? atoi(eh) != 0 : (mx > 24 && (double)mx >= 1.5 * mean));
-    // Where do the columns of a slot lie?  On a structured mesh the 64 rows of a slice have consecutive columns and a gather touches 4 lines
-    // of each of the three planes of the published vector; on an unstructured one it touches ~50 of each, and a vector stored node by node
-    // (24-byte records) costs half of those.  Sampled on the device (every 8th slice), decided here: node by node where the planes cost 30 lines
-    // and more per slot and half again the records' (606k-tet Delaunay probe: 80 against 44 lines, 18.9 -> 16.4 us per iteration; the cube
-    // after a cut: 19 against 15, and there the planes are the faster form, 19.4 against 20.6, each load touching 4 lines instead of 12).  FEMBRAIN_PIPE_XYZ=0/1 overrides.  (The table-driven instantiation carries the layout.)
-    bool want_xyz = false;
-    // (a re-sync that changes the mesh by a few per cent keeps the counts of the plan before it: the read-back is a host wait)
-    const bool keep_lines = h->pipe_gather_lines[0] > 0.0 && h->pipe_lines_nodes > 0 && std::abs(P.n_local - h->pipe_lines_nodes) * 20 <= h->pipe_lines_nodes;
-    if (keep_lines) {
-      const char* ex = getenv("FEMBRAIN_PIPE_XYZ");
-      want_xyz = P.n_local < (1 << 24) &&
-                 (ex ? atoi(ex) != 0 : (h->pipe_gather_lines[0] >= 30.0 && h->pipe_gather_lines[0] >= 1.5 * h->pipe_gather_lines[1]));
-    } else {
-      h->pipe_gather_lines[0] = h->pipe_gather_lines[1] = 0.0;
-      h->pipe_lines_nodes = 0;
-    }
-    if (!keep_lines && P.n_local < (1 << 24) && h->colidx.p) {
-      FB_TRY(h->pipe_lines.alloc(4));
-      FB_HIP(hipMemsetAsync(h->pipe_lines.p, 0, 4 * sizeof(unsigned long long), s));
-      hipLaunchKernelGGL(k_gather_lines, dim3(64), dim3(256), 0, s, P.n_slices, 8, h->slice_off.p, h->colidx.p, h->pipe_lines.p);
-      FB_HIP(hipGetLastError());
-      unsigned long long got[3] = {0, 0, 0};
-      FB_HIP(hipMemcpyAsync(got, h->pipe_lines.p, sizeof got, hipMemcpyDeviceToHost, s));
-      FB_HIP(hipStreamSynchronize(s));
-      if (got[2]) { h->pipe_gather_lines[0] = 3.0 * (double)got[0] / (double)got[2]; h->pipe_gather_lines[1] = (double)got[1] / (double)got[2]; h->pipe_lines_nodes = P.n_local; }
-      const char* ex = getenv("FEMBRAIN_PIPE_XYZ");
-      want_xyz = ex ? atoi(ex) != 0 : (got[2] && h->pipe_gather_lines[0] >= 30.0 && h->pipe_gather_lines[0] >= 1.5 * h->pipe_gather_lines[1]);
-    }
-    h->pipe_xyz = h->pipe_rows == 2 && want_xyz;  // (the two-row kernel: a template parameter; the one-row kernel: with its task table, below)
-    if (h->pipe_rows == 1 && (want_h || want_xyz) && w <= kPipeMaxWaves) {
-      const int help_waves = std::max(0, kPipeMaxWaves - w - 1);   // (the 12-wavefront kernel: slices, helpers, the service wavefront)
-      std::vector<int4> tasks((size_t)nb * kPipeTaskStride, make_int4(-1, 0, 0, 0));
-      int most = 0, all = 0, deepest = 0;
-      const int min_len = getenv("FEMBRAIN_PIPE_HELP_MINLEN") ? atoi(getenv("FEMBRAIN_PIPE_HELP_MINLEN")) : 16;  // (development)
-      // FEMBRAIN_PIPE_LDS_BY_WIDTH=1 (measured and NOT the default): the workgroup's LDS dealt to its slices by width instead of in equal
-      // shares, so that every wavefront streams about the same number of slots (the 27-slot slices of a cut among slices of 15 would keep 17
-      // here instead of 5).  It is slower -- cut cube 21.9 against 20.1 us per iteration, Delaunay probe 22.0 against 18.6: a resident slot
-      // still gathers its x entries from L2 / the fabric, and the compiled loop over resident slots has 6 slots' gathers in flight where
-      // the hand-written stream never drains; on these meshes the product waits for gathers, not for matrix bytes.
-      const bool even_share = !(getenv("FEMBRAIN_PIPE_LDS_BY_WIDTH") && atoi(getenv("FEMBRAIN_PIPE_LDS_BY_WIDTH")) != 0);
-      // (with the node-by-node vector a resident slot's gathers cost a third of the lines, and slices that keep up to 12 slots in LDS instead
-      // of 6 pay: sliver-free unstructured probe 16.2 -> 14.4 us per iteration, Delaunay probe 16.25 -> 15.9; 18 buys nothing more)
-      // -- from 6 slices per CU on: with fewer, idle wavefronts split the streams (helpers) and a long LDS loop in the owner only delays them:
-      // 27,000 / 46,656 / 64,000-node lattices 11.0 / 12.2 / 13.5 us per iteration with 6 slots against 12.9 / 13.4 / 14.1 with 12
-      const int lds_cap = want_xyz && w >= 6 ? 12 : 6;
-      for (int b = 0; b < nb; b++) {
-        int first, count;
-        pipe_deal(h->pipe_wg_first_host.empty() ? nullptr : h->pipe_wg_first_host.data(), P.n_slices, nb, b, &first, &count);
-        int4* tk = &tasks[(size_t)b * kPipeTaskStride];
-        std::vector<int> wd(count), res(count);
-        for (int j = 0; j < count; j++) wd[j] = P.slice_off[first + j + 1] - P.slice_off[first + j];
-        // LDS-resident slots: equal shares (the plain kernel's deal), or by width: the lowest level L with sum_j max(0, wd_j - L) <= the
-        // workgroup's wavefront-slots -- every slice then streams min(wd, L) slots -- and what is left over one more for the first slices that
-        // still stream.  First with the helpers' hand-over area set aside; a workgroup that gets no helper is dealt again with all of it.
-        auto deal_lds = [&](int lds_slots) {
-          if (even_share) {
-            // (most slots of a slice in LDS: the unroll bound of the plain kernel, 6 -- or FEMBRAIN_PIPE_LDS_CAP, development: further groups of
-            // six run in the table-driven kernel's second loop)
-            const int cap = getenv("FEMBRAIN_PIPE_LDS_CAP") ? std::max(1, atoi(getenv("FEMBRAIN_PIPE_LDS_CAP"))) : lds_cap;
-            const int lbase = std::min(cap, lds_slots / std::max(count, 1)), lrem = lbase < cap ? std::min(count, lds_slots - lbase * count) : 0;
-            for (int j = 0; j < count; j++) res[j] = std::min(wd[j], lbase + (j < lrem ? 1 : 0));
-            return;
-          }
-          int L = 0, widest = 0;
-          for (int j = 0; j < count; j++) widest = std::max(widest, wd[j]);
-          for (L = 0; L <= widest; L++) {
-            int sum = 0;
-            for (int j = 0; j < count; j++) sum += std::max(0, wd[j] - L);
-            if (sum <= lds_slots) break;
-          }
-          int used = 0;
-          for (int j = 0; j < count; j++) { res[j] = std::max(0, wd[j] - L); used += res[j]; }
-          for (int j = 0; j < count && used < lds_slots; j++) if (res[j] < wd[j]) { res[j]++; used++; }
-        };
-        struct Stream { int wave, slice, k0, k1, floor; };
-        std::vector<Stream> st;
-        int n_h = 0;
-        auto deal_streams = [&]() {
-          st.clear();
-          n_h = 0;
-          for (int j = 0; j < kPipeTaskStride; j++) tk[j] = make_int4(-1, 0, 0, 0);
-          for (int j = 0; j < count; j++) st.push_back({j, j, 0, wd[j], res[j]});
-          std::vector<unsigned> mask(count, 0u);
-          for (int hw = count; want_h && hw < w + help_waves && n_h < kPipeMaxHelpers; hw++) {  // idle slice wavefronts first, then the extra ones
-            int best = -1, len = 0;
-            for (int i = 0; i < (int)st.size(); i++) {
-              const int l = st[i].k1 - std::max(st[i].k0, st[i].floor);  // what it streams
-              if (l > len) { len = l; best = i; }
-            }
-            if (best < 0 || len < min_len) break;
-            const int lo = std::max(st[best].k0, st[best].floor), mid = lo + (st[best].k1 - lo + 1) / 2;
-            const Stream up = {hw, st[best].slice, mid, st[best].k1, mid};
-            st[best].k1 = mid;
-            st.push_back(up);
-            tk[hw] = make_int4(up.slice, up.k0, up.k1, n_h);
-            mask[up.slice] |= 1u << n_h;  // the owner adds this helper's partial sums
-            n_h++;
-          }
-          for (const Stream& S : st) {
-            if (S.wave < count) tk[S.wave] = make_int4(res[S.wave], 0, S.k1, (int)mask[S.wave]);  // owner: resident slots, (their place: below), end of its own stream, its helpers
-            else { tk[S.wave].y = S.k0; tk[S.wave].z = S.k1; }                                   // (ends moved by later splits)
-          }
-          int at = 0;
-          for (int j = 0; j < count; j++) { tk[j].y = at; at += res[j]; }
-        };
-        deal_lds(lds_all - lds_help);
-        deal_streams();
-        if (n_h == 0) { deal_lds(lds_all); deal_streams(); }
-        for (int j = 0; j < count; j++) deepest = std::max(deepest, res[j]);
-        if (const char* dbg = getenv("FEMBRAIN_PIPE_HELP_DEBUG")) {  // development: 1 = owners keep their whole slice, helpers get empty ranges (their zero sums are still added); 2 = owners keep it all and add nothing, helpers work for nothing
-          for (int j = 0; j < count; j++) { tk[j].z = wd[j]; if (atoi(dbg) == 2) tk[j].w = 0; }
-          if (atoi(dbg) == 1) for (int hw = count; hw < kPipeTaskStride; hw++) if (tk[hw].x >= 0) tk[hw].y = tk[hw].z;
-        }
-        if (const char* tr = getenv("FEMBRAIN_PIPE_TRUNCATE"))  // development, WRONG RESULTS: owners stop n slots short of their slice -- what an iteration would cost with that many fewer streamed slots per slice (half storage)
-          for (int j = 0; j < count; j++) tk[j].z = std::max(tk[j].x, tk[j].z - atoi(tr));
-        most = std::max(most, n_h);
-        all += n_h;
-      }
-      if (all > 0 || deepest > 6 || want_xyz || (eh && atoi(eh) == 2)) {  // (=2, development: the task table without a single helper)
-        FB_TRY(h->pipe_tasks.upload(tasks, s));
-        h->pipe_wmax = 12;
-        h->pipe_klt = deepest;
-        h->pipe_help_waves = help_waves; h->pipe_n_help = most; h->pipe_help_tasks = all;
-        h->pipe_xyz = want_xyz;
-        if (getenv("FEMBRAIN_TIMING")) fprintf(stderr, "[fembrain] persistent solver: %d helper tasks (at most %d per workgroup), widest slice %d slots, mean %.1f, up to %d slots of a slice in LDS; a slot's gathers touch %.1f lines in planes, %.1f node by node -> %s\n", all, most, mx, mean, deepest, h->pipe_gather_lines[0], h->pipe_gather_lines[1], want_xyz ? "node by node" : "planes");
-      }
-    }
-  }
-  FB_TRY(h->pipe_post.alloc((size_t)2 * nb * 4));
-  zb.add(h->pipe_post);
-  h->pipe_flag_extra = P.n_ranks > 1 ? kP2PMaxRanks : 0;
-  FB_TRY(h->pipe_flags.alloc((size_t)nb + h->pipe_flag_extra + 16));
-  zb.add(h->pipe_flags);
-  const size_t n_pad = (size_t)P.n_slices * 64, nv = (size_t)3 * P.n_local + 2;
-  FB_TRY(h->pipe_planes.alloc(2 * 3 * n_pad));
-  zb.add(h->pipe_planes);
-  FB_TRY(h->pipe_z.alloc(nv));
-  FB_TRY(h->pipe_s.alloc(nv));
-  FB_TRY(h->pipe_state.alloc(2));
-  zb.add(h->pipe_state);
-  if (getenv("FEMBRAIN_PERSIST_TIMING")) {
-    FB_TRY(h->persist_timing.alloc((size_t)nb * kPipeMaxWaves * 6));
-    FB_TRY(h->persist_timing.zero(s));
-  } else {
-    h->persist_timing.release();
-  }
-  // producer lists: the workgroups that own the rows this workgroup's columns lie in, exactly (k_slice_producers)
-  static_assert(kPipeMaxBlocks <= 256, "k_slice_producers holds 256 workgroups in its 8 mask words");
-  const bool poll_all = getenv("FEMBRAIN_PERSIST_POLL_ALL") && atoi(getenv("FEMBRAIN_PERSIST_POLL_ALL")) != 0;  // development aid
-  FB_TRY(h->pipe_owner.alloc((size_t)std::max(1, P.n_slices)));
-  FB_TRY(h->pipe_mask.alloc((size_t)std::max(1, P.n_slices) * 8));
-  FB_TRY(h->pipe_prod.alloc((size_t)nb * kPipeMaxProducers));
-  FB_TRY(h->pipe_prod_count.alloc((size_t)nb));
-  FB_TRY(h->pipe_prod_xcd.alloc((size_t)nb));
-  FB_TRY(h->pipe_stats.alloc(2));
-  zb.add(h->pipe_stats);
-  FB_TRY(zb.flush());
-  hipLaunchKernelGGL(k_slice_owner, dim3(ceil_div(nb, kBlock)), dim3(kBlock), 0, s, P.n_slices, nb, h->pipe_wg_first.p, h->pipe_owner.p);
-  hipLaunchKernelGGL(k_slice_producers, dim3(ceil_div(std::max(1, P.n_slices), kWavesPerBlock)), dim3(kBlock), 0, s, P.n_slices, P.n_owned, h->slice_off.p, h->colidx.p,
-                     h->pipe_owner.p, h->pipe_mask.p);
-  hipLaunchKernelGGL(k_wg_producers, dim3(ceil_div(nb, kBlock)), dim3(kBlock), 0, s, P.n_slices, nb, h->pipe_wg_first.p, h->pipe_mask.p, poll_all ? 1 : 0, h->pipe_prod.p, h->pipe_prod_count.p,
-                     h->pipe_prod_xcd.p, h->pipe_stats.p);
-  FB_HIP(hipGetLastError());
-  h->pipe_stats_pending = true;  // (the longest list is fetched when fb_fem_pcg_path asks)
-  h->pipe_max_producers = 0;
-  FB_TRY(h->pipe_xcc.alloc((size_t)nb));
-  zb.add(h->pipe_xcc);
-  FB_TRY(zb.flush());
-  {
-    // interior workgroups publish with plain stores where the iteration is latency-bound (measured, us per iteration with / without:
-    // 9.5 / 10.2 at 466 slices, 9.5 / 9.9 at 1,000; 17.4 / 17.1 at 2,744 = 1M tets, where the matrix stream evicts the lines from
-    // L2 anyway): up to 8 slices per CU.  FEMBRAIN_PIPE_PLAIN_STORES=0/1 overrides.
-    const char* e = getenv("FEMBRAIN_PIPE_PLAIN_STORES");
-    h->pipe_plain_local = e ? atoi(e) : (w <= 8 ? 1 : 0);
-  }
-  return setup_pipe_mirror(h);
 }
 
 int upload_plan(fb_fem_s* h, const double* xyz_global, const float* xyz_device = nullptr, const double* xyz_device64 = nullptr) {
@@ -1143,6 +431,8 @@ int launch_rows(fb_fem_s* h, const AsmParams& ap, const double* qvel, const doub
 }
 
 // pass 1 + pass 2 of the system of the current state (Keff, rhs, invdiag)
+}  // namespace
+namespace fb {
 int assemble_system(fb_fem_s* h) {
   const double hh = h->prm.timestep, cM = h->prm.damping_mass, cK = h->prm.damping_stiffness;
   FB_TRY(halo_exchange(h, h->q.p));
@@ -1173,6 +463,8 @@ int assemble_system(fb_fem_s* h) {
   h->system_valid = true;
   return FB_OK;
 }
+}  // namespace fb
+namespace {
 
 template <typename MT, int MODE>
 int launch_spmv(fb_fem_s* h, const double* x, double* y, const double* b, double* partial, int parity) {
@@ -1391,173 +683,6 @@ bool host_finished(const CGState& s) {
 
 // Jacobi-PCG on the assembled system, rhs b -> h->x.  iters_out: + converged / - not (CGSolver.cpp:189).
 
-// One launch of the pipelined persistent solver (pcg_pipe.hip.h): `start` 1 = new solve from x = 0, 2 = new solve from the x in
-// memory, 0 = continue; at most n_iters iterations
-// 9 or 10 slices per CU in the plain 12-wavefront kernel: the LDS has room for 7 slots of a slice (65 / 9), one more than the (12, 6)
-// instantiation's unroll bound takes -- the (12, 7) instantiation is the same kernel with that bound (unsharded Jacobi handles without the
-// task table; FEMBRAIN_PIPE_KLT7=0 keeps (12, 6))
-static bool pipe_klt7(const fb_fem_s* h) {
-  const char* e = getenv("FEMBRAIN_PIPE_KLT7");
-  return h->persist && !h->shard_persist && h->pipe_rows == 1 && h->pipe_wmax == 12 && !h->pipe_tasks.p && h->prm.pcg_variant != FB_PCG_BLOCK_JACOBI &&
-         (h->persist_waves == 9 || h->persist_waves == 10) && !getenv("FEMBRAIN_PERSIST_TIMING") && !(e && atoi(e) == 0);
-}
-int launch_pipe(fb_fem_s* h, const double* b, int start, int n_iters, double eps, int max_iter) {
-  PipeArgs pa;
-  pa.post = h->pipe_post.p; pa.flags = h->pipe_flags.p; pa.error = h->pipe_flags.p + h->persist_blocks + h->pipe_flag_extra + 4; pa.seqs = h->pipe_flags.p + h->persist_blocks + h->pipe_flag_extra + 8;
-  pa.producers = h->pipe_prod.p; pa.prod_count = h->pipe_prod_count.p; pa.prod_xcd = h->pipe_prod_xcd.p; pa.plain_local = h->pipe_plain_local; pa.xcc = h->pipe_xcc.p;
-  pa.start = start; pa.n_iters = n_iters; pa.eps2 = eps * eps; pa.max_iter = max_iter;
-  pa.timeout_ticks = h->persist_timeout_ticks;
-  pa.timing = h->persist_timing.p;
-  pa.planes = h->pipe_planes.p; pa.n_pad = h->shard_persist ? (size_t)ceil_div(h->plan.n_local, 64) * 64 : (size_t)h->plan.n_slices * 64;
-  pa.pstate = h->pipe_state.p;
-  pa.tasks = h->pipe_tasks.p; pa.n_help = h->pipe_n_help;
-  pa.wg_first = h->pipe_wg_first.p;
-  // the LDS window, where the instantiation launched below is the one it was planned for
-  const bool mir = h->pipe_mir.p && h->pipe_mir_klt == (pa.timing ? 6 : (pipe_klt7(h) ? 7 : 6));
-  pa.mirror = mir ? h->pipe_mir.p : nullptr; pa.mir_addr = h->pipe_mir_addr.p; pa.mir_wg = h->pipe_mir_wg.p; pa.mir_pool = h->pipe_mir_pool.p;
-  // LDS: the sync buffers, then KLT slots of every slice; the request is the whole 160 KB of a CU, so exactly one workgroup lands on each
-  const size_t lds = 160 * 1024;
-  // one wavefront more than slices where the instantiation has room: it collects the sums while the others multiply
-  const bool want_service = !(getenv("FEMBRAIN_PIPE_SERVICE_WAVE") && atoi(getenv("FEMBRAIN_PIPE_SERVICE_WAVE")) == 0);
-  const int cwaves = h->pipe_rows == 2 ? ceil_div(h->persist_waves, 2) : h->persist_waves;  // wavefronts that own slices
-  pa.service = (h->shard_persist || want_service) && cwaves + h->pipe_help_waves < h->pipe_wmax ? 1 : 0;
-  // values of the first streamed slots pulled into L2 during the neighbour wait: pays where the product is bandwidth-bound (9 and more
-  // slices per CU: -6 % per iteration at 1M tets; neutral at 1,000 slices).  FEMBRAIN_PIPE_PREFETCH=0..4 overrides.
-  const int prefetch = getenv("FEMBRAIN_PIPE_PREFETCH") ? std::max(0, std::min(4, atoi(getenv("FEMBRAIN_PIPE_PREFETCH")))) : -1;
-  pa.prefetch_slots = prefetch >= 0 ? prefetch : (h->persist_waves >= 9 ? (h->pipe_rows == 2 ? 3 : 4) : 0);
-  const dim3 grid(h->persist_blocks), block(64 * (cwaves + h->pipe_help_waves + pa.service));  // slices | helpers | the service wavefront
-  FB_HIP(hipEventRecord(h->ev_p[0], h->stream));
-  ShardArgs sa;
-  memset(&sa, 0, sizeof sa);
-  if (h->shard_persist) {
-    sa.rank = h->plan.rank; sa.n_ranks = h->plan.n_ranks; sa.n_owned = h->plan.n_owned; sa.n_halo = h->plan.n_local - h->plan.n_owned;
-    sa.box = h->sbox; sa.peer_box = h->sbox_peers.p; sa.peer_seg = h->sh_peer_seg.p; sa.halo_cap = h->sbox_halo_cap;
-    sa.halo_off = h->sh_halo_off.p; sa.row_send_off = h->sh_row_send_off.p; sa.row_send_rank = h->sh_row_send_rank.p; sa.row_send_pos = h->sh_row_send_pos.p;
-    sa.wg_send_mask = h->sh_wg_send_mask.p; sa.n_senders = h->sh_n_senders.p; sa.proxy_wg = h->sh_proxy_wg.p; sa.n_proxy = h->sh_n_proxy; sa.wg_duty = h->sh_wg_duty.p; sa.wg_range = h->sh_wg_range.p;
-    sa.delay_ticks = remote_delay_ticks();
-  }
-  // (the attribute is per device and cheap to set: set at every launch)
-#define FB_PIPE(C16, WMAX, KLT, TIMING, SHARD)                                                                                                        \
-  do {                                                                                                                                                \
-    FB_HIP(hipFuncSetAttribute((const void*)k_pcg_pipe<float, C16, WMAX, KLT, TIMING, SHARD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    hipLaunchKernelGGL((k_pcg_pipe<float, C16, WMAX, KLT, TIMING, SHARD>), grid, block, lds, h->stream, sell_view(h), (const float*)h->vals.p,       \
-                       (const float*)h->dlo.p, h->invdiag.p, b, h->x.p, h->r.p, h->Ad.p, h->pipe_z.p, h->pipe_s.p, h->d.p, h->st.p, pa, sa);          \
-  } while (0)
-#define FB_PIPE_HELP(C16, TIMING, XYZ)                                                                                                                \
-  do {                                                                                                                                                \
-    FB_HIP(hipFuncSetAttribute((const void*)k_pcg_pipe<float, C16, 12, 6, TIMING, false, false, true, XYZ>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                               (int)lds));                                                                                                           \
-    hipLaunchKernelGGL((k_pcg_pipe<float, C16, 12, 6, TIMING, false, false, true, XYZ>), grid, block, lds, h->stream, sell_view(h),                  \
-                       (const float*)h->vals.p, (const float*)h->dlo.p, h->invdiag.p, b, h->x.p, h->r.p, h->Ad.p, h->pipe_z.p, h->pipe_s.p, h->d.p, \
-                       h->st.p, pa, sa);                                                                                                             \
-  } while (0)
-#define FB_PIPE_BJ(C16, WMAX, KLT)                                                                                                                     \
-  do {                                                                                                                                                \
-    FB_HIP(hipFuncSetAttribute((const void*)k_pcg_pipe<float, C16, WMAX, KLT, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,       \
-                               (int)lds));                                                                                                           \
-    hipLaunchKernelGGL((k_pcg_pipe<float, C16, WMAX, KLT, false, false, true>), grid, block, lds, h->stream, sell_view(h), (const float*)h->vals.p,  \
-                       (const float*)h->dlo.p, h->invblk.p, b, h->x.p, h->r.p, h->Ad.p, h->pipe_z.p, h->pipe_s.p, h->d.p, h->st.p, pa, sa);           \
-  } while (0)
-#define FB_PIPE2(C16, SHARD, XYZ)                                                                                                                     \
-  do {                                                                                                                                                \
-    FB_HIP(hipFuncSetAttribute((const void*)k_pcg_pipe2<C16, SHARD, XYZ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                     \
-    hipLaunchKernelGGL((k_pcg_pipe2<C16, SHARD, XYZ>), grid, block, lds, h->stream, sell_view(h), (const float*)h->vals.p, (const float*)h->dlo.p,   \
-                       h->invdiag.p, b, h->x.p, h->r.p, h->Ad.p, h->pipe_z.p, h->pipe_s.p, h->d.p, h->st.p, pa, sa);                                  \
-  } while (0)
-  static_assert(sizeof(double) * kPipeSyncDoubles + (size_t)kPipeMaxWaves * 2 * kPipe2LdsWordsPerRow * 64 * 4 <= 160 * 1024, "LDS budget of k_pcg_pipe2");
-  // the instantiations: (wavefronts, most LDS slots per wavefront) = (8, 8) up to 8 slices per CU, (12, 6) up to 12; 16- or 32-bit column words;
-  // two rows per lane (k_pcg_pipe2) for 13..24 slices per CU; SHARD = true on a sharded handle (32-bit local column ids)
-  if (h->prm.pcg_variant == FB_PCG_BLOCK_JACOBI) {  // (setup_persist: unsharded, one row per lane)
-    if (pa.timing) return fail(FB_EINVAL, "FEMBRAIN_PERSIST_TIMING is built for the Jacobi kernel");
-    if (h->pipe_wmax == 8) { if (h->c16) FB_PIPE_BJ(true, 8, 8); else FB_PIPE_BJ(false, 8, 8); }
-    else { if (h->c16) FB_PIPE_BJ(true, 12, 6); else FB_PIPE_BJ(false, 12, 6); }
-  } else if (h->shard_persist) {
-    if (h->pipe_rows == 2) FB_PIPE2(false, true, false);
-    else if (h->pipe_wmax == 8) FB_PIPE(false, 8, 8, false, true);
-    else FB_PIPE(false, 12, 6, false, true);
-  } else if (h->pipe_rows == 2) {
-    if (h->pipe_xyz) { if (h->c16) FB_PIPE2(true, false, true); else FB_PIPE2(false, false, true); }
-    else { if (h->c16) FB_PIPE2(true, false, false); else FB_PIPE2(false, false, false); }
-  } else if (h->pipe_tasks.p) {  // helper wavefronts (setup_persist): the (12, 6) kernel compiled with them
-    if (h->pipe_xyz) {  // (the published vector node by node)
-      if (pa.timing) { if (h->c16) FB_PIPE_HELP(true, true, true); else FB_PIPE_HELP(false, true, true); }
-      else { if (h->c16) FB_PIPE_HELP(true, false, true); else FB_PIPE_HELP(false, false, true); }
-    } else {
-      if (pa.timing) { if (h->c16) FB_PIPE_HELP(true, true, false); else FB_PIPE_HELP(false, true, false); }
-      else { if (h->c16) FB_PIPE_HELP(true, false, false); else FB_PIPE_HELP(false, false, false); }
-    }
-  } else if (pa.timing) {  // development build with the phase clocks: the 1M-tet configuration and the small one
-    if (h->pipe_wmax == 12 && h->c16) FB_PIPE(true, 12, 6, true, false);
-    else if (h->pipe_wmax == 12) FB_PIPE(false, 12, 6, true, false);
-    else if (h->pipe_wmax == 5 && h->c16) FB_PIPE(true, 5, 16, true, false);
-    else if (h->pipe_wmax == 8 && h->c16) FB_PIPE(true, 8, 8, true, false);
-    else if (h->pipe_wmax == 8) FB_PIPE(false, 8, 8, true, false);
-    else return fail(FB_EINVAL, "FEMBRAIN_PERSIST_TIMING is built for one row per lane: (12, 6) and (5, 16) with 16-bit column words, (8, 8)");
-  } else if (h->pipe_wmax == 5) { if (h->c16) FB_PIPE(true, 5, 16, false, false); else FB_PIPE(false, 5, 16, false, false); }
-  else if (h->pipe_wmax == 8) { if (h->c16) FB_PIPE(true, 8, 8, false, false); else FB_PIPE(false, 8, 8, false, false); }
-  else if (pipe_klt7(h)) { if (h->c16) FB_PIPE(true, 12, 7, false, false); else FB_PIPE(false, 12, 7, false, false); }
-  else { if (h->c16) FB_PIPE(true, 12, 6, false, false); else FB_PIPE(false, 12, 6, false, false); }
-#undef FB_PIPE2
-#undef FB_PIPE_BJ
-#undef FB_PIPE_HELP
-#undef FB_PIPE
-  FB_HIP(hipGetLastError());
-  FB_HIP(hipEventRecord(h->ev_p[1], h->stream));
-  return FB_OK;
-}
-
-void print_pipe_timing(fb_fem_s* h) {
-  std::vector<long long> tm((size_t)h->persist_blocks * kPipeMaxWaves * 6);
-  if (h->persist_timing.download(tm.data(), tm.size(), h->stream) != FB_OK) return;
-  (void)h->persist_timing.zero(h->stream);
-  const char* names[5] = {"publish (drained)", "flag+wait+acquire", "product", "sums sweep", "recurrences(+refresh)"};
-  for (int k = 0; k < 5; k++) {
-    double mn = 1e30, mx = 0, av = 0;
-    int cnt = 0;
-    for (int b = 0; b < h->persist_blocks; b++)
-      for (int w = 0; w < h->persist_waves; w++) {
-        const long long* t = &tm[((size_t)b * kPipeMaxWaves + w) * 6];
-        if (t[5] <= 0) continue;
-        const double us = (double)t[k] / (double)t[5] * 0.01;
-        mn = std::min(mn, us); mx = std::max(mx, us); av += us; cnt++;
-      }
-    fprintf(stderr, "[fembrain] pipelined PCG %-22s per iteration: avg %.2f us  min %.2f  max %.2f (over %d waves)\n", names[k], av / std::max(cnt, 1), mn, mx, cnt);
-  }
-  if (getenv("FEMBRAIN_PERSIST_TIMING") && atoi(getenv("FEMBRAIN_PERSIST_TIMING")) >= 2) {
-    // where the slow products are: by wavefront index, by XCD (workgroup & 7), and the slowest workgroups
-    for (int k = 1; k <= 2; k++) {
-      fprintf(stderr, "[fembrain] %s by wavefront:", names[k]);
-      for (int w = 0; w < h->persist_waves; w++) {
-        double av = 0; int cnt = 0;
-        for (int b = 0; b < h->persist_blocks; b++) { const long long* t = &tm[((size_t)b * kPipeMaxWaves + w) * 6]; if (t[5] > 0) { av += (double)t[k] / (double)t[5] * 0.01; cnt++; } }
-        fprintf(stderr, " %.2f", av / std::max(cnt, 1));
-      }
-      fprintf(stderr, "\n[fembrain] %s by XCD (avg / max over its workgroups' slowest wavefront):", names[k]);
-      for (int x = 0; x < 8; x++) {
-        double av = 0, mx = 0; int cnt = 0;
-        for (int b = x; b < h->persist_blocks; b += 8) {
-          double wmx = 0;
-          for (int w = 0; w < h->persist_waves; w++) { const long long* t = &tm[((size_t)b * kPipeMaxWaves + w) * 6]; if (t[5] > 0) wmx = std::max(wmx, (double)t[k] / (double)t[5] * 0.01); }
-          av += wmx; mx = std::max(mx, wmx); cnt++;
-        }
-        fprintf(stderr, " %.2f/%.2f", av / std::max(cnt, 1), mx);
-      }
-      fprintf(stderr, "\n");
-    }
-    std::vector<std::pair<double, int>> slow;
-    for (int b = 0; b < h->persist_blocks; b++) {
-      double wmx = 0;
-      for (int w = 0; w < h->persist_waves; w++) { const long long* t = &tm[((size_t)b * kPipeMaxWaves + w) * 6]; if (t[5] > 0) wmx = std::max(wmx, (double)t[2] / (double)t[5] * 0.01); }
-      slow.push_back({wmx, b});
-    }
-    std::sort(slow.begin(), slow.end());
-    fprintf(stderr, "[fembrain] slowest product of a workgroup: median %.2f us, fastest", slow[slow.size() / 2].first);
-    for (int k = 0; k < 6 && k < (int)slow.size(); k++) fprintf(stderr, " wg%d %.2f", slow[k].second, slow[k].first);
-    fprintf(stderr, "; slowest");
-    for (int k = 0; k < 12 && k < (int)slow.size(); k++) fprintf(stderr, " wg%d %.2f", slow[slow.size() - 1 - k].second, slow[slow.size() - 1 - k].first);
-    fprintf(stderr, "\n");
-  }
-}
 
 int pcg_solve(fb_fem_s* h, const double* b, double eps, int max_iter, int* iters_out, CGState* final_state, bool allow_persist = true);
 
@@ -1573,16 +698,16 @@ int pcg_solve_pipe(fb_fem_s* h, const double* b, double eps, int max_iter, int* 
   memset(&fin, 0, sizeof fin);
   for (;;) {
     FB_TRY(launch_pipe(h, b, start, cut, eps, max_iter));
-    h->persist_launches++;
+    h->ps.persist_launches++;
     unsigned int err = 0;
     FB_HIP(hipMemcpyAsync(&h->st_host[0], h->st.p, sizeof(CGState), hipMemcpyDeviceToHost, s));
-    FB_HIP(hipMemcpyAsync(&err, h->pipe_flags.p + h->persist_blocks + h->pipe_flag_extra + 4, sizeof err, hipMemcpyDeviceToHost, s));
+    FB_HIP(hipMemcpyAsync(&err, h->ps.pipe_flags.p + h->ps.persist_blocks + h->ps.pipe_flag_extra + 4, sizeof err, hipMemcpyDeviceToHost, s));
     FB_HIP(hipStreamSynchronize(s));
     {
       float ms = 0;
-      if (hipEventElapsedTime(&ms, h->ev_p[0], h->ev_p[1]) == hipSuccess) h->persist_seconds += ms * 1e-3;
+      if (hipEventElapsedTime(&ms, h->ev_p[0], h->ev_p[1]) == hipSuccess) h->ps.persist_seconds += ms * 1e-3;
     }
-    if (h->shard_persist) {  // a time-out on any rank sends every rank to the two-launch solver, together
+    if (h->ps.shard_persist) {  // a time-out on any rank sends every rank to the two-launch solver, together
       std::vector<unsigned int> errs((size_t)h->plan.n_ranks);
       FB_TRY(comm_allgather_bytes(h->comm, &err, errs.data(), sizeof err, s));
       for (unsigned int e2 : errs) err |= e2;
@@ -1591,28 +716,28 @@ int pcg_solve_pipe(fb_fem_s* h, const double* b, double eps, int max_iter, int* 
       // A wait inside the launch gave up: the workgroups were not all resident (the device is shared with another process's
       // kernels?).  The launch wrote nothing back, so the solve is repeated from the same start with a launch per phase, and
       // this handle stays with that; fb_step_info.pcg_path / persist_fallbacks tell the host.
-      FB_TRY(h->pipe_flags.zero(s));
-      FB_TRY(h->pipe_post.zero(s));
-      h->persist = false;
-      h->persist_broken = true;
-      h->persist_fallbacks++;
-      h->clean_solves = 0;
-      if (h->persist_fallbacks > 1) h->rearm_after = std::min(h->rearm_after * 2, 1 << 20);
+      FB_TRY(h->ps.pipe_flags.zero(s));
+      FB_TRY(h->ps.pipe_post.zero(s));
+      h->ps.persist = false;
+      h->ps.persist_broken = true;
+      h->ps.persist_fallbacks++;
+      h->ps.clean_solves = 0;
+      if (h->ps.persist_fallbacks > 1) h->ps.rearm_after = std::min(h->ps.rearm_after * 2, 1 << 20);
       if (getenv("FEMBRAIN_PERSIST_STRICT") && atoi(getenv("FEMBRAIN_PERSIST_STRICT")) != 0)
-        return fail(FB_EDEVICE, "persistent PCG: a wait inside the launch timed out after %.1f ms (the workgroups were not all resident?)", h->persist_timeout_ticks * 1e-5);
-      fprintf(stderr, "[fembrain] persistent PCG: a wait timed out after %.1f ms; this handle falls back to the two-launch iteration\n", h->persist_timeout_ticks * 1e-5);
+        return fail(FB_EDEVICE, "persistent PCG: a wait inside the launch timed out after %.1f ms (the workgroups were not all resident?)", h->ps.persist_timeout_ticks * 1e-5);
+      fprintf(stderr, "[fembrain] persistent PCG: a wait timed out after %.1f ms; this handle falls back to the two-launch iteration\n", h->ps.persist_timeout_ticks * 1e-5);
       h->pcg_warm = warm;
       const int rc = pcg_solve(h, b, eps, max_iter, iters_out, final_state, false);
       h->last_pcg_path = FB_PCG_PATH_FALLBACK;
       return rc;
     }
-    h->persist_iterations += h->st_host[0].iter - (start == 0 ? fin.iter : 0);
+    h->ps.persist_iterations += h->st_host[0].iter - (start == 0 ? fin.iter : 0);
     fin = h->st_host[0];
     if (fin.done) break;
     if (fin.iter > max_iter) return fail(FB_EDEVICE, "internal: persistent PCG ran past max_iter (iter %d)", fin.iter);
     start = 0;
   }
-  if (h->persist_timing.p && h->pipe_rows == 1) print_pipe_timing(h);
+  if (h->ps.persist_timing.p && h->ps.pipe_rows == 1) print_pipe_timing(h);
   h->last_pcg_path = FB_PCG_PATH_PERSISTENT;
   const double rho = fin.rho[fin.iter & 1];
   const bool converged = !(rho > fin.eps2 * fin.rho0);
@@ -1665,17 +790,17 @@ int pcg_solve_pipe(fb_fem_s* h, const double* b, double eps, int max_iter, int* 
 constexpr double kPersistMinEps = 1e-8;
 
 int pcg_solve(fb_fem_s* h, const double* b, double eps, int max_iter, int* iters_out, CGState* final_state, bool allow_persist) {
-  if (allow_persist && !h->persist && h->persist_broken && !h->shard_persist && h->plan.n_ranks == 1 && h->rearm_after > 0 && h->clean_solves >= h->rearm_after) {
-    h->persist = true;  // the set-up of the persistent solver is still in place (flags and sums were cleared when it fell back)
-    h->persist_broken = false;
-    h->persist_rearms++;
+  if (allow_persist && !h->ps.persist && h->ps.persist_broken && !h->ps.shard_persist && h->plan.n_ranks == 1 && h->ps.rearm_after > 0 && h->ps.clean_solves >= h->ps.rearm_after) {
+    h->ps.persist = true;  // the set-up of the persistent solver is still in place (flags and sums were cleared when it fell back)
+    h->ps.persist_broken = false;
+    h->ps.persist_rearms++;
     read_persist_timeout(h);
-    fprintf(stderr, "[fembrain] persistent PCG: re-armed after %d two-launch solves\n", h->clean_solves);
+    fprintf(stderr, "[fembrain] persistent PCG: re-armed after %d two-launch solves\n", h->ps.clean_solves);
   }
-  if (allow_persist && h->persist && eps >= kPersistMinEps &&
+  if (allow_persist && h->ps.persist && eps >= kPersistMinEps &&
       (h->prm.pcg_variant == FB_PCG_MERGED || h->prm.pcg_variant == FB_PCG_PERSISTENT || h->prm.pcg_variant == FB_PCG_BLOCK_JACOBI))
     return pcg_solve_pipe(h, b, eps, max_iter, iters_out, final_state);
-  if (allow_persist && h->persist_broken) h->clean_solves++;
+  if (allow_persist && h->ps.persist_broken) h->ps.clean_solves++;
   h->last_pcg_path = FB_PCG_PATH_TWO_LAUNCH;
   // The merged recurrence for rho (rho' = rho - 2 alpha S1 + alpha^2 S2) loses digits the literal sum r.r/diag keeps: measured on
   // the 17,576-node cube it stalls above 1e-12 where the literal sequence converges.  Tolerances below kPersistMinEps therefore run
@@ -2067,73 +1192,6 @@ int build(fb_fem_s* h, int n_nodes, const double* xyz, int n_tets, const int* te
   return FB_OK;
 }
 
-// The collective half: every rank allocates its box, the ranks exchange the IPC handles, the halo sizes and how many of their
-// workgroups send to whom, map each other's boxes, and agree that all of it worked -- otherwise every rank alike runs the
-// two-launch iteration.
-int attach_pipe_shard(fb_fem_s* h) {
-  const FemPlan& P = h->plan;
-  const int R = P.n_ranks, me = P.rank;
-  if (R < 2 || !h->comm) return FB_OK;
-  if (!(getenv("FEMBRAIN_SHARDED_PERSIST") && atoi(getenv("FEMBRAIN_SHARDED_PERSIST")) != 0)) return FB_OK;  // (the same on every rank)
-  {  // a re-sync: the previous box and mappings go first
-    const bool keep = h->shard_persist;
-    release_shard_persist(h);
-    h->shard_persist = keep;
-  }
-  struct Meta { hipIpcMemHandle_t handle; long long n_halo; int halo_off[kP2PMaxRanks + 1]; int senders_to[kP2PMaxRanks]; int ok; };
-  Meta mine;
-  memset(&mine, 0, sizeof mine);
-  bool ok = h->shard_persist && R <= kP2PMaxRanks;
-  // the box is sized by the largest halo of all ranks, so a first round agrees on that
-  long long nh = ok ? P.n_local - P.n_owned : -1;
-  std::vector<long long> nhs((size_t)R);
-  FB_TRY(comm_allgather_bytes(h->comm, &nh, nhs.data(), sizeof nh, h->stream));
-  long long cap = 1;
-  for (int q = 0; q < R; q++) { if (nhs[q] < 0) ok = false; cap = std::max(cap, nhs[q]); }
-  const ShardBoxLayout BL = shard_box_layout(cap);
-  if (ok) {
-    ok = hipExtMallocWithFlags((void**)&h->sbox, BL.bytes, hipDeviceMallocFinegrained) == hipSuccess;
-    ok = ok && hipMemsetAsync(h->sbox, 0, BL.bytes, h->stream) == hipSuccess && hipStreamSynchronize(h->stream) == hipSuccess;
-    ok = ok && hipIpcGetMemHandle(&mine.handle, h->sbox) == hipSuccess;
-    (void)hipGetLastError();
-    mine.n_halo = P.n_local - P.n_owned;
-    for (int q = 0; q <= R; q++) mine.halo_off[q] = P.halo_off[q];
-    std::vector<unsigned int> wg_mask((size_t)h->persist_blocks);
-    ok = ok && h->sh_wg_send_mask.download(wg_mask.data(), wg_mask.size(), h->stream) == FB_OK;
-    for (unsigned int m : wg_mask)
-      for (int q = 0; q < R; q++) mine.senders_to[q] += (m >> q) & 1u;
-  }
-  mine.ok = ok ? 1 : 0;
-  std::vector<Meta> all((size_t)R);
-  FB_TRY(comm_allgather_bytes(h->comm, &mine, all.data(), sizeof(Meta), h->stream));
-  bool all_ok = true;
-  for (int q = 0; q < R; q++) all_ok = all_ok && all[q].ok;
-  int opened_ok = 1;
-  std::vector<char*> peers((size_t)R, nullptr);
-  std::vector<int> seg((size_t)R, 0), senders((size_t)R, 0);
-  if (all_ok) {
-    for (int q = 0; q < R; q++) {
-      seg[q] = all[q].halo_off[me];
-      senders[q] = all[q].senders_to[me];
-      if (q == me) { peers[q] = h->sbox; continue; }
-      void* ptr = nullptr;
-      if (hipIpcOpenMemHandle(&ptr, all[q].handle, hipIpcMemLazyEnablePeerAccess) != hipSuccess) { (void)hipGetLastError(); opened_ok = 0; break; }
-      h->sbox_opened[q] = ptr;
-      peers[q] = (char*)ptr;
-    }
-  }
-  std::vector<int> oks((size_t)R);
-  FB_TRY(comm_allgather_bytes(h->comm, &opened_ok, oks.data(), sizeof(int), h->stream));
-  for (int q = 0; q < R; q++) all_ok = all_ok && oks[q];
-  if (!all_ok) { release_shard_persist(h); h->persist = false; return FB_OK; }
-  h->sbox_halo_cap = cap;
-  FB_TRY(h->sbox_peers.upload(peers.data(), peers.size(), h->stream));
-  FB_TRY(h->sh_peer_seg.upload(seg, h->stream));
-  FB_TRY(h->sh_n_senders.upload(senders, h->stream));
-  h->persist = true;
-  if (getenv("FEMBRAIN_TIMING")) fprintf(stderr, "[fembrain] rank %d: sharded persistent solver attached (%d workgroups, up to %d slices per CU, %d fewer where halo rows are gathered, %d proxies per source rank, halo %lld of cap %lld)\n", me, h->persist_blocks, h->persist_waves, h->sh_relief, h->sh_n_proxy, (long long)(P.n_local - P.n_owned), cap);
-  return FB_OK;
-}
 
 // Collective, BEFORE the rank-local build: FB_RENUMBER_AUTO on a sharded handle ("the same contiguous-range rule after an
 // RCM / space-filling-curve renumbering").  Equal ranges of the caller's ids are slabs of the body only while the caller numbers plane
@@ -2307,10 +1365,6 @@ int create_common(fb_fem_t* out, int n_nodes, const double* xyz, int n_tets, con
   return FB_OK;
 }
 
-#define CHECK_HANDLE(h)                                                                                                        \
-  if (!(h)) return fail(FB_EINVAL, "null FEM handle");                                                                        \
-  if ((h)->poisoned) return fail(FB_EINVAL, "handle unusable after a failed fb_fem_resync: re-sync it with a valid mesh or destroy it"); \
-  FB_HIP(hipSetDevice((h)->prm.device))
 
 // global-length host vector -> local device vector (owned + halo)
 int upload_global_vec(fb_fem_s* h, const double* g, DevBuf<double>& dst) {
@@ -2525,19 +1579,6 @@ int fb_fem_set_exchange_mode(fb_fem_t h, int mode) {
   return FB_OK;
 }
 
-int fb_fem_sharded_persist(fb_fem_t h) {
-  if (!h) return 0;
-  return h->shard_persist && h->persist ? 1 : 0;
-}
-
-int fb_fem_set_sharded_persist(fb_fem_t h, int on) {
-  CHECK_HANDLE(h);
-  if (!h->shard_persist || !h->sbox) return fail(FB_EINVAL, "the sharded persistent solver is not attached to this handle (FEMBRAIN_SHARDED_PERSIST=1 at creation, <= %d slices per CU)", 2 * (kPipeMaxWaves - 1));
-  if (on && h->persist_broken) return fail(FB_EDEVICE, "the sharded persistent solver of this handle timed out before; it stays with the two-launch iteration");
-  FB_HIP(hipStreamSynchronize(h->stream));
-  h->persist = on != 0;
-  return FB_OK;
-}
 
 // collective re-sync of a sharded handle; node_splits NULL keeps the handle's ranges when the node count is unchanged, else equal ranges
 static int resync_sharded(fb_fem_t h, int n_nodes, const double* xyz, int n_tets, const int* tets, int n_fixed_dofs, const int* fixed_dofs,
@@ -3129,7 +2170,7 @@ int newmark_step(fb_fem_s* h, fb_step_info* info) {
     info->rho0 = fin.rho0;
     info->rho = fin.rho[fin.iter & 1];
     info->pcg_path = h->last_pcg_path;
-    info->persist_fallbacks = h->persist_fallbacks;
+    info->persist_fallbacks = h->ps.persist_fallbacks;
     info->newton_iterations = newton;
   }
   if (!ok) return fail(FB_ESOLVER, "PCG sparse solver returned non-zero exit status %d", -total);
@@ -3179,7 +2220,7 @@ int fb_fem_step(fb_fem_t h, fb_step_info* info) {
     info->rho0 = fin.rho0;
     info->rho = fin.rho[fin.iter & 1];
     info->pcg_path = h->last_pcg_path;
-    info->persist_fallbacks = h->persist_fallbacks;
+    info->persist_fallbacks = h->ps.persist_fallbacks;
     info->newton_iterations = 1;
   }
   if (!ok) return fail(FB_ESOLVER, "PCG sparse solver returned non-zero exit status %d", iters);
@@ -3561,102 +2602,6 @@ int fb_fem_time_assembly(fb_fem_t h, int reps, double* seconds_per_assembly) {
   return FB_OK;
 }
 
-int fb_fem_persist_info(fb_fem_t h, int* waves_per_cu, int* workgroups, int* lds_slots) {
-  if (!h) return fail(FB_EINVAL, "null FEM handle");
-  if (waves_per_cu) *waves_per_cu = h->persist ? h->persist_waves : 0;
-  if (workgroups) *workgroups = h->persist ? h->persist_blocks : 0;
-  if (lds_slots) {
-    *lds_slots = 0;
-    if (h->persist) *lds_slots = h->pipe_klt;
-  }
-  return h->persist ? 1 : 0;
-}
-
-int fb_fem_pcg_path(fb_fem_t h, char* name, int name_len, int* persist_launches, int* persist_fallbacks, int* max_producers) {
-  if (!h) return fail(FB_EINVAL, "null FEM handle");
-  if (name && name_len > 0) {
-    if (h->persist && h->shard_persist && h->pipe_rows == 2) snprintf(name, name_len, "k_pcg_pipe2_shard");
-    else if (h->persist && h->shard_persist) snprintf(name, name_len, "k_pcg_pipe_shard<%d,%d>", h->pipe_wmax, h->pipe_wmax == 8 ? 8 : 6);
-    else if (h->persist && h->pipe_rows == 2) snprintf(name, name_len, "k_pcg_pipe2<%s>", h->c16 ? "c16" : "c32");
-    else if (h->persist)
-      snprintf(name, name_len, "k_pcg_pipe<float,%s,%d,%d%s>", h->c16 ? "c16" : "c32", h->pipe_wmax, h->pipe_wmax == 5 ? 16 : (h->pipe_wmax == 8 ? 8 : (pipe_klt7(h) ? 7 : 6)),
-               h->prm.pcg_variant == FB_PCG_BLOCK_JACOBI ? ",bj" : "");
-    else name[0] = 0;
-  }
-  if (persist_launches) *persist_launches = h->persist_launches;
-  if (persist_fallbacks) *persist_fallbacks = h->persist_fallbacks;
-  if (max_producers && h->persist && h->pipe_stats_pending) {
-    int st[2] = {0, 0};
-    FB_TRY(h->pipe_stats.download(st, 2, h->stream));
-    h->pipe_max_producers = st[1] ? -1 : st[0];
-    h->pipe_stats_pending = false;
-  }
-  if (max_producers) *max_producers = h->persist ? h->pipe_max_producers : 0;
-  return h->last_pcg_path;
-}
-
-int fb_fem_persist_rearms(fb_fem_t h) { return h ? h->persist_rearms : 0; }
-int fb_fem_persist_helpers(fb_fem_t h) { return h && h->persist ? h->pipe_help_tasks : 0; }
-int fb_fem_persist_mirror(fb_fem_t h, int* mirror_layers, int* pool_entries, int* plain_slots) {
-  if (!h) return fail(FB_EINVAL, "null FEM handle");
-  if (h->pipe_mir_pending) {
-    FB_TRY(h->pipe_mir_stats.download(h->pipe_mir_got, 3, h->stream));
-    h->pipe_mir_pending = false;
-  }
-  const bool on = h->persist && h->pipe_mir.p;
-  if (mirror_layers) *mirror_layers = on ? h->pipe_mir_got[0] : 0;
-  if (pool_entries) *pool_entries = on ? h->pipe_mir_got[1] : 0;
-  if (plain_slots) *plain_slots = on ? h->pipe_mir_got[2] : 0;
-  return on && h->pipe_mir_got[0] > 0 ? 1 : 0;
-}
-
-int fb_fem_persist_gather(fb_fem_t h, double* lines_planes, double* lines_records) {
-  if (lines_planes) *lines_planes = h && h->persist ? h->pipe_gather_lines[0] : 0.0;
-  if (lines_records) *lines_records = h && h->persist ? h->pipe_gather_lines[1] : 0.0;
-  return h && h->persist && h->pipe_xyz ? 1 : 0;
-}
-
-int fb_fem_persist_stats(fb_fem_t h, int* launches, double* seconds, long long* iterations) {
-  if (!h) return fail(FB_EINVAL, "null FEM handle");
-  if (launches) *launches = h->persist_launches;
-  if (seconds) *seconds = h->persist_seconds;
-  if (iterations) *iterations = h->persist_iterations;
-  return FB_OK;
-}
-
-int fb_fem_time_persist(fb_fem_t h, int reps, int n_iters, double* seconds_per_launch) {
-  CHECK_HANDLE(h);
-  if (reps < 1 || n_iters < 1 || n_iters > 100000 || !seconds_per_launch) return fail(FB_EINVAL, "bad arguments");
-  if (!h->persist) return fail(FB_EINVAL, "this handle does not run the persistent PCG iterations");
-  if (!h->system_valid) FB_TRY(assemble_system(h));
-  double total = 0.0;
-  for (int r = -1; r < reps; r++) {  // r = -1: warm-up
-    float ms = 0;
-    // a solve of the current right-hand side with a tolerance it cannot reach, cut after n_iters iterations
-    FB_HIP(hipEventRecord(h->ev[0], h->stream));
-    FB_TRY(launch_pipe(h, h->rhs.p, 1, n_iters, 1e-30, 1 << 30));
-    FB_HIP(hipEventRecord(h->ev[1], h->stream));
-    FB_HIP(hipStreamSynchronize(h->stream));
-    FB_HIP(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    if (r >= 0) total += ms * 1e-3;
-  }
-  unsigned int err = 0;
-  FB_HIP(hipMemcpy(&err, h->pipe_flags.p + h->persist_blocks + h->pipe_flag_extra + 4, sizeof err, hipMemcpyDeviceToHost));
-  if (err) {
-    FB_TRY(h->pipe_flags.zero(h->stream));
-    FB_TRY(h->pipe_post.zero(h->stream));
-    if (h->shard_persist) {
-      // the peers' cumulative box counters are ahead of the flags just cleared: this handle must not launch the sharded kernel again
-      // (ADVICE r3); its solves run the two-launch iteration until a re-sync attaches fresh boxes
-      h->persist = false;
-      h->persist_broken = true;
-    }
-    return fail(FB_EDEVICE, "persistent PCG: a wait inside the launch timed out");
-  }
-  h->system_valid = false;
-  *seconds_per_launch = total / reps;
-  return FB_OK;
-}
 
 int fb_fem_iteration_bytes(fb_fem_t h, double* bytes) {
   if (!h || !bytes) return fail(FB_EINVAL, "null argument");

@@ -1,4 +1,4 @@
-// Persistent PIPELINED Jacobi-PCG (included by fem.hip only): a whole solve of CGSolver.cpp:129-190 inside ONE launch, for
+// Persistent PIPELINED Jacobi-PCG (included by fem_persist.hip only): a whole solve of CGSolver.cpp:129-190 inside ONE launch, for
 // systems whose vectors fit on the chip.  One workgroup per CU owns a fixed run of SELL slices, one wavefront per slice, one
 // lane per block row; the lane keeps its row of x, r, w, z, s, p and 1/diag in REGISTERS for the whole solve.
 //
@@ -77,7 +77,7 @@ struct PipeArgs {
   // then take the upper part of a wide slice's slots.  tasks[b][wv] of a HELPER = (slice of the workgroup, first slot, end slot, its number
   // in the workgroup = its place in the LDS hand-over), slice -1 = no task; of the wavefront that OWNS a slice = (slots of the slice resident
   // in LDS, where in LDS (in wavefront-slots), end of what it streams itself, bit mask of the helpers whose partial sums it adds -- ascending:
-  // a fixed order).  The resident slots of a workgroup are dealt by WIDTH (fem.hip, setup_persist): the slices stream equal numbers of slots
+  // a fixed order).  The resident slots of a workgroup are dealt by WIDTH (pcg_pipe_plan.h, pipe_deal_lds): the slices stream equal numbers of slots
   // as far as the LDS goes, where the plain kernel gives every slice the same share.  nullptr: the plain kernel (every regular mesh).
   const int* wg_first;        // the deal of the slices to the workgroups balanced by slots (pipe_deal), or nullptr: equal numbers of slices
   const int4* tasks;          // [n_blocks][kPipeTaskStride]
@@ -135,7 +135,7 @@ __host__ __device__ inline void pipe_slices(int n_slices, int n_blocks, int b, i
 }
 
 // ... or, where the slices of a mesh differ much in width (hull nodes of a Delaunay mesh: 59 slots against 19 on average), from a table
-// the host has balanced by SLOTS (fem.hip setup_persist): a CU's product takes as long as the slots it streams, whoever streams them --
+// the host has balanced by SLOTS (pcg_pipe_plan.h pipe_deal_by_slots): a CU's product takes as long as the slots it streams, whoever streams them --
 // the workgroups of the hull took 18 us per product against 7.5 on average with an equal number of slices each (profiles/r05_delaunay_phase_table.txt).
 // wg_first: n_blocks + 1 first slices, ascending inside every XCD's share; nullptr: the formula above.
 __host__ __device__ inline void pipe_deal(const int* wg_first, int n_slices, int n_blocks, int b, int* first, int* count) {

@@ -1,6 +1,6 @@
 // The LDS window of the persistent solver's one-row kernel (k_pcg_pipe, (12, 6) and (12, 7)): which slot layers of a slice are kept in LDS, and
 // which of them are read as the transpose of another row's block instead of being stored again.  Host and device use the same functions
-// (fem.hip: k_pipe_mirror_plan; plan_api.cpp: the host model the CPU suite checks).
+// (fem_persist.hip: k_pipe_mirror_plan; plan_api.cpp: the host model the CPU suite checks).
 //
 // A = A^T bitwise, and a workgroup owns a contiguous run of slices: where a row's block (r, c) has its column in a row of
 // the SAME workgroup below it (the -1, -55, -56 neighbours of the cube), the block (c, r) = (r, c)^T is one of that row's upper blocks, which the

@@ -59,7 +59,7 @@ struct ShardArgs {
   int n_proxy;                        // proxies per source rank: proxy (s, k) copies the k-th chunk of rank s's segment
   const int* proxy_wg;                // [n_ranks * n_proxy] the workgroup whose spare wavefront is proxy (s, k) (-1: nothing to copy)
   const int* wg_duty;                 // [n_blocks * kShardDuties] the proxies (s * n_proxy + k) of every workgroup, -1 padded
-  const int2* wg_range;               // [n_blocks] first slice and slice count of every workgroup (those that gather halo rows get fewer: fem.hip)
+  const int2* wg_range;               // [n_blocks] first slice and slice count of every workgroup (those that gather halo rows get fewer: pcg_pipe_plan.h shard_deal)
   long long delay_ticks;              // development (FEMBRAIN_REMOTE_DELAY_US, p2p_device.hip.h remote_delay)
 };
 constexpr int kShardProxies = 16;     // at most, per source rank

@@ -92,7 +92,7 @@ int fb_plan_shard_vote(int n_nodes, int n_tets, const int* tets, int n_ranks, in
   return FB_OK;
 }
 
-// Host model of k_pipe_mirror_plan (fem.hip / pcg_pipe.hip.h) over the plan's SELL layout, the slices dealt in equal numbers to nb workgroups
+// Host model of k_pipe_mirror_plan (fem_persist.hip / pcg_pipe.hip.h) over the plan's SELL layout, the slices dealt in equal numbers to nb workgroups
 // as pipe_slices does: the same functions of pcg_pipe_mirror.h, the wavefront-wide counts as loops over the 64 lanes.  out[0] = mirror layers,
 // out[1] = pool entries, out[2] = fewest plain layers of a slice, out[3] = workgroups that keep mirrors.
 int fb_plan_mirror_model(fb_plan_t p, int nb, int c16, int klt, int out[4]) {

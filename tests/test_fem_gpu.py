@@ -1241,7 +1241,7 @@ def test_persistent_solver_with_helper_wavefronts(gpu, monkeypatch, kind, m, for
     if minlen:
         monkeypatch.setenv("FEMBRAIN_PIPE_HELP_MINLEN", minlen)
     if not even:
-        # the LDS dealt to the slices of a workgroup by WIDTH instead of in equal shares (opt-in: measured slower, fem.hip setup_persist): every
+        # the LDS dealt to the slices of a workgroup by WIDTH instead of in equal shares (opt-in: measured slower, pcg_pipe_plan.h pipe_deal_lds): every
         # slice streams the same number of slots as far as the LDS goes.  The small cubes are then resident as a whole, up to 15 slots of a
         # slice where the unrolled loop takes 6, nothing is streamed and nobody helps: bit for bit the plain kernel
         monkeypatch.setenv("FEMBRAIN_PIPE_LDS_BY_WIDTH", "1")
