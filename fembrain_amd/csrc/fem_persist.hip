@@ -276,7 +276,7 @@ int alloc_persist(fb_fem_s* h, int nb, const PersistKnobs& kn) {
   FB_TRY(ps.pipe_state.alloc(2));
   zb.add(ps.pipe_state);
   if (kn.timing) {
-    FB_TRY(ps.persist_timing.alloc((size_t)nb * kPipeMaxWaves * 6));
+    FB_TRY(ps.persist_timing.alloc((size_t)nb * kPipeMaxWaves * kPipeTimingSlots));
     FB_TRY(ps.persist_timing.zero(s));
   } else {
     ps.persist_timing.release();
@@ -505,7 +505,7 @@ int launch_pipe(fb_fem_s* h, const double* b, int start, int n_iters, double eps
 }
 
 void print_pipe_timing(fb_fem_s* h) {
-  std::vector<long long> tm((size_t)h->ps.persist_blocks * kPipeMaxWaves * 6);
+  std::vector<long long> tm((size_t)h->ps.persist_blocks * kPipeMaxWaves * kPipeTimingSlots);
   if (h->ps.persist_timing.download(tm.data(), tm.size(), h->stream) != FB_OK) return;
   (void)h->ps.persist_timing.zero(h->stream);
   const char* names[5] = {"publish (drained)", "flag+wait+acquire", "product", "sums sweep", "recurrences(+refresh)"};
@@ -514,12 +514,34 @@ void print_pipe_timing(fb_fem_s* h) {
     int cnt = 0;
     for (int b = 0; b < h->ps.persist_blocks; b++)
       for (int w = 0; w < h->ps.persist_waves; w++) {
-        const long long* t = &tm[((size_t)b * kPipeMaxWaves + w) * 6];
+        const long long* t = &tm[((size_t)b * kPipeMaxWaves + w) * kPipeTimingSlots];
         if (t[5] <= 0) continue;
         const double us = (double)t[k] / (double)t[5] * 0.01;
         mn = std::min(mn, us); mx = std::max(mx, us); av += us; cnt++;
       }
     fprintf(stderr, "[fembrain] pipelined PCG %-22s per iteration: avg %.2f us  min %.2f  max %.2f (over %d waves)\n", names[k], av / std::max(cnt, 1), mn, mx, cnt);
+  }
+  if (h->ps.kernel && h->ps.kernel->wmax == 12 && !h->ps.kernel->help) {
+    // the product phase of the LDS window's kernels in its three parts (words 6, 7 and the rest of word 2), over all wavefronts and over
+    // the slowest wavefront of every workgroup -- the one its barrier waits for
+    const char* parts[3] = {"product: streamed [0,a)", "product: on-chip run", "product: streamed rest"};
+    for (int k = 0; k < 3; k++) {
+      double av = 0, mx = 0, sav = 0;
+      int cnt = 0, wgs = 0;
+      for (int b = 0; b < h->ps.persist_blocks; b++) {
+        double slowest = -1, part = 0;
+        for (int w = 0; w < h->ps.persist_waves; w++) {
+          const long long* t = &tm[((size_t)b * kPipeMaxWaves + w) * kPipeTimingSlots];
+          if (t[5] <= 0) continue;
+          const double us = (double)(k == 0 ? t[6] : (k == 1 ? t[7] : t[2] - t[6] - t[7])) / (double)t[5] * 0.01;
+          av += us; mx = std::max(mx, us); cnt++;
+          if ((double)t[2] > slowest) { slowest = (double)t[2]; part = us; }
+        }
+        if (slowest >= 0) { sav += part; wgs++; }
+      }
+      fprintf(stderr, "[fembrain] pipelined PCG %-24s per iteration: avg %.2f us  max %.2f; in the slowest wavefront of a workgroup: avg %.2f\n", parts[k], av / std::max(cnt, 1), mx,
+              sav / std::max(wgs, 1));
+    }
   }
   if (h->ps.pipe_timing_level >= 2) {
     // where the slow products are: by wavefront index, by XCD (workgroup & 7), and the slowest workgroups
@@ -527,7 +549,7 @@ void print_pipe_timing(fb_fem_s* h) {
       fprintf(stderr, "[fembrain] %s by wavefront:", names[k]);
       for (int w = 0; w < h->ps.persist_waves; w++) {
         double av = 0; int cnt = 0;
-        for (int b = 0; b < h->ps.persist_blocks; b++) { const long long* t = &tm[((size_t)b * kPipeMaxWaves + w) * 6]; if (t[5] > 0) { av += (double)t[k] / (double)t[5] * 0.01; cnt++; } }
+        for (int b = 0; b < h->ps.persist_blocks; b++) { const long long* t = &tm[((size_t)b * kPipeMaxWaves + w) * kPipeTimingSlots]; if (t[5] > 0) { av += (double)t[k] / (double)t[5] * 0.01; cnt++; } }
         fprintf(stderr, " %.2f", av / std::max(cnt, 1));
       }
       fprintf(stderr, "\n[fembrain] %s by XCD (avg / max over its workgroups' slowest wavefront):", names[k]);
@@ -535,7 +557,7 @@ void print_pipe_timing(fb_fem_s* h) {
         double av = 0, mx = 0; int cnt = 0;
         for (int b = x; b < h->ps.persist_blocks; b += 8) {
           double wmx = 0;
-          for (int w = 0; w < h->ps.persist_waves; w++) { const long long* t = &tm[((size_t)b * kPipeMaxWaves + w) * 6]; if (t[5] > 0) wmx = std::max(wmx, (double)t[k] / (double)t[5] * 0.01); }
+          for (int w = 0; w < h->ps.persist_waves; w++) { const long long* t = &tm[((size_t)b * kPipeMaxWaves + w) * kPipeTimingSlots]; if (t[5] > 0) wmx = std::max(wmx, (double)t[k] / (double)t[5] * 0.01); }
           av += wmx; mx = std::max(mx, wmx); cnt++;
         }
         fprintf(stderr, " %.2f/%.2f", av / std::max(cnt, 1), mx);
@@ -545,7 +567,7 @@ void print_pipe_timing(fb_fem_s* h) {
     std::vector<std::pair<double, int>> slow;
     for (int b = 0; b < h->ps.persist_blocks; b++) {
       double wmx = 0;
-      for (int w = 0; w < h->ps.persist_waves; w++) { const long long* t = &tm[((size_t)b * kPipeMaxWaves + w) * 6]; if (t[5] > 0) wmx = std::max(wmx, (double)t[2] / (double)t[5] * 0.01); }
+      for (int w = 0; w < h->ps.persist_waves; w++) { const long long* t = &tm[((size_t)b * kPipeMaxWaves + w) * kPipeTimingSlots]; if (t[5] > 0) wmx = std::max(wmx, (double)t[2] / (double)t[5] * 0.01); }
       slow.push_back({wmx, b});
     }
     std::sort(slow.begin(), slow.end());

@@ -31,6 +31,7 @@
 #pragma once
 #include "fem_kernels.h"
 #include "pcg_pipe_stream.hip.h"
+#include "pcg_pipe_onchip.hip.h"
 #include "pcg_pipe_mirror.h"
 
 namespace fb {
@@ -67,7 +68,8 @@ struct PipeArgs {
   double eps2;                // squared tolerance (start != 0; a continued solve reads the CGState)
   int max_iter;
   long long timeout_ticks;    // wall_clock64 ticks (100 MHz)
-  long long* timing;          // development aid (FEMBRAIN_PERSIST_TIMING=1), else null: per wavefront 6 accumulated phase times
+  long long* timing;          // development aid (FEMBRAIN_PERSIST_TIMING=1), else null: per wavefront kPipeTimingSlots words: 5 accumulated phase times,
+                              // the iterations, and of the product phase the first streamed part and the on-chip run (the LDS window's kernels)
   double* planes;             // [2][3][n_pad]: the published vector as the gathers read it, x | y | z planes
   size_t n_pad;               // rows padded to whole slices
   double* pstate;             // [2] gamma_old, alpha_old between the launches of one solve
@@ -92,6 +94,7 @@ struct PipeArgs {
   const int* mir_pool;
 };
 constexpr int kPipeTaskStride = 16;
+constexpr int kPipeTimingSlots = 8;  // PipeArgs::timing words per wavefront
 constexpr int kPipeMaxHelpers = 8;   // per workgroup
 constexpr int pipe_help_slots(bool c16) { return c16 ? 6 : 5; }  // LDS wavefront-slots set aside for their partial sums (8 x 3 x 64 doubles = 12,288 B, at the end of the slots)
 static_assert(pipe_help_slots(true) * pipe_slot_bytes(true) >= kPipeMaxHelpers * 3 * 64 * 8 && pipe_help_slots(false) * pipe_slot_bytes(false) >= kPipeMaxHelpers * 3 * 64 * 8, "helpers' hand-over area");
@@ -378,7 +381,13 @@ namespace fb {
 // k_spmv.  The CU's LDS holds pipe_lds_slots() = 62 / 65 wavefront-slots beside the sync buffers; a workgroup deals them
 // to its `count` live wavefronts, count-th part each and the remainder one more for the first ones (11 slices: 5 slots each and a
 // sixth for seven of them; 10 slices: 6 each), at most KLT per wavefront (the unroll bound of the LDS loop).
-// TIMING: the development build with per-phase clocks (FEMBRAIN_PERSIST_TIMING=1).
+// The product's schedule in the LDS-window instantiations (WMAX = 12, KLT = 6 or 7: kMir below), all in slot order: the low part of the diagonal
+// block (C++), the slots in front of the window streamed (pcg_pipe_stream.hip.h: loads 13..25 deep), the ON-CHIP RUN -- mirror layers, then
+// plain LDS layers -- hand-scheduled with the gathers four slots ahead (pcg_pipe_onchip.hip.h; the C++ loop it replaced waited for each slot's
+// three gathers in turn: 4.1-4.6 of the product's 10 us at 1M tets, profiles/r07_onchip_phase_before.txt), the slots behind the window
+// streamed.  Every other instantiation keeps the C++ loop over its LDS slots.
+// TIMING: the development build with per-phase clocks (FEMBRAIN_PERSIST_TIMING=1); in the LDS-window instantiations the product phase is
+// also clocked at its two seams (first streamed part | on-chip run | second streamed part).
 // SHARD: the kernel of a sharded handle (pcg_shard_box.hip.h; "k_pcg_pipe_shard<WMAX,KLT>" in fb_fem_pcg_path): the slices come from the
 // plan's deal (sa.wg_range), the last wavefront is the spare one (sums, counters, proxy copies), rows a neighbour rank gathers are also
 // stored into its box, the sums go through the rank level; 32-bit column words, write-through stores.  sa is not read otherwise.
@@ -533,7 +542,9 @@ __global__ __launch_bounds__(64 * WMAX) void k_pcg_pipe(SellView sv, const MT* _
   unsigned int pub = pa.seqs[0], sums = pa.seqs[1];  // grid-uniform: written by the previous launch
   const long long t_limit = pa.timeout_ticks;
   bool failed = false;
-  long long tm[TIMING ? 6 : 1] = {0}, tprev = TIMING ? wall_clock64() : 0;  // (TIMING: the phase clocks cost 14 registers per lane)
+  long long tm[TIMING ? 7 : 1] = {0}, tprev = TIMING ? wall_clock64() : 0;  // (TIMING: the phase clocks cost 14 registers per lane)
+  // (TIMING) tm[5], tm[6]: of the product phase, the first streamed part and the on-chip run; the rest of tm[2] is the second streamed part
+  auto seam = [&](int k, long long& t) { if (TIMING) { const long long u = wall_clock64(); tm[k] += u - t; t = u; } };
   auto lap = [&](int k) { if (TIMING) { const long long t = wall_clock64(); tm[k] += t - tprev; tprev = t; } };
 
   // Stores of the next product's input vector into the plane buffer of the next publish number (512 contiguous bytes per wave
@@ -658,6 +669,7 @@ __global__ __launch_bounds__(64 * WMAX) void k_pcg_pipe(SellView sv, const MT* _
       y1 = l01 * vin[0] + l11 * vin[1] + l12 * vin[2];
       y2 = l02 * vin[0] + l12 * vin[1] + l22 * vin[2];
     }
+    long long tseam = tprev;
     if (live) {
       if constexpr (kMir) {
         // the LDS window in slot order: the slots in front of it streamed, then the mirror layers (the same mul / mul / add / mul / add / add
@@ -669,20 +681,11 @@ __global__ __launch_bounds__(64 * WMAX) void k_pcg_pipe(SellView sv, const MT* _
                                       ((unsigned int)so_k * 64u + (unsigned int)lane) * (unsigned int)(C16 ? sizeof(short) : sizeof(int)), vals,
                                       C16 ? (const void*)sv.coldelta : (const void*)sv.colidx, pl, pl + xs, pl + 2 * xs, row, y0, y1, y2);
         }
-        const unsigned int* lmt = (const unsigned int*)((const char*)(lds + kPipeSyncDoubles) + mir_tab) + lane;
-        const unsigned int* lmat = (const unsigned int*)(lds + kPipeSyncDoubles);
-#pragma unroll
-        for (int k = 0; k < kMirMax; k++) if (k < mir_m) {
-          unsigned int addr, col;
-          if constexpr (C16) { const unsigned int wd = lmt[k * 64]; addr = wd >> 16; col = (unsigned int)(row + (int)(short)(wd & 0xffffu)); }
-          else { col = lmt[k * 96]; addr = ((const unsigned short*)(lmt - lane + k * 96 + 64))[lane]; }
-          const unsigned int* pk = lmat + addr;  // the block (col, row): value 3a + b of this row's block is its value 3b + a
-          const double* xp = pl + cs * (size_t)col;
-          const double x0 = xp[0], x1 = xp[xs], x2 = xp[2 * xs];
-          y0 += (double)__uint_as_float(pk[0 * 64]) * x0 + (double)__uint_as_float(pk[3 * 64]) * x1 + (double)__uint_as_float(pk[6 * 64]) * x2;
-          y1 += (double)__uint_as_float(pk[1 * 64]) * x0 + (double)__uint_as_float(pk[4 * 64]) * x1 + (double)__uint_as_float(pk[7 * 64]) * x2;
-          y2 += (double)__uint_as_float(pk[2 * 64]) * x0 + (double)__uint_as_float(pk[5 * 64]) * x1 + (double)__uint_as_float(pk[8 * 64]) * x2;
-        }
+        seam(5, tseam);
+        // the on-chip run, m mirror layers and then KL plain ones: hand-scheduled, the gathers four slots ahead (pcg_pipe_onchip.hip.h)
+        const char* lbase = (const char*)(lds + kPipeSyncDoubles);
+        pipe_onchip_slots<C16>(mir_m, max(KL, 0), (const unsigned int*)(lbase + mir_tab) + lane, (const unsigned short*)(lbase + mir_tab) + lane, lres, lcd, lbase, pl, pl + xs,
+                               pl + 2 * xs, row, y0, y1, y2);
       }
       if (sizeof(MT) == 4 && KLT >= 16) {
         // whole slices in LDS, five wavefronts per CU: registers to spare, so ALL gathers of the product are in flight before the first
@@ -703,7 +706,7 @@ __global__ __launch_bounds__(64 * WMAX) void k_pcg_pipe(SellView sv, const MT* _
           y1 += (double)__uint_as_float(lk[3 * 64]) * x0 + (double)__uint_as_float(lk[4 * 64]) * x1 + (double)__uint_as_float(lk[5 * 64]) * x2;
           y2 += (double)__uint_as_float(lk[6 * 64]) * x0 + (double)__uint_as_float(lk[7 * 64]) * x1 + (double)__uint_as_float(lk[8 * 64]) * x2;
         }
-      } else if (sizeof(MT) == 4) {
+      } else if (sizeof(MT) == 4 && !kMir) {
 #pragma unroll
         for (int k = 0; k < KLT; k++) if (k < KL) {  // LDS-resident slots
           const unsigned int* lk = lres + (size_t)k * kValWords * 64;
@@ -732,6 +735,10 @@ __global__ __launch_bounds__(64 * WMAX) void k_pcg_pipe(SellView sv, const MT* _
             }
           }
         }
+      }
+      if constexpr (kMir) {
+        if (TIMING) asm volatile("" : "+v"(y0), "+v"(y1), "+v"(y2));  // (the clock is read behind the sums, not beside them)
+        seam(6, tseam);
       }
       // the streamed slots: hand-pipelined loads (pcg_pipe_stream.hip.h); those from own_k1 on are a helper's
       const int n_str = own_k1 - k_after;
@@ -967,8 +974,10 @@ __global__ __launch_bounds__(64 * WMAX) void k_pcg_pipe(SellView sv, const MT* _
     lap(4);  // recurrences
   }
   if (TIMING && lane == 0) {
-    for (int k = 0; k < 5; k++) atomicAdd((unsigned long long*)pa.timing + ((size_t)blockIdx.x * kPipeMaxWaves + wv) * 6 + k, (unsigned long long)tm[k]);
-    atomicAdd((unsigned long long*)pa.timing + ((size_t)blockIdx.x * kPipeMaxWaves + wv) * 6 + 5, (unsigned long long)it_done);
+    unsigned long long* tw = (unsigned long long*)pa.timing + ((size_t)blockIdx.x * kPipeMaxWaves + wv) * kPipeTimingSlots;
+    for (int k = 0; k < 5; k++) atomicAdd(tw + k, (unsigned long long)tm[k]);
+    atomicAdd(tw + 5, (unsigned long long)it_done);
+    atomicAdd(tw + 6, (unsigned long long)tm[5]); atomicAdd(tw + 7, (unsigned long long)tm[6]);
   }
   if (failed) return;  // nothing written back: the host re-solves from the vectors it handed over
   // The iteration cap ended the solve: x is left in pg and the start vector stays -- the host checks the iterate's true residual and

@@ -18,6 +18,9 @@
 // so a product has the bits of k_spmv's.
 // Registers: operands are allocated by the compiler; the 36 temporaries are v120..v155 (clobbers) -- a kernel using this has at
 // least 156 registers per lane, which every k_pcg_pipe instantiation needs for its state anyway.
+// A product of the LDS-window kernels calls this twice, for the slots in front of the window and for those behind it; the on-chip run
+// between them is pcg_pipe_onchip.hip.h, which uses the same 36 temporaries and FBP_ROW's arithmetic.  Each of the three parts fills and
+// drains its own pipeline (vmcnt(0) at its end).
 #pragma once
 #include <hip/hip_runtime.h>
 
