@@ -38,6 +38,7 @@ class GpuPoly:
                                         _l.fptr(blob.prims), len(blob.mtx), _l.fptr(blob.mtx)))
         self.counts = None
         self.dims = None
+        self.lower = self.cellsize = None   # origin (fp32) and cell size of the swept grid, as handed to the library
 
     def close(self):
         if getattr(self, "h", None):
@@ -75,6 +76,7 @@ class GpuPoly:
         d = (C.c_int * 3)()
         _l.check(self._L.fb_poly_sweep(self.h, cellsize, d))
         self.dims = tuple(d)
+        self.lower, self.cellsize = self.blob.bbox[0], cellsize
         return self.dims
 
     def sweep_grid(self, lower, cellsize, dims):
@@ -82,6 +84,7 @@ class GpuPoly:
         dm = np.asarray(dims, dtype=np.int32)
         _l.check(self._L.fb_poly_sweep_grid(self.h, _l.fptr(lo), cellsize, _l.iptr(dm)))
         self.dims = tuple(int(x) for x in dm)
+        self.lower, self.cellsize = lo, cellsize
         return self.dims
 
     # ---- multi-GPU field path: one z-slab of a larger grid (fembrain_hip.h, "z-slabs of one grid") ----

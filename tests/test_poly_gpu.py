@@ -10,6 +10,7 @@ from fembrain_amd.blobtree import make_tree, read_blob, sphere_blob
 from fembrain_amd.poly import GpuPoly
 from oracle.pyfield import OrcPoly
 
+import poly_inputs as pi
 from meshchecks import surface_mesh_checks
 
 pytestmark = pytest.mark.gpu
@@ -18,21 +19,15 @@ GOLD = os.path.join(os.path.dirname(__file__), "golden")
 OF_RIGHT_OP, OF_LEFT_OP, OF_RANGE, OF_UNARY = 1, 2, 4, 8
 
 
-def _trees():
-    pts = [(0, (0.1 * i - 0.3, 0.05 * i, 0.02 * i * i), (0, 0, 0), (0, 0, 0)) for i in range(6)]
-    mixed = [(0, (0, 0, 0), (0, 0, 0), (0, 0, 0)), (1, (-0.5, 0.2, 0), (0.6, 0.3, 0.1), (0, 0, 0)), (5, (0.3, -0.4, 0.2), (0, 0, 0), (0.25, 0, 0)),
-             (2, (0, 0, -0.6), (0, 1, 0), (0.2, 0.7, 0)), (3, (0.5, 0.5, 0.5), (0, 0, 1), (0.3, 0, 0)), (4, (-0.5, -0.5, 0.4), (1, 0, 0), (0.3, 0, 0)),
-             (7, (0.2, 0.7, -0.3), (1.0, 0.8, 0.64), (1.0 / 0.8 ** 4, -2.0 / 0.64, 1.0))]
-    return {
-        "sphere": sphere_blob(),
-        "blend6_noops": make_tree(pts),
-        "range_blend": make_tree(pts, [(4, 0, 5, OF_RANGE, 0, 0)]),
-        # op0 = union(op1, op2); op1 = dif(prim0, prim1); op2 = smoothdif(op3, prim2); op3 = range(3..6)
-        "nested": make_tree(mixed, [(0, 1, 2, OF_LEFT_OP | OF_RIGHT_OP, 0, 0), (2, 0, 1, 0, 0, 0), (3, 3, 2, OF_LEFT_OP, 0, 0), (4, 3, 6, OF_RANGE, 0, 0)]),
-        # two range operators under an intersection: the second range inherits the first one's running field
-        "two_ranges": make_tree(pts, [(1, 1, 2, OF_LEFT_OP | OF_RIGHT_OP, 0, 0), (4, 0, 2, OF_RANGE, 0, 0), (4, 3, 5, OF_RANGE, 0, 0)]),
-        "ricci": make_tree(pts[:2], [(5, 0, 1, 0, 2.0, 0.5)]),
-    }
+_trees = pi.trees
+
+
+def _assert_pipeline_on_device_grid(blob, g, own, mesh_checks=None):
+    """everything after the field against the oracle run on the device's own grid samples (no sample can classify differently on the two
+    sides); the grid itself against the oracle's own sweep `own`.  Returns the device's outputs."""
+    o = pi.oracle_on_device_grid(blob, g, own=own)
+    pi.run_pipeline(g)
+    return pi.assert_pipeline_equals(g, o, pi.normals_tol(blob, np.array_equal(o.xyzf, own)), mesh_checks=mesh_checks)
 
 
 @pytest.mark.parametrize("name", ["sphere", "blend6_noops", "range_blend", "nested", "two_ranges", "ricci"])
@@ -102,6 +97,7 @@ def test_grid_classification_bit_exact(gpu, name, cellsize):
         assert np.array_equal(tets, otets) and np.array_equal(xyz, oxyz)
     else:
         assert (flags != o.edge_flags).sum() <= 8 * (~safe).sum()
+    _assert_pipeline_on_device_grid(blob, g, ogrid)
 
 
 def test_sphere_256_properties(gpu):
@@ -205,6 +201,7 @@ def test_non_multiple_of_64_row_length_grid(gpu):
         xyz, tets = g.read_tetmesh()
         oxyz, otets = o.tetrahedralize()
         assert np.array_equal(tets, otets) and np.array_equal(xyz, oxyz)
+    _assert_pipeline_on_device_grid(blob, g, og)
 
 
 @pytest.mark.parametrize("dims,cell", [((64, 19, 23), 0.035), ((128, 11, 9), 0.018), ((192, 7, 5), 0.012)])
@@ -216,7 +213,7 @@ def test_row_aligned_grids_classify_without_the_position_masks(gpu, monkeypatch,
     o = OrcPoly(blob)
     og = o.sweep_grid(lo, cell, dims)
     oc = o.classify()
-    out = []
+    out, full = [], []
     for masks in ("0", "1"):
         monkeypatch.setenv("FEMBRAIN_CLASSIFY_MASKS", masks)
         g = GpuPoly(blob)
@@ -226,9 +223,11 @@ def test_row_aligned_grids_classify_without_the_position_masks(gpu, monkeypatch,
         g.tetrahedralize()
         xyz, tets = g.read_tetmesh()
         out.append((flags, cnt, cfg, xyz, tets, (c.n_crossed_edges, c.n_surface_cells, c.n_included_cells, c.n_tet_vertices)))
+        full.append(_assert_pipeline_on_device_grid(blob, g, og))
     monkeypatch.delenv("FEMBRAIN_CLASSIFY_MASKS")
     for a, b in zip(out[0][:5], out[1][:5]):
         assert np.array_equal(a, b)
+    pi.assert_runs_identical(full[0], full[1])
     assert out[0][5] == out[1][5] and out[0][5][2] > 0
     if (np.abs(og[:, 3] - 0.5) > 1e-5).all():
         flags, cnt, cfg, xyz, tets, counts = out[0]
@@ -236,6 +235,27 @@ def test_row_aligned_grids_classify_without_the_position_masks(gpu, monkeypatch,
         assert counts == (oc["n_crossed_edges"], oc["n_surface_cells"], oc["n_included_cells"], oc["n_tet_vertices"])
         oxyz, otets = o.tetrahedralize()
         assert np.array_equal(tets, otets) and np.array_equal(xyz, oxyz)
+
+
+@pytest.mark.parametrize("case", pi.WORD_EDGE_CASES, ids=pi.case_id)
+def test_pipeline_on_word_edge_grids(gpu, monkeypatch, case):
+    """Grids at the edges of the 64-point words the classification, the scans and the emission kernels work on (tests/poly_inputs.py), the body
+    next to the first or the last grid corner: sweep, classification, tet mesh, surface and surface binding against the oracle on the device's
+    samples.  A row length that is a multiple of 64 runs k_classify<ROWS64> and the kernel that loads the masks: both against the oracle, and
+    against each other."""
+    tree, dims, where = case
+    blob, lower, cell, own = pi.oracle_case(tree, dims, where)
+    runs = []
+    for masks in ((None, "1") if dims[0] % 64 == 0 else (None,)):
+        monkeypatch.delenv("FEMBRAIN_CLASSIFY_MASKS", raising=False)
+        if masks is not None:
+            monkeypatch.setenv("FEMBRAIN_CLASSIFY_MASKS", masks)
+        g = GpuPoly(blob)
+        assert g.sweep_grid(lower, cell, dims) == dims
+        pi.run_pipeline(g)
+        runs.append(pi.assert_pipeline_equals(g, pi.oracle_on_device_grid(blob, g, own=own), pi.normals_tol(blob)))
+        g.close()
+    pi.assert_runs_identical(runs[0], runs[-1])
 
 
 # ---- marching-cubes surface (GPUPoly::run) ---------------------------------------------------------------------------
@@ -253,23 +273,24 @@ def test_surface_matches_oracle(gpu, name, cellsize):
     c = g.classify()
     oc = o.classify()
     exact_field = np.array_equal(grid, og)
-    if not exact_field and (np.abs(og[:, 3] - 0.5) <= 1e-5).any():
-        pytest.skip("a grid sample within rounding of the iso value: the two classifications may differ")
-    assert c.n_crossed_edges == oc["n_crossed_edges"]
-    c = g.surface()
-    xyz, nrm, tri = g.read_surface()
-    oxyz, onrm, otri = o.surface()
-    assert c.n_surface_vertices == len(oxyz) == c.n_crossed_edges and c.n_surface_indices == 3 * len(otri)
-    assert np.array_equal(tri, otri)
-    if exact_field:
-        assert np.array_equal(xyz, oxyz)
-        assert np.abs(nrm - onrm).max() <= (1e-6 if name in ("sphere", "blend6_noops", "range_blend", "two_ranges") else 2e-2)
-    else:
-        assert np.abs(xyz - oxyz).max() <= 1e-5
-        assert np.abs(nrm - onrm).max() <= 2e-2
     lo = np.asarray(blob.bbox[0], np.float64)
-    surface_mesh_checks(xyz, nrm, tri, box=None if name == "sphere" or name.endswith(".blob") else (lo, lo + cellsize * (np.array(g.dims) - 1)),
-                        smooth=name != "nested")
+    checks = dict(box=None if name == "sphere" or name.endswith(".blob") else (lo, lo + cellsize * (np.array(g.dims) - 1)), smooth=name != "nested")
+    if exact_field or (np.abs(og[:, 3] - 0.5) > 1e-5).all():   # (otherwise the oracle's own samples may classify differently)
+        assert c.n_crossed_edges == oc["n_crossed_edges"]
+        c = g.surface()
+        xyz, nrm, tri = g.read_surface()
+        oxyz, onrm, otri = o.surface()
+        assert c.n_surface_vertices == len(oxyz) == c.n_crossed_edges and c.n_surface_indices == 3 * len(otri)
+        assert np.array_equal(tri, otri)
+        if exact_field:
+            assert np.array_equal(xyz, oxyz)
+            assert np.abs(nrm - onrm).max() <= (1e-6 if name in ("sphere", "blend6_noops", "range_blend", "two_ranges") else 2e-2)
+        else:
+            assert np.abs(xyz - oxyz).max() <= 1e-5
+            assert np.abs(nrm - onrm).max() <= 2e-2
+        surface_mesh_checks(xyz, nrm, tri, **checks)
+    # and with the oracle on the device's samples: every case, bit for bit
+    _assert_pipeline_on_device_grid(blob, g, og, mesh_checks=checks)
 
 
 def test_surface_sphere_256(gpu):
@@ -350,19 +371,20 @@ def test_instanced_models_match_oracle(gpu, name, cellsize):
     og = o.sweep(cellsize)
     grid = g.read_grid()
     assert np.array_equal(grid, og) if exact else np.abs(grid[:, 3] - og[:, 3]).max() <= 2e-6
-    if not np.array_equal(grid, og):
-        return
-    c, oc = g.classify(), o.classify()
-    flags, cnt, cfg = g.read_classification()
-    assert np.array_equal(flags, o.edge_flags) and np.array_equal(cfg, o.config)
-    g.tetrahedralize()
-    xyz, tets = g.read_tetmesh()
-    oxyz, otets = o.tetrahedralize()
-    assert np.array_equal(tets, otets) and np.array_equal(xyz, oxyz)
-    g.surface()
-    sx, sn, st = g.read_surface()
-    ox, on, ot = o.surface()
-    assert np.array_equal(st, ot) and np.array_equal(sx, ox) and np.abs(sn - on).max() <= 2e-2
+    if np.array_equal(grid, og):
+        c, oc = g.classify(), o.classify()
+        flags, cnt, cfg = g.read_classification()
+        assert np.array_equal(flags, o.edge_flags) and np.array_equal(cfg, o.config)
+        g.tetrahedralize()
+        xyz, tets = g.read_tetmesh()
+        oxyz, otets = o.tetrahedralize()
+        assert np.array_equal(tets, otets) and np.array_equal(xyz, oxyz)
+        g.surface()
+        sx, sn, st = g.read_surface()
+        ox, on, ot = o.surface()
+        assert np.array_equal(st, ot) and np.array_equal(sx, ox) and np.abs(sn - on).max() <= 2e-2
+    # whether or not the grids are equal: the oracle on the device's samples
+    _assert_pipeline_on_device_grid(blob, g, og)
 
 
 def test_surface_follows_the_tet_mesh_displacements(gpu):
@@ -640,6 +662,24 @@ def test_slab_pieces_concatenate_to_the_single_grid_mesh(gpu, name, world):
     assert np.array_equal(np.concatenate([p[0] for p in pieces]), xyz)
     assert np.array_equal(np.concatenate([p[1] for p in pieces]), tets)
     assert sum(len(p[1]) for p in pieces) == g.counts.n_tets and min(len(p[1]) for p in pieces[1:-1] or pieces) >= 0
+
+
+@pytest.mark.parametrize("where", list(pi.PLACEMENTS))
+@pytest.mark.parametrize("dims,world", pi.SLAB_CASES, ids=["%dx%dx%d-%d" % (*d, w) for d, w in pi.SLAB_CASES])
+def test_slab_pieces_concatenate_on_word_edge_grids(gpu, dims, world, where):
+    """the same, with slabs of less than a word, of a word and a bit, and of rows of whole words; the single-grid mesh itself is pinned to the
+    oracle by test_pipeline_on_word_edge_grids"""
+    blob, lower, cell, _ = pi.oracle_case("blend6_noops", dims, where)
+    g = GpuPoly(blob)
+    g.sweep_grid(lower, cell, dims)
+    g.classify()
+    g.tetrahedralize()
+    xyz, tets = g.read_tetmesh()
+    assert len(tets) > 0
+    pieces = _sharded_mesh(blob, lower, cell, dims, world)
+    assert np.array_equal(np.concatenate([p[0] for p in pieces]), xyz)
+    assert np.array_equal(np.concatenate([p[1] for p in pieces]), tets)
+    assert sum(len(p[1]) for p in pieces) == g.counts.n_tets
 
 
 def test_slab_grid_samples_equal_the_whole_grid(gpu):
