@@ -2356,7 +2356,15 @@ long long fb_fem_device_plan_get(fb_fem_t h, const char* name, int* out, long lo
   else if (h->device_plan && n == "bptr") { src = h->d_bptr.p; cnt = P.n_owned + 1; }
   else if (h->device_plan && n == "bcol") { src = h->d_bcol.p; cnt = P.n_blocks; }
   else if (h->device_plan && n == "blk_slot") { src = h->d_blk_slot.p; cnt = P.n_blocks; }
-  else return fail(FB_EINVAL, "no device plan array '%s'", name);
+  else {
+    // the persistent solver's plan (fem_persist.hip): assembled on the host
+    std::vector<int> v;
+    const int got = persist_plan_array(h, name, &v);
+    if (got < 0) return got;
+    if (!got) return fail(FB_EINVAL, "no device plan array '%s'", name);
+    if (out && capacity > 0) memcpy(out, v.data(), sizeof(int) * (size_t)std::min<long long>((long long)v.size(), capacity));
+    return (long long)v.size();
+  }
   if (out && capacity > 0 && cnt > 0) {
     FB_HIP(hipMemcpyAsync(out, src, sizeof(int) * (size_t)std::min(cnt, capacity), hipMemcpyDeviceToHost, h->stream));
     FB_HIP(hipStreamSynchronize(h->stream));

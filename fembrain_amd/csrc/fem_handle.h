@@ -267,5 +267,6 @@ void release_shard_persist(fb_fem_s* h);
 void read_persist_timeout(fb_fem_s* h);
 int launch_pipe(fb_fem_s* h, const double* b, int start, int n_iters, double eps, int max_iter);
 void print_pipe_timing(fb_fem_s* h);
+int persist_plan_array(fb_fem_s* h, const char* name, std::vector<int>* out);  // fb_fem_device_plan_get's pipe_* names
 
 }  // namespace fb

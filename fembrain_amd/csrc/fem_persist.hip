@@ -579,6 +579,39 @@ void print_pipe_timing(fb_fem_s* h) {
   }
 }
 
+// What the live plan decided, for fb_fem_device_plan_get (read-only): "pipe_tasks" the int4 rows of the task table ([workgroup][kPipeTaskStride],
+// pcg_pipe_plan.h), "pipe_windows" per slice (first slot a, mirror layers m, plain resident slots p) of the LDS window (pcg_pipe_mirror.h),
+// "pipe_wg_first" the deal by slots (pipe_deal's table).  1: filled, 0: no such name or this plan has none, < 0: an error.
+int persist_plan_array(fb_fem_s* h, const char* name, std::vector<int>* out) {
+  PersistState& ps = h->ps;
+  const std::string n(name);
+  out->clear();
+  if (!ps.persist) return 0;
+  if (n == "pipe_tasks" && ps.pipe_tasks.p) {
+    out->resize((size_t)4 * ps.persist_blocks * kPipeTaskStride);
+    FB_TRY(ps.pipe_tasks.download((int4*)out->data(), (size_t)ps.persist_blocks * kPipeTaskStride, h->stream));
+    return 1;
+  }
+  if (n == "pipe_wg_first" && !ps.pipe_wg_first_host.empty()) { *out = ps.pipe_wg_first_host; return 1; }
+  if (n == "pipe_windows" && ps.pipe_mir.p) {
+    const int nb = ps.persist_blocks, ns = h->plan.n_slices;
+    std::vector<int4> mt((size_t)nb * kPipeMaxWaves);
+    FB_TRY(ps.pipe_mir.download(mt.data(), mt.size(), h->stream));
+    out->assign((size_t)3 * ns, 0);
+    for (int b = 0; b < nb; b++) {
+      int first, count;
+      pipe_deal(ps.pipe_wg_first_host.empty() ? nullptr : ps.pipe_wg_first_host.data(), ns, nb, b, &first, &count);
+      for (int w = 0; w < count && w < kPipeMaxWaves && first + w < ns; w++) {
+        const int x = mt[(size_t)b * kPipeMaxWaves + w].x;
+        int* o = &(*out)[(size_t)3 * (first + w)];
+        o[0] = x & 0xff; o[1] = (x >> 8) & 0xff; o[2] = (x >> 16) & 0xff;
+      }
+    }
+    return 1;
+  }
+  return 0;
+}
+
 }  // namespace fb
 
 extern "C" {

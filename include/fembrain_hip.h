@@ -398,7 +398,12 @@ int fb_fem_pcg(fb_fem_t h, const double* rhs, double* x, double eps, int max_ite
  * launch measured with HIP events on the handle's stream. */
 /* Plan arrays as the device holds them (what the per-step kernels read), for checking the device-side plan builder against
  * the host one (fembrain_hip_testing.h, fb_plan_get -- same names: bptr, bcol, blk_slot, slice_off, colidx, slot_coff,
- * slot_ccnt, contrib).  Copies at most `capacity` int32 words, returns the element count or a negative code. */
+ * slot_ccnt, contrib).  Copies at most `capacity` int32 words, returns the element count or a negative code.
+ * Of a handle that solves in persistent launches also what that solver planned, where the plan has it: "pipe_wg_first" (the slices
+ * dealt to the workgroups by slots: n_workgroups + 1 first slices, then n_workgroups counts), "pipe_tasks" (the task table, 16 rows of
+ * four words per workgroup: an owner's resident slots, their place, the end of its stream and its helpers' mask; a helper's slice in the
+ * workgroup, first and last slot and number) and "pipe_windows" (per slice: first slot of the LDS window, mirror layers, plain resident
+ * slots).  A plan without one answers as for an unknown name. */
 long long fb_fem_device_plan_get(fb_fem_t h, const char* name, int* out, long long capacity);
 /* 1 if the plan of this handle was built on the device (unsharded handles, unless FEMBRAIN_PLAN_DEVICE=0), else 0 */
 int fb_fem_plan_on_device(fb_fem_t h);

@@ -13,6 +13,7 @@ from fembrain_amd import lib as fl
 from fembrain_amd.fem import Deformable, FemIntegrator, bsr_to_scipy
 from fembrain_amd.meshgen import cube_fixed_plane_i0, fixed_vertices_to_dofs, truth_cube
 from oracle.pyoracle import OrcFem
+from product_inputs import _delaunay_lattice
 
 pytestmark = pytest.mark.gpu
 
@@ -54,6 +55,23 @@ def test_pattern_elements_assembly(gpu, prec, tol):
     for e in (0, 1, 77, len(t) - 1):
         assert np.abs(K0[e] - o.K0(e)).max() <= 1e-11 * np.abs(o.K0(e)).max()
         assert np.abs(Mi[e] - o.Minv(e)).max() <= 1e-11 * np.abs(o.Minv(e)).max()
+    # ... the cube's gradient matrices are mostly zeros, so a transposed or permuted MFMA operand can pass there: EVERY element of the
+    # 400-point Delaunay mesh, both orientations, dense gradients
+    pts, td, fixed_d, _ = _random_delaunay()
+    od = OrcFem(pts, td)
+    gd = FemIntegrator(pts, td, fixed_d, matrix_precision=prec)
+    K0d, Mid = gd.element_stiffness(0, len(td))
+    worst = [0.0, 0.0]
+    for e in range(len(td)):
+        ko, mo_ = od.K0(e), od.Minv(e)
+        worst = [max(worst[0], np.abs(K0d[e] - ko).max() / np.abs(ko).max()), max(worst[1], np.abs(Mid[e] - mo_).max() / np.abs(mo_).max())]
+    print("k_element_K0_mfma on %d Delaunay elements: worst relative error K0 %.2e, Minv %.2e" % (len(td), worst[0], worst[1]))
+    assert worst[0] <= 1e-11 and worst[1] <= 1e-11, worst
+    # a range of elements is the same rows of the full call, bit for bit
+    for first, count in ((1, 1), (3, 5), (len(td) - 2, 2)):
+        Kr, Mr = gd.element_stiffness(first, count)
+        assert np.array_equal(Kr, K0d[first:first + count]) and np.array_equal(Mr, Mid[first:first + count]), (first, count)
+    gd.close()
     # a5: mass
     conv = _oracle_bsr(o)
     mo = conv(o.mass_on_pattern())[:, 0, 0]
@@ -686,10 +704,8 @@ def test_config2_blobtree_model_100k_tets_end_to_end(gpu):
     assert np.abs(qg - qo).max() <= 2e-4 * np.abs(qo).max()
 
 
-def test_random_delaunay_mesh(gpu):
-    """An unstructured mesh with no grid regularity at all: Delaunay tetrahedra of random points (slivers below 1e-7 volume
-    dropped), mixed orientations as scipy returns them, irregular valences (row lengths 5..40).  Pattern bit-exact, warped
-    assembly to the fp64 tolerance, two steps against the oracle."""
+def _random_delaunay():
+    """400 random points, Delaunay tetrahedra in both orientations as scipy returns them (slivers below 1e-7 volume dropped)"""
     from scipy.spatial import Delaunay
     rng = np.random.default_rng(42)
     pts = rng.uniform(0, 1, size=(400, 3))
@@ -697,7 +713,14 @@ def test_random_delaunay_mesh(gpu):
     vol = np.einsum("ij,ij->i", pts[t[:, 1]] - pts[t[:, 0]], np.cross(pts[t[:, 2]] - pts[t[:, 0]], pts[t[:, 3]] - pts[t[:, 0]])) / 6
     t = np.ascontiguousarray(t[np.abs(vol) > 1e-7])
     assert len(t) > 1500 and (vol > 0).any() and (vol < 0).any()
-    fixed = fixed_vertices_to_dofs(np.nonzero(pts[:, 0] < 0.1)[0])
+    return pts, t, fixed_vertices_to_dofs(np.nonzero(pts[:, 0] < 0.1)[0]), rng
+
+
+def test_random_delaunay_mesh(gpu):
+    """An unstructured mesh with no grid regularity at all: Delaunay tetrahedra of random points (slivers below 1e-7 volume
+    dropped), mixed orientations as scipy returns them, irregular valences (row lengths 5..40).  Pattern bit-exact, warped
+    assembly to the fp64 tolerance, two steps against the oracle."""
+    pts, t, fixed, rng = _random_delaunay()
     o = OrcFem(pts, t)
     o.integrator(fixed)
     g = FemIntegrator(pts, t, fixed, matrix_precision=fl.FB_MATRIX_F64)
@@ -1201,20 +1224,6 @@ def test_published_vector_node_by_node_gives_the_same_iterates(gpu, monkeypatch,
         out.append((it, x))
         g.close()
     assert out[0][0] == out[1][0] and np.array_equal(out[0][1], out[1][1])
-
-
-def _delaunay_lattice(m, seed=2):
-    """Delaunay tetrahedra of an m^3 lattice with jittered points: hull nodes with 40 and more neighbours next to interior nodes with 15"""
-    from scipy.spatial import Delaunay
-    rng = np.random.default_rng(seed)
-    g = np.stack(np.meshgrid(*[np.arange(m)] * 3, indexing="ij"), -1).reshape(-1, 3).astype(float)
-    pts = (g + rng.uniform(-0.35, 0.35, size=g.shape)) * 0.1
-    t = Delaunay(pts).simplices.astype(np.int32)
-    vol = np.einsum("ij,ij->i", pts[t[:, 1]] - pts[t[:, 0]], np.cross(pts[t[:, 2]] - pts[t[:, 0]], pts[t[:, 3]] - pts[t[:, 0]])) / 6
-    keep = np.abs(vol) > 1e-9
-    t, vol = t[keep], vol[keep]
-    t[vol < 0] = t[vol < 0][:, [0, 2, 1, 3]]
-    return pts, np.ascontiguousarray(t), fixed_vertices_to_dofs(np.nonzero(g[:, 0] == 0)[0])
 
 
 @pytest.mark.parametrize("kind,m,force,minlen,even", [("cube", 14, "1", "4", True), ("cube", 26, "1", "4", True), ("cube", 26, "1", None, False), ("cube", 40, "1", None, False),
