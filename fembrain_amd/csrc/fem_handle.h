@@ -1,6 +1,6 @@
-// The FEM handle (fb_fem_t of include/fembrain_hip.h) and what the two units that work on it share: fem.hip (life cycle, assembly,
-// the two-launch solver, the C ABI) and fem_persist.hip (the persistent solver's host side).  Internal: not installed, included by
-// these two units only.
+// The FEM handle (fb_fem_t of include/fembrain_hip.h) and what the units that work on it share: fem.hip (life cycle, assembly,
+// the two-launch solver, the C ABI), fem_persist.hip (the persistent solver's host side) and haptic.hip (the probe's entry points).
+// Internal: not installed, included by these units only.
 #pragma once
 #include "comm.h"
 #include "common.h"
@@ -11,6 +11,7 @@
 #include "delta.h"
 #include "subdivide.h"
 #include "surface.h"
+#include "haptic.h"
 
 namespace fb {
 
@@ -153,6 +154,7 @@ struct fb_fem_s {
   CutWork cut;            // fb_fem_cut: the last cut's codes, edges, pieces and new nodes (fb_fem_read_cut)
   DevBuf<double> carry;   // fb_fem_cut, FB_CUT_CARRY: the state in the caller's order across the re-sync
   SurfaceWork surf;       // fb_fem_surface: the boundary of the current mesh (surface.h); empty until somebody asks
+  HapticWork hap;         // fb_fem_add_haptic_forces / pick / volume: level array and scratch (haptic.h); empty until somebody asks
   std::vector<int> fixed_caller;  // the constrained DOFs in the caller's numbering (unsharded): what fb_fem_cut keeps
   DevBuf<int4> tets_next, tets_caller;   // (the element list being built; swapped with `tets`)
   DevBuf<double> x0_next;

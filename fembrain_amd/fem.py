@@ -313,6 +313,48 @@ class FemIntegrator:
         _l.check(self._L.fb_fem_floor_collision(self.h, floor_y, restitution, C.byref(n)))
         return n.value
 
+    # -- the haptic probe on the device (fb_fem_add_haptic_forces / pick / volume; unsharded handles) --
+    def add_haptic_forces(self, indices, forces, neighborhood_size):
+        """``Deformable::applyHapticForces`` on the device: adds ``forces[s]`` to node ``indices[s]`` and, with the fall-off
+        (size - j) / size, to the nodes of ring j = 1 .. size-1 around it -- into the current external force vector, bit for bit what
+        ``spread_haptic_forces`` adds.  At most ``lib.FB_HAPTIC_MAX_SOURCES`` sources."""
+        ids = _l.as_i32(indices)
+        f = _l.as_f64(forces, 3 * len(ids))
+        _l.check(self._L.fb_fem_add_haptic_forces(self.h, len(ids), _l.iptr(ids), _l.dptr(f), int(neighborhood_size)))
+
+    def pick_vertex(self, wpos):
+        """(index, position (3,), squared distance) of the node closest to ``wpos`` at the current state; of equal distances the lowest id"""
+        w = _l.as_f64(wpos, 3)
+        idx, xyz, d2 = C.c_int(-1), np.zeros(3), C.c_double(0)
+        _l.check(self._L.fb_fem_pick_vertex(self.h, _l.dptr(w), C.byref(idx), _l.dptr(xyz), C.byref(d2)))
+        return idx.value, xyz, d2.value
+
+    def pick_box(self, lo, hi, capacity=None, ids=None, xyz=None):
+        """(count, ids, positions) of the nodes with lo <= x0 + q <= hi, ascending ids.  capacity None: room for every node; 0: the
+        count only (ids and positions None).  ids / xyz: the caller's arrays to fill (at least ``capacity`` / ``3 capacity`` long);
+        only the first min(count, capacity) entries are written, and the returned views end there."""
+        lo, hi = _l.as_f64(lo, 3), _l.as_f64(hi, 3)
+        cap = self.n_nodes if capacity is None else int(capacity)
+        n = C.c_int(0)
+        if cap == 0:
+            _l.check(self._L.fb_fem_pick_box(self.h, _l.dptr(lo), _l.dptr(hi), 0, None, None, C.byref(n)))
+            return n.value, None, None
+        ids = np.zeros(cap, np.int32) if ids is None else ids
+        xyz = np.zeros((cap, 3)) if xyz is None else xyz
+        if ids.dtype != np.int32 or xyz.dtype != np.float64 or ids.size < cap or xyz.size < 3 * cap or not (ids.flags.c_contiguous and xyz.flags.c_contiguous):
+            raise ValueError("ids: contiguous int32 of at least capacity, xyz: contiguous float64 of at least 3 capacity")
+        _l.check(self._L.fb_fem_pick_box(self.h, _l.dptr(lo), _l.dptr(hi), cap, _l.iptr(ids), _l.dptr(xyz), C.byref(n)))
+        m = min(n.value, cap)
+        return n.value, ids.reshape(-1)[:m], xyz.reshape(-1)[:3 * m].reshape(m, 3)
+
+    def volume(self, per_element=False):
+        """Volume of the mesh at the current state (``Deformable::computeVolume``); with ``per_element`` (total, volumes (n_tets,)) in
+        ``read_mesh``'s element order"""
+        t = C.c_double(0)
+        pe = np.zeros(int(self._L.fb_fem_num_tets(self.h))) if per_element else None
+        _l.check(self._L.fb_fem_volume(self.h, C.byref(t), _l.dptr(pe)))
+        return (t.value, pe) if per_element else t.value
+
     # -- inspection (parity tests) --
     def num_tets(self):
         return self._L.fb_fem_num_tets(self.h)
@@ -466,7 +508,9 @@ class Deformable:
 
     GRAVITY_FORCE = -10000.0  # Deformable.cpp:335
 
-    def __init__(self, verts, tets, fixed_vertices=(), floor_y=None, gravity=True, **kw):
+    def __init__(self, verts, tets, fixed_vertices=(), floor_y=None, gravity=True, haptic_on_device=True, **kw):
+        """haptic_on_device: haptic forces, picking and volume run on the device where the handle allows (unsharded, at most
+        ``lib.FB_HAPTIC_MAX_SOURCES`` sources); False keeps the host route (what the tests compare against)."""
         self.fixed_vertices = sorted(int(v) for v in fixed_vertices)
         fd = fixed_vertices_to_dofs(self.fixed_vertices) if len(self.fixed_vertices) else np.zeros(0, np.int32)
         self.integrator = FemIntegrator(verts, tets, fd, **kw)
@@ -479,6 +523,7 @@ class Deformable:
         self.haptic_in_progress = False
         self.haptic_force_neighborhood_size = 5  # DEFAULT_FORCE_NEIGHBORHOOD_SIZE, Deformable.h:41
         self._pattern = None
+        self.haptic_on_device = bool(haptic_on_device) and kw.get("shard") is None
         self.on_deform = None  # FOnApplyDeformations(dof, q), Deformable.h:46
 
     def set_deform_callback(self, fn):
@@ -503,7 +548,15 @@ class Deformable:
     def timestep(self):
         it = self.integrator
         apply_gravity = self.gravity and self.ct_collided == 0
-        if self.haptic_in_progress and self.haptic_indices:
+        if self.haptic_in_progress and self.haptic_indices and self.haptic_on_device and len(self.haptic_indices) <= _l.FB_HAPTIC_MAX_SOURCES:
+            if apply_gravity:
+                it.set_uniform_force(1, self.GRAVITY_FORCE)
+            else:
+                it.set_external_forces_to_zero()
+            it.add_haptic_forces(self.haptic_indices, self.haptic_forces, self.haptic_force_neighborhood_size)
+        elif self.haptic_in_progress and self.haptic_indices:
+            if self.dof != it.r:  # (the mesh was cut: new nodes, new neighbours)
+                self.dof, self._pattern = it.r, None
             f = np.zeros(self.dof)
             if apply_gravity:
                 f[1::3] += self.GRAVITY_FORCE
@@ -534,3 +587,50 @@ class Deformable:
 
     def reset_deformations(self):
         self.integrator.reset_to_rest()
+
+    def cut(self, strip, mode="bake"):
+        """``FemIntegrator.cut``; the host route's copy of the pattern is dropped with the old mesh"""
+        info, delta = self.integrator.cut(strip, mode=mode)
+        self.dof, self._pattern = self.integrator.r, None
+        return info, delta
+
+    def _positions(self):
+        it = self.integrator
+        return np.asarray(it.verts, np.float64).reshape(-1, 3) + it.get_q_state()[0].reshape(-1, 3)
+
+    def pick_vertex(self, wpos):
+        """``Deformable::pickVertex`` (Deformable.cpp:422-428): (index, position) of the node of the displaced mesh closest to wpos"""
+        if self.haptic_on_device:
+            idx, xyz, _ = self.integrator.pick_vertex(wpos)
+            return idx, xyz
+        p = self._positions()
+        d = p - np.asarray(wpos, np.float64)
+        d2 = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2]
+        idx = int(np.argmin(d2))  # (the first of equal minima)
+        return idx, p[idx].copy()
+
+    def pick_vertices(self, box_lo, box_hi):
+        """``Deformable::pickVertices`` (Deformable.cpp:430-448): (positions (k, 3), ascending indices (k,)) inside the box, bounds included"""
+        if self.haptic_on_device:
+            _, ids, xyz = self.integrator.pick_box(box_lo, box_hi)
+            return xyz, ids
+        p = self._positions()
+        ids = np.nonzero(((p >= np.asarray(box_lo, np.float64)) & (p <= np.asarray(box_hi, np.float64))).all(axis=1))[0].astype(np.int32)
+        return p[ids], ids
+
+    def compute_volume(self):
+        """``Deformable::computeVolume`` (Deformable.cpp:260-279) at the current state"""
+        if self.haptic_on_device:
+            return self.integrator.volume()
+        p, t = self._positions(), np.asarray(self.integrator.tets)
+        u, v, w = p[t[:, 0]] - p[t[:, 3]], p[t[:, 1]] - p[t[:, 3]], p[t[:, 2]] - p[t[:, 3]]
+        det = (u[:, 0] * (v[:, 1] * w[:, 2] - v[:, 2] * w[:, 1]) + u[:, 1] * (v[:, 2] * w[:, 0] - v[:, 0] * w[:, 2])) + u[:, 2] * (v[:, 0] * w[:, 1] - v[:, 1] * w[:, 0])
+        return float(np.sum(np.abs(det) / 6.0))
+
+    def haptic_start_at(self, wpos):
+        """``Deformable::hapticStart(const vec3d&)`` (Deformable.cpp:519-532): picks the node closest to wpos; refuses a clamped one"""
+        idx, _ = self.pick_vertex(wpos)
+        if idx in self.fixed_vertices:
+            return False
+        self.haptic_start(idx)
+        return True

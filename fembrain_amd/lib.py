@@ -23,6 +23,7 @@ FB_RESYNC_FULL, FB_RESYNC_DELTA_MERGED, FB_RESYNC_DELTA_REBUILT = 0, 1, 2
 FB_CUT_BAKE, FB_CUT_CARRY = 0, 1
 FB_CUT_NOTHING, FB_CUT_DONE, FB_CUT_UNHANDLED, FB_CUT_DRY = 0, 1, 2, 3
 FB_CUT_UNHANDLED_IDS = 64  # unhandled element ids fb_fem_read_cut returns at most (subdivide.h kCutUnhandledIds)
+FB_HAPTIC_MAX_SOURCES = 256  # sources fb_fem_add_haptic_forces takes in one call
 
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
@@ -144,6 +145,10 @@ def lib():
         "fb_fem_set_cg": (C.c_int, [vp, C.c_double, C.c_int]),
         "fb_fem_set_constrained_dofs": (C.c_int, [vp, C.c_int, _ip]),
         "fb_fem_floor_collision": (C.c_int, [vp, C.c_double, C.c_double, _ip]),
+        "fb_fem_add_haptic_forces": (C.c_int, [vp, C.c_int, _ip, _dp, C.c_int]),
+        "fb_fem_pick_vertex": (C.c_int, [vp, _dp, _ip, _dp, _dp]),
+        "fb_fem_pick_box": (C.c_int, [vp, _dp, _dp, C.c_int, _ip, _dp, _ip]),
+        "fb_fem_volume": (C.c_int, [vp, _dp, _dp]),
         "fb_fem_num_nodes": (C.c_int, [vp]),
         "fb_fem_num_tets": (C.c_int, [vp]),
         "fb_fem_num_blocks": (C.c_int, [vp]),

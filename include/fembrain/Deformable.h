@@ -134,6 +134,27 @@ class HipIntegrator {
     check(fb_fem_floor_collision(h_, floorY, restitution, &n));
     return n;
   }
+  // The haptic probe on the device (fembrain_hip.h): ring-spread forces added into the current external forces, picking, volume.
+  // Node ids are the caller's.  AddHapticForces takes at most FB_HAPTIC_MAX_SOURCES sources.
+  void AddHapticForces(int n, const int* nodeIds, const double* forces3, int neighbourhoodSize) {
+    check(fb_fem_add_haptic_forces(h_, n, nodeIds, forces3, neighbourhoodSize));
+  }
+  int PickVertex(const double wpos[3], double xyz[3], double* dist2 = nullptr) {
+    int index = -1;
+    check(fb_fem_pick_vertex(h_, wpos, &index, xyz, dist2));
+    return index;
+  }
+  // ids / xyz: room for `capacity` entries (3 doubles each); returns the full count, of which min(count, capacity) were written
+  int PickBox(const double lo[3], const double hi[3], int capacity, int* ids, double* xyz) {
+    int found = 0;
+    check(fb_fem_pick_box(h_, lo, hi, capacity, ids, xyz, &found));
+    return found;
+  }
+  double Volume(double* perElement = nullptr) {
+    double total = 0.0;
+    check(fb_fem_volume(h_, &total, perElement));
+    return total;
+  }
   void RebuildElements() { check(fb_fem_rebuild_elements(h_)); }
   void Resync(int numVertices, const double* rest, int numElements, const int* elements, int nFixed, const int* fixed) {
     mass_.clear(); bptr_.clear(); bcol_.clear();
@@ -256,7 +277,17 @@ class Deformable {
   void timestep() {
     if (m_lpIntegrator == nullptr) return;
     const bool applyGravity = m_bApplyGravity && (m_ctCollided == 0);
-    if (m_bHapticInProgress && !m_vHapticIndices.empty()) {
+    if (m_bHapticInProgress && !m_vHapticIndices.empty() && m_vHapticIndices.size() <= (size_t)FB_HAPTIC_MAX_SOURCES &&
+        m_vHapticForces.size() >= m_vHapticIndices.size()) {
+      // the probe on the device: gravity or zero generated there, then the ring-spread forces added (fb_fem_add_haptic_forces)
+      if (applyGravity) m_lpIntegrator->SetUniformForce(1, -10000.0);
+      else m_lpIntegrator->SetExternalForcesToZero();
+      m_hapticStage.resize(3 * m_vHapticIndices.size());
+      for (size_t i = 0; i < m_vHapticIndices.size(); i++) {
+        m_hapticStage[3 * i] = m_vHapticForces[i].x; m_hapticStage[3 * i + 1] = m_vHapticForces[i].y; m_hapticStage[3 * i + 2] = m_vHapticForces[i].z;
+      }
+      m_lpIntegrator->AddHapticForces((int)m_vHapticIndices.size(), m_vHapticIndices.data(), m_hapticStage.data(), m_hapticForceNeighorhoodSize);
+    } else if (m_bHapticInProgress && !m_vHapticIndices.empty()) {  // more sources than the device call takes: the host walk
       std::fill(m_arrExtForces.begin(), m_arrExtForces.end(), 0.0);
       if (applyGravity)
         for (U32 i = 1; i < m_dof; i += 3) m_arrExtForces[i] += -10000.0;
@@ -392,7 +423,8 @@ class Deformable {
 
   // Deformable::applyHapticForces (Deformable.cpp:634-706): each haptic force acts on its vertex and, with the linear
   // fall-off (size - j)/size, on the vertices first reached in ring j of a breadth-first walk over mesh edges.  Vertex
-  // neighbours are the off-diagonal columns of the stiffness pattern (vertices sharing a tet edge).
+  // neighbours are the off-diagonal columns of the stiffness pattern (vertices sharing a tet edge).  The host walk: timestep() runs
+  // it only for more than FB_HAPTIC_MAX_SOURCES sources (the pattern is fetched then, and only then).
   bool applyHapticForces() {
     if (m_vHapticIndices.empty() || !m_bHapticInProgress) return false;
     if (m_bptr.empty()) {
@@ -471,30 +503,33 @@ class Deformable {
   void setDeformCallback(FOnApplyDeformations fOnDeform) { m_fOnDeform = fOnDeform; }
   double getSolverTime() const { return m_lpIntegrator->GetSystemSolveTime(); }
   // Deformable::pickVertex (Deformable.cpp:422-428): closest vertex of the displaced mesh to a world position
+  // (VolMesh::findClosestVertex: d = dx dx + dy dy + dz dz on rest + q, the first of equal minima), on the device: 40 bytes come back
   int pickVertex(const vec3d& wpos, vec3d& vertex) {
-    m_lpIntegrator->GetqState(m_q.data(), nullptr, nullptr);
-    int best = -1;
-    double bd = 0.0;
-    for (size_t i = 0; i < m_rest.size() / 3; i++) {
-      const double dx = m_rest[3 * i] + m_q[3 * i] - wpos.x, dy = m_rest[3 * i + 1] + m_q[3 * i + 1] - wpos.y, dz = m_rest[3 * i + 2] + m_q[3 * i + 2] - wpos.z;
-      const double d = dx * dx + dy * dy + dz * dz;
-      if (best < 0 || d < bd) { best = (int)i; bd = d; }
-    }
-    if (best >= 0) { vertex.x = m_rest[3 * (size_t)best] + m_q[3 * (size_t)best]; vertex.y = m_rest[3 * (size_t)best + 1] + m_q[3 * (size_t)best + 1]; vertex.z = m_rest[3 * (size_t)best + 2] + m_q[3 * (size_t)best + 2]; }
+    const double w[3] = {wpos.x, wpos.y, wpos.z};
+    double p[3] = {0.0, 0.0, 0.0};
+    const int best = m_lpIntegrator->PickVertex(w, p);
+    if (best >= 0) { vertex.x = p[0]; vertex.y = p[1]; vertex.z = p[2]; }
     return best;
   }
   // Deformable::pickVertices (Deformable.cpp:430-448)
   int pickVertices(const vec3d& boxLo, const vec3d& boxHi, std::vector<vec3d>& arrFoundCoords, std::vector<int>& arrFoundIndices) {
-    m_lpIntegrator->GetqState(m_q.data(), nullptr, nullptr);
-    arrFoundCoords.clear(); arrFoundIndices.clear();
-    for (size_t i = 0; i < m_rest.size() / 3; i++) {
-      vec3d v = {m_rest[3 * i] + m_q[3 * i], m_rest[3 * i + 1] + m_q[3 * i + 1], m_rest[3 * i + 2] + m_q[3 * i + 2]};
-      if (v.x >= boxLo.x && v.x <= boxHi.x && v.y >= boxLo.y && v.y <= boxHi.y && v.z >= boxLo.z && v.z <= boxHi.z) {
-        arrFoundCoords.push_back(v);
-        arrFoundIndices.push_back((int)i);
-      }
+    // on the device, ascending index order: one call with the capacity remembered from earlier picks (a probe's box holds a few dozen
+    // nodes), a second one only when the box holds more than that
+    const double lo[3] = {boxLo.x, boxLo.y, boxLo.z}, hi[3] = {boxHi.x, boxHi.y, boxHi.z};
+    arrFoundCoords.clear();
+    arrFoundIndices.resize((size_t)m_boxCapacity);
+    m_boxStage.resize(3 * (size_t)m_boxCapacity);
+    int n = m_lpIntegrator->PickBox(lo, hi, m_boxCapacity, arrFoundIndices.data(), m_boxStage.data());
+    if (n > m_boxCapacity) {
+      while (m_boxCapacity < n) m_boxCapacity *= 2;
+      arrFoundIndices.resize((size_t)m_boxCapacity);
+      m_boxStage.resize(3 * (size_t)m_boxCapacity);
+      n = std::min(m_boxCapacity, m_lpIntegrator->PickBox(lo, hi, m_boxCapacity, arrFoundIndices.data(), m_boxStage.data()));  // (the state does not change in between)
     }
-    return (int)arrFoundCoords.size();
+    const int got = std::max(n, 0);
+    arrFoundIndices.resize((size_t)got);
+    for (int i = 0; i < got; i++) arrFoundCoords.push_back(vec3d(m_boxStage[3 * (size_t)i], m_boxStage[3 * (size_t)i + 1], m_boxStage[3 * (size_t)i + 2]));
+    return got;
   }
   // Deformable::hapticStart(const vec3d&) (Deformable.cpp:519-532): refuses a clamped vertex
   bool hapticStart(const vec3d& wpos) {
@@ -506,12 +541,7 @@ class Deformable {
   }
   // Deformable::isVolumeChanged (Deformable.h:128); the rest volume is taken at the first call after a (re)build
   bool isVolumeChanged() {
-    if (m_restVolume < 0.0) {
-      std::vector<double> keep(m_q);
-      std::fill(m_q.begin(), m_q.end(), 0.0);
-      m_restVolume = volumeOf(m_q);
-      m_q.swap(keep);
-    }
+    if (m_restVolume < 0.0) m_restVolume = volumeOf(std::vector<double>(m_rest.size(), 0.0));  // (the rest shape: the host's copy of it, no transfer)
     return std::abs(computeVolume() - m_restVolume) > 0.0001;
   }
   std::string getModelName() const { return m_strModelName; }
@@ -531,10 +561,13 @@ class Deformable {
     for (size_t i = 0; i < p.size() && i < m_q.size(); i++) p[i] += m_q[i];
     return p;
   }
-  // Deformable::computeVolume (Deformable.cpp:260-279) on the current displaced positions
+  // Deformable::computeVolume (Deformable.cpp:260-279) on the current displaced positions, on the device (fb_fem_volume): 8 bytes come
+  // back, or with arrStore the volume of every element too.  count must then be the DEVICE's element count (= countCells() of this class,
+  // which follows every cut): anything else throws instead of leaving the array unwritten or overrunning it
   double computeVolume(double* arrStore = nullptr, U32 count = 0) {
-    m_lpIntegrator->GetqState(m_q.data(), nullptr, nullptr);
-    return volumeOf(m_q, arrStore, count);
+    if (arrStore != nullptr && (int)count != fb_fem_num_tets(m_lpIntegrator->handle()))
+      throw std::invalid_argument("computeVolume: arrStore holds another number of elements than the mesh has");
+    return m_lpIntegrator->Volume(arrStore);
   }
 
  private:
@@ -560,18 +593,18 @@ class Deformable {
     m_dampingMassCoeff = 0.0; m_dampingStiffnessCoeff = 0.01; m_timeStep = 0.0333; m_ctTimeStep = 0;
     m_hapticForceNeighorhoodSize = 5;  // DEFAULT_FORCE_NEIGHBORHOOD_SIZE, Deformable.h:41
     m_bApplyGravity = true;  // left uninitialised by the reference's init(); true is what its .sim files set
-    m_lpIntegrator = nullptr; m_lpSurface = nullptr; m_hasFloor = false; m_floorY = 0.0; m_dof = 0; m_restVolume = -1.0;
+    m_boxCapacity = 64; m_lpIntegrator = nullptr; m_lpSurface = nullptr; m_hasFloor = false; m_floorY = 0.0; m_dof = 0; m_restVolume = -1.0;
   }
   std::vector<double> m_rest;
   std::vector<int> m_elements;
   std::vector<int> m_vFixedVertices, m_vFixedDofs, m_vHapticIndices, m_bptr, m_bcol;
   std::vector<vec3d> m_vHapticForces;
-  std::vector<double> m_q, m_qVel, m_arrExtForces;
+  std::vector<double> m_q, m_qVel, m_arrExtForces, m_hapticStage, m_boxStage;
   HipIntegrator* m_lpIntegrator;
   SurfaceMesh* m_lpSurface;
   FOnApplyDeformations m_fOnDeform;
   U32 m_dof, m_ctCollided, m_ctTimeStep;
-  int m_idxPulledVertex, m_device, m_hapticForceNeighorhoodSize;
+  int m_idxPulledVertex, m_device, m_hapticForceNeighorhoodSize, m_boxCapacity;
   bool m_bHapticInProgress, m_bApplyGravity, m_hasFloor;
   double m_dampingMassCoeff, m_dampingStiffnessCoeff, m_timeStep, m_floorY, m_restVolume;
   std::string m_strModelName;

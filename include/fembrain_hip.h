@@ -360,6 +360,36 @@ int fb_fem_set_constrained_dofs(fb_fem_t h, int n_fixed_dofs, const int* fixed_d
  * n_collided (may be NULL) counts nodes with rest_y + q_y <= floor_y before the clamp. */
 int fb_fem_floor_collision(fb_fem_t h, double floor_y, double restitution, int* n_collided);
 
+/* ---- The haptic probe, on the device ----
+ * What FemBrain's AvatarProbe drives every frame while the user touches the tissue: Deformable::applyHapticForces
+ * (src/deformable/Deformable.cpp:634-706), pickVertex / pickVertices (:422-448) and computeVolume (:260-279).  The probe's own
+ * contact logic (its box faces, its vertex hash) stays with the host.  Unsharded handles only (FB_EINVAL otherwise, as
+ * fb_fem_read_mesh), device- or host-built plan alike; node ids are the CALLER's, also on a renumbered handle.  A handle that never
+ * calls these allocates and launches nothing extra.
+ *
+ * fb_fem_add_haptic_forces ADDS into the current external force vector (set gravity or zero first, as Deformable::timestep does):
+ * first forces3[3 s .. 3 s + 2] to node_ids[s] for s ascending (duplicate ids allowed); then for every source s ascending, to every node
+ * first reached in ring j = 1 .. size-1 of a breadth-first walk from it, mag_j * forces3[s] with mag_j = 1.0 * (size - j) / (double)size.
+ * Neighbours are the nodes sharing an element.  Each addition is one fp64 multiply and one fp64 add in that order per node: the
+ * result is bit for bit the host walk's.  n == 0 is a no-op; neighbourhood_size outside [1, 255], a null pointer with n > 0,
+ * n > FB_HAPTIC_MAX_SOURCES or an id outside [0, n_nodes) return FB_EINVAL before anything is launched or changed.  The walk is
+ * (size - 1) passes over the element list per batch of 32 sources, so the cost grows with both: a caller with more sources than
+ * FB_HAPTIC_MAX_SOURCES spreads on the host and uses fb_fem_set_external_forces. */
+#define FB_HAPTIC_MAX_SOURCES 256
+int fb_fem_add_haptic_forces(fb_fem_t h, int n, const int* node_ids, const double* forces3, int neighbourhood_size);
+/* VolMesh::findClosestVertex: the node with the smallest d = dx*dx + dy*dy + dz*dz, (dx, dy, dz) = (x0 + q) - wpos in fp64; of equal d
+ * the lowest id.  index, xyz (its current position) and dist2 may each be NULL.  One copy of 40 bytes leaves the device. */
+int fb_fem_pick_vertex(fb_fem_t h, const double wpos[3], int* index, double xyz[3], double* dist2);
+/* Deformable::pickVertices: the nodes with lo <= x0 + q <= hi on all three axes (inclusive), ascending ids in ids[] and their positions
+ * in xyz[3 ..].  *n_found is the full count also when it exceeds capacity; only the first min(count, capacity) entries are written.
+ * capacity == 0 (ids and xyz may then be NULL) returns the count only. */
+int fb_fem_pick_box(fb_fem_t h, const double lo[3], const double hi[3], int capacity, int* ids, double* xyz, int* n_found);
+/* Deformable::computeVolume: per element |u . (v x w)| / 6, u, v, w = p0 - p3, p1 - p3, p2 - p3 on x0 + q, evaluated as
+ * u0 (v1 w2 - v2 w1) + u1 (v2 w0 - v0 w2) + u2 (v0 w1 - v1 w0).  per_element[fb_fem_num_tets] (may be NULL) is in fb_fem_read_mesh's
+ * element order.  *total is their sum in a fixed tree that depends on the element count only (256 consecutive elements per leaf group):
+ * the same bits from call to call, within n_tets * 2^-53 * total of any other order. */
+int fb_fem_volume(fb_fem_t h, double* total, double* per_element);
+
 /* ---- inspection entry points (what the parity tests compare against the oracle) ---- */
 int fb_fem_num_nodes(fb_fem_t h);   /* global */
 int fb_fem_num_tets(fb_fem_t h);    /* local (all for an unsharded handle) */
