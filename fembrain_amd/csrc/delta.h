@@ -60,6 +60,12 @@ int delta_upload_device(hipStream_t s, int n_tets_old, int n_removed, const int*
 int delta_relabel_nodes(hipStream_t s, MeshDelta& D, int n_nodes, const int* map);
 // the new element list: kept elements in their order (node ids through imap, nullptr = as they are), changed ones with their new nodes, added ones behind
 int delta_tets(hipStream_t s, const MeshDelta& D, const int4* tets_old, const int* imap, int4* tets_new);
+// A per-element byte (the material ids of fb_fem_set_element_materials) through the same change: removed elements drop out, kept and
+// changed ones keep theirs in order (k_delta_tets' estate / pos), added ones get 0 -- or, for the pieces of a cut, their parent's:
+// parent j = parents[j] (an old element id, n_parents of them) owns the added elements [piece_off[j], piece_off[j] + piece_cnt[j]).
+// ids_new: at least max(1, n_tets_new) bytes.
+int delta_element_bytes(hipStream_t s, const MeshDelta& D, const unsigned char* ids_old, unsigned char* ids_new, int n_parents = 0, const int* parents = nullptr,
+                        const int* piece_off = nullptr, const int* piece_cnt = nullptr);
 // A renumbered handle: the new nodes take their place in the slab order under the key geometry the order was built with (frozen until the
 // next full rebuild), ties behind the old nodes.  Outputs D.imap, D.newint, D.node_keys and the two maps of the new order.
 // n_windows > 0: the order has the second stage (renumber.h, sigma_window): keys_old are its keys, win_keys the slab key of every window's first node.

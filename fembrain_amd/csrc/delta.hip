@@ -59,6 +59,25 @@ __global__ __launch_bounds__(kB) void k_delta_tets(int n_old, const int4* __rest
   tets_new[pos[e]] = t;
 }
 
+__global__ __launch_bounds__(kB) void k_delta_bytes(int n_old, const unsigned char* __restrict__ estate, const int* __restrict__ pos, const unsigned char* __restrict__ ids_old,
+                                                    unsigned char* __restrict__ ids_new) {
+  const int e = blockIdx.x * kB + threadIdx.x;
+  if (e >= n_old || estate[e] == 1) return;
+  ids_new[pos[e]] = ids_old[e];
+}
+
+// the pieces of cut element parents[j] inherit its byte (at most 6 pieces: subdivide.hip)
+__global__ __launch_bounds__(kB) void k_delta_piece_bytes(int n_parents, const int* __restrict__ parents, const int* __restrict__ piece_off, const int* __restrict__ piece_cnt,
+                                                          int n_old, int n_added, const unsigned char* __restrict__ ids_old, unsigned char* __restrict__ ids_added) {
+  const int j = blockIdx.x * kB + threadIdx.x;
+  if (j >= n_parents) return;
+  const int parent = parents[j];
+  if (parent < 0 || parent >= n_old) return;
+  const unsigned char id = ids_old[parent];
+  const int lo = piece_off[j], hi = min(lo + piece_cnt[j], n_added);
+  for (int p = max(lo, 0); p < hi; p++) ids_added[p] = id;
+}
+
 __global__ __launch_bounds__(kB) void k_delta_keys(int n, const double* __restrict__ xyz, SlabKeyGeom g, unsigned long long* __restrict__ keys, uint32_t* __restrict__ ids) {
   const int i = blockIdx.x * kB + threadIdx.x;
   if (i >= n) return;
@@ -616,6 +635,20 @@ int delta_tets(hipStream_t s, const MeshDelta& D, const int4* tets_old, const in
   hipLaunchKernelGGL(k_delta_tets, grid_for(D.n_tets_old), dim3(kB), 0, s, D.n_tets_old, tets_old, D.estate.p, D.pos.p, imap, D.n_changed, D.changed_ids, D.changed_nodes, tets_new);
   FB_HIP(hipGetLastError());
   if (D.n_added) FB_HIP(hipMemcpyAsync(tets_new + D.n_kept, D.added, sizeof(int4) * (size_t)D.n_added, hipMemcpyDeviceToDevice, s));
+  return FB_OK;
+}
+
+int delta_element_bytes(hipStream_t s, const MeshDelta& D, const unsigned char* ids_old, unsigned char* ids_new, int n_parents, const int* parents, const int* piece_off,
+                        const int* piece_cnt) {
+  if (D.n_tets_old > 0) {
+    hipLaunchKernelGGL(k_delta_bytes, grid_for(D.n_tets_old), dim3(kB), 0, s, D.n_tets_old, D.estate.p, D.pos.p, ids_old, ids_new);
+    FB_HIP(hipGetLastError());
+  }
+  if (D.n_added) FB_HIP(hipMemsetAsync(ids_new + D.n_kept, 0, (size_t)D.n_added, s));
+  if (D.n_added && n_parents > 0) {
+    hipLaunchKernelGGL(k_delta_piece_bytes, grid_for(n_parents), dim3(kB), 0, s, n_parents, parents, piece_off, piece_cnt, D.n_tets_old, D.n_added, ids_old, ids_new + D.n_kept);
+    FB_HIP(hipGetLastError());
+  }
   return FB_OK;
 }
 

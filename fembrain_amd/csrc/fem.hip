@@ -112,6 +112,24 @@ int upload_masks(fb_fem_s* h) {
   return h->nodemask.upload(nm, h->stream);
 }
 
+// The material-aware instantiations of the element-major kernels need the LDS sizes of the plan as the uniform ones do: set when the
+// plan of a handle with an element map is (re)built, and when a handle gets its map.
+int material_kernel_attributes(fb_fem_s* h) {
+  if (!h->asm_tets) return FB_OK;
+  const bool tangent = h->prm.exact_tangent && !h->prm.linear;
+  const void* kerns[2][2][2] = {{{(const void*)k_assemble_tets<float, 2, false, false, true>, (const void*)k_assemble_tets<float, 2, false, true, true>},
+                                 {(const void*)k_assemble_tets<float, 2, true, false, true>, (const void*)k_assemble_tets<float, 2, true, true, true>}},
+                                {{(const void*)k_assemble_tets<double, 2, false, false, true>, (const void*)k_assemble_tets<double, 2, false, true, true>},
+                                 {(const void*)k_assemble_tets<double, 2, true, false, true>, (const void*)k_assemble_tets<double, 2, true, true, true>}}};
+  for (int nm = 0; nm < 2; nm++) FB_HIP(hipFuncSetAttribute(kerns[h->f64 ? 1 : 0][tangent ? 1 : 0][nm], hipFuncAttributeMaxDynamicSharedMemorySize, h->asm_lds));
+  if (h->asm_staged) {
+    FB_HIP(hipFuncSetAttribute((const void*)k_assemble_tets_st<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, h->asm_lds_st));
+    FB_HIP(hipFuncSetAttribute((const void*)k_assemble_tets_st<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, h->asm_lds_st));
+    FB_HIP(hipFuncSetAttribute((const void*)k_mass_blocks<float, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (kBlock / 64) * h->asm_max_width * 64 * (int)sizeof(double)));
+  }
+  return FB_OK;
+}
+
 int upload_plan(fb_fem_s* h, const double* xyz_global, const float* xyz_device = nullptr, const double* xyz_device64 = nullptr) {
   const FemPlan& P = h->plan;
   hipStream_t s = h->stream;
@@ -223,6 +241,7 @@ int upload_plan(fb_fem_s* h, const double* xyz_global, const float* xyz_device =
         FB_HIP(hipFuncSetAttribute((const void*)k_mass_blocks<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (kBlock / 64) * mw * 64 * (int)sizeof(double)));
         if (getenv("FEMBRAIN_TIMING")) fprintf(stderr, "[fembrain] staged element-major assembly: %d workgroups, %d B of LDS each (%d per CU)\n", h->asm_grid_st, h->asm_lds_st, per_cu_st);
       }
+      if (h->mat_ids.p) FB_TRY(material_kernel_attributes(h));
     } else {
       h->asm_staged = false;
       h->inc_off.release(); h->inc.release(); h->inc_slot.release();
@@ -284,6 +303,40 @@ int upload_plan(fb_fem_s* h, const double* xyz_global, const float* xyz_device =
   return FB_OK;
 }
 
+// ---- per-element materials ----
+inline bool has_material_map(const fb_fem_s* h) { return h->mat_ids.p != nullptr; }
+
+inline void lame_of(double E, double nu, double* lambda, double* mu) {
+  *lambda = (nu * E) / ((1 + nu) * (1 - 2 * nu));
+  *mu = E / (2 * (1 + nu));
+}
+
+// the device table of n materials under the handle's force scaling: lambda | mu | rho/20, padded with entry 0
+int upload_material_table(fb_fem_s* h, int n, const double* E, const double* nu, const double* rho) {
+  std::vector<double> tab((size_t)3 * kMaxMaterials);
+  for (int i = 0; i < kMaxMaterials; i++) {
+    const int k = i < n ? i : 0;  // (padding: any byte indexes a valid material)
+    lame_of(E[k] * h->force_scale, nu[k], &tab[i], &tab[kMaxMaterials + i]);
+    tab[2 * kMaxMaterials + i] = rho[k] / 20.0;
+  }
+  return h->mat_tab.upload(tab, h->stream);
+}
+
+// lambda / mu of the handle (= material 0) and, where an element map exists, the device table.  rho_changed: the mass entries
+// (k_mass_blocks) are to be formed again -- they do not depend on E or nu
+int refresh_materials(fb_fem_s* h, bool rho_changed) {
+  if (has_material_map(h)) FB_TRY(upload_material_table(h, (int)h->mat_E.size(), h->mat_E.data(), h->mat_nu.data(), h->mat_rho.data()));
+  lame_of(h->prm.E * h->force_scale, h->prm.nu, &h->lambda, &h->mu);
+  h->system_valid = false;
+  if (rho_changed) h->mass_valid = false;
+  return FB_OK;
+}
+
+inline void asm_materials(const fb_fem_s* h, AsmParams& ap) {
+  ap.lambda = h->lambda; ap.mu = h->mu; ap.rho20 = h->prm.rho / 20.0;
+  ap.mtab = has_material_map(h) ? h->mat_tab.p : nullptr;
+}
+
 int launch_rest(fb_fem_s* h, int* first_flat = nullptr) {
   h->mass_valid = false;  // (the rest volumes may change)
   const int nt = h->plan.n_tets;
@@ -317,12 +370,13 @@ int halo_exchange(fb_fem_s* h, double* vec, int width = 3) {
 template <typename MT>
 int launch_warp(fb_fem_s* h, const double* u, double* rot) {
   const int nt = h->plan.n_tets;
-  if (h->kcorr.p)
-    hipLaunchKernelGGL((k_tet_warp<MT, true>), dim3(ceil_div(nt, kBlock)), dim3(kBlock), 0, h->stream, nt, h->tets.p, h->x0.p, u, h->rest.p, (MT*)h->rec.p, h->fe.p,
-                       rot, h->lambda, h->mu, h->prm.linear != 0 ? 1 : 0, (MT*)h->kcorr.p);
-  else
-    hipLaunchKernelGGL((k_tet_warp<MT, false>), dim3(ceil_div(nt, kBlock)), dim3(kBlock), 0, h->stream, nt, h->tets.p, h->x0.p, u, h->rest.p, (MT*)h->rec.p, h->fe.p,
-                       rot, h->lambda, h->mu, h->prm.linear != 0 ? 1 : 0, (MT*)nullptr);
+#define FB_TET_WARP(TANGENT, MAT, KCORR)                                                                                                                          \
+  hipLaunchKernelGGL((k_tet_warp<MT, TANGENT, MAT>), dim3(ceil_div(nt, kBlock)), dim3(kBlock), 0, h->stream, nt, h->tets.p, h->x0.p, u, h->rest.p, (MT*)h->rec.p, \
+                     h->fe.p, rot, h->lambda, h->mu, h->prm.linear != 0 ? 1 : 0, (MT*)(KCORR), (const uint8_t*)h->mat_ids.p, (const double*)h->mat_tab.p)
+  if (has_material_map(h)) { if (h->kcorr.p) FB_TET_WARP(true, true, h->kcorr.p); else FB_TET_WARP(false, true, nullptr); }
+  else if (h->kcorr.p) FB_TET_WARP(true, false, h->kcorr.p);
+  else FB_TET_WARP(false, false, nullptr);
+#undef FB_TET_WARP
   FB_HIP(hipGetLastError());
   return FB_OK;
 }
@@ -344,6 +398,7 @@ int launch_rows(fb_fem_s* h, const AsmParams& ap, const double* qvel, const doub
   // on a stream of its own BESIDE the element-major launch -- one wavefront takes ~0.8 ms for a 59-slot slice (one latency-bound slot after
   // the other) while the element-major kernel does the other 1,300 slices of the 606k-tet probe in 0.19 ms; the two write disjoint slices.
   // (A CU-masked handle has no second stream with the same mask: the pass then follows in order.)
+  const bool mat = has_material_map(h);
   const bool wide_pass = h->asm_tets && !mblk_out && h->asm_wide > 0;
   bool wide_beside = false;
   if (wide_pass) {
@@ -355,6 +410,9 @@ int launch_rows(fb_fem_s* h, const AsmParams& ap, const double* qvel, const doub
     if (wide_beside) {
       FB_HIP(hipEventRecord(h->ev_side[0], h->stream));  // (the records and element forces of this assembly are complete)
       FB_HIP(hipStreamWaitEvent(h->side, h->ev_side[0], 0));
+      if (mat) hipLaunchKernelGGL((k_assemble_wide<MT, true>), dim3(h->asm_wide_grid), dim3(kWideBlock), 0, h->side, sell_view(h), h->wide_list.p, h->asm_wide, h->asm_wide_slots,
+                                  h->wide_scratch.p, h->slot_coff.p, h->slot_ccnt.p, h->contrib.p, (const MT*)h->rec.p, h->fe.p, o, ap, (const MT*)h->kcorr.p);
+      else
       hipLaunchKernelGGL(k_assemble_wide<MT>, dim3(h->asm_wide_grid), dim3(kWideBlock), 0, h->side, sell_view(h), h->wide_list.p, h->asm_wide, h->asm_wide_slots,
                          h->wide_scratch.p, h->slot_coff.p, h->slot_ccnt.p, h->contrib.p, (const MT*)h->rec.p, h->fe.p, o, ap, (const MT*)h->kcorr.p);
       FB_HIP(hipGetLastError());
@@ -363,8 +421,11 @@ int launch_rows(fb_fem_s* h, const AsmParams& ap, const double* qvel, const doub
   }
   if (h->asm_tets && h->asm_staged && std::is_same<MT, float>::value && !h->kcorr.p && !mblk_out) {
     if (!h->mass_valid) {  // once per rebuild of the rest data
+      if (mat) hipLaunchKernelGGL((k_mass_blocks<float, true>), dim3(ceil_div(h->plan.n_slices, kBlock / 64)), dim3(kBlock), (size_t)(kBlock / 64) * h->asm_max_width * 64 * sizeof(double),
+                                  h->stream, sell_view(h), h->inc_off.p, h->inc.p, h->inc_slot.p, h->volf.p, ap.rho20, h->asm_max_width, h->mblk.p, (const uint8_t*)h->mat_ids.p, ap.mtab);
+      else
       hipLaunchKernelGGL(k_mass_blocks<float>, dim3(ceil_div(h->plan.n_slices, kBlock / 64)), dim3(kBlock), (size_t)(kBlock / 64) * h->asm_max_width * 64 * sizeof(double),
-                         h->stream, sell_view(h), h->inc_off.p, h->inc.p, h->inc_slot.p, h->volf.p, ap.rho20, h->asm_max_width, h->mblk.p);
+                         h->stream, sell_view(h), h->inc_off.p, h->inc.p, h->inc_slot.p, h->volf.p, ap.rho20, h->asm_max_width, h->mblk.p, (const uint8_t*)nullptr, (const double*)nullptr);
       FB_HIP(hipGetLastError());
       h->mass_valid = true;
     }
@@ -375,10 +436,13 @@ int launch_rows(fb_fem_s* h, const AsmParams& ap, const double* qvel, const doub
       FB_HIP(hipMemset(prof, 0, 16 * sizeof(unsigned long long)));
     }
     const AsmOut<float>& of = reinterpret_cast<const AsmOut<float>&>(o);
-    if (qacc) hipLaunchKernelGGL(k_assemble_tets_st<true>, dim3(h->asm_grid_st), dim3(kBlock), (size_t)h->asm_lds_st, h->stream, sell_view(h), h->inc_off.p, h->inc.p, h->inc_slot.p,
-                                 (const float*)h->rec.p, h->fe.p, of, ap, h->asm_max_width, prof);
-    else hipLaunchKernelGGL(k_assemble_tets_st<false>, dim3(h->asm_grid_st), dim3(kBlock), (size_t)h->asm_lds_st, h->stream, sell_view(h), h->inc_off.p, h->inc.p, h->inc_slot.p,
-                            (const float*)h->rec.p, h->fe.p, of, ap, h->asm_max_width, prof);
+#define FB_ASM_ST(NEWMARK, MAT)                                                                                                                                  \
+  hipLaunchKernelGGL((k_assemble_tets_st<NEWMARK, MAT>), dim3(h->asm_grid_st), dim3(kBlock), (size_t)h->asm_lds_st, h->stream, sell_view(h), h->inc_off.p, h->inc.p, \
+                     h->inc_slot.p, (const float*)h->rec.p, h->fe.p, of, ap, h->asm_max_width, prof)
+    if (mat) { if (qacc) FB_ASM_ST(true, true); else FB_ASM_ST(false, true); }
+    else if (qacc) FB_ASM_ST(true, false);
+    else FB_ASM_ST(false, false);
+#undef FB_ASM_ST
     if (prof) {
       FB_HIP(hipStreamSynchronize(h->stream));
       unsigned long long t[16];
@@ -395,11 +459,15 @@ int launch_rows(fb_fem_s* h, const AsmParams& ap, const double* qvel, const doub
       FB_HIP(hipMalloc((void**)&prof, 16 * sizeof(unsigned long long)));
       FB_HIP(hipMemset(prof, 0, 16 * sizeof(unsigned long long)));
     }
-#define FB_ASM_TETS(TANGENT, NEWMARK)                                                                                                                        \
-  hipLaunchKernelGGL((k_assemble_tets<MT, G, TANGENT, NEWMARK>), dim3(h->asm_grid), dim3(kBlock), (size_t)h->asm_lds, h->stream, sell_view(h), h->inc_off.p, \
+#define FB_ASM_TETS(TANGENT, NEWMARK, MAT)                                                                                                                        \
+  hipLaunchKernelGGL((k_assemble_tets<MT, G, TANGENT, NEWMARK, MAT>), dim3(h->asm_grid), dim3(kBlock), (size_t)h->asm_lds, h->stream, sell_view(h), h->inc_off.p, \
                      h->inc.p, h->inc_slot.p, (const MT*)h->rec.p, h->fe.p, o, ap, (const MT*)h->kcorr.p, h->asm_max_width, prof)
-    if (h->kcorr.p) { if (qacc) FB_ASM_TETS(true, true); else FB_ASM_TETS(true, false); }
-    else { if (qacc) FB_ASM_TETS(false, true); else FB_ASM_TETS(false, false); }
+    if (mat) {
+      if (h->kcorr.p) { if (qacc) FB_ASM_TETS(true, true, true); else FB_ASM_TETS(true, false, true); }
+      else { if (qacc) FB_ASM_TETS(false, true, true); else FB_ASM_TETS(false, false, true); }
+    } else
+    if (h->kcorr.p) { if (qacc) FB_ASM_TETS(true, true, false); else FB_ASM_TETS(true, false, false); }
+    else { if (qacc) FB_ASM_TETS(false, true, false); else FB_ASM_TETS(false, false, false); }
 #undef FB_ASM_TETS
     if (prof) {  // FEMBRAIN_ASM_PROFILE=1: where the wavefronts of k_assemble_tets spend their time (100 MHz ticks summed over the workgroups)
       FB_HIP(hipStreamSynchronize(h->stream));
@@ -410,6 +478,9 @@ int launch_rows(fb_fem_s* h, const AsmParams& ap, const double* qvel, const doub
                 t[4 * w] * 0.01 / h->asm_grid, t[4 * w + 1] * 0.01 / h->asm_grid, t[4 * w + 2] * 0.01 / h->asm_grid, t[4 * w + 3] * 0.01 / h->asm_grid);
       (void)hipFree(prof);
     }
+  } else if (mat) {
+    hipLaunchKernelGGL((k_assemble_rows<MT, true>), dim3(h->grid), dim3(kBlock), 0, h->stream, sell_view(h), h->slot_coff.p, h->slot_ccnt.p,
+                       h->contrib.p, (const MT*)h->rec.p, h->fe.p, o, ap, (const MT*)h->kcorr.p, 0);
   } else {
     hipLaunchKernelGGL(k_assemble_rows<MT>, dim3(h->grid), dim3(kBlock), 0, h->stream, sell_view(h), h->slot_coff.p, h->slot_ccnt.p,
                        h->contrib.p, (const MT*)h->rec.p, h->fe.p, o, ap, (const MT*)h->kcorr.p, 0);
@@ -419,12 +490,19 @@ int launch_rows(fb_fem_s* h, const AsmParams& ap, const double* qvel, const doub
   } else if (wide_pass) {
     AsmOut<MT> ow = o;
     ow.mblk_in = nullptr;
-    if (getenv("FEMBRAIN_ASM_WIDE_ROWS"))  // development aid: the one-wavefront-per-slice form (same bits)
+    if (getenv("FEMBRAIN_ASM_WIDE_ROWS")) {  // development aid: the one-wavefront-per-slice form (same bits)
+      if (mat) hipLaunchKernelGGL((k_assemble_rows<MT, true>), dim3(h->grid), dim3(kBlock), 0, h->stream, sell_view(h), h->slot_coff.p, h->slot_ccnt.p,
+                                  h->contrib.p, (const MT*)h->rec.p, h->fe.p, ow, ap, (const MT*)h->kcorr.p, h->asm_max_width);
+      else
       hipLaunchKernelGGL(k_assemble_rows<MT>, dim3(h->grid), dim3(kBlock), 0, h->stream, sell_view(h), h->slot_coff.p, h->slot_ccnt.p,
                          h->contrib.p, (const MT*)h->rec.p, h->fe.p, ow, ap, (const MT*)h->kcorr.p, h->asm_max_width);
-    else
+    } else if (mat) {
+      hipLaunchKernelGGL((k_assemble_wide<MT, true>), dim3(h->asm_wide_grid), dim3(kWideBlock), 0, h->stream, sell_view(h), h->wide_list.p, h->asm_wide, h->asm_wide_slots,
+                         h->wide_scratch.p, h->slot_coff.p, h->slot_ccnt.p, h->contrib.p, (const MT*)h->rec.p, h->fe.p, ow, ap, (const MT*)h->kcorr.p);
+    } else {
       hipLaunchKernelGGL(k_assemble_wide<MT>, dim3(h->asm_wide_grid), dim3(kWideBlock), 0, h->stream, sell_view(h), h->wide_list.p, h->asm_wide, h->asm_wide_slots,
                          h->wide_scratch.p, h->slot_coff.p, h->slot_ccnt.p, h->contrib.p, (const MT*)h->rec.p, h->fe.p, ow, ap, (const MT*)h->kcorr.p);
+    }
   }
   FB_HIP(hipGetLastError());
   return FB_OK;
@@ -438,7 +516,7 @@ int assemble_system(fb_fem_s* h) {
   FB_TRY(halo_exchange(h, h->q.p));
   FB_TRY(halo_exchange(h, h->qvel.p));
   AsmParams ap;
-  ap.lambda = h->lambda; ap.mu = h->mu; ap.rho20 = h->prm.rho / 20.0;
+  asm_materials(h, ap);
   const double* qacc = nullptr;
   if (h->prm.integrator == FB_INTEGRATOR_NEWMARK) {
     // implicitNewmarkSparse.cpp:218-236: K_eff = K + alpha4 (cK K + cM M) + alpha1 M;  residual = -(M qaccel + (cK K + cM M) qvel + f_int - f_ext)
@@ -1180,6 +1258,11 @@ int build(fb_fem_s* h, int n_nodes, const double* xyz, int n_tets, const int* te
       return fail(FB_EINVAL, "element %d has zero (or non-finite) rest volume", h->plan.tet_global.empty() ? e : h->plan.tet_global[e]);
   }
   lap("volume check");
+  if (has_material_map(h) && !h->map_from_delta) {  // a new mesh: every element is material 0 again, the table stays (a delta re-sync swaps its own map in afterwards)
+    FB_TRY(h->mat_ids.alloc((size_t)std::max(1, n_tets)));
+    FB_TRY(h->mat_ids.zero(h->stream));
+    h->mat_hi = 0;
+  }
   FB_TRY(upload_plan(h, xyz, dm ? dm->xyz : nullptr, dm ? dm->xyz64 : nullptr));
   lap("upload");
   if (h->device_plan) {
@@ -1312,6 +1395,7 @@ int create_common(fb_fem_t* out, int n_nodes, const double* xyz, int n_tets, con
   }
   h->lambda = (params->nu * params->E) / ((1 + params->nu) * (1 - 2 * params->nu));
   h->mu = params->E / (2 * (1 + params->nu));
+  h->mat_E.assign(1, params->E); h->mat_nu.assign(1, params->nu); h->mat_rho.assign(1, params->rho);  // the one-entry table of the params
   int rc = FB_OK;
   do {
    // collective, before anything rank-local can fail: the node order of a sharded handle under FB_RENUMBER_AUTO
@@ -1690,6 +1774,13 @@ int resync_delta(fb_fem_s* h, int n_removed, const int* removed, int n_changed, 
   else
     FB_TRY(delta_upload(s, nt_old, n_removed, removed, n_changed, changed_ids, changed_nodes, n_added, added, n_new_nodes, new_xyz, D, W));
   const int nt_new = D.n_tets_new();
+  if (has_material_map(h)) {
+    // the element map through the change, on the device: kept and changed elements keep their material in order, the pieces of a cut
+    // inherit their parent's (k_cut_pieces' cut_tets / piece_off), other added elements get 0.  Swapped in when the re-sync is complete.
+    FB_TRY(h->mat_ids_next.alloc((size_t)std::max(1, nt_new)));
+    if (device_src) FB_TRY(delta_element_bytes(s, D, h->mat_ids.p, h->mat_ids_next.p, h->cut.n_cut, h->cut.cut_tets.p, h->cut.piece_off.p, h->cut.pcount.p));
+    else FB_TRY(delta_element_bytes(s, D, h->mat_ids.p, h->mat_ids_next.p));
+  }
   lap("change uploaded");
   const char* env = getenv("FEMBRAIN_RESYNC_DELTA");
   bool merge = h->csr_ready && !(env && !strcmp(env, "rebuild"));
@@ -1715,7 +1806,15 @@ int resync_delta(fb_fem_s* h, int n_removed, const int* removed, int n_changed, 
     FB_TRY(tet_span_device(s, nt_new, h->tets_next.p, n_new, nullptr, W, &span, &mean));
     if (mode == FB_RENUMBER_ON || (n_new >= kRenumberMinNodes && span > renumber_span_limit(n_new))) merge = false;
   }
-  if (!merge) return resync_delta_rebuild(h, n_old, n_new, n_fixed, fixed);
+  if (!merge) {
+    h->map_from_delta = true;  // (the full builder leaves the map alone: the old one is still being read by the kernels queued above)
+    const int rc = resync_delta_rebuild(h, n_old, n_new, n_fixed, fixed);
+    h->map_from_delta = false;
+    // (also where the builder failed half way: the handle is poisoned then and launches nothing until a re-sync succeeds, but the map's
+    // length follows the element count the plan may already have)
+    if (has_material_map(h)) h->mat_ids.swap(h->mat_ids_next);
+    return rc;
+  }
 
   // ---- the node order ----
   if (h->ren.active) {
@@ -1782,6 +1881,7 @@ int resync_delta(fb_fem_s* h, int n_removed, const int* removed, int n_changed, 
   h->device_plan = true;
   h->host_pattern = false;
   lap("plan");
+  if (has_material_map(h)) h->mat_ids.swap(h->mat_ids_next);
   FB_TRY(upload_plan(h, nullptr));
   lap("per-step arrays");
   FB_TRY(rest_state_checked(h));
@@ -2283,12 +2383,92 @@ int fb_fem_set_internal_force_scaling(fb_fem_t h, double factor) {
   if (!(factor > 0) || !std::isfinite(factor)) return fail(FB_EINVAL, "internal force scaling factor must be positive");
   // f_int and K are linear in Young's modulus, so scaling both (integratorBase.cpp:46, implicitNewmarkSparse.cpp:200-204;
   // PS_VolumeConservingIntegrator.cpp:84-90) is scaling the Lame parameters the element kernels use
-  const double E = h->prm.E * factor, nu = h->prm.nu;
-  h->lambda = (nu * E) / ((1 + nu) * (1 - 2 * nu));
-  h->mu = E / (2 * (1 + nu));
+  // (every material's E: the table of a handle with an element map is made again)
+  const double before = h->force_scale;
+  h->force_scale = factor;
+  const int rc = refresh_materials(h, false);  // (the mass does not depend on E)
+  if (rc != FB_OK) h->force_scale = before;
+  return rc;
+}
+
+// ---- per-element materials ----
+int fb_fem_set_materials(fb_fem_t h, int n_materials, const double* E, const double* nu, const double* rho) {
+  CHECK_HANDLE(h);
+  if (n_materials < 1 || n_materials > kMaxMaterials) return fail(FB_EINVAL, "a material table has 1 to %d entries, not %d", kMaxMaterials, n_materials);
+  if (!E || !nu || !rho) return fail(FB_EINVAL, "null material array");
+  for (int i = 0; i < n_materials; i++)  // what VolumetricMesh's parser accepts (volumetricMesh.cpp:327): E > 0, -1 < nu < 0.5, rho > 0
+    if (!(E[i] > 0) || !(nu[i] > -1.0 && nu[i] < 0.5) || !(rho[i] > 0) || !std::isfinite(E[i]) || !std::isfinite(nu[i]) || !std::isfinite(rho[i]))
+      return fail(FB_EINVAL, "material %d: E = %g, nu = %g, rho = %g (E > 0, -1 < nu < 0.5, rho > 0, all finite)", i, E[i], nu[i], rho[i]);
+  if (h->plan.n_ranks > 1 && n_materials > 1) return fail(FB_EINVAL, "a sharded handle has one material");
+  if (n_materials <= h->mat_hi) return fail(FB_EINVAL, "elements use material ids up to %d: the table cannot shrink to %d entries", h->mat_hi, n_materials);
+  // the device table first (on the handle's stream, behind the launches that read the old one): if that fails the host side is untouched
+  if (has_material_map(h)) FB_TRY(upload_material_table(h, n_materials, E, nu, rho));
+  h->mat_E.assign(E, E + n_materials); h->mat_nu.assign(nu, nu + n_materials); h->mat_rho.assign(rho, rho + n_materials);
+  h->prm.E = E[0]; h->prm.nu = nu[0]; h->prm.rho = rho[0];
+  lame_of(h->prm.E * h->force_scale, h->prm.nu, &h->lambda, &h->mu);
   h->system_valid = false;
+  h->mass_valid = false;
   return FB_OK;
 }
+
+int fb_fem_num_materials(fb_fem_t h) { return h ? (int)h->mat_E.size() : 0; }
+
+int fb_fem_read_materials(fb_fem_t h, double* E, double* nu, double* rho) {
+  if (!h) return fail(FB_EINVAL, "null FEM handle");
+  for (size_t i = 0; i < h->mat_E.size(); i++) {
+    if (E) E[i] = h->mat_E[i];
+    if (nu) nu[i] = h->mat_nu[i];
+    if (rho) rho[i] = h->mat_rho[i];
+  }
+  return FB_OK;
+}
+
+int fb_fem_set_element_materials(fb_fem_t h, int first, int count, const unsigned char* ids) {
+  CHECK_HANDLE(h);
+  if (h->plan.n_ranks > 1) return fail(FB_EINVAL, "a sharded handle has one material: no element map");
+  const int nt = h->plan.n_tets;
+  if (first < 0 || count < 0 || first > nt || count > nt - first) return fail(FB_EINVAL, "element range [%d,%d) outside [0,%d)", first, first + count, nt);
+  if (count && !ids) return fail(FB_EINVAL, "null id array");
+  const int n = (int)h->mat_E.size();
+  int hi = 0;
+  for (int k = 0; k < count; k++) {  // on the host, before anything is uploaded: no kernel sees an id outside the table
+    if (ids[k] >= n) return fail(FB_EINVAL, "element %d: material id %d, the table has %d entries", first + k, (int)ids[k], n);
+    hi = std::max(hi, (int)ids[k]);
+  }
+  if (count == 0) return FB_OK;
+  if (!has_material_map(h)) {
+    if (hi == 0) return FB_OK;  // (every element is material 0 already: still no map)
+    // The first map.  The table, the kernels' attributes and the filled id array are made first and the array becomes the handle's LAST:
+    // mat_ids is what says "this handle has a map", so a failure on the way leaves a handle without one, as it was.
+    FB_TRY(upload_material_table(h, n, h->mat_E.data(), h->mat_nu.data(), h->mat_rho.data()));
+    FB_TRY(material_kernel_attributes(h));
+    SlackScope slack(handle_slack(h, h->plan.n_global, nt));  // the handle's slack rule, as for the element buffers
+    DevBuf<unsigned char> fresh;
+    FB_TRY(fresh.alloc((size_t)std::max(1, nt)));
+    FB_TRY(fresh.zero(h->stream));
+    FB_HIP(hipMemcpyAsync(fresh.p + first, ids, (size_t)count, hipMemcpyHostToDevice, h->stream));
+    FB_HIP(hipStreamSynchronize(h->stream));
+    h->mat_ids.swap(fresh);
+  } else {
+    FB_HIP(hipMemcpyAsync(h->mat_ids.p + first, ids, (size_t)count, hipMemcpyHostToDevice, h->stream));
+    FB_HIP(hipStreamSynchronize(h->stream));
+  }
+  h->mat_hi = std::max(h->mat_hi, hi);
+  h->system_valid = false;
+  h->mass_valid = false;
+  return FB_OK;
+}
+
+int fb_fem_read_element_materials(fb_fem_t h, int first, int count, unsigned char* ids) {
+  CHECK_HANDLE(h);
+  const int nt = h->plan.n_tets;
+  if (first < 0 || count < 0 || first > nt || count > nt - first) return fail(FB_EINVAL, "element range [%d,%d) outside [0,%d)", first, first + count, nt);
+  if (count && !ids) return fail(FB_EINVAL, "null id array");
+  if (!has_material_map(h)) { if (count) memset(ids, 0, (size_t)count); return FB_OK; }
+  return h->mat_ids.download(ids, (size_t)count, h->stream, (size_t)first);
+}
+
+long long fb_fem_element_map_bytes(fb_fem_t h) { return h && has_material_map(h) ? (long long)(h->mat_ids.cap * sizeof(unsigned char)) : 0; }
 
 int fb_fem_set_cg(fb_fem_t h, double eps, int max_iter) {
   CHECK_HANDLE(h);
@@ -2441,8 +2621,12 @@ int fb_fem_element_stiffness(fb_fem_t h, int first, int count, double* K0, doubl
   if (Minv) FB_TRY(dM.alloc((size_t)16 * std::min(count, kChunk)));
   for (int done = 0; done < count; done += kChunk) {
     const int n = std::min(kChunk, count - done);
-    hipLaunchKernelGGL(k_element_K0_mfma, dim3(ceil_div(n, kWavesPerBlock)), dim3(kBlock), 0, h->stream, first + done, n, h->rest.p,
-                       h->lambda, h->mu, dK.p, Minv ? dM.p : nullptr, h->x0.p, h->tets.p);
+    if (has_material_map(h))
+      hipLaunchKernelGGL(k_element_K0_mfma<true>, dim3(ceil_div(n, kWavesPerBlock)), dim3(kBlock), 0, h->stream, first + done, n, h->rest.p,
+                         h->lambda, h->mu, dK.p, Minv ? dM.p : nullptr, h->x0.p, h->tets.p, (const uint8_t*)h->mat_ids.p, (const double*)h->mat_tab.p);
+    else
+      hipLaunchKernelGGL(k_element_K0_mfma<false>, dim3(ceil_div(n, kWavesPerBlock)), dim3(kBlock), 0, h->stream, first + done, n, h->rest.p,
+                         h->lambda, h->mu, dK.p, Minv ? dM.p : nullptr, h->x0.p, h->tets.p, (const uint8_t*)nullptr, (const double*)nullptr);
     FB_HIP(hipGetLastError());
     FB_TRY(dK.download(K0 + (size_t)144 * done, (size_t)144 * n, h->stream));
     if (Minv) FB_TRY(dM.download(Minv + (size_t)16 * done, (size_t)16 * n, h->stream));
@@ -2459,8 +2643,12 @@ int fb_fem_time_element_stiffness(fb_fem_t h, int reps, double* seconds_per_pass
   auto pass = [&]() {
     for (int done = 0; done < nt; done += kChunk) {
       const int n = std::min(kChunk, nt - done);
-      hipLaunchKernelGGL(k_element_K0_mfma, dim3(ceil_div(n, kWavesPerBlock)), dim3(kBlock), 0, h->stream, done, n, h->rest.p, h->lambda, h->mu, dK.p,
-                         (double*)nullptr, h->x0.p, h->tets.p);
+      if (has_material_map(h))
+        hipLaunchKernelGGL(k_element_K0_mfma<true>, dim3(ceil_div(n, kWavesPerBlock)), dim3(kBlock), 0, h->stream, done, n, h->rest.p, h->lambda, h->mu, dK.p,
+                           (double*)nullptr, h->x0.p, h->tets.p, (const uint8_t*)h->mat_ids.p, (const double*)h->mat_tab.p);
+      else
+        hipLaunchKernelGGL(k_element_K0_mfma<false>, dim3(ceil_div(n, kWavesPerBlock)), dim3(kBlock), 0, h->stream, done, n, h->rest.p, h->lambda, h->mu, dK.p,
+                           (double*)nullptr, h->x0.p, h->tets.p, (const uint8_t*)nullptr, (const double*)nullptr);
     }
   };
   pass();
@@ -2481,7 +2669,7 @@ int fb_fem_assemble(fb_fem_t h, const double* u, double* f, double* K_blocks) {
   FB_TRY(upload_global_vec(h, u, h->tmp));
   FB_TRY(h->Ad.zero(h->stream));  // stands in for qvel and fext (both unused in raw mode)
   AsmParams ap;
-  ap.lambda = h->lambda; ap.mu = h->mu; ap.rho20 = h->prm.rho / 20.0;
+  asm_materials(h, ap);
   ap.s_k = 1.0; ap.s_m = 0.0; ap.g_k = 0.0; ap.g_m = 0.0; ap.g_a = 0.0; ap.rhs_scale = 0.0; ap.apply_mask = 0;
   if (h->f64) {
     FB_TRY(launch_warp<double>(h, h->tmp.p, nullptr));

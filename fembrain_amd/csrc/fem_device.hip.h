@@ -145,19 +145,36 @@ __device__ inline void k0_apply(const double b[4][3], double V, double lambda, d
     }
 }
 
+// Per-element materials (fb_fem_set_materials / fb_fem_set_element_materials).  The table is three planes of kMaxMaterials doubles --
+// lambda | mu | rho/20 -- always allocated in full and padded with entry 0, so that ANY byte indexes inside it; the ids themselves are
+// checked on the host before they reach the device.  MAT is a template parameter of every kernel that reads a material: a handle
+// without an element map launches the instantiations without it, whose code is what it was.
+// k_tet_warp<.., MAT> writes the id into the V lane of quarter 1 of the step record ((float)id is exact up to 255; quarter 0 keeps V):
+// the assembly kernels that hold the whole record anyway get the id without another gather.
+constexpr int kMaxMaterials = 256;
+template <typename MT>
+__device__ __forceinline__ int rec_mat_id(MT w) { return (int)w & (kMaxMaterials - 1); }
+
 // kcorr (may be null): warp = 2 of CorotationalLinearFEMForceModel (corotationalLinearFEM.cpp:296-428) -- the two terms the
 // derivative of the element rotation adds to the element stiffness, as a row-major 12 x 12 matrix per element (MT):
 //   term 1: column l = blockdiag(dR/dx_l) K0 (R^T x - x0),   term 2: column l = R K0 blockdiag(dR/dx_l)^T x
 // with dR/dF from G omega = 2 skew_part(.), G = (tr(S) I - S) R^T (S = the symmetric polar factor R^T F, R before the flip).
 // TANGENT (warp = 2) is a template parameter: as a run-time branch its registers (512 + scratch) cost the default kernel a third of
 // its speed
-template <typename MT, bool TANGENT>
+template <typename MT, bool TANGENT, bool MAT = false>
 __global__ __launch_bounds__(kBlock) void k_tet_warp(int nt, const int4* __restrict__ tets, const double* __restrict__ x0,
                                                      const double* __restrict__ u, const double* __restrict__ rest,
                                                      MT* __restrict__ rec, double* __restrict__ fe, double* __restrict__ rot,
-                                                     double lambda, double mu, int linear, MT* __restrict__ kcorr) {
+                                                     double lambda, double mu, int linear, MT* __restrict__ kcorr,
+                                                     const uint8_t* __restrict__ mat_ids, const double* __restrict__ mtab) {
   const int e = blockIdx.x * kBlock + threadIdx.x;
   if (e >= nt) return;
+  int mid = 0;
+  if (MAT) {  // the element's own Lame parameters
+    mid = mat_ids[e];
+    lambda = mtab[mid];
+    mu = mtab[kMaxMaterials + mid];
+  }
   const int4 t = tets[e];
   const int id[4] = {t.x, t.y, t.z, t.w};
   double b[4][3], X0[4][3], P[4][3];
@@ -296,7 +313,7 @@ __global__ __launch_bounds__(kBlock) void k_tet_warp(int nt, const int4* __restr
       f[3 * k + a] = V * (R[3 * a] * sb[0] + R[3 * a + 1] * sb[1] + R[3 * a + 2] * sb[2]);
       rc[4 * k + a] = (MT)c[a];
     }
-    rc[4 * k + 3] = (MT)V;  // V rides in the 4th lane of every gradient: one 4-wide load gives (c_k, V)
+    rc[4 * k + 3] = (MAT && k == 1) ? (MT)mid : (MT)V;  // V rides in the 4th lane of every gradient: one 4-wide load gives (c_k, V); MAT: quarter 1 carries the material id
   }
   if (rot) {
 #pragma unroll
@@ -323,6 +340,7 @@ struct AsmParams {
   double g_a;                // rhs operator on qacc = g_a M (Newmark: M qaccel), 0 otherwise
   double rhs_scale;          // rhs = rhs_scale (t + fint - fext): -h (FemBrain's step), -1 (Newmark)
   int apply_mask;
+  const double* mtab;        // MAT instantiations: the material table (lambda | mu | rho/20, kMaxMaterials each); lambda, mu, rho20 above are unused there
 };
 
 // what both assembly kernels (k_assemble_rows: slot-major, k_assemble_tets: element-major) write
@@ -475,11 +493,13 @@ struct RowAlgebra {
 };
 
 // one element contribution (i, j) to the block sums: the same three stages in the same order in both kernels
-template <typename MT>
+template <typename MT, bool MAT = false>
 __device__ __forceinline__ void add_contribution(double* K, double& m, const double* ci, const double* cj, double V, int i, int j, uint32_t e, const AsmParams& ap,
-                                                 const MT* __restrict__ kcorr) {
+                                                 const MT* __restrict__ kcorr, int mid = 0) {
   const double dij = ci[0] * cj[0] + ci[1] * cj[1] + ci[2] * cj[2];
-  const double vl = V * ap.lambda, vm = V * ap.mu;
+  const double lambda = MAT ? ap.mtab[mid] : ap.lambda, mu = MAT ? ap.mtab[kMaxMaterials + mid] : ap.mu;
+  const double rho20 = MAT ? ap.mtab[2 * kMaxMaterials + mid] : ap.rho20;
+  const double vl = V * lambda, vm = V * mu;
 #pragma unroll
   for (int a = 0; a < 3; a++)
 #pragma unroll
@@ -492,10 +512,10 @@ __device__ __forceinline__ void add_contribution(double* K, double& m, const dou
 #pragma unroll
       for (int b = 0; b < 3; b++) K[3 * a + b] += 0.5 * ((double)C[12 * (3 * i + a) + 3 * j + b] + (double)C[12 * (3 * j + b) + 3 * i + a]);
   }
-  m += ap.rho20 * V * (i == j ? 2.0 : 1.0);
+  m += rho20 * V * (i == j ? 2.0 : 1.0);
 }
 
-template <typename MT>
+template <typename MT, bool MAT = false>
 __global__ __launch_bounds__(kBlock) void k_assemble_rows(SellView sv, const int* __restrict__ slot_coff,
                                                           const int* __restrict__ slot_ccnt, const uint32_t* __restrict__ contrib,
                                                           const MT* __restrict__ rec, const double* __restrict__ fe, AsmOut<MT> o, AsmParams ap,
@@ -527,12 +547,14 @@ __global__ __launch_bounds__(kBlock) void k_assemble_rows(SellView sv, const int
 #pragma unroll
         for (int u = 0; u < kG; u++) cw[u] = (t0 + u < ccnt) ? contrib[((size_t)coff + t0 + u) * 64 + lane] : 0xFFFFFFFFu;
         mt4 rI[kG], rJ[kG];
+        MT rV[kG], rM[kG];  // (MAT) V and the material id: lanes 3 of quarters 0 and 1, the record's own cache line
 #pragma unroll
         for (int u = 0; u < kG; u++) {
           const uint32_t c = cw[u] == 0xFFFFFFFFu ? 0u : cw[u];  // padding reads element 0's record and is discarded below
           const mt4* r = (const mt4*)(rec + 16 * (size_t)(c >> 4));
           rI[u] = r[(c >> 2) & 3];
           rJ[u] = r[c & 3];
+          if (MAT) { rV[u] = rec[16 * (size_t)(c >> 4) + 3]; rM[u] = rec[16 * (size_t)(c >> 4) + 7]; }
         }
 #pragma unroll
         for (int u = 0; u < kG; u++) {
@@ -544,7 +566,8 @@ __global__ __launch_bounds__(kBlock) void k_assemble_rows(SellView sv, const int
           const mt4 ri = rI[u], rj = rJ[u];
           const double ci[3] = {(double)ri.x, (double)ri.y, (double)ri.z};
           const double cj[3] = {(double)rj.x, (double)rj.y, (double)rj.z};
-          add_contribution<MT>(K, m, ci, cj, (double)ri.w, i, j, e, ap, kcorr);
+          if (MAT) add_contribution<MT, true>(K, m, ci, cj, (double)rV[u], i, j, e, ap, kcorr, rec_mat_id(rM[u]));
+          else add_contribution<MT>(K, m, ci, cj, (double)ri.w, i, j, e, ap, kcorr);
           if (diag) {
             const double* f = fe + 12 * (size_t)e + 3 * i;
             ra.fi[0] += f[0]; ra.fi[1] += f[1]; ra.fi[2] += f[2];
@@ -569,7 +592,7 @@ __global__ __launch_bounds__(kBlock) void k_assemble_rows(SellView sv, const int
 // Sums and their order are k_assemble_rows': same bits (tests/test_fem_gpu.py).
 constexpr int kWideTerms = 20;   // per slot and lane: t terms 0..2, qacc terms 3..5, u 6..14, m 15, contribution count 16, element forces 17..19
 constexpr int kWideBlock = 512;
-template <typename MT>
+template <typename MT, bool MAT = false>
 __global__ __launch_bounds__(kWideBlock) void k_assemble_wide(SellView sv, const int* __restrict__ wide_list, int n_wide, int max_slots, double* __restrict__ scratch,
                                                               const int* __restrict__ slot_coff, const int* __restrict__ slot_ccnt,
                                                               const uint32_t* __restrict__ contrib, const MT* __restrict__ rec, const double* __restrict__ fe,
@@ -610,12 +633,14 @@ __global__ __launch_bounds__(kWideBlock) void k_assemble_wide(SellView sv, const
 #pragma unroll
         for (int u = 0; u < kG; u++) cw[u] = (t0 + u < ccnt) ? contrib[((size_t)coff + t0 + u) * 64 + lane] : 0xFFFFFFFFu;
         mt4 rI[kG], rJ[kG];
+        MT rV[kG], rM[kG];  // (MAT) as in k_assemble_rows
 #pragma unroll
         for (int u = 0; u < kG; u++) {
           const uint32_t c = cw[u] == 0xFFFFFFFFu ? 0u : cw[u];
           const mt4* r = (const mt4*)(rec + 16 * (size_t)(c >> 4));
           rI[u] = r[(c >> 2) & 3];
           rJ[u] = r[c & 3];
+          if (MAT) { rV[u] = rec[16 * (size_t)(c >> 4) + 3]; rM[u] = rec[16 * (size_t)(c >> 4) + 7]; }
         }
 #pragma unroll
         for (int u = 0; u < kG; u++) {
@@ -627,7 +652,8 @@ __global__ __launch_bounds__(kWideBlock) void k_assemble_wide(SellView sv, const
           const mt4 ri = rI[u], rj = rJ[u];
           const double ci[3] = {(double)ri.x, (double)ri.y, (double)ri.z};
           const double cj[3] = {(double)rj.x, (double)rj.y, (double)rj.z};
-          add_contribution<MT>(K, m, ci, cj, (double)ri.w, i, j, e, ap, kcorr);
+          if (MAT) add_contribution<MT, true>(K, m, ci, cj, (double)rV[u], i, j, e, ap, kcorr, rec_mat_id(rM[u]));
+          else add_contribution<MT>(K, m, ci, cj, (double)ri.w, i, j, e, ap, kcorr);
           if (diag) {
             const double* f = fe + 12 * (size_t)e + 3 * i;
             fi[0] += f[0]; fi[1] += f[1]; fi[2] += f[2];
@@ -719,7 +745,7 @@ constexpr int kAsmExtra = 3 + 1;  // LDS rows of 64 doubles after the accumulato
 
 // elements of the rows, wavefront A (row A of the blocks).  Software pipeline over groups of G list rows: the words of group g+2
 // and the records of group g+1 are in flight while group g is added up.
-template <typename MT, int G, int A, bool TANGENT>
+template <typename MT, int G, int A, bool TANGENT, bool MAT = false>
 __device__ __forceinline__ void tets_accumulate(double* acc, int lane, int io, int height, const uint32_t* __restrict__ inc, const uint32_t* __restrict__ inc_slot,
                                                 const MT* __restrict__ rec, const AsmParams& ap, const MT* __restrict__ kcorr) {
   typedef MT mt4 __attribute__((ext_vector_type(4)));
@@ -763,8 +789,9 @@ __device__ __forceinline__ void tets_accumulate(double* acc, int lane, int io, i
       const int i = (int)(w0[u] & 3);
       const mt4 ri = i == 0 ? r0[u][0] : (i == 1 ? r0[u][1] : (i == 2 ? r0[u][2] : r0[u][3]));
       const double ci[3] = {(double)ri.x, (double)ri.y, (double)ri.z};
-      const double V = (double)ri.w;
-      const double vl = V * ap.lambda, vm = V * ap.mu;
+      const double V = MAT ? (double)r0[u][0].w : (double)ri.w;
+      const int mid = MAT ? rec_mat_id(r0[u][1].w) : 0;
+      const double vl = V * (MAT ? ap.mtab[mid] : ap.lambda), vm = V * (MAT ? ap.mtab[kMaxMaterials + mid] : ap.mu);
       // the four blocks of an element sit in four different slots (its nodes are distinct): all twelve accumulators are read
       // before any is written back, one LDS round trip per element instead of four
       double* p[4];
@@ -805,7 +832,7 @@ __device__ __forceinline__ void tets_accumulate(double* acc, int lane, int io, i
 }
 
 // wavefront 3: the mass entries of the four blocks, the element forces and the length of the list
-template <typename MT, int G>
+template <typename MT, int G, bool MAT = false>
 __device__ __forceinline__ void tets_mass_and_forces(double* acc, double* facc, double* nacc, int lane, int io, int height, int zero_slots,
                                                      const uint32_t* __restrict__ inc, const uint32_t* __restrict__ inc_slot, const MT* __restrict__ rec,
                                                      const double* __restrict__ fe, const AsmParams& ap) {
@@ -819,6 +846,7 @@ __device__ __forceinline__ void tets_mass_and_forces(double* acc, double* facc, 
   int nd = 0;
   uint32_t w[G], sl[G], w1[G], s1[G];
   double V[G], f[G][3];
+  MT M[G];  // (MAT) the material id as the record holds it
   auto load_words = [&](int t0, uint32_t* ww, uint32_t* ss) {
 #pragma unroll
     for (int u = 0; u < G; u++) {
@@ -829,22 +857,24 @@ __device__ __forceinline__ void tets_mass_and_forces(double* acc, double* facc, 
       ss[u] = in ? b : 0u;
     }
   };
-  auto load_values = [&](const uint32_t* ww, double* VV, double (*ff)[3]) {
+  auto load_values = [&](const uint32_t* ww, double* VV, double (*ff)[3], MT* MM) {
 #pragma unroll
     for (int u = 0; u < G; u++) {
       const uint32_t c = ww[u] == kNoInc ? 0u : ww[u];
-      VV[u] = (double)rec[16 * (size_t)(c >> 2) + 4 * (c & 3) + 3];
+      VV[u] = (double)rec[16 * (size_t)(c >> 2) + (MAT ? 0 : 4 * (c & 3)) + 3];
+      if (MAT) MM[u] = rec[16 * (size_t)(c >> 2) + 7];
       const double* fp = fe + 12 * (size_t)(c >> 2) + 3 * (c & 3);
       ff[u][0] = fp[0]; ff[u][1] = fp[1]; ff[u][2] = fp[2];
     }
   };
   load_words(0, w, sl);
-  load_values(w, V, f);
+  load_values(w, V, f, M);
   load_words(G, w1, s1);
   for (int t0 = 0; t0 < height; t0 += G) {
     double V1[G], f1[G][3];
+    MT M1[G];
     uint32_t w2[G], s2[G];
-    load_values(w1, V1, f1);
+    load_values(w1, V1, f1, M1);
     load_words(t0 + 2 * G, w2, s2);
 #pragma unroll
     for (int u = 0; u < G; u++) {
@@ -858,14 +888,16 @@ __device__ __forceinline__ void tets_mass_and_forces(double* acc, double* facc, 
         p[j] = acc + ((sl[u] >> (8 * j)) & 255u) * 640 + 9 * 64 + lane;
         m[j] = p[j][0];
       }
+      const double rho20 = MAT ? ap.mtab[2 * kMaxMaterials + rec_mat_id(M[u])] : ap.rho20;
 #pragma unroll
-      for (int j = 0; j < 4; j++) p[j][0] = m[j] + ap.rho20 * V[u] * (i == j ? 2.0 : 1.0);
+      for (int j = 0; j < 4; j++) p[j][0] = m[j] + rho20 * V[u] * (i == j ? 2.0 : 1.0);
       fi[0] += f[u][0]; fi[1] += f[u][1]; fi[2] += f[u][2];
     }
 #pragma unroll
     for (int u = 0; u < G; u++) {
       w[u] = w1[u]; sl[u] = s1[u]; w1[u] = w2[u]; s1[u] = s2[u];
       V[u] = V1[u]; f[u][0] = f1[u][0]; f[u][1] = f1[u][1]; f[u][2] = f1[u][2];
+      if (MAT) M[u] = M1[u];
     }
   }
   facc[lane] = fi[0]; facc[64 + lane] = fi[1]; facc[128 + lane] = fi[2];
@@ -1015,7 +1047,7 @@ __device__ __forceinline__ int next_narrow(const SellView& sv, int s, int per, i
   return s;
 }
 
-template <typename MT, int G, bool TANGENT, bool NEWMARK>
+template <typename MT, int G, bool TANGENT, bool NEWMARK, bool MAT = false>
 __global__ __launch_bounds__(kBlock) void k_assemble_tets(SellView sv, const int* __restrict__ inc_off, const uint32_t* __restrict__ inc,
                                                           const uint32_t* __restrict__ inc_slot, const MT* __restrict__ rec, const double* __restrict__ fe,
                                                           AsmOut<MT> o, AsmParams ap, const MT* __restrict__ kcorr, int max_width, unsigned long long* __restrict__ prof) {
@@ -1035,10 +1067,10 @@ __global__ __launch_bounds__(kBlock) void k_assemble_tets(SellView sv, const int
   for (int s = next_narrow(sv, xcd * chunk + (blockIdx.x >> 3), per, hi, max_width); s < hi; s = next_narrow(sv, s + per, per, hi, max_width)) {
     const int so = sv.slice_off[s], width = sv.slice_off[s + 1] - so;
     const int io = inc_off[s], height = inc_off[s + 1] - io;
-    if (wq == 0) tets_accumulate<MT, G, 0, TANGENT>(acc, lane, io, height, inc, inc_slot, rec, ap, kcorr);
-    else if (wq == 1) tets_accumulate<MT, G, 1, TANGENT>(acc, lane, io, height, inc, inc_slot, rec, ap, kcorr);
-    else if (wq == 2) tets_accumulate<MT, G, 2, TANGENT>(acc, lane, io, height, inc, inc_slot, rec, ap, kcorr);
-    else tets_mass_and_forces<MT, G>(acc, facc, nacc, lane, io, height, prev_width, inc, inc_slot, rec, fe, ap);
+    if (wq == 0) tets_accumulate<MT, G, 0, TANGENT, MAT>(acc, lane, io, height, inc, inc_slot, rec, ap, kcorr);
+    else if (wq == 1) tets_accumulate<MT, G, 1, TANGENT, MAT>(acc, lane, io, height, inc, inc_slot, rec, ap, kcorr);
+    else if (wq == 2) tets_accumulate<MT, G, 2, TANGENT, MAT>(acc, lane, io, height, inc, inc_slot, rec, ap, kcorr);
+    else tets_mass_and_forces<MT, G, MAT>(acc, facc, nacc, lane, io, height, prev_width, inc, inc_slot, rec, fe, ap);
     prev_width = width;
     lap(0);
     __syncthreads();
@@ -1082,10 +1114,10 @@ __global__ __launch_bounds__(kBlock) void k_assemble_tets(SellView sv, const int
 constexpr int kAsmStride = 576;                  // doubles per slot: 9 value rows of 64
 constexpr int kAsmStageDoubles = 2 * 4 * 64 * 2;  // two buffers of 4 quarters x 64 lanes x 16 bytes
 
-template <typename MT>
+template <typename MT, bool MAT = false>
 __global__ __launch_bounds__(kBlock) void k_mass_blocks(SellView sv, const int* __restrict__ inc_off, const uint32_t* __restrict__ inc,
                                                         const uint32_t* __restrict__ inc_slot, const float* __restrict__ volf, double rho20, int max_width,
-                                                        double* __restrict__ mblk) {
+                                                        double* __restrict__ mblk, const uint8_t* __restrict__ mat_ids, const double* __restrict__ mtab) {
   extern __shared__ double macc[];  // [wavefront][slot][64]
   const int wq = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int s = blockIdx.x * (kBlock / 64) + wq;
@@ -1107,10 +1139,12 @@ __global__ __launch_bounds__(kBlock) void k_mass_blocks(SellView sv, const int* 
   for (int t0 = 0; t0 < height; t0 += G) {
     uint32_t w[G], sl[G];
     double V[G];
+    uint8_t M[G];  // (MAT) the element's material (element 0's for padding: the id array has at least one entry)
 #pragma unroll
     for (int u = 0; u < G; u++) {
       w[u] = t0 + u < height ? wn[u] : kNoInc; sl[u] = sn[u];
       V[u] = (double)volf[(w[u] == kNoInc ? 0u : w[u]) >> 2];  // what k_tet_warp stores in the record
+      if (MAT) M[u] = mat_ids[(w[u] == kNoInc ? 0u : w[u]) >> 2];
     }
 #pragma unroll
     for (int u = 0; u < G; u++) {  // the next group's words
@@ -1129,7 +1163,7 @@ __global__ __launch_bounds__(kBlock) void k_mass_blocks(SellView sv, const int* 
         m[j] = p[j][0];
       }
 #pragma unroll
-      for (int j = 0; j < 4; j++) p[j][0] = m[j] + rho20 * V[u] * (i == j ? 2.0 : 1.0);
+      for (int j = 0; j < 4; j++) p[j][0] = m[j] + (MAT ? mtab[2 * kMaxMaterials + M[u]] : rho20) * V[u] * (i == j ? 2.0 : 1.0);
     }
   }
   for (int k = 0; k < width; k++) mblk[((size_t)so + k) * 64 + lane] = acc[k * 64 + lane];
@@ -1141,7 +1175,7 @@ __global__ __launch_bounds__(kBlock) void k_mass_blocks(SellView sv, const int* 
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // value wavefront A of k_assemble_tets_st: tets_accumulate with the records read from the staging buffers
-template <int A>
+template <int A, bool MAT = false>
 __device__ __forceinline__ void tets_accumulate_st(double* acc, const float4* stage, int lane, int io, int height, const uint32_t* __restrict__ inc,
                                                    const uint32_t* __restrict__ inc_slot, const AsmParams& ap) {
 #pragma unroll
@@ -1168,8 +1202,9 @@ __device__ __forceinline__ void tets_accumulate_st(double* acc, const float4* st
       const int i = (int)(w0 & 3);
       const float4 ri = i == 0 ? q0 : (i == 1 ? q1 : (i == 2 ? q2 : q3));
       const double ci[3] = {(double)ri.x, (double)ri.y, (double)ri.z};
-      const double V = (double)ri.w;
-      const double vl = V * ap.lambda, vm = V * ap.mu;
+      const double V = MAT ? (double)q0.w : (double)ri.w;
+      const int mid = MAT ? rec_mat_id(q1.w) : 0;
+      const double vl = V * (MAT ? ap.mtab[mid] : ap.lambda), vm = V * (MAT ? ap.mtab[kMaxMaterials + mid] : ap.mu);
       double* p[4];
       double K[4][3];
 #pragma unroll
@@ -1271,7 +1306,7 @@ __device__ __forceinline__ void tets_accumulate_st(double* acc, const float4* st
     nacc[lane] = (double)nd;                                                                   \
   }
 
-template <bool NEWMARK>
+template <bool NEWMARK, bool MAT = false>
 __global__ __launch_bounds__(kBlock) void k_assemble_tets_st(SellView sv, const int* __restrict__ inc_off, const uint32_t* __restrict__ inc,
                                                              const uint32_t* __restrict__ inc_slot, const float* __restrict__ rec, const double* __restrict__ fe,
                                                              AsmOut<float> o, AsmParams ap, int max_width, unsigned long long* __restrict__ prof) {
@@ -1309,9 +1344,9 @@ __global__ __launch_bounds__(kBlock) void k_assemble_tets_st(SellView sv, const 
     for (int s = s_first; s < hi; s = next_narrow(sv, s + per, per, hi, max_width)) {
       const int so = sv.slice_off[s], width = sv.slice_off[s + 1] - so;
       const int io = inc_off[s], height = inc_off[s + 1] - io;
-      if (wq == 0) tets_accumulate_st<0>(acc, stage, lane, io, height, inc, inc_slot, ap);
-      else if (wq == 1) tets_accumulate_st<1>(acc, stage, lane, io, height, inc, inc_slot, ap);
-      else tets_accumulate_st<2>(acc, stage, lane, io, height, inc, inc_slot, ap);
+      if (wq == 0) tets_accumulate_st<0, MAT>(acc, stage, lane, io, height, inc, inc_slot, ap);
+      else if (wq == 1) tets_accumulate_st<1, MAT>(acc, stage, lane, io, height, inc, inc_slot, ap);
+      else tets_accumulate_st<2, MAT>(acc, stage, lane, io, height, inc, inc_slot, ap);
       lap(0);
       __syncthreads();
       lap(1);
@@ -1996,13 +2031,20 @@ __device__ inline double strainB(const double* b, int s, int col) {
   }
 }
 
+template <bool MAT = false>
 __global__ __launch_bounds__(kBlock) void k_element_K0_mfma(int first, int count, const double* __restrict__ rest,
                                                             double lambda, double mu, double* __restrict__ K0,
                                                             double* __restrict__ Minv, const double* __restrict__ x0,
-                                                            const int4* __restrict__ tets) {
+                                                            const int4* __restrict__ tets, const uint8_t* __restrict__ mat_ids,
+                                                            const double* __restrict__ mtab) {
   const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
   if (wave >= count) return;  // wave-uniform
   const int e = first + wave;
+  if (MAT) {  // (wave-uniform: one element per wavefront)
+    const int mid = mat_ids[e];
+    lambda = mtab[mid];
+    mu = mtab[kMaxMaterials + mid];
+  }
   const int lane = threadIdx.x & 63;
   const double* r = rest + 16 * (size_t)e;
   const double V = r[12];

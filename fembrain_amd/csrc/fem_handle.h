@@ -133,6 +133,15 @@ struct fb_fem_s {
   double lambda = 0, mu = 0;
   int grid = 8;
   bool f64 = false;
+  // Per-element materials (fb_fem_set_materials / fb_fem_set_element_materials).  The table lives on the host; entry 0 is prm.E / nu / rho
+  // and what lambda / mu above are made of.  The element map and the device table exist only once a map was set: a handle without one
+  // allocates nothing here and launches the kernels' uniform instantiations.
+  std::vector<double> mat_E, mat_nu, mat_rho;    // 1 .. kMaxMaterials entries
+  double force_scale = 1.0;                      // fb_fem_set_internal_force_scaling: scales every material's E
+  bool map_from_delta = false;                   // fb_fem_resync_delta's full rebuild is running: build() leaves the map to it
+  int mat_hi = 0;                                // upper bound of the ids in use (the table may not shrink to it or below)
+  DevBuf<unsigned char> mat_ids, mat_ids_next;   // material id per element, caller's element order (at least one entry: padding lanes read element 0)
+  DevBuf<double> mat_tab;                        // lambda | mu | rho/20, kMaxMaterials doubles each, padded with entry 0
   // mesh
   DevBuf<int4> tets;
   DevBuf<double> x0, rest, fe;

@@ -295,6 +295,44 @@ class FemIntegrator:
     def set_internal_force_scaling_factor(self, factor):
         _l.check(self._L.fb_fem_set_internal_force_scaling(self.h, factor))
 
+    # -- per-element materials (fb_fem_set_materials / fb_fem_set_element_materials; unsharded handles) --
+    def set_materials(self, E, nu, rho, element_ids=None):
+        """The material table: E, nu, rho scalars or equally long sequences of 1 .. ``lib.FB_MAX_MATERIALS`` entries; entry 0 is the
+        material of every element without an id.  ``element_ids`` (one id per element, caller's element order) sets the whole map
+        in the same call.  The reference reads each element's material (corotationalLinearFEM.cpp:55-66, tetMesh.cpp:171)."""
+        E, nu, rho = (np.atleast_1d(np.asarray(a, np.float64)).reshape(-1) for a in (E, nu, rho))
+        if not (len(E) == len(nu) == len(rho)):
+            raise ValueError("E, nu and rho must be equally long")
+        E, nu, rho = (np.ascontiguousarray(a) for a in (E, nu, rho))
+        _l.check(self._L.fb_fem_set_materials(self.h, len(E), _l.dptr(E), _l.dptr(nu), _l.dptr(rho)))
+        if element_ids is not None:
+            self.set_element_materials(element_ids)
+
+    def set_element_materials(self, ids, first=0):
+        """Material ids (0 .. 255, below the table's length) of elements first .. first + len(ids) - 1 in the caller's element order"""
+        a = np.asarray(ids).reshape(-1)
+        if a.size and (a.min() < 0 or a.max() > 255):
+            raise ValueError("material ids are 0 .. 255")
+        a = np.ascontiguousarray(a, dtype=np.uint8)
+        _l.check(self._L.fb_fem_set_element_materials(self.h, int(first), len(a), _l.bptr(a)))
+
+    def materials(self):
+        """(E, nu, rho) arrays of the table, as set (the internal force scaling factor is not folded in)"""
+        n = int(self._L.fb_fem_num_materials(self.h))
+        E, nu, rho = np.zeros(n), np.zeros(n), np.zeros(n)
+        _l.check(self._L.fb_fem_read_materials(self.h, _l.dptr(E), _l.dptr(nu), _l.dptr(rho)))
+        return E, nu, rho
+
+    def element_materials(self):
+        """The material id of every element of the mesh the device holds (uint8, ``read_mesh``'s element order)"""
+        ids = np.zeros(int(self._L.fb_fem_num_tets(self.h)), np.uint8)
+        _l.check(self._L.fb_fem_read_element_materials(self.h, 0, len(ids), _l.bptr(ids)))
+        return ids
+
+    def element_map_bytes(self):
+        """Bytes the element map holds on the device; 0 for a handle that never got a non-zero id (it allocates none)"""
+        return int(self._L.fb_fem_element_map_bytes(self.h))
+
     def set_cg(self, eps, max_iter):
         _l.check(self._L.fb_fem_set_cg(self.h, eps, max_iter))
 
@@ -580,6 +618,14 @@ class Deformable:
 
     def get_solver_time(self):
         return self.integrator.get_system_solve_time()
+
+    def set_materials(self, E, nu, rho, element_ids=None):
+        """``FemIntegrator.set_materials``: the body's material table and, with ``element_ids``, the material of every element"""
+        self.integrator.set_materials(E, nu, rho, element_ids)
+
+    def set_element_materials(self, ids, first=0):
+        """``FemIntegrator.set_element_materials``"""
+        self.integrator.set_element_materials(ids, first)
 
     def surface_mesh(self, update=False):
         """What the host draws: ``FemIntegrator.surface()``, or with ``update`` ``FemIntegrator.surface_update()``"""

@@ -24,6 +24,7 @@ FB_CUT_BAKE, FB_CUT_CARRY = 0, 1
 FB_CUT_NOTHING, FB_CUT_DONE, FB_CUT_UNHANDLED, FB_CUT_DRY = 0, 1, 2, 3
 FB_CUT_UNHANDLED_IDS = 64  # unhandled element ids fb_fem_read_cut returns at most (subdivide.h kCutUnhandledIds)
 FB_HAPTIC_MAX_SOURCES = 256  # sources fb_fem_add_haptic_forces takes in one call
+FB_MAX_MATERIALS = 256  # entries of a handle's material table (fb_fem_set_materials)
 
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
@@ -143,6 +144,12 @@ def lib():
         "fb_fem_set_damping": (C.c_int, [vp, C.c_double, C.c_double]),
         "fb_fem_set_internal_force_scaling": (C.c_int, [vp, C.c_double]),
         "fb_fem_set_cg": (C.c_int, [vp, C.c_double, C.c_int]),
+        "fb_fem_set_materials": (C.c_int, [vp, C.c_int, _dp, _dp, _dp]),
+        "fb_fem_num_materials": (C.c_int, [vp]),
+        "fb_fem_read_materials": (C.c_int, [vp, _dp, _dp, _dp]),
+        "fb_fem_set_element_materials": (C.c_int, [vp, C.c_int, C.c_int, _bp]),
+        "fb_fem_read_element_materials": (C.c_int, [vp, C.c_int, C.c_int, _bp]),
+        "fb_fem_element_map_bytes": (C.c_longlong, [vp]),
         "fb_fem_set_constrained_dofs": (C.c_int, [vp, C.c_int, _ip]),
         "fb_fem_floor_collision": (C.c_int, [vp, C.c_double, C.c_double, _ip]),
         "fb_fem_add_haptic_forces": (C.c_int, [vp, C.c_int, _ip, _dp, C.c_int]),

@@ -111,6 +111,94 @@ def read_veg(path):
     return np.ascontiguousarray(v[:, 1:4]), np.ascontiguousarray((e[:, 1:5] - base).astype(np.int32))
 
 
+# VolumetricMesh::E_default / nu_default / density_default (volumetricMesh.cpp:40-42)
+VEG_DEFAULT_MATERIAL = (1e9, 0.45, 1000.0)  # (E, nu, rho)
+
+
+def read_veg_materials(path):
+    """``read_veg`` plus what the file says about materials: ``(verts, tets, [(E, nu, rho), ...], ids)`` with one uint8 id per element
+    into the list, ready for ``FemIntegrator.set_materials(*zip(*materials), element_ids=ids)``.
+
+    The parser of VolumetricMesh (reference vegafem volumetricMesh.cpp:283-532) restated:
+    ``*MATERIAL name`` followed by ``ENU, rho, E, nu`` (accepted: E > 0, -1 < nu < 0.5, rho > 0); ``*SET name`` followed by 1-indexed
+    element numbers, comma-separated over any number of lines; ``*REGION`` followed by ``set, material``, applied in file order so
+    that a later region overrides an earlier one; the set ``allElements`` exists without being declared.  Elements no region reaches
+    get the file's LAST material (the reference's region of ``numMaterials - 1``), or, in a file without any material, a default one.
+    The reference builds that default as ``ENuMaterial(name, E_default, nu_default, density_default)`` against a constructor that
+    takes (name, density, E, nu) -- density 1e9, E 0.45, nu 1000; that slip is not reproduced, the default here is E 1e9, nu 0.45,
+    rho 1000.  A material that is not ENU raises, as CorotationalLinearFEM's constructor throws on one (corotationalLinearFEM.cpp:61-64);
+    so do a set or material a region names before it is declared, an element number outside the mesh and more than 256 materials."""
+    verts, tets = read_veg(path)
+    n_el = len(tets)
+    with open(path, "r") as f:
+        lines = [ln.strip() for ln in f]
+    lines = [ln for ln in lines if ln and not ln.startswith("#")]
+    materials, names = [], []
+    sets = {"allElements": None}  # None: every element
+    ids = np.full(n_el, -1, np.int64)
+    k, in_set = 0, None
+    while k < len(lines):
+        ln = lines[k]
+        k += 1
+        if ln.startswith("*"):
+            in_set = None
+            squeezed = "".join(ln.split())
+            if squeezed.startswith("*MATERIAL"):
+                name = squeezed[len("*MATERIAL"):]
+                if k >= len(lines):
+                    raise ValueError("%s: material %r has no parameter line" % (path, name))
+                parts = "".join(lines[k].split()).split(",")
+                k += 1
+                if parts[0] != "ENU":
+                    raise ValueError("%s: material %r is %s; the corotational linear FEM takes ENU materials only" % (path, name, parts[0]))
+                try:
+                    rho, E, nu = (float(x) for x in parts[1:4])
+                except ValueError:
+                    raise ValueError("%s: material %r: expected ENU, rho, E, nu" % (path, name))
+                if not (E > 0 and -1.0 < nu < 0.5 and rho > 0 and np.isfinite([E, nu, rho]).all()):
+                    raise ValueError("%s: material %r: E = %g, nu = %g, rho = %g" % (path, name, E, nu, rho))
+                names.append(name)
+                materials.append((E, nu, rho))
+            elif squeezed.startswith("*SET"):
+                in_set = squeezed[len("*SET"):]
+                sets[in_set] = []
+            elif squeezed.startswith("*REGION"):
+                if k >= len(lines):
+                    raise ValueError("%s: *REGION without a line" % path)
+                parts = "".join(lines[k].split()).split(",")
+                k += 1
+                if len(parts) != 2:
+                    raise ValueError("%s: a region is 'set, material', not %r" % (path, lines[k - 1]))
+                if parts[0] not in sets:
+                    raise ValueError("%s: region names set %r, which is not declared before it" % (path, parts[0]))
+                if parts[1] not in names:
+                    raise ValueError("%s: region names material %r, which is not declared before it" % (path, parts[1]))
+                m = names.index(parts[1])
+                members = sets[parts[0]]
+                if members is None:
+                    ids[:] = m
+                else:
+                    ids[np.asarray(members, np.int64) - 1] = m
+            continue
+        if in_set is not None:
+            for tok in "".join(ln.split()).split(","):
+                if not tok:
+                    continue
+                if not tok.isdigit():
+                    raise ValueError("%s: set %r: %r is not an element number" % (path, in_set, tok))
+                e = int(tok)
+                if e < 1 or e > n_el:
+                    raise ValueError("%s: set %r: element %d outside 1 .. %d" % (path, in_set, e, n_el))
+                sets[in_set].append(e)
+    if (ids < 0).any():
+        if not materials:
+            materials.append(VEG_DEFAULT_MATERIAL)
+        ids[ids < 0] = len(materials) - 1
+    if len(materials) > 256:
+        raise ValueError("%s: %d materials; a handle's table holds 256" % (path, len(materials)))
+    return verts, tets, materials, ids.astype(np.uint8)
+
+
 def apply_delta(v, t, delta):
     """The mesh a topology delta describes (the contract of ``fb_fem_resync_delta``): ``changed`` elements get their new nodes in
     place, ``removed`` elements are erased keeping the order of the rest (``VolMesh::remove_cell_core``: ``m_vCells.erase``, reference

@@ -10,6 +10,7 @@
 // every fixture model.
 #pragma once
 #include <algorithm>
+#include <cctype>
 #include <cfloat>
 #include <cmath>
 #include <cstdio>
@@ -410,7 +411,7 @@ inline bool readBlobFile(const char* path, LinearBlobTreeData& out, std::string*
 namespace FEM {
 
 // Vega text mesh (data/models/blobtree/peanut.veg): "*VERTICES\n n 3 0 0\n id x y z ..." and "*ELEMENTS\nTET\n m 4 0\n id a b c d ..." with
-// 1-indexed ids; materials and regions are ignored on this path.  elements come back 0-indexed.
+// 1-indexed ids; materials and regions are ignored by this overload (the one below reads them).  elements come back 0-indexed.
 inline bool readVegFile(const char* path, std::vector<double>& vertices, std::vector<int>& elements, std::string* error = nullptr) {
   std::ifstream f(path);
   if (!f) { if (error) *error = std::string(path) + ": cannot open"; return false; }
@@ -436,6 +437,96 @@ inline bool readVegFile(const char* path, std::vector<double>& vertices, std::ve
     if (error) *error = std::string(path) + ": vertex / element counts do not match the headers";
     return false;
   }
+  return true;
+}
+
+// One entry of a .veg file's material list: ENU materials only (what CorotationalLinearFEM takes, corotationalLinearFEM.cpp:61-64)
+struct VegMaterial { std::string name; double E, nu, rho; };
+
+// The same mesh with what the file says about materials, as VolumetricMesh's parser reads it (vegafem volumetricMesh.cpp:283-532):
+// "*MATERIAL name" + "ENU, rho, E, nu" (accepted: E > 0, -1 < nu < 0.5, rho > 0), "*SET name" + 1-indexed element numbers, comma-separated
+// over any number of lines, "*REGION" + "set, material" applied in file order (a later region overrides an earlier one); the set
+// "allElements" exists undeclared.  elementMaterials gets one id per element into `materials`.  Elements no region reaches get the
+// file's LAST material, or -- in a file without any -- a default one of E 1e9, nu 0.45, rho 1000 (VolumetricMesh::E_default ...; the
+// reference hands them to ENuMaterial(name, density, E, nu) in the wrong order, which is not reproduced).  Refused: a material that is
+// not ENU, a set or material a region names before it is declared, an element number outside the mesh, more than 256 materials.
+// Same results as fembrain_amd.meshgen.read_veg_materials (tests/test_materials_ref.py).
+inline bool readVegFile(const char* path, std::vector<double>& vertices, std::vector<int>& elements, std::vector<VegMaterial>& materials,
+                        std::vector<unsigned char>& elementMaterials, std::string* error = nullptr) {
+  materials.clear(); elementMaterials.clear();
+  if (!readVegFile(path, vertices, elements, error)) return false;
+  const long ne = (long)(elements.size() / 4);
+  auto bad = [&](const std::string& why) { if (error) *error = std::string(path) + ": " + why; return false; };
+  auto squeeze = [](const std::string& in) { std::string o; for (char c : in) if (!std::isspace((unsigned char)c)) o.push_back(c); return o; };
+  auto split = [](const std::string& in) { std::vector<std::string> o(1); for (char c : in) { if (c == ',') o.emplace_back(); else o.back().push_back(c); } return o; };
+  std::ifstream f(path);
+  std::vector<std::string> lines;
+  for (std::string line; std::getline(f, line);) {
+    line = SKETCH::blobio::trim(line);
+    if (!line.empty() && line[0] != '#') lines.push_back(line);
+  }
+  std::vector<std::string> setNames(1, "allElements");
+  std::vector<std::vector<long>> setMembers(1);  // (set 0: every element)
+  std::vector<int> ids((size_t)ne, -1);
+  int inSet = -1;
+  for (size_t k = 0; k < lines.size();) {
+    const std::string sq = squeeze(lines[k++]);
+    if (sq[0] == '*') {
+      inSet = -1;
+      if (sq.compare(0, 9, "*MATERIAL") == 0) {
+        VegMaterial m;
+        m.name = sq.substr(9);
+        if (k >= lines.size()) return bad("material " + m.name + " has no parameter line");
+        const std::vector<std::string> parts = split(squeeze(lines[k++]));
+        if (parts[0] != "ENU") return bad("material " + m.name + " is " + parts[0] + "; the corotational linear FEM takes ENU materials only");
+        char* end = nullptr;
+        double val[3] = {0, 0, 0};
+        for (int c = 0; c < 3; c++) {
+          if (parts.size() < 4 || parts[1 + c].empty()) return bad("material " + m.name + ": expected ENU, rho, E, nu");
+          val[c] = std::strtod(parts[1 + c].c_str(), &end);
+          if (*end) return bad("material " + m.name + ": expected ENU, rho, E, nu");
+        }
+        m.rho = val[0]; m.E = val[1]; m.nu = val[2];
+        if (!(m.E > 0 && m.nu > -1.0 && m.nu < 0.5 && m.rho > 0 && std::isfinite(m.E) && std::isfinite(m.nu) && std::isfinite(m.rho)))
+          return bad("material " + m.name + ": E > 0, -1 < nu < 0.5, rho > 0");
+        materials.push_back(m);
+      } else if (sq.compare(0, 4, "*SET") == 0) {
+        const std::string name = sq.substr(4);
+        size_t at = 0;
+        while (at < setNames.size() && setNames[at] != name) at++;
+        if (at == setNames.size()) { setNames.push_back(name); setMembers.emplace_back(); }
+        else setMembers[at].clear();
+        inSet = (int)at;
+      } else if (sq.compare(0, 7, "*REGION") == 0) {
+        if (k >= lines.size()) return bad("*REGION without a line");
+        const std::vector<std::string> parts = split(squeeze(lines[k++]));
+        if (parts.size() != 2) return bad("a region is 'set, material'");
+        size_t st = 0, mt = 0;
+        while (st < setNames.size() && setNames[st] != parts[0]) st++;
+        while (mt < materials.size() && materials[mt].name != parts[1]) mt++;
+        if (st == setNames.size()) return bad("region names set " + parts[0] + ", which is not declared before it");
+        if (mt == materials.size()) return bad("region names material " + parts[1] + ", which is not declared before it");
+        if (st == 0 && setMembers[0].empty()) std::fill(ids.begin(), ids.end(), (int)mt);
+        else for (long e : setMembers[st]) ids[(size_t)e - 1] = (int)mt;
+      }
+      continue;
+    }
+    if (inSet >= 0) {
+      for (const std::string& tok : split(sq)) {
+        if (tok.empty()) continue;
+        for (char c : tok) if (!std::isdigit((unsigned char)c)) return bad("set " + setNames[inSet] + ": " + tok + " is not an element number");
+        const long e = std::strtol(tok.c_str(), nullptr, 10);
+        if (e < 1 || e > ne) return bad("set " + setNames[inSet] + ": element " + tok + " outside the mesh");
+        setMembers[inSet].push_back(e);
+      }
+    }
+  }
+  bool unassigned = false;
+  for (int id : ids) unassigned = unassigned || id < 0;
+  if (unassigned && materials.empty()) materials.push_back(VegMaterial{"defaultMaterial", 1e9, 0.45, 1000.0});
+  if (materials.size() > 256) return bad("more than 256 materials");
+  elementMaterials.resize((size_t)ne);
+  for (long e = 0; e < ne; e++) elementMaterials[(size_t)e] = (unsigned char)(ids[(size_t)e] < 0 ? materials.size() - 1 : (size_t)ids[(size_t)e]);
   return true;
 }
 

@@ -100,6 +100,18 @@ class HipIntegrator {
   void SetDampingMassCoef(double c) { prm_.damping_mass = c; check(fb_fem_set_damping(h_, prm_.damping_mass, prm_.damping_stiffness)); }
   void SetDampingStiffnessCoef(double c) { prm_.damping_stiffness = c; check(fb_fem_set_damping(h_, prm_.damping_mass, prm_.damping_stiffness)); }
   void SetInternalForceScalingFactor(double f) { check(fb_fem_set_internal_force_scaling(h_, f)); }
+  // Per-element materials (fembrain_hip.h; the reference reads VolumetricMesh::getElementMaterial(el) of every element,
+  // corotationalLinearFEM.cpp:55-66): a table of 1..256 ENU materials, entry 0 for every element without an id, and one id per element
+  // in the caller's element order.  A re-sync from a whole mesh returns the ids to 0; a cut hands every piece its parent's id.
+  void SetMaterials(int n, const double* E, const double* nu, const double* density) {
+    check(fb_fem_set_materials(h_, n, E, nu, density));
+    prm_.E = E[0]; prm_.nu = nu[0]; prm_.rho = density[0];
+    mass_.clear();  // (GetTotalMass / GetKineticEnergy read the mass blocks again)
+  }
+  void SetElementMaterials(int first, int count, const unsigned char* ids) { check(fb_fem_set_element_materials(h_, first, count, ids)); mass_.clear(); }
+  int GetNumMaterials() const { return fb_fem_num_materials(h_); }
+  void GetMaterials(double* E, double* nu, double* density) { check(fb_fem_read_materials(h_, E, nu, density)); }
+  void GetElementMaterials(int first, int count, unsigned char* ids) { check(fb_fem_read_element_materials(h_, first, count, ids)); }
   bool setConstrainedDOF(int num, int* arr) {
     if (num == 0 || arr == nullptr) return false;  // integratorBaseSparse.cpp:73-75
     check(fb_fem_set_constrained_dofs(h_, num, arr));
@@ -470,6 +482,18 @@ class Deformable {
   void hapticEnd() { m_bHapticInProgress = false; m_idxPulledVertex = -1; m_vHapticIndices.clear(); }
   bool isHapticInProgress() const { return m_bHapticInProgress; }
   void hapticSetCurrentForces(const std::vector<int>& indices, const std::vector<vec3d>& forces) { m_vHapticIndices = indices; m_vHapticForces = forces; }
+  // the materials of the body's elements (HipIntegrator::SetMaterials / SetElementMaterials): E, nu, density equally long, 1..256 entries;
+  // ids one per element of the current mesh from `first` on.  syncForceModel() from the whole mesh returns the ids to 0.
+  void setMaterials(const std::vector<double>& E, const std::vector<double>& nu, const std::vector<double>& density) {
+    if (E.empty() || E.size() != nu.size() || E.size() != density.size()) throw std::invalid_argument("E, nu and density must be equally long and not empty");
+    m_lpIntegrator->SetMaterials((int)E.size(), E.data(), nu.data(), density.data());
+  }
+  void setElementMaterials(const std::vector<unsigned char>& ids, int first = 0) { m_lpIntegrator->SetElementMaterials(first, (int)ids.size(), ids.data()); }
+  std::vector<unsigned char> getElementMaterials() {
+    std::vector<unsigned char> ids((size_t)fb_fem_num_tets(m_lpIntegrator->handle()));
+    m_lpIntegrator->GetElementMaterials(0, (int)ids.size(), ids.data());
+    return ids;
+  }
   void setDampingStiffnessCoeff(double s) { m_dampingStiffnessCoeff = s; m_lpIntegrator->SetDampingStiffnessCoef(s); }
   double getDampingStiffnessCoeff() const { return m_dampingStiffnessCoeff; }
   void setDampingMassCoeff(double m) { m_dampingMassCoeff = m; m_lpIntegrator->SetDampingMassCoef(m); }

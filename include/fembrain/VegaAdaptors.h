@@ -57,6 +57,44 @@ class HipCorotationalForceModel : public ForceModel {
     xyz_.swap(xyz); tets_.swap(tets);
     create(nv, ne, E, nu, rho, warp, device);
   }
+  // The mesh's OWN materials, element by element, as CorotationalLinearFEM reads them (corotationalLinearFEM.cpp:55-66:
+  // getElementMaterial(el), downcastENuMaterial; a material that is not ENU makes the model unusable -- ok() is false -- where the
+  // reference throws).  The mesh's material list becomes the handle's table, in its order; every element gets the index of its
+  // material.  Needs the reference's volumetricMeshENuMaterial.h included before this constructor is used; at most 256 materials.
+  template <class Mesh>
+  explicit HipCorotationalForceModel(const Mesh* mesh, int warp = 1, int device = 0) : h_(NULL), h64_(NULL) {
+    const int nv = mesh->getNumVertices(), ne = mesh->getNumElements(), nm = mesh->getNumMaterials();
+    std::vector<double> xyz(3 * (size_t)nv);
+    std::vector<int> tets(4 * (size_t)ne);
+    for (int i = 0; i < nv; i++)
+      for (int k = 0; k < 3; k++) xyz[3 * (size_t)i + k] = (*mesh->getVertex(i))[k];
+    for (int e = 0; e < ne; e++)
+      for (int k = 0; k < 4; k++) tets[4 * (size_t)e + k] = mesh->getVertexIndex(e, k);
+    xyz_.swap(xyz); tets_.swap(tets);
+    if (nm < 1 || nm > 256) {
+      fprintf(stderr, "HipCorotationalForceModel: the mesh has %d materials (1 to 256 are taken)\n", nm);
+      return;
+    }
+    matE_.resize((size_t)nm); matNu_.resize((size_t)nm); matRho_.resize((size_t)nm);
+    for (int m = 0; m < nm; m++) {
+      if (downcastENuMaterial(mesh->getMaterial(m)) == NULL) {
+        fprintf(stderr, "HipCorotationalForceModel: material %d is not ENU (CorotationalLinearFEM takes ENU materials only)\n", m);
+        return;
+      }
+      matE_[m] = downcastENuMaterial(mesh->getMaterial(m))->getE();
+      matNu_[m] = downcastENuMaterial(mesh->getMaterial(m))->getNu();
+      matRho_[m] = mesh->getMaterial(m)->getDensity();
+    }
+    matIds_.resize((size_t)ne);
+    for (int e = 0; e < ne; e++) {
+      int m = 0;
+      while (m < nm && mesh->getMaterial(m) != mesh->getElementMaterial(e)) m++;
+      if (m == nm) { fprintf(stderr, "HipCorotationalForceModel: element %d has a material outside the mesh's list\n", e); return; }
+      matIds_[e] = (unsigned char)m;
+    }
+    create(nv, ne, matE_[0], matNu_[0], matRho_[0], warp, device);
+    if (h_ && !applyMaterials(h_)) { fb_fem_destroy(h_); h_ = NULL; }
+  }
   HipCorotationalForceModel(int nv, const double* xyz, int ne, const int* tets, double E, double nu, double rho, int warp = 1, int device = 0)
       : h_(NULL), h64_(NULL), xyz_(xyz, xyz + 3 * (size_t)nv), tets_(tets, tets + 4 * (size_t)ne) {
     create(nv, ne, E, nu, rho, warp, device);
@@ -123,6 +161,17 @@ class HipCorotationalForceModel : public ForceModel {
       h64_ = NULL;
       return false;
     }
+    if (!applyMaterials(h64_)) { fb_fem_destroy(h64_); h64_ = NULL; return false; }
+    return true;
+  }
+  // the per-element constructor's table and map on a handle (nothing to do for the uniform constructors)
+  bool applyMaterials(fb_fem_t h) {
+    if (matIds_.empty()) return true;
+    if (fb_fem_set_materials(h, (int)matE_.size(), &matE_[0], &matNu_[0], &matRho_[0]) != FB_OK ||
+        fb_fem_set_element_materials(h, 0, (int)matIds_.size(), &matIds_[0]) != FB_OK) {
+      fprintf(stderr, "HipCorotationalForceModel (materials): %s\n", fb_last_error());
+      return false;
+    }
     return true;
   }
   static void check(int rc, const char* what) {
@@ -135,6 +184,8 @@ class HipCorotationalForceModel : public ForceModel {
   std::vector<int> tets_;
   std::vector<int> bptr_, bcol_;
   std::vector<double> blocks_;
+  std::vector<double> matE_, matNu_, matRho_;
+  std::vector<unsigned char> matIds_;
 };
 
 // CGSolver(int n, blackBoxProductType, void* data): data = the fb_fem_t whose assembled Keff multiplies

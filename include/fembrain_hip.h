@@ -344,6 +344,35 @@ int fb_fem_set_damping(fb_fem_t h, double damping_mass, double damping_stiffness
 /* IntegratorBase::SetInternalForceScalingFactor (integratorBase.h; default 1): internal forces and tangent stiffness
  * are multiplied by `factor` from the next assembly on (both are linear in Young's modulus, which is what is scaled) */
 int fb_fem_set_internal_force_scaling(fb_fem_t h, double factor);
+
+/* ---- Per-element materials ----
+ * The reference reads every element's own material (corotationalLinearFEM.cpp:55-66: getElementMaterial(el); tetMesh.cpp:171 and
+ * generateMassMatrix.cpp: getElementDensity(el)).  A handle has a TABLE of 1..256 materials and, once one was set, a MAP of one id
+ * byte per element, in the caller's element order (the node renumbering does not reorder elements).  Entry 0 is the material of
+ * every element without an id; a fresh handle has the one-entry table of its fb_fem_params.  Unsharded handles only: a sharded
+ * handle that is given more than one material, or a map, refuses.
+ *
+ * fb_fem_set_materials replaces the table.  Accepted is what VolumetricMesh's parser accepts (volumetricMesh.cpp:327): E > 0,
+ * -1 < nu < 0.5, rho > 0, all finite; a table that would shrink to or below an id in use is refused (the handle keeps an upper bound
+ * of the ids it was given, reset by fb_fem_resync).  With n_materials = 1 on a handle without a map it replaces the handle's E, nu,
+ * rho and nothing else.  fb_fem_set_internal_force_scaling scales every material's E.
+ * fb_fem_set_element_materials sets the ids of elements [first, first + count); an id >= fb_fem_num_materials or a bad range is refused.
+ * The ids are checked on the host before they reach the device.  Every refusal is FB_EINVAL and leaves the handle as it was.
+ * fb_fem_read_materials fills arrays of fb_fem_num_materials entries (any may be NULL); fb_fem_read_element_materials reads ids back
+ * (zeros from a handle without a map).
+ *
+ * The map follows the mesh: fb_fem_resync returns every id to 0 and keeps the table; fb_fem_resync_delta drops the removed elements,
+ * keeps the ids of kept and changed ones in order and gives appended ones 0 until the caller sets them; after fb_fem_cut (FB_CUT_DONE,
+ * either mode) every piece has the id of the element it was cut from -- on the device, nothing crosses the bus.
+ * A handle that never gets a non-zero id allocates no map and launches the kernels it always launched; fb_fem_element_map_bytes says
+ * how many bytes the map holds (0: none).  A map whose ids all name a material equal to material 0 reproduces that handle bit for bit. */
+int fb_fem_set_materials(fb_fem_t h, int n_materials, const double* E, const double* nu, const double* rho);
+int fb_fem_num_materials(fb_fem_t h);
+int fb_fem_read_materials(fb_fem_t h, double* E, double* nu, double* rho);
+int fb_fem_set_element_materials(fb_fem_t h, int first, int count, const unsigned char* ids);
+int fb_fem_read_element_materials(fb_fem_t h, int first, int count, unsigned char* ids);
+long long fb_fem_element_map_bytes(fb_fem_t h);
+
 int fb_fem_set_cg(fb_fem_t h, double eps, int max_iter);
 /* Newmark parameters (implicitNewmarkSparse.h: NewmarkBeta 0.25, NewmarkGamma 0.5; IntegratorBase: maxIterations 1, epsilon
  * 1e-6): the Newton loop stops when |residual|^2 / |first residual|^2 < epsilon^2 or after max_newton_iterations.  Each Newton
