@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 
 #include <chrono>
 
@@ -33,7 +34,6 @@ __global__ __launch_bounds__(kBlock) void k_widen_positions(long long n, const f
   if (i < n) out[i] = (double)in[i];
 }
 
-// FB_RENUMBER_* of this handle: fb_fem_params.renumber unless FEMBRAIN_RENUMBER=0/1 says otherwise; a sharded handle renumbers on request only
 // Zero fills of a (re-)build, batched: about twenty buffers are cleared, and a fill per buffer costs 4-5 us of launch each however
 // small it is.  add() notes them (4-byte granularity), flush() clears up to kZeroMax per launch.
 struct ZeroList { unsigned int* p[kZeroMax]; unsigned long long end[kZeroMax]; unsigned int tail_words[kZeroMax]; int n; };  // end: running total of 16-byte chunks
@@ -95,6 +95,7 @@ int fresh_order_percent() {
   return e ? std::max(0, atoi(e)) : kFreshOrderPercent;
 }
 
+// FB_RENUMBER_* of this handle: fb_fem_params.renumber unless FEMBRAIN_RENUMBER=0/1 says otherwise; a sharded handle renumbers on request only
 int renumber_mode(const fb_fem_s* h) {
   if (const char* e = getenv("FEMBRAIN_RENUMBER")) return atoi(e) != 0 ? FB_RENUMBER_ON : FB_RENUMBER_OFF;
   if (h->prm.renumber == 0 && h->shard_auto_on) return FB_RENUMBER_ON;  // (a sharded handle under AUTO whose ranks voted for it)
@@ -112,27 +113,139 @@ int upload_masks(fb_fem_s* h) {
   return h->nodemask.upload(nm, h->stream);
 }
 
-// The material-aware instantiations of the element-major kernels need the LDS sizes of the plan as the uniform ones do: set when the
-// plan of a handle with an element map is (re)built, and when a handle gets its map.
-int material_kernel_attributes(fb_fem_s* h) {
-  if (!h->asm_tets) return FB_OK;
-  const bool tangent = h->prm.exact_tangent && !h->prm.linear;
-  const void* kerns[2][2][2] = {{{(const void*)k_assemble_tets<float, 2, false, false, true>, (const void*)k_assemble_tets<float, 2, false, true, true>},
-                                 {(const void*)k_assemble_tets<float, 2, true, false, true>, (const void*)k_assemble_tets<float, 2, true, true, true>}},
-                                {{(const void*)k_assemble_tets<double, 2, false, false, true>, (const void*)k_assemble_tets<double, 2, false, true, true>},
-                                 {(const void*)k_assemble_tets<double, 2, true, false, true>, (const void*)k_assemble_tets<double, 2, true, true, true>}}};
-  for (int nm = 0; nm < 2; nm++) FB_HIP(hipFuncSetAttribute(kerns[h->f64 ? 1 : 0][tangent ? 1 : 0][nm], hipFuncAttributeMaxDynamicSharedMemorySize, h->asm_lds));
-  if (h->asm_staged) {
-    FB_HIP(hipFuncSetAttribute((const void*)k_assemble_tets_st<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, h->asm_lds_st));
-    FB_HIP(hipFuncSetAttribute((const void*)k_assemble_tets_st<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, h->asm_lds_st));
-    FB_HIP(hipFuncSetAttribute((const void*)k_mass_blocks<float, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (kBlock / 64) * h->asm_max_width * 64 * (int)sizeof(double)));
+// (the plan builders ask for spmv_c16 before upload_plan asks for all of it: a dozen getenv calls per plan build, twice)
+HostKnobs read_host_knobs() {
+  HostKnobs k;
+  const char *ak = getenv("FEMBRAIN_ASM_KERNEL"), *per_cu = getenv("FEMBRAIN_ASM_PER_CU"), *wide_grid = getenv("FEMBRAIN_ASM_WIDE_GRID");
+  const char *nt = getenv("FEMBRAIN_SPMV_NT"), *c16 = getenv("FEMBRAIN_SPMV_C16");
+  k.asm_rows = ak && !strcmp(ak, "rows"), k.asm_tets1 = ak && !strcmp(ak, "tets1");
+  if (per_cu) k.asm_per_cu = std::max(1, atoi(per_cu));
+  if (wide_grid) k.asm_wide_grid = std::max(1, atoi(wide_grid));
+  k.asm_wide_rows = getenv("FEMBRAIN_ASM_WIDE_ROWS") != nullptr;
+  k.asm_profile = getenv("FEMBRAIN_ASM_PROFILE") != nullptr;
+  if (nt) k.spmv_nt = atoi(nt) != 0 ? 1 : 0;
+  k.spmv_c16 = !(c16 && atoi(c16) == 0);
+  k.verbose = getenv("FEMBRAIN_TIMING") != nullptr;
+  return k;
+}
+
+// ---- the SpMV's instantiations, all of them: what selects one, and its address ----
+// f64: storage of the matrix values; mode 0..3 (k_spmv); split: wavefronts per slice, 0 = k_spmv, 2 | 4 = k_spmv_split (which has neither NT
+// nor C16); xch 2: the halo refresh and the sums' post in the kernel (MODE 3 only); c16: 0 | 1 | 2 as fb_fem_s::c16
+struct SpmvKernel { bool f64; int mode, split, xch; bool nt; int c16; const void* fn; };
+#define FB_K_SPMV(MT, MODE, XCH, NT, C16) {std::is_same<MT, double>::value, MODE, 0, XCH, NT, C16, (const void*)k_spmv<MT, MODE, XCH, NT, C16>}
+#define FB_K_SPLIT(MT, MODE, SPLIT, XCH) {std::is_same<MT, double>::value, MODE, SPLIT, XCH, false, 0, (const void*)k_spmv_split<MT, MODE, SPLIT, XCH>}
+#define FB_K_SPMV_FORMS(MT, MODE, XCH)                                                                                           \
+  FB_K_SPMV(MT, MODE, XCH, false, 0), FB_K_SPMV(MT, MODE, XCH, false, 1), FB_K_SPMV(MT, MODE, XCH, false, 2), FB_K_SPMV(MT, MODE, XCH, true, 0), \
+      FB_K_SPMV(MT, MODE, XCH, true, 1), FB_K_SPMV(MT, MODE, XCH, true, 2), FB_K_SPLIT(MT, MODE, 2, XCH), FB_K_SPLIT(MT, MODE, 4, XCH)
+#define FB_K_SPMV_MODES(MT) FB_K_SPMV_FORMS(MT, 0, 0), FB_K_SPMV_FORMS(MT, 1, 0), FB_K_SPMV_FORMS(MT, 2, 0), FB_K_SPMV_FORMS(MT, 3, 0), FB_K_SPMV_FORMS(MT, 3, 2)
+const SpmvKernel kSpmvKernels[] = {FB_K_SPMV_MODES(float), FB_K_SPMV_MODES(double)};
+#undef FB_K_SPMV_MODES
+#undef FB_K_SPMV_FORMS
+#undef FB_K_SPLIT
+#undef FB_K_SPMV
+static_assert(sizeof kSpmvKernels / sizeof kSpmvKernels[0] == 80, "60 k_spmv and 20 k_spmv_split");
+// spmv() fills one argument array for all of them
+typedef void (*SpmvSignature)(SellView, const double*, const double*, const double*, double*, const double*, const double*, double*, CGState*, int, P2PArgs);
+static_assert(std::is_same<decltype(&k_spmv<double, 3, 2, true, 1>), SpmvSignature>::value && std::is_same<decltype(&k_spmv_split<double, 0, 4, 0>), SpmvSignature>::value, "spmv()");
+
+// The rows this plan launches, one per MODE and the XCH = 2 one (fb_fem_set_exchange_mode may ask for it on any sharded handle later),
+// stored in the handle.  A combination that was not built is refused here.
+int resolve_spmv_kernels(fb_fem_s* h) {
+  auto find = [h](int mode, int xch) -> const void* {
+    for (const SpmvKernel& k : kSpmvKernels)
+      if (k.f64 == h->f64 && k.mode == mode && k.xch == xch && k.split == h->split && (h->split || (k.nt == h->spmv_nt && k.c16 == h->c16))) return k.fn;
+    return nullptr;
+  };
+  bool all = true;
+  for (int mode = 0; mode < 4; mode++) all = (h->spmv_fn[mode] = find(mode, 0)) != nullptr && all;
+  all = (h->spmv_xch_fn = find(3, 2)) != nullptr && all;
+  if (!all) return fail(FB_EINVAL, "no SpMV kernel was built for %s values, %d wavefronts per slice, column words of form %d", h->f64 ? "fp64" : "fp32", h->split, h->c16);
+  return FB_OK;
+}
+
+// ---- the assembly families' instantiations, all of them ----
+enum AsmFamily { kFamWarp, kFamTets, kFamTetsSt, kFamRows, kFamWide, kFamMass, kFamK0 };
+// f64: storage of the records and the matrix values; tangent: the exact tangent's terms (kcorr present); newmark: qacc passed; mat: the
+// handle has an element map.  false where a family has no such parameter
+struct AsmKernel { AsmFamily family; bool f64, tangent, newmark, mat; const void* fn; };
+constexpr int kAsmG = 2;  // k_assemble_tets: list rows whose records are in flight per lane (measured at 1M tets, fp32: 224 us with 4, 209 with 2, 211 with 1)
+#define FB_K_WARP(MT, TANGENT, MAT) {kFamWarp, std::is_same<MT, double>::value, TANGENT, false, MAT, (const void*)k_tet_warp<MT, TANGENT, MAT>}
+#define FB_K_TETS(MT, TANGENT, NEWMARK, MAT) {kFamTets, std::is_same<MT, double>::value, TANGENT, NEWMARK, MAT, (const void*)k_assemble_tets<MT, kAsmG, TANGENT, NEWMARK, MAT>}
+#define FB_K_SLOTS(FAMILY, KERNEL, MT, MAT) {FAMILY, std::is_same<MT, double>::value, false, false, MAT, (const void*)KERNEL<MT, MAT>}
+#define FB_K_TETS_ST(NEWMARK, MAT) {kFamTetsSt, false, false, NEWMARK, MAT, (const void*)k_assemble_tets_st<NEWMARK, MAT>}
+#define FB_K_BY_STORAGE(MT, MAT)                                                                                                              \
+  FB_K_WARP(MT, false, MAT), FB_K_WARP(MT, true, MAT), FB_K_TETS(MT, false, false, MAT), FB_K_TETS(MT, false, true, MAT), FB_K_TETS(MT, true, false, MAT), \
+      FB_K_TETS(MT, true, true, MAT), FB_K_SLOTS(kFamRows, k_assemble_rows, MT, MAT), FB_K_SLOTS(kFamWide, k_assemble_wide, MT, MAT)
+#define FB_K_BY_MAT(MAT)                                                                                          \
+  FB_K_BY_STORAGE(float, MAT), FB_K_BY_STORAGE(double, MAT), FB_K_TETS_ST(false, MAT), FB_K_TETS_ST(true, MAT),   \
+      {kFamMass, false, false, false, MAT, (const void*)k_mass_blocks<float, MAT>}, {kFamK0, false, false, false, MAT, (const void*)k_element_K0_mfma<MAT>}
+// (the material-aware ones first, as the code named them before there was a table: the compiler emits the kernels in this order, and its
+// output for k_assemble_tets_st is the same instruction for instruction only in that one)
+const AsmKernel kAsmKernels[] = {FB_K_BY_MAT(true), FB_K_BY_MAT(false)};
+#undef FB_K_BY_MAT
+#undef FB_K_BY_STORAGE
+#undef FB_K_TETS_ST
+#undef FB_K_SLOTS
+#undef FB_K_TETS
+#undef FB_K_WARP
+static_assert(sizeof kAsmKernels / sizeof kAsmKernels[0] == 40, "8 k_tet_warp, 16 k_assemble_tets, 4 each of _tets_st / _rows / _wide, 2 each of k_mass_blocks / k_element_K0_mfma");
+// the launches below fill one argument array per family: its order is the kernel's parameter list, pinned here
+template <typename... P> using KernelOf = void (*)(P...);
+typedef const uint32_t* CU32;
+static_assert(std::is_same<decltype(&k_tet_warp<double, true, true>), KernelOf<int, const int4*, const double*, const double*, const double*, double*, double*, double*, double, double, int,
+                                                                               double*, const uint8_t*, const double*>>::value, "launch_warp");
+static_assert(std::is_same<decltype(&k_assemble_tets<double, kAsmG, true, true, true>), KernelOf<SellView, const int*, CU32, CU32, const double*, const double*, AsmOut<double>, AsmParams,
+                                                                                                 const double*, int, unsigned long long*>>::value, "launch_rows, element-major");
+static_assert(std::is_same<decltype(&k_assemble_tets_st<true, true>), KernelOf<SellView, const int*, CU32, CU32, const float*, const double*, AsmOut<float>, AsmParams, int,
+                                                                               unsigned long long*>>::value, "launch_rows, staged");
+static_assert(std::is_same<decltype(&k_assemble_rows<double, true>), KernelOf<SellView, const int*, const int*, CU32, const double*, const double*, AsmOut<double>, AsmParams, const double*,
+                                                                              int>>::value, "launch_asm_rows");
+static_assert(std::is_same<decltype(&k_assemble_wide<double, true>), KernelOf<SellView, const int*, int, int, double*, const int*, const int*, CU32, const double*, const double*,
+                                                                              AsmOut<double>, AsmParams, const double*>>::value, "launch_asm_wide");
+static_assert(std::is_same<decltype(&k_mass_blocks<float, true>), KernelOf<SellView, const int*, CU32, CU32, const float*, double, int, double*, const uint8_t*, const double*>>::value,
+              "launch_rows, mass entries");
+static_assert(std::is_same<decltype(&k_element_K0_mfma<true>), KernelOf<int, int, const double*, double, double, double*, double*, const double*, const int4*, const uint8_t*,
+                                                                        const double*>>::value, "launch_element_K0");
+
+size_t mass_blocks_lds(const fb_fem_s* h) { return (size_t)(kBlock / 64) * h->asm_max_width * 64 * sizeof(double); }
+
+// The rows a plan launches, stored in the handle, and the dynamic-LDS size of those that have one (beyond 64 KB an attribute of the function, set
+// before the launch on the handle's device).  For every plan (upload_plan) and when a handle gets its element map later (mat).  Both values of
+// NEWMARK: a Newmark handle assembles without qacc too (fb_fem_assemble, fb_fem_mass).  The handle keeps what it had if anything fails.
+int resolve_asm_kernels(fb_fem_s* h, bool mat) {
+  const bool tangent = h->kcorr.p != nullptr;
+  bool all = true;
+  auto find = [&](AsmFamily family, bool f64, bool tg, bool newmark) -> const void* {
+    for (const AsmKernel& k : kAsmKernels)
+      if (k.family == family && k.f64 == f64 && k.tangent == tg && k.newmark == newmark && k.mat == mat) return k.fn;
+    all = false;
+    return nullptr;
+  };
+  AsmKernels K;
+  K.warp = find(kFamWarp, h->f64, tangent, false);
+  K.rows = find(kFamRows, h->f64, false, false);
+  K.wide = find(kFamWide, h->f64, false, false);
+  K.k0 = find(kFamK0, false, false, false);
+  for (int nm = 0; nm < 2; nm++) {
+    if (h->asm_tets) K.tets[nm] = find(kFamTets, h->f64, tangent, nm != 0);
+    if (h->asm_staged) K.tets_st[nm] = find(kFamTetsSt, false, false, nm != 0);  // (an element-major plan with fp32 records and the plain tangent)
   }
+  if (h->asm_staged) K.mass = find(kFamMass, false, false, false);
+  if (!all) return fail(FB_EINVAL, "no assembly kernel was built for %s records%s%s", h->f64 ? "fp64" : "fp32", tangent ? ", exact tangent" : "", mat ? ", element map" : "");
+  for (int nm = 0; nm < 2; nm++) {
+    if (K.tets[nm]) FB_HIP(hipFuncSetAttribute(K.tets[nm], hipFuncAttributeMaxDynamicSharedMemorySize, h->asm_lds));
+    if (K.tets_st[nm]) FB_HIP(hipFuncSetAttribute(K.tets_st[nm], hipFuncAttributeMaxDynamicSharedMemorySize, h->asm_lds_st));
+  }
+  if (K.mass) FB_HIP(hipFuncSetAttribute(K.mass, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mass_blocks_lds(h)));
+  h->asm_k = K;
   return FB_OK;
 }
 
 int upload_plan(fb_fem_s* h, const double* xyz_global, const float* xyz_device = nullptr, const double* xyz_device64 = nullptr) {
   const FemPlan& P = h->plan;
   hipStream_t s = h->stream;
+  const HostKnobs kn = h->knobs = read_host_knobs();
   if (!h->device_plan) {  // (the device builder has put the tets and the plan arrays in place already)
     std::vector<int4> t4(P.n_tets);
     for (int e = 0; e < P.n_tets; e++) t4[e] = make_int4(P.tets[4 * (size_t)e], P.tets[4 * (size_t)e + 1], P.tets[4 * (size_t)e + 2], P.tets[4 * (size_t)e + 3]);
@@ -199,53 +312,38 @@ int upload_plan(fb_fem_s* h, const double* xyz_global, const float* xyz_device =
     if (n_wide > 0) {  // k_assemble_wide: one workgroup per wide slice while their scratch areas stay under 64 MB, fewer (each taking several) beyond
       const size_t area = (size_t)widest * kWideTerms * 64;  // doubles
       h->asm_wide_grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_wide, ((size_t)64 << 20) / (area * sizeof(double))));
-      if (const char* wg = getenv("FEMBRAIN_ASM_WIDE_GRID")) h->asm_wide_grid = std::max(1, std::min(h->asm_wide_grid, atoi(wg)));  // (tests: several slices per workgroup)
+      if (kn.asm_wide_grid) h->asm_wide_grid = std::min(h->asm_wide_grid, kn.asm_wide_grid);  // (tests: several slices per workgroup)
       FB_TRY(h->wide_list.upload(wide, s));
       FB_TRY(h->wide_scratch.alloc(area * (size_t)h->asm_wide_grid));
     }
     hipDeviceProp_t prop;
     FB_HIP(hipGetDeviceProperties(&prop, h->prm.device));
     const int lds_cu = (int)std::min<size_t>(std::max<size_t>(prop.maxSharedMemoryPerMultiProcessor, prop.sharedMemPerBlock), 160 * 1024);  // gfx950: 160 KB per CU
-    const char* e = getenv("FEMBRAIN_ASM_KERNEL");
     h->asm_max_width = mw;
     h->asm_lds = (mw * 10 + kAsmExtra) * 64 * (int)sizeof(double);
-    h->asm_tets = mw >= 2 && mw <= kIncMaxWidth && h->asm_lds <= lds_cu && h->asm_lds <= (int)prop.sharedMemPerBlock && !(e && !strcmp(e, "rows"));
+    h->asm_tets = mw >= 2 && mw <= kIncMaxWidth && h->asm_lds <= lds_cu && h->asm_lds <= (int)prop.sharedMemPerBlock && !kn.asm_rows;
     if (h->asm_tets) {
       FB_TRY(build_incidence_device(s, P.n_slices, P.n_owned, h->slice_off.p, h->colidx.p, h->slot_coff.p, h->slot_ccnt.p, h->contrib.p, h->tets.p, h->inc_off,
                                     h->inc, h->inc_slot, h->plan_ws, P.n_ranks == 1));
-      int per_cu = std::max(1, lds_cu / h->asm_lds);
-      if (const char* pc = getenv("FEMBRAIN_ASM_PER_CU")) per_cu = std::max(1, std::min(per_cu, atoi(pc)));  // development aid
-      const int cus = std::max(8, (prop.multiProcessorCount / 8) * 8);
-      const int chunk = ceil_div(P.n_slices, 8);
+      auto per_cu_of = [&](int lds) { return std::max(1, kn.asm_per_cu ? std::min(lds_cu / lds, kn.asm_per_cu) : lds_cu / lds); };  // (FEMBRAIN_ASM_PER_CU: development aid)
+      const int per_cu = per_cu_of(h->asm_lds), cus = std::max(8, (prop.multiProcessorCount / 8) * 8), chunk = ceil_div(P.n_slices, 8);
       h->asm_grid = 8 * std::max(1, std::min(chunk, (cus / 8) * per_cu));
-      if (getenv("FEMBRAIN_TIMING")) fprintf(stderr, "[fembrain] element-major assembly: %d workgroups, %d B of LDS each (%d per CU; device reports %zu / %zu)\n", h->asm_grid, h->asm_lds, per_cu, (size_t)prop.maxSharedMemoryPerMultiProcessor, (size_t)prop.sharedMemPerBlock);
+      if (kn.verbose) fprintf(stderr, "[fembrain] element-major assembly: %d workgroups, %d B of LDS each (%d per CU; device reports %zu / %zu)\n", h->asm_grid, h->asm_lds, per_cu, (size_t)prop.maxSharedMemoryPerMultiProcessor, (size_t)prop.sharedMemPerBlock);
       const bool tangent = h->prm.exact_tangent && !h->prm.linear;
-      const void* kerns[2][2][2] = {{{(const void*)k_assemble_tets<float, 2, false, false>, (const void*)k_assemble_tets<float, 2, false, true>},
-                                     {(const void*)k_assemble_tets<float, 2, true, false>, (const void*)k_assemble_tets<float, 2, true, true>}},
-                                    {{(const void*)k_assemble_tets<double, 2, false, false>, (const void*)k_assemble_tets<double, 2, false, true>},
-                                     {(const void*)k_assemble_tets<double, 2, true, false>, (const void*)k_assemble_tets<double, 2, true, true>}}};
-      for (int nm = 0; nm < 2; nm++) {  // (a Newmark handle assembles without qacc too: fb_fem_assemble)
-        const void* kern = kerns[h->f64 ? 1 : 0][tangent ? 1 : 0][nm];
-        FB_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, h->asm_lds));
-      }
       // fp32 records and the plain tangent: the staged form (one record fetch per row and element, mass entries precomputed);
       // FEMBRAIN_ASM_KERNEL=tets1 keeps the unstaged element-major kernel (same bits)
       h->asm_lds_st = (mw * 9 + kAsmExtra) * 64 * (int)sizeof(double) + kAsmStageDoubles * (int)sizeof(double);
-      h->asm_staged = !h->f64 && !tangent && h->asm_lds_st <= lds_cu && h->asm_lds_st <= (int)prop.sharedMemPerBlock && !(e && !strcmp(e, "tets1"));
+      h->asm_staged = !h->f64 && !tangent && h->asm_lds_st <= lds_cu && h->asm_lds_st <= (int)prop.sharedMemPerBlock && !kn.asm_tets1;
       if (h->asm_staged) {
-        int per_cu_st = std::max(1, lds_cu / h->asm_lds_st);
-        if (const char* pc = getenv("FEMBRAIN_ASM_PER_CU")) per_cu_st = std::max(1, std::min(per_cu_st, atoi(pc)));
+        const int per_cu_st = per_cu_of(h->asm_lds_st);
         h->asm_grid_st = 8 * std::max(1, std::min(chunk, (cus / 8) * per_cu_st));
-        FB_HIP(hipFuncSetAttribute((const void*)k_assemble_tets_st<false>, hipFuncAttributeMaxDynamicSharedMemorySize, h->asm_lds_st));
-        FB_HIP(hipFuncSetAttribute((const void*)k_assemble_tets_st<true>, hipFuncAttributeMaxDynamicSharedMemorySize, h->asm_lds_st));
-        FB_HIP(hipFuncSetAttribute((const void*)k_mass_blocks<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (kBlock / 64) * mw * 64 * (int)sizeof(double)));
-        if (getenv("FEMBRAIN_TIMING")) fprintf(stderr, "[fembrain] staged element-major assembly: %d workgroups, %d B of LDS each (%d per CU)\n", h->asm_grid_st, h->asm_lds_st, per_cu_st);
+        if (kn.verbose) fprintf(stderr, "[fembrain] staged element-major assembly: %d workgroups, %d B of LDS each (%d per CU)\n", h->asm_grid_st, h->asm_lds_st, per_cu_st);
       }
-      if (h->mat_ids.p) FB_TRY(material_kernel_attributes(h));
     } else {
       h->asm_staged = false;
       h->inc_off.release(); h->inc.release(); h->inc_slot.release();
     }
+    FB_TRY(resolve_asm_kernels(h, h->mat_ids.p != nullptr));  // (with the LDS sizes above)
     h->mass_valid = false;
   }
   if (h->prm.pcg_variant == FB_PCG_BLOCK_JACOBI) {
@@ -282,8 +380,7 @@ int upload_plan(fb_fem_s* h, const double* xyz_global, const float* xyz_device =
   {
     // bytes one PCG iteration moves: matrix values + indices + the 12 vector streams of the two kernels
     const double iter_bytes = (double)P.n_slots * 64 * (9.0 * mt_size(h) + 4.0) + 12.0 * 24.0 * P.n_local;
-    const char* e = getenv("FEMBRAIN_SPMV_NT");
-    h->spmv_nt = e ? atoi(e) != 0 : iter_bytes > 384.0 * 1024 * 1024;  // measured: -2 % at 341 MB, +11 % at 469 MB, +15 % at 1.1 GB
+    h->spmv_nt = kn.spmv_nt >= 0 ? kn.spmv_nt != 0 : iter_bytes > 384.0 * 1024 * 1024;  // measured: -2 % at 341 MB, +11 % at 469 MB, +15 % at 1.1 GB
   }
   // small meshes: one 16-byte pair per thread in the merged vector pass (8.9 vs 9.3 us per iteration at 105k tets; on the 1M-tet
   // mesh the extra blocks cost more in the partial-sum prologue than they save: 29.9 vs 29.1)
@@ -298,6 +395,7 @@ int upload_plan(fb_fem_s* h, const double* xyz_global, const float* xyz_device =
   FB_TRY(h->st.alloc(1));
   FB_TRY(h->st.zero(s));
   FB_TRY(h->counter.alloc(1));
+  FB_TRY(resolve_spmv_kernels(h));  // (split, spmv_nt and c16 are final)
   if (!h->device_plan) FB_HIP(hipStreamSynchronize(s));  // (a device-built plan: the rest-state check that follows waits for all of it)
   h->system_valid = false;
   return FB_OK;
@@ -367,23 +465,62 @@ int halo_exchange(fb_fem_s* h, double* vec, int width = 3) {
   return comm_exchange_nodes(h->comm, h->sendbuf.p, P.send_off.data(), vec + (size_t)width * P.n_owned, P.halo_off.data(), width, h->stream);
 }
 
-template <typename MT>
 int launch_warp(fb_fem_s* h, const double* u, double* rot) {
-  const int nt = h->plan.n_tets;
-#define FB_TET_WARP(TANGENT, MAT, KCORR)                                                                                                                          \
-  hipLaunchKernelGGL((k_tet_warp<MT, TANGENT, MAT>), dim3(ceil_div(nt, kBlock)), dim3(kBlock), 0, h->stream, nt, h->tets.p, h->x0.p, u, h->rest.p, (MT*)h->rec.p, \
-                     h->fe.p, rot, h->lambda, h->mu, h->prm.linear != 0 ? 1 : 0, (MT*)(KCORR), (const uint8_t*)h->mat_ids.p, (const double*)h->mat_tab.p)
-  if (has_material_map(h)) { if (h->kcorr.p) FB_TET_WARP(true, true, h->kcorr.p); else FB_TET_WARP(false, true, nullptr); }
-  else if (h->kcorr.p) FB_TET_WARP(true, false, h->kcorr.p);
-  else FB_TET_WARP(false, false, nullptr);
-#undef FB_TET_WARP
-  FB_HIP(hipGetLastError());
+  int nt = h->plan.n_tets, linear = h->prm.linear != 0 ? 1 : 0;
+  void* args[] = {&nt, &h->tets.p, &h->x0.p, &u, &h->rest.p, &h->rec.p, &h->fe.p, &rot, &h->lambda, &h->mu, &linear, &h->kcorr.p, &h->mat_ids.p, &h->mat_tab.p};
+  FB_HIP(hipLaunchKernel(h->asm_k.warp, dim3(ceil_div(nt, kBlock)), dim3(kBlock), args, 0, h->stream));
+  return FB_OK;
+}
+
+int launch_element_K0(fb_fem_s* h, int first, int n, double* K0, double* Minv) {
+  void* args[] = {&first, &n, &h->rest.p, &h->lambda, &h->mu, &K0, &Minv, &h->x0.p, &h->tets.p, &h->mat_ids.p, &h->mat_tab.p};
+  FB_HIP(hipLaunchKernel(h->asm_k.k0, dim3(ceil_div(n, kWavesPerBlock)), dim3(kBlock), args, 0, h->stream));
+  return FB_OK;
+}
+
+// k_assemble_wide: the slices of wide_list, on stream s
+template <typename MT>
+int launch_asm_wide(fb_fem_s* h, hipStream_t s, AsmOut<MT> o, AsmParams ap) {
+  SellView sv = sell_view(h);
+  void* args[] = {&sv, &h->wide_list.p, &h->asm_wide, &h->asm_wide_slots, &h->wide_scratch.p, &h->slot_coff.p, &h->slot_ccnt.p, &h->contrib.p, &h->rec.p, &h->fe.p, &o, &ap, &h->kcorr.p};
+  FB_HIP(hipLaunchKernel(h->asm_k.wide, dim3(h->asm_wide_grid), dim3(kWideBlock), args, 0, s));
+  return FB_OK;
+}
+
+// k_assemble_rows: the slices at least min_width slots wide (0: all of them)
+template <typename MT>
+int launch_asm_rows(fb_fem_s* h, AsmOut<MT> o, AsmParams ap, int min_width) {
+  SellView sv = sell_view(h);
+  void* args[] = {&sv, &h->slot_coff.p, &h->slot_ccnt.p, &h->contrib.p, &h->rec.p, &h->fe.p, &o, &ap, &h->kcorr.p, &min_width};
+  FB_HIP(hipLaunchKernel(h->asm_k.rows, dim3(h->grid), dim3(kBlock), args, 0, h->stream));
+  return FB_OK;
+}
+
+// FEMBRAIN_ASM_PROFILE=1: where an element-major kernel's wavefronts spend their time (16 counters or null to `launch`; 100 MHz ticks summed over `grid` workgroups)
+template <typename Launch>
+int launch_profiled(fb_fem_s* h, const char* kernel, int grid, Launch launch) {
+  unsigned long long* prof = nullptr;
+  if (h->knobs.asm_profile) {
+    FB_HIP(hipMalloc((void**)&prof, 16 * sizeof(unsigned long long)));
+    FB_HIP(hipMemset(prof, 0, 16 * sizeof(unsigned long long)));
+  }
+  FB_HIP(launch(prof));
+  if (prof) {
+    FB_HIP(hipStreamSynchronize(h->stream));
+    unsigned long long t[16];
+    FB_HIP(hipMemcpy(t, prof, sizeof t, hipMemcpyDeviceToHost));
+    for (int w = 0; w < 4; w++)
+      fprintf(stderr, "[fembrain] %s wavefront %d: elements %.1f us, wait %.1f, algebra %.1f, wait %.1f (mean per workgroup)\n", kernel, w, t[4 * w] * 0.01 / grid,
+              t[4 * w + 1] * 0.01 / grid, t[4 * w + 2] * 0.01 / grid, t[4 * w + 3] * 0.01 / grid);
+    (void)hipFree(prof);
+  }
   return FB_OK;
 }
 
 template <typename MT>
-int launch_rows(fb_fem_s* h, const AsmParams& ap, const double* qvel, const double* fext, double* mblk_out, double* fint_out,
+int launch_rows(fb_fem_s* h, AsmParams ap, const double* qvel, const double* fext, double* mblk_out, double* fint_out,
                 double* rhs, double* invdiag, const double* qacc = nullptr) {
+  const AsmKernels& K = h->asm_k;
   AsmOut<MT> o;
   o.dofmask = h->dofmask.p; o.nodemask = h->nodemask.p; o.qvel = qvel; o.fext = fext; o.qacc = qacc; o.vals = (MT*)h->vals.p; o.dlo = (MT*)h->dlo.p; o.mblk_out = mblk_out;
   o.fint_out = fint_out; o.rhs = rhs; o.invdiag = invdiag;
@@ -398,7 +535,6 @@ int launch_rows(fb_fem_s* h, const AsmParams& ap, const double* qvel, const doub
   // on a stream of its own BESIDE the element-major launch -- one wavefront takes ~0.8 ms for a 59-slot slice (one latency-bound slot after
   // the other) while the element-major kernel does the other 1,300 slices of the 606k-tet probe in 0.19 ms; the two write disjoint slices.
   // (A CU-masked handle has no second stream with the same mask: the pass then follows in order.)
-  const bool mat = has_material_map(h);
   const bool wide_pass = h->asm_tets && !mblk_out && h->asm_wide > 0;
   bool wide_beside = false;
   if (wide_pass) {
@@ -406,111 +542,48 @@ int launch_rows(fb_fem_s* h, const AsmParams& ap, const double* qvel, const doub
       if (hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); h->side = nullptr; }
       for (auto& e : h->ev_side) if (h->side && !e && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); }
     }
-    wide_beside = h->side && h->ev_side[0] && h->ev_side[1] && !getenv("FEMBRAIN_ASM_WIDE_ROWS");
+    wide_beside = h->side && h->ev_side[0] && h->ev_side[1] && !h->knobs.asm_wide_rows;
     if (wide_beside) {
       FB_HIP(hipEventRecord(h->ev_side[0], h->stream));  // (the records and element forces of this assembly are complete)
       FB_HIP(hipStreamWaitEvent(h->side, h->ev_side[0], 0));
-      if (mat) hipLaunchKernelGGL((k_assemble_wide<MT, true>), dim3(h->asm_wide_grid), dim3(kWideBlock), 0, h->side, sell_view(h), h->wide_list.p, h->asm_wide, h->asm_wide_slots,
-                                  h->wide_scratch.p, h->slot_coff.p, h->slot_ccnt.p, h->contrib.p, (const MT*)h->rec.p, h->fe.p, o, ap, (const MT*)h->kcorr.p);
-      else
-      hipLaunchKernelGGL(k_assemble_wide<MT>, dim3(h->asm_wide_grid), dim3(kWideBlock), 0, h->side, sell_view(h), h->wide_list.p, h->asm_wide, h->asm_wide_slots,
-                         h->wide_scratch.p, h->slot_coff.p, h->slot_ccnt.p, h->contrib.p, (const MT*)h->rec.p, h->fe.p, o, ap, (const MT*)h->kcorr.p);
-      FB_HIP(hipGetLastError());
+      FB_TRY(launch_asm_wide(h, h->side, o, ap));
       FB_HIP(hipEventRecord(h->ev_side[1], h->side));
     }
   }
-  if (h->asm_tets && h->asm_staged && std::is_same<MT, float>::value && !h->kcorr.p && !mblk_out) {
+  SellView sv = sell_view(h);
+  if (h->asm_tets && h->asm_staged && std::is_same<MT, float>::value && !h->kcorr.p && !mblk_out) {  // (never for MT = double: k_assemble_tets_st takes AsmOut<float>)
     if (!h->mass_valid) {  // once per rebuild of the rest data
-      if (mat) hipLaunchKernelGGL((k_mass_blocks<float, true>), dim3(ceil_div(h->plan.n_slices, kBlock / 64)), dim3(kBlock), (size_t)(kBlock / 64) * h->asm_max_width * 64 * sizeof(double),
-                                  h->stream, sell_view(h), h->inc_off.p, h->inc.p, h->inc_slot.p, h->volf.p, ap.rho20, h->asm_max_width, h->mblk.p, (const uint8_t*)h->mat_ids.p, ap.mtab);
-      else
-      hipLaunchKernelGGL(k_mass_blocks<float>, dim3(ceil_div(h->plan.n_slices, kBlock / 64)), dim3(kBlock), (size_t)(kBlock / 64) * h->asm_max_width * 64 * sizeof(double),
-                         h->stream, sell_view(h), h->inc_off.p, h->inc.p, h->inc_slot.p, h->volf.p, ap.rho20, h->asm_max_width, h->mblk.p, (const uint8_t*)nullptr, (const double*)nullptr);
-      FB_HIP(hipGetLastError());
+      void* args[] = {&sv, &h->inc_off.p, &h->inc.p, &h->inc_slot.p, &h->volf.p, &ap.rho20, &h->asm_max_width, &h->mblk.p, &h->mat_ids.p, &ap.mtab};
+      FB_HIP(hipLaunchKernel(K.mass, dim3(ceil_div(h->plan.n_slices, kBlock / 64)), dim3(kBlock), args, mass_blocks_lds(h), h->stream));
       h->mass_valid = true;
     }
     o.mblk_in = h->mblk.p;
-    unsigned long long* prof = nullptr;
-    if (getenv("FEMBRAIN_ASM_PROFILE")) {
-      FB_HIP(hipMalloc((void**)&prof, 16 * sizeof(unsigned long long)));
-      FB_HIP(hipMemset(prof, 0, 16 * sizeof(unsigned long long)));
-    }
-    const AsmOut<float>& of = reinterpret_cast<const AsmOut<float>&>(o);
-#define FB_ASM_ST(NEWMARK, MAT)                                                                                                                                  \
-  hipLaunchKernelGGL((k_assemble_tets_st<NEWMARK, MAT>), dim3(h->asm_grid_st), dim3(kBlock), (size_t)h->asm_lds_st, h->stream, sell_view(h), h->inc_off.p, h->inc.p, \
-                     h->inc_slot.p, (const float*)h->rec.p, h->fe.p, of, ap, h->asm_max_width, prof)
-    if (mat) { if (qacc) FB_ASM_ST(true, true); else FB_ASM_ST(false, true); }
-    else if (qacc) FB_ASM_ST(true, false);
-    else FB_ASM_ST(false, false);
-#undef FB_ASM_ST
-    if (prof) {
-      FB_HIP(hipStreamSynchronize(h->stream));
-      unsigned long long t[16];
-      FB_HIP(hipMemcpy(t, prof, sizeof t, hipMemcpyDeviceToHost));
-      for (int w = 0; w < 4; w++)
-        fprintf(stderr, "[fembrain] k_assemble_tets_st wavefront %d: elements %.1f us, wait %.1f, algebra %.1f, wait %.1f (mean per workgroup)\n", w,
-                t[4 * w] * 0.01 / h->asm_grid_st, t[4 * w + 1] * 0.01 / h->asm_grid_st, t[4 * w + 2] * 0.01 / h->asm_grid_st, t[4 * w + 3] * 0.01 / h->asm_grid_st);
-      (void)hipFree(prof);
-    }
+    FB_TRY(launch_profiled(h, "k_assemble_tets_st", h->asm_grid_st, [&](unsigned long long* prof) {
+      void* args[] = {&sv, &h->inc_off.p, &h->inc.p, &h->inc_slot.p, &h->rec.p, &h->fe.p, &o, &ap, &h->asm_max_width, &prof};
+      return hipLaunchKernel(K.tets_st[qacc ? 1 : 0], dim3(h->asm_grid_st), dim3(kBlock), args, (size_t)h->asm_lds_st, h->stream);
+    }));
   } else if (h->asm_tets && !mblk_out) {  // (the per-block mass read-back, fb_fem_mass, goes through the slot-major kernel)
-    constexpr int G = 2;  // list rows whose records are in flight per lane (measured at 1M tets, fp32: 224 us with 4, 209 with 2, 211 with 1)
-    unsigned long long* prof = nullptr;
-    if (getenv("FEMBRAIN_ASM_PROFILE")) {
-      FB_HIP(hipMalloc((void**)&prof, 16 * sizeof(unsigned long long)));
-      FB_HIP(hipMemset(prof, 0, 16 * sizeof(unsigned long long)));
-    }
-#define FB_ASM_TETS(TANGENT, NEWMARK, MAT)                                                                                                                        \
-  hipLaunchKernelGGL((k_assemble_tets<MT, G, TANGENT, NEWMARK, MAT>), dim3(h->asm_grid), dim3(kBlock), (size_t)h->asm_lds, h->stream, sell_view(h), h->inc_off.p, \
-                     h->inc.p, h->inc_slot.p, (const MT*)h->rec.p, h->fe.p, o, ap, (const MT*)h->kcorr.p, h->asm_max_width, prof)
-    if (mat) {
-      if (h->kcorr.p) { if (qacc) FB_ASM_TETS(true, true, true); else FB_ASM_TETS(true, false, true); }
-      else { if (qacc) FB_ASM_TETS(false, true, true); else FB_ASM_TETS(false, false, true); }
-    } else
-    if (h->kcorr.p) { if (qacc) FB_ASM_TETS(true, true, false); else FB_ASM_TETS(true, false, false); }
-    else { if (qacc) FB_ASM_TETS(false, true, false); else FB_ASM_TETS(false, false, false); }
-#undef FB_ASM_TETS
-    if (prof) {  // FEMBRAIN_ASM_PROFILE=1: where the wavefronts of k_assemble_tets spend their time (100 MHz ticks summed over the workgroups)
-      FB_HIP(hipStreamSynchronize(h->stream));
-      unsigned long long t[16];
-      FB_HIP(hipMemcpy(t, prof, sizeof t, hipMemcpyDeviceToHost));
-      for (int w = 0; w < 4; w++)
-        fprintf(stderr, "[fembrain] k_assemble_tets wavefront %d: elements %.1f us, wait %.1f, algebra %.1f, wait %.1f (mean per workgroup)\n", w,
-                t[4 * w] * 0.01 / h->asm_grid, t[4 * w + 1] * 0.01 / h->asm_grid, t[4 * w + 2] * 0.01 / h->asm_grid, t[4 * w + 3] * 0.01 / h->asm_grid);
-      (void)hipFree(prof);
-    }
-  } else if (mat) {
-    hipLaunchKernelGGL((k_assemble_rows<MT, true>), dim3(h->grid), dim3(kBlock), 0, h->stream, sell_view(h), h->slot_coff.p, h->slot_ccnt.p,
-                       h->contrib.p, (const MT*)h->rec.p, h->fe.p, o, ap, (const MT*)h->kcorr.p, 0);
+    FB_TRY(launch_profiled(h, "k_assemble_tets", h->asm_grid, [&](unsigned long long* prof) {
+      void* args[] = {&sv, &h->inc_off.p, &h->inc.p, &h->inc_slot.p, &h->rec.p, &h->fe.p, &o, &ap, &h->kcorr.p, &h->asm_max_width, &prof};
+      return hipLaunchKernel(K.tets[qacc ? 1 : 0], dim3(h->asm_grid), dim3(kBlock), args, (size_t)h->asm_lds, h->stream);
+    }));
   } else {
-    hipLaunchKernelGGL(k_assemble_rows<MT>, dim3(h->grid), dim3(kBlock), 0, h->stream, sell_view(h), h->slot_coff.p, h->slot_ccnt.p,
-                       h->contrib.p, (const MT*)h->rec.p, h->fe.p, o, ap, (const MT*)h->kcorr.p, 0);
+    FB_TRY(launch_asm_rows(h, o, ap, 0));
   }
   if (wide_pass && wide_beside) {
     FB_HIP(hipStreamWaitEvent(h->stream, h->ev_side[1], 0));
   } else if (wide_pass) {
     AsmOut<MT> ow = o;
     ow.mblk_in = nullptr;
-    if (getenv("FEMBRAIN_ASM_WIDE_ROWS")) {  // development aid: the one-wavefront-per-slice form (same bits)
-      if (mat) hipLaunchKernelGGL((k_assemble_rows<MT, true>), dim3(h->grid), dim3(kBlock), 0, h->stream, sell_view(h), h->slot_coff.p, h->slot_ccnt.p,
-                                  h->contrib.p, (const MT*)h->rec.p, h->fe.p, ow, ap, (const MT*)h->kcorr.p, h->asm_max_width);
-      else
-      hipLaunchKernelGGL(k_assemble_rows<MT>, dim3(h->grid), dim3(kBlock), 0, h->stream, sell_view(h), h->slot_coff.p, h->slot_ccnt.p,
-                         h->contrib.p, (const MT*)h->rec.p, h->fe.p, ow, ap, (const MT*)h->kcorr.p, h->asm_max_width);
-    } else if (mat) {
-      hipLaunchKernelGGL((k_assemble_wide<MT, true>), dim3(h->asm_wide_grid), dim3(kWideBlock), 0, h->stream, sell_view(h), h->wide_list.p, h->asm_wide, h->asm_wide_slots,
-                         h->wide_scratch.p, h->slot_coff.p, h->slot_ccnt.p, h->contrib.p, (const MT*)h->rec.p, h->fe.p, ow, ap, (const MT*)h->kcorr.p);
-    } else {
-      hipLaunchKernelGGL(k_assemble_wide<MT>, dim3(h->asm_wide_grid), dim3(kWideBlock), 0, h->stream, sell_view(h), h->wide_list.p, h->asm_wide, h->asm_wide_slots,
-                         h->wide_scratch.p, h->slot_coff.p, h->slot_ccnt.p, h->contrib.p, (const MT*)h->rec.p, h->fe.p, ow, ap, (const MT*)h->kcorr.p);
-    }
+    if (h->knobs.asm_wide_rows) FB_TRY(launch_asm_rows(h, ow, ap, h->asm_max_width));  // development aid: the one-wavefront-per-slice form (same bits)
+    else FB_TRY(launch_asm_wide(h, h->stream, ow, ap));
   }
-  FB_HIP(hipGetLastError());
   return FB_OK;
 }
 
-// pass 1 + pass 2 of the system of the current state (Keff, rhs, invdiag)
 }  // namespace
 namespace fb {
+// pass 1 + pass 2 of the system of the current state (Keff, rhs, invdiag)
 int assemble_system(fb_fem_s* h) {
   const double hh = h->prm.timestep, cM = h->prm.damping_mass, cK = h->prm.damping_stiffness;
   FB_TRY(halo_exchange(h, h->q.p));
@@ -531,96 +604,24 @@ int assemble_system(fb_fem_s* h) {
     ap.g_a = 0.0; ap.rhs_scale = -hh;
   }
   ap.apply_mask = 1;
-  if (h->f64) {
-    FB_TRY(launch_warp<double>(h, h->q.p, nullptr));
-    FB_TRY(launch_rows<double>(h, ap, h->qvel.p, h->fext.p, nullptr, h->fint.p, h->rhs.p, h->invdiag.p, qacc));
-  } else {
-    FB_TRY(launch_warp<float>(h, h->q.p, nullptr));
-    FB_TRY(launch_rows<float>(h, ap, h->qvel.p, h->fext.p, nullptr, h->fint.p, h->rhs.p, h->invdiag.p, qacc));
-  }
+  FB_TRY(launch_warp(h, h->q.p, nullptr));
+  FB_TRY(h->f64 ? launch_rows<double>(h, ap, h->qvel.p, h->fext.p, nullptr, h->fint.p, h->rhs.p, h->invdiag.p, qacc)
+                : launch_rows<float>(h, ap, h->qvel.p, h->fext.p, nullptr, h->fint.p, h->rhs.p, h->invdiag.p, qacc));
   h->system_valid = true;
   return FB_OK;
 }
 }  // namespace fb
 namespace {
 
-template <typename MT, int MODE>
-int launch_spmv(fb_fem_s* h, const double* x, double* y, const double* b, double* partial, int parity) {
-  if (h->split == 4) {
-    hipLaunchKernelGGL((k_spmv_split<MT, MODE, 4>), dim3(h->sgrid), dim3(kBlock), 0, h->stream, sell_view(h), (const MT*)h->vals.p, (const MT*)h->dlo.p, x, y,
-                       b, h->invdiag.p, partial, h->st.p, parity, P2PArgs());
-    FB_HIP(hipGetLastError());
-    return FB_OK;
-  }
-  if (h->split == 2) {
-    hipLaunchKernelGGL((k_spmv_split<MT, MODE, 2>), dim3(h->sgrid), dim3(kBlock), 0, h->stream, sell_view(h), (const MT*)h->vals.p, (const MT*)h->dlo.p, x, y,
-                       b, h->invdiag.p, partial, h->st.p, parity, P2PArgs());
-    FB_HIP(hipGetLastError());
-    return FB_OK;
-  }
-  if (h->c16 == 2 && h->spmv_nt)
-    hipLaunchKernelGGL((k_spmv<MT, MODE, 0, true, 2>), dim3(h->grid), dim3(kBlock), 0, h->stream, sell_view(h), (const MT*)h->vals.p, (const MT*)h->dlo.p, x,
-                       y, b, h->invdiag.p, partial, h->st.p, parity, P2PArgs());
-  else if (h->c16 == 2)
-    hipLaunchKernelGGL((k_spmv<MT, MODE, 0, false, 2>), dim3(h->grid), dim3(kBlock), 0, h->stream, sell_view(h), (const MT*)h->vals.p, (const MT*)h->dlo.p, x,
-                       y, b, h->invdiag.p, partial, h->st.p, parity, P2PArgs());
-  else if (h->c16 && h->spmv_nt)
-    hipLaunchKernelGGL((k_spmv<MT, MODE, 0, true, 1>), dim3(h->grid), dim3(kBlock), 0, h->stream, sell_view(h), (const MT*)h->vals.p, (const MT*)h->dlo.p, x,
-                       y, b, h->invdiag.p, partial, h->st.p, parity, P2PArgs());
-  else if (h->c16)
-    hipLaunchKernelGGL((k_spmv<MT, MODE, 0, false, 1>), dim3(h->grid), dim3(kBlock), 0, h->stream, sell_view(h), (const MT*)h->vals.p, (const MT*)h->dlo.p, x,
-                       y, b, h->invdiag.p, partial, h->st.p, parity, P2PArgs());
-  else if (h->spmv_nt)
-    hipLaunchKernelGGL((k_spmv<MT, MODE, 0, true>), dim3(h->grid), dim3(kBlock), 0, h->stream, sell_view(h), (const MT*)h->vals.p, (const MT*)h->dlo.p, x, y,
-                       b, h->invdiag.p, partial, h->st.p, parity, P2PArgs());
-  else
-    hipLaunchKernelGGL((k_spmv<MT, MODE>), dim3(h->grid), dim3(kBlock), 0, h->stream, sell_view(h), (const MT*)h->vals.p, (const MT*)h->dlo.p, x, y, b,
-                       h->invdiag.p, partial, h->st.p, parity, P2PArgs());
-  FB_HIP(hipGetLastError());
+// One SpMV launch in the plan's instantiation of MODE (k_spmv: 0 y = A x, 1 with d . q, 2 r = b - A x, 3 the three merged sums).  xch: MODE 3 of a
+// sharded handle on the peer-to-peer transport, which also gathers the halo columns from the inbox and whose last block posts the sums (XCH = 2).
+// Called thousands of times per solve and under stream capture: a kernel launch through the stored address and nothing else.
+int spmv(fb_fem_s* h, int mode, const double* x, double* y, const double* b, double* partial, int parity, const P2PArgs* xch = nullptr) {
+  SellView sv = sell_view(h);
+  P2PArgs pa = xch ? *xch : P2PArgs();
+  void* args[] = {&sv, &h->vals.p, &h->dlo.p, &x, &y, &b, &h->invdiag.p, &partial, &h->st.p, &parity, &pa};
+  FB_HIP(hipLaunchKernel(xch ? h->spmv_xch_fn : h->spmv_fn[mode], dim3(h->sgrid), dim3(kBlock), args, 0, h->stream));
   return FB_OK;
-}
-
-// the merged-iteration SpMV of a sharded handle on the peer-to-peer transport: its last block posts the three sums;
-// XCH = 2 also gathers the halo columns from the inbox (sent by the neighbours' previous vector pass)
-template <typename MT, int XCH>
-int launch_spmv_xch(fb_fem_s* h, const double* x, double* y, const double* b, double* partial, int parity, const P2PArgs& pa) {
-  if (h->split == 4) {
-    hipLaunchKernelGGL((k_spmv_split<MT, 3, 4, XCH>), dim3(h->sgrid), dim3(kBlock), 0, h->stream, sell_view(h), (const MT*)h->vals.p, (const MT*)h->dlo.p, x,
-                       y, b, h->invdiag.p, partial, h->st.p, parity, pa);
-    FB_HIP(hipGetLastError());
-    return FB_OK;
-  }
-  if (h->split == 2) {
-    hipLaunchKernelGGL((k_spmv_split<MT, 3, 2, XCH>), dim3(h->sgrid), dim3(kBlock), 0, h->stream, sell_view(h), (const MT*)h->vals.p, (const MT*)h->dlo.p, x,
-                       y, b, h->invdiag.p, partial, h->st.p, parity, pa);
-    FB_HIP(hipGetLastError());
-    return FB_OK;
-  }
-  if (h->c16 == 2 && h->spmv_nt)
-    hipLaunchKernelGGL((k_spmv<MT, 3, XCH, true, 2>), dim3(h->grid), dim3(kBlock), 0, h->stream, sell_view(h), (const MT*)h->vals.p, (const MT*)h->dlo.p, x, y,
-                       b, h->invdiag.p, partial, h->st.p, parity, pa);
-  else if (h->c16 == 2)
-    hipLaunchKernelGGL((k_spmv<MT, 3, XCH, false, 2>), dim3(h->grid), dim3(kBlock), 0, h->stream, sell_view(h), (const MT*)h->vals.p, (const MT*)h->dlo.p, x, y,
-                       b, h->invdiag.p, partial, h->st.p, parity, pa);
-  else if (h->c16 && h->spmv_nt)
-    hipLaunchKernelGGL((k_spmv<MT, 3, XCH, true, 1>), dim3(h->grid), dim3(kBlock), 0, h->stream, sell_view(h), (const MT*)h->vals.p, (const MT*)h->dlo.p, x, y,
-                       b, h->invdiag.p, partial, h->st.p, parity, pa);
-  else if (h->c16)
-    hipLaunchKernelGGL((k_spmv<MT, 3, XCH, false, 1>), dim3(h->grid), dim3(kBlock), 0, h->stream, sell_view(h), (const MT*)h->vals.p, (const MT*)h->dlo.p, x, y,
-                       b, h->invdiag.p, partial, h->st.p, parity, pa);
-  else if (h->spmv_nt)
-    hipLaunchKernelGGL((k_spmv<MT, 3, XCH, true>), dim3(h->grid), dim3(kBlock), 0, h->stream, sell_view(h), (const MT*)h->vals.p, (const MT*)h->dlo.p, x, y,
-                       b, h->invdiag.p, partial, h->st.p, parity, pa);
-  else
-    hipLaunchKernelGGL((k_spmv<MT, 3, XCH>), dim3(h->grid), dim3(kBlock), 0, h->stream, sell_view(h), (const MT*)h->vals.p, (const MT*)h->dlo.p, x, y, b,
-                       h->invdiag.p, partial, h->st.p, parity, pa);
-  FB_HIP(hipGetLastError());
-  return FB_OK;
-}
-
-template <int MODE>
-int spmv(fb_fem_s* h, const double* x, double* y, const double* b, double* partial, int parity) {
-  return h->f64 ? launch_spmv<double, MODE>(h, x, y, b, partial, parity) : launch_spmv<float, MODE>(h, x, y, b, partial, parity);
 }
 
 // multi-GPU: fold the per-block partials into one scalar and all-reduce it; returns the device scalar pointer
@@ -661,14 +662,14 @@ int pcg_iteration(fb_fem_s* h, int it, const double* b) {
   const bool refresh = (it % 30 == 0);
   double* sc = nullptr;
   if (variant == FB_PCG_BLOCK_JACOBI) {  // literal sequence, z = B^-1 r (unsharded: the partials are summed by the consumers)
-    FB_TRY(spmv<1>(h, h->d.p, h->Ad.p, nullptr, h->part_a.p, parity));
+    FB_TRY(spmv(h, 1, h->d.p, h->Ad.p, nullptr, h->part_a.p, parity));
     if (!refresh) {
       hipLaunchKernelGGL(k_bj_update<false>, dim3(h->grid), dim3(kBlock), 0, h->stream, P.n_slices, P.n_owned, h->st.p, parity, h->part_a.p, h->sgrid, h->d.p,
                          h->Ad.p, h->invblk.p, h->x.p, h->r.p, h->part_b.p);
     } else {
       hipLaunchKernelGGL(k_bj_update<true>, dim3(h->grid), dim3(kBlock), 0, h->stream, P.n_slices, P.n_owned, h->st.p, parity, h->part_a.p, h->sgrid, h->d.p,
                          h->Ad.p, h->invblk.p, h->x.p, h->r.p, h->part_b.p);
-      FB_TRY(spmv<2>(h, h->x.p, h->r.p, b, h->part_c.p, parity));  // r = b - A x (its Jacobi-weighted sum is not used)
+      FB_TRY(spmv(h, 2, h->x.p, h->r.p, b, h->part_c.p, parity));  // r = b - A x (its Jacobi-weighted sum is not used)
       hipLaunchKernelGGL(k_bj_rho, dim3(h->grid), dim3(kBlock), 0, h->stream, P.n_slices, P.n_owned, h->st.p, h->r.p, h->invblk.p, h->part_b.p);
     }
     hipLaunchKernelGGL(k_bj_direction, dim3(h->grid), dim3(kBlock), 0, h->stream, P.n_slices, P.n_owned, h->st.p, parity, h->part_b.p, h->grid, h->r.p,
@@ -684,11 +685,10 @@ int pcg_iteration(fb_fem_s* h, int it, const double* b) {
     pa.send_ids = h->send_local.p; pa.send_off = h->send_off_dev.p; pa.halo_off = h->halo_off_dev.p; pa.slice_halo = h->slice_halo.p;
     if (h->xch_mode == FB_XCH_P2P_FUSED) {
       pa.halo_seq = p2p_next_halo(h->p2p);
-      FB_TRY(h->f64 ? (launch_spmv_xch<double, 2>(h, h->d.p, h->Ad.p, h->r.p, h->part_a.p, parity, pa))
-                    : (launch_spmv_xch<float, 2>(h, h->d.p, h->Ad.p, h->r.p, h->part_a.p, parity, pa)));
+      FB_TRY(spmv(h, 3, h->d.p, h->Ad.p, h->r.p, h->part_a.p, parity, &pa));
     } else {
       FB_TRY(halo_exchange(h, h->d.p));
-      FB_TRY(spmv<3>(h, h->d.p, h->Ad.p, h->r.p, h->part_a.p, parity));
+      FB_TRY(spmv(h, 3, h->d.p, h->Ad.p, h->r.p, h->part_a.p, parity));
     }
     hipLaunchKernelGGL((k_cg_fused<true>), dim3(h->grid), dim3(kBlock), 0, h->stream, P.n_slices, P.n_owned, h->st.p, parity, h->part_a.p, h->sgrid,
                        (const double*)nullptr, h->Ad.p, h->invdiag.p, h->x.p, h->r.p, h->d.p, pa);
@@ -698,14 +698,14 @@ int pcg_iteration(fb_fem_s* h, int it, const double* b) {
   FB_TRY(halo_exchange(h, h->d.p));
   if (!refresh && (variant == FB_PCG_MERGED || variant == FB_PCG_PERSISTENT)) {
     // merged-reduction iteration: SpMV with the three sums, then one fused vector pass (one reduction / all-reduce)
-    FB_TRY(spmv<3>(h, h->d.p, h->Ad.p, h->r.p, h->part_a.p, parity));
+    FB_TRY(spmv(h, 3, h->d.p, h->Ad.p, h->r.p, h->part_a.p, parity));
     FB_TRY(global_scalar(h, h->part_a.p, &sc, true, 3, 0, h->sgrid));
     hipLaunchKernelGGL((k_cg_fused<false>), dim3(h->vgrid), dim3(kBlock), 0, h->stream, P.n_slices, P.n_owned, h->st.p, parity, h->part_a.p, h->sgrid,
                        sc, h->Ad.p, h->invdiag.p, h->x.p, h->r.p, h->d.p, P2PArgs());
     FB_HIP(hipGetLastError());
     return FB_OK;
   }
-  FB_TRY(spmv<1>(h, h->d.p, h->Ad.p, nullptr, h->part_a.p, parity));
+  FB_TRY(spmv(h, 1, h->d.p, h->Ad.p, nullptr, h->part_a.p, parity));
   FB_TRY(global_scalar(h, h->part_a.p, &sc, true, 1, 0, h->sgrid));
   if (!refresh) {
     hipLaunchKernelGGL(k_cg_update<false>, dim3(h->grid), dim3(kBlock), 0, h->stream, P.n_slices, P.n_owned, h->st.p, parity,
@@ -716,7 +716,7 @@ int pcg_iteration(fb_fem_s* h, int it, const double* b) {
                        h->part_a.p, h->sgrid, sc, h->d.p, h->Ad.p, h->invdiag.p, h->x.p, h->r.p, h->part_b.p);
     FB_HIP(hipGetLastError());
     FB_TRY(halo_exchange(h, h->x.p));
-    FB_TRY(spmv<2>(h, h->x.p, h->r.p, b, h->part_b.p, parity));
+    FB_TRY(spmv(h, 2, h->x.p, h->r.p, b, h->part_b.p, parity));
   }
   FB_TRY(global_scalar(h, h->part_b.p, &sc, true, 1, 0, refresh ? h->sgrid : h->grid));
   // part_b comes from the exact-residual SpMV on refresh iterations, from the vector kernel otherwise
@@ -731,8 +731,6 @@ void drop_graph(fb_fem_s* h) {
   h->batch_graph = nullptr;
   h->graph_rhs = nullptr;
 }
-
-int pcg_iteration(fb_fem_s* h, int it, const double* b);
 
 // captures iterations 1..30 (parity and the position of the exact-residual iteration repeat with period 30)
 int ensure_batch_graph(fb_fem_s* h, const double* b, int batch) {
@@ -760,8 +758,6 @@ bool host_finished(const CGState& s) {
 }
 
 // Jacobi-PCG on the assembled system, rhs b -> h->x.  iters_out: + converged / - not (CGSolver.cpp:189).
-
-
 int pcg_solve(fb_fem_s* h, const double* b, double eps, int max_iter, int* iters_out, CGState* final_state, bool allow_persist = true);
 
 // Jacobi-PCG inside persistent launches (normally ONE): CGSolver.cpp:129-190 in its pipelined form
@@ -831,7 +827,7 @@ int pcg_solve_pipe(fb_fem_s* h, const double* b, double eps, int max_iter, int* 
     if (cap_check && h->prm.pcg_variant != FB_PCG_BLOCK_JACOBI) {  // (block-Jacobi carries r . B^-1 r: not what the product kernel sums)
       FB_TRY(h->st.zero(s));  // done = 0: the product below is not a no-op
       FB_TRY(halo_exchange(h, h->d.p));
-      FB_TRY(spmv<2>(h, h->d.p, h->r.p, b, h->part_b.p, 0));
+      FB_TRY(spmv(h, 2, h->d.p, h->r.p, b, h->part_b.p, 0));
       double* sc = nullptr;
       FB_TRY(global_scalar(h, h->part_b.p, &sc, false, 1, 0, h->sgrid));
       hipLaunchKernelGGL(k_cg_begin, dim3(1), dim3(kBlock), 0, s, h->st.p, h->part_b.p, h->sgrid, sc, eps, max_iter);
@@ -893,7 +889,7 @@ int pcg_solve(fb_fem_s* h, const double* b, double eps, int max_iter, int* iters
     h->pcg_warm = false;
     FB_TRY(h->st.zero(s));  // done = 0: the SpMV below is not a no-op
     FB_TRY(halo_exchange(h, h->x.p));
-    FB_TRY(spmv<2>(h, h->x.p, h->r.p, b, h->part_b.p, 0));
+    FB_TRY(spmv(h, 2, h->x.p, h->r.p, b, h->part_b.p, 0));
     if (h->prm.pcg_variant == FB_PCG_BLOCK_JACOBI) {  // d = B^-1 r and rho = r . B^-1 r (the SpMV's Jacobi-weighted sum is not used)
       hipLaunchKernelGGL(k_bj_init_warm, dim3(h->grid), dim3(kBlock), 0, s, P.n_slices, P.n_owned, h->r.p, h->invblk.p, h->d.p, h->part_b.p);
       FB_HIP(hipGetLastError());
@@ -1046,7 +1042,7 @@ int build_plan_on_device(fb_fem_s* h, int n_nodes, int n_tets, const int* tets, 
   }
   FB_TRY(rc);
   P.n_blocks = D.n_blocks; P.n_slices = D.n_slices; P.n_slots = D.n_slots; P.n_crows = D.n_crows;
-  h->c16 = (D.deltas_fit16 && !(getenv("FEMBRAIN_SPMV_C16") && atoi(getenv("FEMBRAIN_SPMV_C16")) == 0)) ? 1 : 0;
+  h->c16 = (D.deltas_fit16 && read_host_knobs().spmv_c16) ? 1 : 0;
   P.slice_off = D.slice_off_host;
   h->csr_ready = true;
   return FB_OK;
@@ -1165,7 +1161,7 @@ int build_shard_plan_on_device(fb_fem_s* h, int n_nodes, int n_tets, const int* 
   if (h->plan_ws.bytes() > ((size_t)2 << 30)) h->plan_ws.release();
   FB_TRY(rc);
   P.n_blocks = D.n_blocks; P.n_slices = D.n_slices; P.n_slots = D.n_slots; P.n_crows = D.n_crows;
-  h->c16 = (D.deltas_fit16 && !(getenv("FEMBRAIN_SPMV_C16") && atoi(getenv("FEMBRAIN_SPMV_C16")) == 0)) ? 2 : 0;  // the halo form
+  h->c16 = (D.deltas_fit16 && read_host_knobs().spmv_c16) ? 2 : 0;  // the halo form
   P.slice_off = D.slice_off_host;
   return FB_OK;
 }
@@ -1876,7 +1872,7 @@ int resync_delta(fb_fem_s* h, int n_removed, const int* removed, int n_changed, 
   h->d_bptr.swap(D.bptr2); h->d_bcol.swap(D.bcol2); h->d_blk_slot.swap(D.blk_slot2); h->d_ucnt.swap(D.ucnt2);
   h->csr_ready = true;
   P.n_blocks = Dp.n_blocks; P.n_slices = Dp.n_slices; P.n_slots = Dp.n_slots; P.n_crows = Dp.n_crows;
-  h->c16 = (Dp.deltas_fit16 && !(getenv("FEMBRAIN_SPMV_C16") && atoi(getenv("FEMBRAIN_SPMV_C16")) == 0)) ? 1 : 0;
+  h->c16 = (Dp.deltas_fit16 && read_host_knobs().spmv_c16) ? 1 : 0;
   P.slice_off = Dp.slice_off_host;
   h->device_plan = true;
   h->host_pattern = false;
@@ -2438,16 +2434,16 @@ int fb_fem_set_element_materials(fb_fem_t h, int first, int count, const unsigne
   if (count == 0) return FB_OK;
   if (!has_material_map(h)) {
     if (hi == 0) return FB_OK;  // (every element is material 0 already: still no map)
-    // The first map.  The table, the kernels' attributes and the filled id array are made first and the array becomes the handle's LAST:
-    // mat_ids is what says "this handle has a map", so a failure on the way leaves a handle without one, as it was.
+    // The first map.  The table, the filled id array and the material-aware kernels (resolve_asm_kernels) are made first and the array becomes the
+    // handle's LAST: mat_ids is what says "this handle has a map", so a failure on the way leaves a handle without one, as it was.
     FB_TRY(upload_material_table(h, n, h->mat_E.data(), h->mat_nu.data(), h->mat_rho.data()));
-    FB_TRY(material_kernel_attributes(h));
     SlackScope slack(handle_slack(h, h->plan.n_global, nt));  // the handle's slack rule, as for the element buffers
     DevBuf<unsigned char> fresh;
     FB_TRY(fresh.alloc((size_t)std::max(1, nt)));
     FB_TRY(fresh.zero(h->stream));
     FB_HIP(hipMemcpyAsync(fresh.p + first, ids, (size_t)count, hipMemcpyHostToDevice, h->stream));
     FB_HIP(hipStreamSynchronize(h->stream));
+    FB_TRY(resolve_asm_kernels(h, true));
     h->mat_ids.swap(fresh);
   } else {
     FB_HIP(hipMemcpyAsync(h->mat_ids.p + first, ids, (size_t)count, hipMemcpyHostToDevice, h->stream));
@@ -2621,13 +2617,7 @@ int fb_fem_element_stiffness(fb_fem_t h, int first, int count, double* K0, doubl
   if (Minv) FB_TRY(dM.alloc((size_t)16 * std::min(count, kChunk)));
   for (int done = 0; done < count; done += kChunk) {
     const int n = std::min(kChunk, count - done);
-    if (has_material_map(h))
-      hipLaunchKernelGGL(k_element_K0_mfma<true>, dim3(ceil_div(n, kWavesPerBlock)), dim3(kBlock), 0, h->stream, first + done, n, h->rest.p,
-                         h->lambda, h->mu, dK.p, Minv ? dM.p : nullptr, h->x0.p, h->tets.p, (const uint8_t*)h->mat_ids.p, (const double*)h->mat_tab.p);
-    else
-      hipLaunchKernelGGL(k_element_K0_mfma<false>, dim3(ceil_div(n, kWavesPerBlock)), dim3(kBlock), 0, h->stream, first + done, n, h->rest.p,
-                         h->lambda, h->mu, dK.p, Minv ? dM.p : nullptr, h->x0.p, h->tets.p, (const uint8_t*)nullptr, (const double*)nullptr);
-    FB_HIP(hipGetLastError());
+    FB_TRY(launch_element_K0(h, first + done, n, dK.p, Minv ? dM.p : nullptr));
     FB_TRY(dK.download(K0 + (size_t)144 * done, (size_t)144 * n, h->stream));
     if (Minv) FB_TRY(dM.download(Minv + (size_t)16 * done, (size_t)16 * n, h->stream));
   }
@@ -2641,19 +2631,12 @@ int fb_fem_time_element_stiffness(fb_fem_t h, int reps, double* seconds_per_pass
   DevBuf<double> dK;
   FB_TRY(dK.alloc((size_t)144 * std::min(nt, kChunk)));  // the 1.15 GB of a 1M-tet K0 set are produced chunk by chunk into the same scratch
   auto pass = [&]() {
-    for (int done = 0; done < nt; done += kChunk) {
-      const int n = std::min(kChunk, nt - done);
-      if (has_material_map(h))
-        hipLaunchKernelGGL(k_element_K0_mfma<true>, dim3(ceil_div(n, kWavesPerBlock)), dim3(kBlock), 0, h->stream, done, n, h->rest.p, h->lambda, h->mu, dK.p,
-                           (double*)nullptr, h->x0.p, h->tets.p, (const uint8_t*)h->mat_ids.p, (const double*)h->mat_tab.p);
-      else
-        hipLaunchKernelGGL(k_element_K0_mfma<false>, dim3(ceil_div(n, kWavesPerBlock)), dim3(kBlock), 0, h->stream, done, n, h->rest.p, h->lambda, h->mu, dK.p,
-                           (double*)nullptr, h->x0.p, h->tets.p, (const uint8_t*)nullptr, (const double*)nullptr);
-    }
+    for (int done = 0; done < nt; done += kChunk) FB_TRY(launch_element_K0(h, done, std::min(kChunk, nt - done), dK.p, nullptr));
+    return FB_OK;
   };
-  pass();
+  FB_TRY(pass());
   FB_HIP(hipEventRecord(h->ev[0], h->stream));
-  for (int r = 0; r < reps; r++) pass();
+  for (int r = 0; r < reps; r++) FB_TRY(pass());
   FB_HIP(hipEventRecord(h->ev[1], h->stream));
   FB_HIP(hipStreamSynchronize(h->stream));
   FB_HIP(hipGetLastError());
@@ -2671,13 +2654,9 @@ int fb_fem_assemble(fb_fem_t h, const double* u, double* f, double* K_blocks) {
   AsmParams ap;
   asm_materials(h, ap);
   ap.s_k = 1.0; ap.s_m = 0.0; ap.g_k = 0.0; ap.g_m = 0.0; ap.g_a = 0.0; ap.rhs_scale = 0.0; ap.apply_mask = 0;
-  if (h->f64) {
-    FB_TRY(launch_warp<double>(h, h->tmp.p, nullptr));
-    FB_TRY(launch_rows<double>(h, ap, h->Ad.p, h->Ad.p, h->mblk.p, h->r.p, nullptr, nullptr));
-  } else {
-    FB_TRY(launch_warp<float>(h, h->tmp.p, nullptr));
-    FB_TRY(launch_rows<float>(h, ap, h->Ad.p, h->Ad.p, h->mblk.p, h->r.p, nullptr, nullptr));
-  }
+  FB_TRY(launch_warp(h, h->tmp.p, nullptr));
+  FB_TRY(h->f64 ? launch_rows<double>(h, ap, h->Ad.p, h->Ad.p, h->mblk.p, h->r.p, nullptr, nullptr)
+                : launch_rows<float>(h, ap, h->Ad.p, h->Ad.p, h->mblk.p, h->r.p, nullptr, nullptr));
   h->system_valid = false;
   if (f) FB_TRY(download_owned(h, h->r, f));
   if (K_blocks) FB_TRY(download_blocks(h, K_blocks));
@@ -2721,7 +2700,7 @@ int fb_fem_spmv(fb_fem_t h, const double* x, double* y) {
   if (!h->system_valid) FB_TRY(assemble_system(h));
   FB_TRY(upload_global_vec(h, x, h->tmp));
   FB_TRY(halo_exchange(h, h->tmp.p));
-  FB_TRY(spmv<0>(h, h->tmp.p, h->Ad.p, nullptr, nullptr, 0));
+  FB_TRY(spmv(h, 0, h->tmp.p, h->Ad.p, nullptr, nullptr, 0));
   return download_owned(h, h->Ad, y);
 }
 
@@ -2748,9 +2727,9 @@ int fb_fem_time_spmv(fb_fem_t h, int reps, double* seconds_per_spmv) {
                      h->part_b.p);
   hipLaunchKernelGGL(k_cg_begin, dim3(1), dim3(kBlock), 0, h->stream, h->st.p, h->part_b.p, h->grid, (const double*)nullptr, 1e-30, 1 << 30);
   FB_HIP(hipGetLastError());
-  FB_TRY(spmv<3>(h, h->d.p, h->Ad.p, h->r.p, h->part_a.p, 0));  // warm
+  FB_TRY(spmv(h, 3, h->d.p, h->Ad.p, h->r.p, h->part_a.p, 0));  // warm
   FB_HIP(hipEventRecord(h->ev[0], h->stream));
-  for (int i = 0; i < reps; i++) FB_TRY(spmv<3>(h, h->d.p, h->Ad.p, h->r.p, h->part_a.p, 0));
+  for (int i = 0; i < reps; i++) FB_TRY(spmv(h, 3, h->d.p, h->Ad.p, h->r.p, h->part_a.p, 0));
   FB_HIP(hipEventRecord(h->ev[1], h->stream));
   FB_HIP(hipStreamSynchronize(h->stream));
   float ms = 0;

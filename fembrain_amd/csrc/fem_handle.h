@@ -115,6 +115,23 @@ struct PersistState {
   }
 };
 
+// The environment knobs of the assembly and the SpMV.  read_host_knobs() (fem.hip) is the one place that reads them, once per plan build
+// (upload_plan: handle creation and every re-sync; the three plan builders that decide c16 ask it too).  Nothing is cached per process.
+struct HostKnobs {
+  bool asm_rows = false, asm_tets1 = false;  // FEMBRAIN_ASM_KERNEL=rows: the slot-major kernel; =tets1: the unstaged element-major one (same bits)
+  int asm_per_cu = 0;          // FEMBRAIN_ASM_PER_CU (development aid): at most so many element-major workgroups per CU; 0 = not set
+  int asm_wide_grid = 0;       // FEMBRAIN_ASM_WIDE_GRID (tests: several slices per workgroup): at most so many workgroups of k_assemble_wide; 0 = not set
+  bool asm_wide_rows = false;  // FEMBRAIN_ASM_WIDE_ROWS (development aid): the wide slices in the one-wavefront-per-slice form (same bits)
+  bool asm_profile = false;    // FEMBRAIN_ASM_PROFILE: where the wavefronts of the element-major kernels spend their time, printed per assembly
+  int spmv_nt = -1;            // FEMBRAIN_SPMV_NT=0/1: matrix values streamed non-temporally; -1 = not set, upload_plan's size rule
+  bool spmv_c16 = true;        // FEMBRAIN_SPMV_C16=0: 32-bit column words even where the 16-bit ones fit
+  bool verbose = false;        // FEMBRAIN_TIMING is set: the two assembly diagnostics of upload_plan
+};
+
+// What a plan launches of the assembly families, resolved from the table of their instantiations (fem.hip resolve_asm_kernels: for every
+// plan, and again when a handle gets its element map).  [2]: without | with qacc; tets_st and mass: staged plans only
+struct AsmKernels { const void *warp = nullptr, *rows = nullptr, *wide = nullptr, *k0 = nullptr, *mass = nullptr, *tets[2] = {nullptr, nullptr}, *tets_st[2] = {nullptr, nullptr}; };
+
 }  // namespace fb
 
 using namespace fb;  // (both units do; the handle's members are fb's types)
@@ -183,6 +200,8 @@ struct fb_fem_s {
   bool asm_staged = false;           // k_assemble_tets_st (records staged in LDS, mass entries precomputed) instead of k_assemble_tets
   int asm_lds_st = 0, asm_grid_st = 0;
   bool mass_valid = false;           // h->mblk holds the mass entries of the current rest data (k_mass_blocks)
+  fb::HostKnobs knobs;               // as the last plan build read them
+  fb::AsmKernels asm_k;              // the assembly kernels of this plan
   // locality renumbering behind the ABI (renumber.h): the handle works in its own node order, ids are mapped on the way in and out
   Renumbering ren;
   DevBuf<double> xyz_in;               // the caller-order rest positions the order was derived from
@@ -226,6 +245,8 @@ struct fb_fem_s {
   int split = 0;       // wavefronts per slice of the SpMV on small / mid-size meshes (k_spmv_split): 0 (row kernel), 2 or 4
   int sgrid = 8;       // blocks (= partial sums) of the SpMV launches; equals grid unless split
   bool spmv_nt = false;  // stream the matrix values non-temporally (systems larger than the Infinity Cache, see k_spmv)
+  const void* spmv_fn[4] = {nullptr, nullptr, nullptr, nullptr};  // the SpMV of this plan by MODE (fem.hip resolve_spmv_kernels), and
+  const void* spmv_xch_fn = nullptr;                              // MODE 3 with the halo refresh in its prologue (XCH = 2)
   int vgrid = 8;       // blocks of the merged vector pass: one 16-byte pair per thread
   hipGraphExec_t batch_graph = nullptr;
   const double* graph_rhs = nullptr;

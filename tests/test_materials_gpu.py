@@ -239,6 +239,46 @@ def test_a_map_of_equal_materials_is_the_uniform_handle_bit_for_bit(gpu, monkeyp
     assert np.abs(out[0][-1]).max() > 0
 
 
+NEWMARK_CASES = [(m, p, k, w, False) for m in ("cube6", "hub") for p in (fl.FB_MATRIX_F64, fl.FB_MATRIX_F32) for k in ("default", "rows", "tets1")
+                 for w in ("warp1", "tangent")] + [("hub", fl.FB_MATRIX_F32, "default", "warp1", True)]
+
+
+@pytest.mark.parametrize("mesh,prec,kernel,warp,newton", NEWMARK_CASES,
+                         ids=["%s-%s-%s-%s%s" % (m, "f64" if p == fl.FB_MATRIX_F64 else "f32", k, w, "-newton3" if n else "") for m, p, k, w, n in NEWMARK_CASES])
+def test_a_map_of_equal_materials_is_the_uniform_newmark_handle_bit_for_bit(gpu, monkeypatch, mesh, prec, kernel, warp, newton):
+    """The Newmark sibling of the test above: the material-aware instantiations that take qacc (k_assemble_tets<.., NEWMARK, MAT>,
+    k_assemble_tets_st<NEWMARK, MAT>) against the uniform ones, and -- a Newmark handle assembles without qacc too -- mass() and the raw
+    assemble().  newton: three Newton iterations per step at a loose tolerance, so that the residual of every DOF (res_all) is written."""
+    if kernel != "default":
+        monkeypatch.setenv("FEMBRAIN_ASM_KERNEL", kernel)
+    v, t, fixed = _mesh(mesh)
+    q, qv, fext, u = _state(mesh)
+    L = fl.lib()
+    staged = prec == fl.FB_MATRIX_F32 and warp != "tangent"
+    out = []
+    for mapped in (False, True):
+        g = _handle(mesh, prec, warp, materials=False, integrator=fl.FB_INTEGRATOR_NEWMARK)
+        if newton:
+            g.set_newmark(0.25, 0.5, 3, 0.5)
+        if mapped:   # three entries equal to the params', every element names a non-zero one: the map exists and is read
+            d = MATS[0]
+            g.set_materials([d[0]] * 3, [d[1]] * 3, [d[2]] * 3, element_ids=1 + (np.arange(len(t)) & 1))
+        assert (g.element_map_bytes() > 0) == mapped
+        assert L.fb_fem_assembly_kernel(g.h) == (0 if kernel == "rows" else (2 if kernel == "default" and staged else 1))
+        if mesh == "hub":
+            assert (L.fb_fem_assembly_wide_slices(g.h) > 0) == (kernel != "rows")
+        g.set_q_state(q, qv)
+        g.set_external_forces(fext)
+        Keff, rhs = g.system()
+        fa, Ka = g.assemble(u)
+        g.reset_to_rest()
+        out.append([Keff, rhs, g.mass(), fa, Ka] + _three_steps(g))
+        g.close()
+    for a, b in zip(*out):
+        assert np.array_equal(a, b)
+    assert np.abs(out[0][-1]).max() > 0
+
+
 def test_a_handle_that_never_sets_a_map_allocates_none(gpu):
     """... and steps to the bytes of a handle that was never asked anything about materials: a one-entry table, or ids that are all 0,
     change the params' material and nothing else."""
