@@ -19,6 +19,7 @@ struct PipeKernel {
   bool c16;             // 16-bit column words
   int wmax, klt;        // wavefronts it is built for; most LDS slots per wavefront (the unroll bound of the loop over resident slots)
   bool timing, shard, bj, help, xyz;
+  bool ahead;           // the run-ahead form: for launches with a service wavefront (pcg_pipe.hip.h)
   const void* fn;
 };
 
@@ -27,10 +28,14 @@ namespace {
 // The instantiations, all of them: (wavefronts, most LDS slots per wavefront) = (8, 8) up to 8 slices per CU, (12, 6) up to 12 -- (12, 7)
 // at 9 and 10 --, (5, 16) on request (PersistKnobs::small); 16- or 32-bit column words; two rows per lane (k_pcg_pipe2) for 13..24 slices
 // per CU; SHARD on a sharded handle (32-bit local column ids); TIMING: the development build with the phase clocks, for the 1M-tet
-// configuration, the small ones and the helpers'; BJ: the block preconditioner; HELP: the task table, which also carries XYZ.
-#define FB_PIPE1(C16, WMAX, KLT, TIMING, SHARD, BJ, HELP, XYZ) \
-  {1, C16, WMAX, KLT, TIMING, SHARD, BJ, HELP, XYZ, (const void*)k_pcg_pipe<float, C16, WMAX, KLT, TIMING, SHARD, BJ, HELP, XYZ>}
-#define FB_PIPE2(C16, SHARD, XYZ) {2, C16, 12, kPipe2Klt, false, SHARD, false, false, XYZ, (const void*)k_pcg_pipe2<C16, SHARD, XYZ>}
+// configuration, the small ones and the helpers'; BJ: the block preconditioner; HELP: the task table, which also carries XYZ.  Every
+// unsharded one-row kernel without the task table comes in two forms, one per launch form: with its barriers (as many slices as
+// wavefronts) and run-ahead (a service wavefront); the others keep their barriers with or without a service wavefront.
+#define FB_PIPE1F(C16, WMAX, KLT, TIMING, SHARD, BJ, HELP, XYZ, AHEAD) \
+  {1, C16, WMAX, KLT, TIMING, SHARD, BJ, HELP, XYZ, AHEAD, (const void*)k_pcg_pipe<float, C16, WMAX, KLT, TIMING, SHARD, BJ, HELP, XYZ, AHEAD>}
+#define FB_PIPE1(C16, WMAX, KLT, TIMING, SHARD, BJ, HELP, XYZ) FB_PIPE1F(C16, WMAX, KLT, TIMING, SHARD, BJ, HELP, XYZ, false)
+#define FB_PIPE1A(C16, WMAX, KLT, TIMING, BJ) FB_PIPE1F(C16, WMAX, KLT, TIMING, false, BJ, false, false, true)
+#define FB_PIPE2(C16, SHARD, XYZ) {2, C16, 12, kPipe2Klt, false, SHARD, false, false, XYZ, false, (const void*)k_pcg_pipe2<C16, SHARD, XYZ>}
 const PipeKernel kPipeKernels[] = {
     FB_PIPE1(true, 5, 16, false, false, false, false, false),  FB_PIPE1(false, 5, 16, false, false, false, false, false),
     FB_PIPE1(true, 8, 8, false, false, false, false, false),   FB_PIPE1(false, 8, 8, false, false, false, false, false),
@@ -46,16 +51,29 @@ const PipeKernel kPipeKernels[] = {
     FB_PIPE1(true, 12, 6, false, false, false, true, true),    FB_PIPE1(false, 12, 6, false, false, false, true, true),
     FB_PIPE1(true, 12, 6, true, false, false, true, false),    FB_PIPE1(false, 12, 6, true, false, false, true, false),
     FB_PIPE1(true, 12, 6, true, false, false, true, true),     FB_PIPE1(false, 12, 6, true, false, false, true, true),
+    FB_PIPE1A(true, 5, 16, false, false),  FB_PIPE1A(false, 5, 16, false, false),  FB_PIPE1A(true, 8, 8, false, false),   FB_PIPE1A(false, 8, 8, false, false),
+    FB_PIPE1A(true, 12, 6, false, false),  FB_PIPE1A(false, 12, 6, false, false),  FB_PIPE1A(true, 12, 7, false, false),  FB_PIPE1A(false, 12, 7, false, false),
+    FB_PIPE1A(true, 5, 16, true, false),   FB_PIPE1A(true, 8, 8, true, false),     FB_PIPE1A(false, 8, 8, true, false),
+    FB_PIPE1A(true, 12, 6, true, false),   FB_PIPE1A(false, 12, 6, true, false),
+    FB_PIPE1A(true, 8, 8, false, true),    FB_PIPE1A(false, 8, 8, false, true),    FB_PIPE1A(true, 12, 6, false, true),   FB_PIPE1A(false, 12, 6, false, true),
     FB_PIPE2(true, false, false),  FB_PIPE2(false, false, false),  FB_PIPE2(true, false, true),  FB_PIPE2(false, false, true),
     FB_PIPE2(false, true, false),
 };
 #undef FB_PIPE2
+#undef FB_PIPE1A
 #undef FB_PIPE1
+#undef FB_PIPE1F
 static_assert(sizeof(double) * kPipeSyncDoubles + (size_t)kPipeMaxWaves * 2 * kPipe2LdsWordsPerRow * 64 * 4 <= 160 * 1024, "LDS budget of k_pcg_pipe2");
 
 int env_int(const char* name, int unset) {
   const char* e = getenv(name);
   return e ? atoi(e) : unset;
+}
+
+// A launch has one wavefront more than slices where the instantiation has room: it collects the sums while the others multiply.
+bool pipe_has_service(const PersistState& ps) {
+  const int cwaves = ps.pipe_rows == 2 ? ceil_div(ps.persist_waves, 2) : ps.persist_waves;  // wavefronts that own slices
+  return cwaves + ps.pipe_help_waves < ps.pipe_wmax;
 }
 
 PersistKnobs read_persist_knobs() {
@@ -98,11 +116,12 @@ int resolve_pipe_kernel(fb_fem_s* h, const PersistKnobs& kn) {
   const bool klt7 = kn.klt7 && want.rows == 1 && ps.pipe_wmax == 12 && !want.shard && !want.bj && !want.help && !want.timing &&
                     (ps.persist_waves == 9 || ps.persist_waves == 10);
   want.wmax = ps.pipe_wmax;
+  want.ahead = want.rows == 1 && !want.shard && !want.help && pipe_has_service(ps);
   want.klt = want.rows == 2 ? kPipe2Klt : (want.wmax == 5 ? 16 : (want.wmax == 8 ? 8 : (klt7 ? 7 : 6)));
   ps.kernel = nullptr;
   for (const PipeKernel& k : kPipeKernels)
     if (k.rows == want.rows && k.c16 == want.c16 && k.wmax == want.wmax && k.klt == want.klt && k.timing == want.timing && k.shard == want.shard && k.bj == want.bj &&
-        k.help == want.help && k.xyz == want.xyz)
+        k.help == want.help && k.xyz == want.xyz && k.ahead == want.ahead)
       ps.kernel = &k;
   if (!ps.kernel) return fail(FB_EINVAL, "FEMBRAIN_PERSIST_TIMING is built for one row per lane: (12, 6) and (5, 16) with 16-bit column words, (8, 8)");
   return FB_OK;
@@ -475,7 +494,8 @@ int launch_pipe(fb_fem_s* h, const double* b, int start, int n_iters, double eps
   pa.mirror = ps.pipe_mir.p; pa.mir_addr = ps.pipe_mir_addr.p; pa.mir_wg = ps.pipe_mir_wg.p; pa.mir_pool = ps.pipe_mir_pool.p;
   // one wavefront more than slices where the instantiation has room: it collects the sums while the others multiply
   const int cwaves = K.rows == 2 ? ceil_div(ps.persist_waves, 2) : ps.persist_waves;  // wavefronts that own slices
-  pa.service = cwaves + ps.pipe_help_waves < ps.pipe_wmax ? 1 : 0;
+  pa.service = pipe_has_service(ps) ? 1 : 0;
+  if (K.ahead != (K.rows == 1 && !K.shard && !K.help && pa.service != 0)) return fail(FB_EINVAL, "internal: the resolved kernel's launch form is not this launch's");
   // values of the first streamed slots pulled into L2 during the neighbour wait: pays where the product is bandwidth-bound (9 and more
   // slices per CU: -6 % per iteration at 1M tets; neutral at 1,000 slices)
   pa.prefetch_slots = ps.persist_waves >= 9 ? (K.rows == 2 ? 3 : 4) : 0;
@@ -508,7 +528,8 @@ void print_pipe_timing(fb_fem_s* h) {
   std::vector<long long> tm((size_t)h->ps.persist_blocks * kPipeMaxWaves * kPipeTimingSlots);
   if (h->ps.persist_timing.download(tm.data(), tm.size(), h->stream) != FB_OK) return;
   (void)h->ps.persist_timing.zero(h->stream);
-  const char* names[5] = {"publish (drained)", "flag+wait+acquire", "product", "sums sweep", "recurrences(+refresh)"};
+  const bool ahead = h->ps.kernel && h->ps.kernel->ahead;  // (run-ahead form: a wavefront's own wait for the totals stands where the sweep's barrier stood)
+  const char* names[5] = {"publish (drained)", "flag+wait+acquire", "product", ahead ? "wait for the totals" : "sums sweep", "recurrences(+refresh)"};
   for (int k = 0; k < 5; k++) {
     double mn = 1e30, mx = 0, av = 0;
     int cnt = 0;

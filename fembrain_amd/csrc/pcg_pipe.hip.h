@@ -28,6 +28,30 @@
 // double-buffered by sequence parity the same way.  Every spin is bounded by the wall clock; on expiry an error word is
 // set, every other spin sees it, the launch drains WITHOUT writing any state back and the host re-solves with the
 // two-launch form (fb_step_info.pcg_path says so).
+//
+// Run-ahead form (round 8; the AHEAD instantiations, chosen per LAUNCH by the host for every launch with a service wavefront of an unsharded
+// handle without helpers -- never per wavefront: all wavefronts of a workgroup execute the same barriers).  The wavefronts of a workgroup
+// finish a product in tiers 1.7 us apart (oldest-first arbitration per SIMD), and the barrier behind the sums, which the data flow does
+// not need, made the fast ones wait for the slowest before any of them started its recurrences and publish stores.  The cross-workgroup
+// protocol above is untouched; inside the workgroup the service wavefront writes the totals and the failure word bc[0..2] and then
+// RELEASES (workgroup scope) a sequence word, bc[6], holding their `sums` number; a wavefront whose product is done ACQUIRES that word
+// until it holds the current number -- it normally does, the collection ran during the product -- reads the totals and goes on alone:
+// convergence test, recurrences, publish, its parts of the next gamma and delta into wsum, the drain of its stores.  The two barriers of
+// product() stay.  (An arrival counter in place of the first of them, so that only wavefront 0 waits for the drains, was measured and did
+// not pay: docs/HISTORY.md B.)
+// Hazards of the form.  The totals need no double buffer: the service wavefront writes iteration i+1's only behind the barrier that follows
+// the poll of product i+1, and every sibling reaches that barrier after it has read iteration i's.  The sequence word is set to the previous
+// launch's last `sums` number before the first product's barriers, the first wait for it lies behind them.  A publish overwrites the
+// buffer of two products ago: this wavefront is behind the barriers of the last product, so every producer (= consumer) of its rows had
+// flagged that product, and a flag follows a barrier of its workgroup behind the product before.  wsum is rewritten behind the barrier
+// that follows wavefront 0's read of it, bc[3] / bc[5] are read behind the barrier they are written in front of, as before.
+// Bounded waits, uniform exits.  Every decision to leave the solver loop is taken from values all wavefronts of the workgroup read alike:
+// the bits of gamma and bc[2] from the hand-over (done, a failed collection), bc[3] behind the poll's barrier (a failed wait for the
+// neighbours), and the count of iterations against n_iters (every wavefront counts the same iterations).  The siblings decide nothing on
+// their own: their wait for the totals has no clock because the service wavefront's collection has one and ALWAYS ends in a hand-over, of
+// totals or of failure, and the service wavefront meets no wait between the barrier behind the poll and its collection.  A wavefront that
+// leaves the loop executes no barrier any more, and no sibling waits at one for it: between the second barrier of a product and the exits
+// that follow it (the hand-over, the iteration count at the head of the loop) there is none, and every sibling takes the same exit.
 #pragma once
 #include "fem_kernels.h"
 #include "pcg_pipe_stream.hip.h"
@@ -396,7 +420,9 @@ namespace fb {
 // HELP: the instantiation with helper wavefronts (PipeArgs::tasks).  A template parameter, not a run-time test: with the helpers' second
 // copy of the streamed product compiled in, the kernel of the headline mesh -- which has none -- ran 3 % slower (16.2 against 15.7 us per
 // iteration on one box, tools/ab_r4 in round 5); with HELP = false nothing of it is there.
-template <typename MT, bool C16, int WMAX, int KLT, bool TIMING, bool SHARD, bool BJ = false, bool HELP = false, bool XYZ = false>
+// AHEAD: the run-ahead form of a launch with a service wavefront (header, "Run-ahead form"); the host picks it per launch (fem_persist.hip), so
+// the instantiations without it are what they were.
+template <typename MT, bool C16, int WMAX, int KLT, bool TIMING, bool SHARD, bool BJ = false, bool HELP = false, bool XYZ = false, bool AHEAD = false>
 __global__ __launch_bounds__(64 * WMAX) void k_pcg_pipe(SellView sv, const MT* __restrict__ vals, const MT* __restrict__ dlo,
                                                         const double* __restrict__ invdiag, const double* __restrict__ bvec, double* __restrict__ xg,
                                                         double* __restrict__ rg, double* __restrict__ wg, double* __restrict__ zg,
@@ -405,14 +431,19 @@ __global__ __launch_bounds__(64 * WMAX) void k_pcg_pipe(SellView sv, const MT* _
   static_assert(!SHARD || (!C16 && !TIMING), "a shard's columns are 32-bit local ids; the phase clocks are built for the unsharded kernel");
   static_assert(!BJ || (!SHARD && !TIMING), "block-Jacobi is for unsharded handles");
   static_assert(!HELP || (!SHARD && !BJ), "helper wavefronts: unsharded handles, the Jacobi preconditioner");
+  static_assert(!AHEAD || (!SHARD && !HELP), "run-ahead: unsharded handles without helper wavefronts (add_helpers needs the barrier)");
   static_assert(sizeof(MT) == 4, "k_pcg_pipe keeps part of the matrix in LDS as fp32 words and streams the rest as fp32");
   extern __shared__ double lds[];  // the request is padded so that one workgroup fills a CU
   double* wsum = lds;                          // [2][16] wave sums
   double* gath = lds + 32;                     // [2][kPipeMaxBlocks] all workgroups' sums
   double* bc = gath + 2 * kPipeMaxBlocks;      // [0..1] totals, [2] a wait failed (sweep), [3] a wait failed (product), [4] a sum poller gave up
+  unsigned int* const tot_seq = (unsigned int*)(bc + 6);  // (AHEAD) the `sums` number whose totals bc[0..2] hold, released by the service wavefront
   const int n_waves = blockDim.x >> 6, nb = gridDim.x;
   if (pa.start == 0 && st->done) return;  // grid-uniform: written by an earlier launch
   if (threadIdx.x == 0) bc[4] = 0.0;      // set by a sum poller that gave up (read after the next barrier)
+  if constexpr (AHEAD) {
+    if (threadIdx.x == 0) *tot_seq = pa.seqs[1];  // no totals of this launch yet (the first product's barriers lie before the first wait for them)
+  }
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   int first, count;
   if constexpr (SHARD) { first = sa.wg_range[blockIdx.x].x; count = sa.wg_range[blockIdx.x].y; }
@@ -871,10 +902,10 @@ __global__ __launch_bounds__(64 * WMAX) void k_pcg_pipe(SellView sv, const MT* _
     if constexpr (SHARD) {
       if (spare) shard_rank_sums(sa, BL, pa, sums, nb, lane, t_limit, bc, failed);
       __syncthreads();
-    } else if (pa.service) {
+    } else if (AHEAD || pa.service) {
       // A workgroup with a wavefront to spare (fewer slices than the instantiation's wavefronts) has its LAST wavefront -- no
       // slice, it idles through the product -- collect the sums meanwhile: same order of additions as below, so the same bits;
-      // the others find the totals behind ONE barrier.
+      // the others find the totals behind ONE barrier, or (AHEAD, the header's run-ahead form) each behind its own wait for their number.
       if (wv == n_waves - 1) {
         const long long t0 = wall_clock64();
         double t0s = 0, t1s = 0;
@@ -882,9 +913,16 @@ __global__ __launch_bounds__(64 * WMAX) void k_pcg_pipe(SellView sv, const MT* _
         failed = uniform_flag(failed);
         if (failed && lane == 0) st_sc1_u32(pa.error, 1u);
         t0s = wave_sum(t0s); t1s = wave_sum(t1s);
-        if (lane == 0) { bc[0] = t0s; bc[1] = t1s; bc[2] = (failed || ld_sc1_u32(pa.error) != 0u) ? 1.0 : 0.0; }
+        if (lane == 0) {
+          bc[0] = t0s; bc[1] = t1s; bc[2] = (failed || ld_sc1_u32(pa.error) != 0u) ? 1.0 : 0.0;
+          if constexpr (AHEAD) __hip_atomic_store(tot_seq, sums, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);  // totals or failure: always handed over
+        }
       }
-      __syncthreads();
+      if constexpr (AHEAD) {
+        while ((unsigned int)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(tot_seq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) != sums) __builtin_amdgcn_s_sleep(1);
+      } else {
+        __syncthreads();
+      }
     } else {
       const int pollers = min(n_waves, 4);
       if (wv < pollers) {
@@ -922,7 +960,7 @@ __global__ __launch_bounds__(64 * WMAX) void k_pcg_pipe(SellView sv, const MT* _
       }
       __syncthreads();
     }
-    lap(3);  // sweep of the sums
+    lap(3);  // sweep of the sums (AHEAD: this wavefront's own wait for the totals)
     if (uniform_flag(bc[2] != 0.0)) { failed = true; break; }  // a wait timed out somewhere: every workgroup leaves within one phase
     if constexpr (HELP) add_helpers(y);  // (every path of the sweep ends in a workgroup barrier: the helpers' sums of this product are in LDS)
     gamma = uniform_f64(bc[0]);
