@@ -1197,6 +1197,7 @@ int build(fb_fem_s* h, int n_nodes, const double* xyz, int n_tets, const int* te
           int rank, const int* splits, const DeviceTetMesh* dm = nullptr) {
   drop_graph(h);  // the buffers it refers to are about to be replaced
   h->surf.valid = false;  // a new mesh generation (fb_fem_surface)
+  h->stress.valid = false;  // (fb_fem_read_stress / fb_fem_surface_stress)
   SlackScope slack(handle_slack(h, n_nodes, n_tets));
   if (n_ranks == 1 && fixed != h->fixed_caller.data()) h->fixed_caller.assign(fixed, fixed + n_fixed);
   if (h->prm.matrix_precision == FB_MATRIX_AUTO) h->f64 = auto_matrix_f64(h, n_nodes, n_ranks);
@@ -1764,6 +1765,7 @@ int resync_delta(fb_fem_s* h, int n_removed, const int* removed, int n_changed, 
   SlackScope slack(handle_slack(h, n_new, nt_old - n_removed + n_added));
   drop_graph(h);
   h->surf.valid = false;  // a new mesh generation (fb_fem_surface)
+  h->stress.valid = false;  // (fb_fem_read_stress / fb_fem_surface_stress)
   if (fixed != h->fixed_caller.data()) h->fixed_caller.assign(fixed, fixed + n_fixed);
   if (device_src)
     FB_TRY(delta_upload_device(s, nt_old, n_removed, removed, n_added, reinterpret_cast<const int4*>(added), n_new_nodes, new_xyz, D, W));
@@ -2100,6 +2102,13 @@ void surface_fill(const SurfaceWork& S, const float* box, fb_fem_surface_info* o
   for (int k = 0; k < 3; k++) { out->aabb_lo[k] = box[k]; out->aabb_hi[k] = box[3 + k]; }
 }
 }  // namespace
+
+extern "C++" {
+namespace fb {  // for stress.hip
+int handle_slack_now(const fb_fem_s* h) { return handle_slack(h, h->plan.n_global, h->plan.n_tets); }
+int surface_current(fb_fem_s* h) { return surface_ready(h, false); }
+}  // namespace fb
+}  // extern "C++"
 
 int fb_fem_surface(fb_fem_t h, fb_fem_surface_info* out) {
   CHECK_HANDLE(h);

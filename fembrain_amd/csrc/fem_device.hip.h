@@ -3,6 +3,7 @@
 #include <type_traits>
 #include "fem_kernels.h"
 #include "p2p_device.hip.h"
+#include "tet_math.hip.h"
 
 namespace fb {
 
@@ -11,14 +12,6 @@ namespace fb {
 // and volume |det|/6 (tetMesh.cpp:184-188).  rest[16*e + 3*k + d] = b_k[d], rest[16*e + 12] = V,
 // rest[16*e + 13 + ...] unused.  One thread per tet.
 // ------------------------------------------------------------------------------------------------------
-__device__ inline void inv3x3(const double* A, double* I) {
-  const double c00 = A[4] * A[8] - A[5] * A[7], c01 = A[5] * A[6] - A[3] * A[8], c02 = A[3] * A[7] - A[4] * A[6];
-  const double id = 1.0 / (A[0] * c00 + A[1] * c01 + A[2] * c02);
-  I[0] = c00 * id; I[1] = (A[2] * A[7] - A[1] * A[8]) * id; I[2] = (A[1] * A[5] - A[2] * A[4]) * id;
-  I[3] = c01 * id; I[4] = (A[0] * A[8] - A[2] * A[6]) * id; I[5] = (A[2] * A[3] - A[0] * A[5]) * id;
-  I[6] = c02 * id; I[7] = (A[1] * A[6] - A[0] * A[7]) * id; I[8] = (A[0] * A[4] - A[1] * A[3]) * id;
-}
-
 // first_flat (may be null): receives the lowest index of an element whose rest volume is zero or not finite -- the check
 // build() otherwise makes on the host, same expression
 // volf (may be null): the rest volume as the fp32 records hold it, one float per element (k_mass_blocks gathers it: 4 MB at 1M tets
@@ -66,50 +59,6 @@ __global__ __launch_bounds__(kBlock) void k_tet_rest(int nt, const int4* __restr
   r[13] = r[14] = r[15] = 0.0;
 }
 
-// scaled-Newton polar decomposition of F (row-major), R out; returns last determinant
-// (vegafem polarDecomposition.cpp:37-108; the iteration is data dependent, capped for safety)
-__device__ inline double one_norm3(const double* A) {
-  return fmax(fmax(fabs(A[0]) + fabs(A[3]) + fabs(A[6]), fabs(A[1]) + fabs(A[4]) + fabs(A[7])), fabs(A[2]) + fabs(A[5]) + fabs(A[8]));
-}
-__device__ inline double inf_norm3(const double* A) {
-  return fmax(fmax(fabs(A[0]) + fabs(A[1]) + fabs(A[2]), fabs(A[3]) + fabs(A[4]) + fabs(A[5])), fabs(A[6]) + fabs(A[7]) + fabs(A[8]));
-}
-
-__device__ inline double polar_rotation(const double* F, double* R, double tol) {
-  double Mk[9], A[9];
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) Mk[3 * i + j] = F[3 * j + i];
-  double M1 = one_norm3(Mk), Mi = inf_norm3(Mk), det = 0.0, E1;
-  int guard = 0;
-  do {
-    A[0] = Mk[4] * Mk[8] - Mk[5] * Mk[7]; A[1] = Mk[5] * Mk[6] - Mk[3] * Mk[8]; A[2] = Mk[3] * Mk[7] - Mk[4] * Mk[6];
-    A[3] = Mk[7] * Mk[2] - Mk[8] * Mk[1]; A[4] = Mk[8] * Mk[0] - Mk[6] * Mk[2]; A[5] = Mk[6] * Mk[1] - Mk[7] * Mk[0];
-    A[6] = Mk[1] * Mk[5] - Mk[2] * Mk[4]; A[7] = Mk[2] * Mk[3] - Mk[0] * Mk[5]; A[8] = Mk[0] * Mk[4] - Mk[1] * Mk[3];
-    det = Mk[0] * A[0] + Mk[1] * A[1] + Mk[2] * A[2];
-    if (det == 0.0) break;
-    const double A1 = one_norm3(A), Ai = inf_norm3(A);
-    const double gamma = sqrt(sqrt((A1 * Ai) / (M1 * Mi)) / fabs(det));
-    const double g1 = gamma * 0.5, g2 = 0.5 / (gamma * det);
-    double Ek[9];
-#pragma unroll
-    for (int i = 0; i < 9; i++) {
-      Ek[i] = Mk[i];
-      Mk[i] = g1 * Mk[i] + g2 * A[i];
-      Ek[i] -= Mk[i];
-    }
-    E1 = one_norm3(Ek);
-    M1 = one_norm3(Mk);
-    Mi = inf_norm3(Mk);
-  } while (E1 > M1 * tol && ++guard < 64);
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) R[3 * i + j] = Mk[3 * j + i];
-  return det;
-}
-
 // ------------------------------------------------------------------------------------------------------
 // a3/a4 pass 1, one thread per tet: F = P M^-1, R = polar(F) (flipped if det < 0), rotated gradients
 // c_k = R b_k and the element force f_e = R K0 (R^T x - x0) in closed form
@@ -151,7 +100,6 @@ __device__ inline void k0_apply(const double b[4][3], double V, double lambda, d
 // without an element map launches the instantiations without it, whose code is what it was.
 // k_tet_warp<.., MAT> writes the id into the V lane of quarter 1 of the step record ((float)id is exact up to 255; quarter 0 keeps V):
 // the assembly kernels that hold the whole record anyway get the id without another gather.
-constexpr int kMaxMaterials = 256;
 template <typename MT>
 __device__ __forceinline__ int rec_mat_id(MT w) { return (int)w & (kMaxMaterials - 1); }
 

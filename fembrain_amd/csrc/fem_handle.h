@@ -1,5 +1,6 @@
 // The FEM handle (fb_fem_t of include/fembrain_hip.h) and what the units that work on it share: fem.hip (life cycle, assembly,
-// the two-launch solver, the C ABI), fem_persist.hip (the persistent solver's host side) and haptic.hip (the probe's entry points).
+// the two-launch solver, the C ABI), fem_persist.hip (the persistent solver's host side), haptic.hip (the probe's entry points) and
+// stress.hip (element stress and strain).
 // Internal: not installed, included by these units only.
 #pragma once
 #include "comm.h"
@@ -12,6 +13,7 @@
 #include "subdivide.h"
 #include "surface.h"
 #include "haptic.h"
+#include "stress.h"
 
 namespace fb {
 
@@ -180,6 +182,7 @@ struct fb_fem_s {
   CutWork cut;            // fb_fem_cut: the last cut's codes, edges, pieces and new nodes (fb_fem_read_cut)
   DevBuf<double> carry;   // fb_fem_cut, FB_CUT_CARRY: the state in the caller's order across the re-sync
   SurfaceWork surf;       // fb_fem_surface: the boundary of the current mesh (surface.h); empty until somebody asks
+  StressWork stress;      // fb_fem_stress: von Mises, energy density, J (and tensors) per element of the last call (stress.h); empty until somebody asks
   HapticWork hap;         // fb_fem_add_haptic_forces / pick / volume: level array and scratch (haptic.h); empty until somebody asks
   std::vector<int> fixed_caller;  // the constrained DOFs in the caller's numbering (unsharded): what fb_fem_cut keeps
   DevBuf<int4> tets_next, tets_caller;   // (the element list being built; swapped with `tets`)
@@ -290,6 +293,8 @@ struct ZeroBatch {   // (fem.hip, next to its kernel)
 
 // fem.hip
 int assemble_system(fb_fem_s* h);
+int handle_slack_now(const fb_fem_s* h);   // the slack rule of this handle's allocations at its current mesh (SlackScope)
+int surface_current(fb_fem_s* h);          // builds the surface where it is stale (fb_fem_surface_update's first step)
 
 // fem_persist.hip
 bool auto_matrix_f64(const fb_fem_s* h, int n_nodes, int n_ranks);

@@ -393,6 +393,54 @@ class FemIntegrator:
         _l.check(self._L.fb_fem_volume(self.h, C.byref(t), _l.dptr(pe)))
         return (t.value, pe) if per_element else t.value
 
+    # -- element stress and strain on the device (fb_fem_stress / read_stress / surface_stress; unsharded handles) --
+    def stress(self, world=False, tensors=False):
+        """Stress and strain of every element at the current state, kept on the device (fb_fem_stress): the bracket of the corotational
+        element force, sigma = lambda tr(H) I + mu (H + H^T) with the assembly's rotation.  Returns the summary: dict of n_elements, flags,
+        max_von_mises / max_element, min_J / min_J_element (of equal values the lowest element), n_inverted (J < 0) and energy
+        (sum of V psi).  ``tensors`` keeps the six-vectors (xx yy zz xy yz zx, tensor components) for ``element_stress``; ``world``
+        stores them rotated to the world frame instead of the element's rest frame."""
+        info = _l.StressInfo()
+        flags = (_l.FB_STRESS_WORLD if world else 0) | (_l.FB_STRESS_TENSORS if tensors else 0)
+        _l.check(self._L.fb_fem_stress(self.h, flags, C.byref(info)))
+        return {name: getattr(info, name) for name, _ in _l.StressInfo._fields_}
+
+    def element_stress(self, first=0, count=None, tensors=None):
+        """The arrays of the last ``stress()`` for elements first .. first + count - 1 (``read_mesh``'s element order): dict of
+        von_mises, energy_density, J (count,) and, where that call kept tensors, stress and strain (count, 6).  ``tensors=True`` asks
+        for the six-vectors and raises where they were not kept; False leaves them out.  Raises FbError(FB_EINVAL) when there is no
+        ``stress()`` of the current mesh."""
+        if count is None:
+            count = int(self._L.fb_fem_num_tets(self.h)) - int(first)
+        n = max(int(count), 0)
+        out = dict(von_mises=np.zeros(n), energy_density=np.zeros(n), J=np.zeros(n))
+        if tensors is None:  # whatever the last call kept: the library says (an empty range with a tensor pointer is refused where none were kept)
+            _l.check(self._L.fb_fem_read_stress(self.h, 0, 0, None, None, None, None, None))   # (no stress of this mesh: raise that)
+            probe = np.zeros(6)
+            tensors = self._L.fb_fem_read_stress(self.h, 0, 0, None, None, None, _l.dptr(probe), None) == _l.FB_OK
+        if tensors:
+            out["stress"], out["strain"] = np.zeros((n, 6)), np.zeros((n, 6))
+        _l.check(self._L.fb_fem_read_stress(self.h, int(first), int(count), _l.dptr(out["von_mises"]), _l.dptr(out["energy_density"]), _l.dptr(out["J"]),
+                                            _l.dptr(out.get("stress")), _l.dptr(out.get("strain"))))
+        return out
+
+    def surface_stress(self):
+        """(V,) float32: per surface vertex, in ``surface()['vertex_ids']`` order, the mean von Mises stress of the elements behind its
+        faces, from the last ``stress()`` (fb_fem_surface_stress) -- the colour to draw on ``surface_update()``'s vertices"""
+        info = _l.SurfaceInfo()
+        _l.check(self._L.fb_fem_read_stress(self.h, 0, 0, None, None, None, None, None))  # (stale: raise before the surface is built)
+        _l.check(self._L.fb_fem_surface(self.h, C.byref(info)))
+        vm = np.zeros(info.n_vertices, np.float32)
+        _l.check(self._L.fb_fem_surface_stress(self.h, _l.fptr(vm)))
+        return vm
+
+    def time_stress(self, reps=20, world=False, tensors=False):
+        """(seconds per stress(), seconds per surface_stress()): medians of ``reps`` HIP-event timings each (fb_fem_time_stress)"""
+        a, b = C.c_double(0), C.c_double(0)
+        flags = (_l.FB_STRESS_WORLD if world else 0) | (_l.FB_STRESS_TENSORS if tensors else 0)
+        _l.check(self._L.fb_fem_time_stress(self.h, reps, flags, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     # -- inspection (parity tests) --
     def num_tets(self):
         return self._L.fb_fem_num_tets(self.h)
@@ -630,6 +678,18 @@ class Deformable:
     def surface_mesh(self, update=False):
         """What the host draws: ``FemIntegrator.surface()``, or with ``update`` ``FemIntegrator.surface_update()``"""
         return self.integrator.surface_update() if update else self.integrator.surface()
+
+    def stress(self, world=False, tensors=False):
+        """``FemIntegrator.stress``: stress and strain of every element on the device, the summary returned"""
+        return self.integrator.stress(world=world, tensors=tensors)
+
+    def element_stress(self, first=0, count=None, tensors=None):
+        """``FemIntegrator.element_stress``"""
+        return self.integrator.element_stress(first, count, tensors)
+
+    def surface_stress(self):
+        """``FemIntegrator.surface_stress``: the per-vertex scalar to draw on ``surface_mesh(update=True)``"""
+        return self.integrator.surface_stress()
 
     def reset_deformations(self):
         self.integrator.reset_to_rest()

@@ -25,6 +25,7 @@ FB_CUT_NOTHING, FB_CUT_DONE, FB_CUT_UNHANDLED, FB_CUT_DRY = 0, 1, 2, 3
 FB_CUT_UNHANDLED_IDS = 64  # unhandled element ids fb_fem_read_cut returns at most (subdivide.h kCutUnhandledIds)
 FB_HAPTIC_MAX_SOURCES = 256  # sources fb_fem_add_haptic_forces takes in one call
 FB_MAX_MATERIALS = 256  # entries of a handle's material table (fb_fem_set_materials)
+FB_STRESS_WORLD, FB_STRESS_TENSORS = 1, 2  # fb_fem_stress flags
 
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
@@ -60,6 +61,11 @@ class CutResult(C.Structure):
 
 class SurfaceInfo(C.Structure):
     _fields_ = [("n_faces", C.c_int), ("n_vertices", C.c_int), ("n_builds", C.c_int), ("aabb_lo", C.c_float * 3), ("aabb_hi", C.c_float * 3)]
+
+
+class StressInfo(C.Structure):
+    _fields_ = [("n_elements", C.c_int), ("flags", C.c_int), ("max_von_mises", C.c_double), ("max_element", C.c_int), ("min_J", C.c_double),
+                ("min_J_element", C.c_int), ("n_inverted", C.c_int), ("energy", C.c_double)]
 
 
 class PolyCounts(C.Structure):
@@ -156,6 +162,10 @@ def lib():
         "fb_fem_pick_vertex": (C.c_int, [vp, _dp, _ip, _dp, _dp]),
         "fb_fem_pick_box": (C.c_int, [vp, _dp, _dp, C.c_int, _ip, _dp, _ip]),
         "fb_fem_volume": (C.c_int, [vp, _dp, _dp]),
+        "fb_fem_stress": (C.c_int, [vp, C.c_int, C.POINTER(StressInfo)]),
+        "fb_fem_read_stress": (C.c_int, [vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+        "fb_fem_surface_stress": (C.c_int, [vp, _fp]),
+        "fb_fem_time_stress": (C.c_int, [vp, C.c_int, C.c_int, _dp, _dp]),
         "fb_fem_num_nodes": (C.c_int, [vp]),
         "fb_fem_num_tets": (C.c_int, [vp]),
         "fb_fem_num_blocks": (C.c_int, [vp]),

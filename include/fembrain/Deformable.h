@@ -167,6 +167,21 @@ class HipIntegrator {
     check(fb_fem_volume(h_, &total, perElement));
     return total;
   }
+  // Element stress and strain on the device (fembrain_hip.h): von Mises stress, energy density and J of every element at the current
+  // state stay on the device, `out` brings the summary.  flags: FB_STRESS_WORLD | FB_STRESS_TENSORS.
+  void ComputeStress(int flags, fb_fem_stress_info* out) { check(fb_fem_stress(h_, flags, out)); }
+  // the arrays of the last ComputeStress for elements first .. first + count - 1; any pointer may be null (stress6 / strain6: 6 per element)
+  void ReadStress(int first, int count, double* vonMises, double* energyDensity, double* J, double* stress6 = nullptr, double* strain6 = nullptr) {
+    check(fb_fem_read_stress(h_, first, count, vonMises, energyDensity, J, stress6, strain6));
+  }
+  // per surface vertex (fb_fem_read_surface's vertex order) the mean von Mises stress of the elements behind its faces
+  void SurfaceStress(std::vector<float>& vonMises) {
+    fb_fem_surface_info info;
+    check(fb_fem_read_stress(h_, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr));  // (no stress of this mesh: throw before the surface is built)
+    check(fb_fem_surface(h_, &info));
+    vonMises.assign((size_t)info.n_vertices, 0.0f);
+    check(fb_fem_surface_stress(h_, vonMises.data()));
+  }
   void RebuildElements() { check(fb_fem_rebuild_elements(h_)); }
   void Resync(int numVertices, const double* rest, int numElements, const int* elements, int nFixed, const int* fixed) {
     mass_.clear(); bptr_.clear(); bcol_.clear();
@@ -523,6 +538,21 @@ class Deformable {
     rec.xpElementType = "TET"; rec.xpForceModel = "COROTATIONAL LINEAR FEM"; rec.xpIntegrator = "JACOBI PRECONDITIONED CG";
     rec.xpModelName = m_strModelName;
   }
+  // Stress of every element at the current state, on the device (HipIntegrator::ComputeStress): returns the summary -- the largest
+  // von Mises stress and its element, the smallest J and its element, the inverted elements, the strain energy.  The per-element arrays
+  // stay on the device for readStress / surfaceStress until the mesh changes (cut, syncForceModel).
+  fb_fem_stress_info computeStress(bool worldFrame = false, bool keepTensors = false) {
+    fb_fem_stress_info info;
+    m_lpIntegrator->ComputeStress((worldFrame ? FB_STRESS_WORLD : 0) | (keepTensors ? FB_STRESS_TENSORS : 0), &info);
+    return info;
+  }
+  // von Mises stress of every element of the last computeStress, in countCells() order
+  void readStress(std::vector<double>& vonMises) {
+    vonMises.assign((size_t)fb_fem_num_tets(m_lpIntegrator->handle()), 0.0);
+    m_lpIntegrator->ReadStress(0, (int)vonMises.size(), vonMises.data(), nullptr, nullptr);
+  }
+  // the colour of the drawn surface: one float per vertex of surfaceMesh(), the mean von Mises stress behind its faces
+  void surfaceStress(std::vector<float>& vonMises) { m_lpIntegrator->SurfaceStress(vonMises); }
   void resetDeformations() { m_lpIntegrator->ResetToRest(); m_vHapticForces.clear(); }
   void setDeformCallback(FOnApplyDeformations fOnDeform) { m_fOnDeform = fOnDeform; }
   double getSolverTime() const { return m_lpIntegrator->GetSystemSolveTime(); }

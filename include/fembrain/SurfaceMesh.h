@@ -55,6 +55,16 @@ class SurfaceMesh {
     HipIntegrator::check(fb_fem_surface_update(m_lpIntegrator->handle(), m_xyz.data(), m_normals.data(), &info));
     setBox(info);
   }
+  // The scalar to draw on the vertices: mean von Mises stress behind each vertex's faces (fb_fem_surface_stress), from the last
+  // HipIntegrator::ComputeStress / Deformable::computeStress of the current mesh; throws where there is none.  vertexStressAt(i) goes
+  // with vertexAt(i).
+  const std::vector<float>& applyStress() {
+    sync();
+    m_lpIntegrator->SurfaceStress(m_stress);
+    return m_stress;
+  }
+  float vertexStressAt(U32 idx) const { return m_stress[idx]; }
+  const std::vector<float>& vertexStress() const { return m_stress; }
   void updateAABB() { applyDisplacements(); }  // (SurfaceMesh.cpp:354-373: the box travels with the positions)
   vec3d aabbLower() { sync(); return m_lo; }
   vec3d aabbUpper() { sync(); return m_hi; }
@@ -101,7 +111,7 @@ class SurfaceMesh {
   int m_builds;
   bool m_stale;
   std::vector<int> m_faces, m_compact, m_faceTets, m_ids;
-  std::vector<float> m_xyz, m_normals;
+  std::vector<float> m_xyz, m_normals, m_stress;
   vec3d m_lo, m_hi;
 };
 

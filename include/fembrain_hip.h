@@ -419,6 +419,51 @@ int fb_fem_pick_box(fb_fem_t h, const double lo[3], const double hi[3], int capa
  * the same bits from call to call, within n_tets * 2^-53 * total of any other order. */
 int fb_fem_volume(fb_fem_t h, double* total, double* per_element);
 
+/* ---- Element stress and strain, on the device ----
+ * The bracket of the corotational element force f_e,i = V R [lambda tr(H) I + mu (H + H^T)] b_i, which the assembly forms every step
+ * (E B (R^T x - x0) of corotationalLinearFEM.cpp:107-137, 270-286) and does not keep.  Unsharded handles only (FB_EINVAL otherwise, as
+ * fb_fem_read_mesh), device- or host-built plan alike, renumbered or not: elements keep the caller's order.  A handle that never calls
+ * these allocates and launches nothing extra.
+ *
+ * For element e: b_k and V are its rest record (shape-function gradients, rest volume); P_k = x0 + q of its nodes; F = sum_k P_k b_k^T,
+ * evaluated as the assembly evaluates it; (lambda_e, mu_e) what the next assembly would use -- the handle's E / nu, or the table entry
+ * of the element's material where a map exists, fb_fem_set_internal_force_scaling folded in.  R = I on a handle created with linear != 0;
+ * otherwise the rotation of the assembly's polar decomposition of F (same routine, tolerance 1e-6), negated when its determinant is
+ * negative.  H = sum_j (R^T P_j - X_j) b_j^T, evaluated as (R^T - I) + R^T sum_j q_j b_j^T (the b_j sum to zero and sum_j X_j b_j^T = I), which keeps
+ * the rounding of x0 + q away from the gradients of a flat element; strain = (H + H^T) / 2, stress = lambda_e tr(H) I + mu_e (H + H^T).  Six-vectors are
+ * xx, yy, zz, xy, yz, zx -- the row order of the reference's B -- and hold TENSOR components: strain_xy is half the engineering shear
+ * B produces.  von Mises = sqrt(((sxx-syy)^2 + (syy-szz)^2 + (szz-sxx)^2) / 2 + 3 (sxy^2 + syz^2 + szx^2)); energy density
+ * psi = stress : strain / 2; J = det F by the plain cofactor expansion; an element is inverted when J < 0.  The tensors are in the
+ * element's rest frame, the one the force model works in; with FB_STRESS_WORLD both are stored as R (.) R^T. */
+#define FB_STRESS_WORLD   1   /* tensors rotated to the world frame */
+#define FB_STRESS_TENSORS 2   /* keep stress6 / strain6 per element (96 B per element more) */
+typedef struct fb_fem_stress_info {
+  int n_elements, flags;
+  double max_von_mises; int max_element;   /* of equal maxima the lowest element */
+  double min_J;         int min_J_element; /* likewise */
+  int n_inverted;
+  double energy;        /* sum of V_e psi_e */
+} fb_fem_stress_info;
+/* Computes on the handle's stream from the current q.  von Mises, psi and J stay on the device per element, the tensors only with
+ * FB_STRESS_TENSORS.  One copy of sizeof(fb_fem_stress_info) leaves the device.  Unknown flag bits return FB_EINVAL and change nothing.
+ * No floating-point atomics: maxima and minima are lexicographic (value, element) folds over per-workgroup partials, `energy` is summed
+ * in fb_fem_volume's fixed tree, which depends on the element count alone -- the same bits from call to call and under either numbering.
+ * A mesh without elements gives zeros and elements -1. */
+int fb_fem_stress(fb_fem_t h, int flags, fb_fem_stress_info* out);
+/* The arrays of the last fb_fem_stress, elements first .. first + count - 1 in fb_fem_read_mesh's element order; any pointer may be
+ * NULL.  stress6 / strain6: 6 doubles per element.  FB_EINVAL (text in fb_last_error) when there is no fb_fem_stress of the current
+ * mesh (none yet, or the mesh changed since: fb_fem_resync, fb_fem_resync_delta, a fb_fem_cut returning FB_CUT_DONE), when the range
+ * is bad, or when a tensor is asked for and the last call did not keep tensors. */
+int fb_fem_read_stress(fb_fem_t h, int first, int count, double* von_mises, double* energy_density, double* J, double* stress6, double* strain6);
+/* For every surface vertex, in fb_fem_read_surface's vertex_ids order: (float) of the mean von Mises stress of the elements behind the
+ * vertex's faces (face_tets) -- an fp64 sum over the vertex's faces in ascending face order, divided by their number.  Builds the
+ * surface first where it is stale, as fb_fem_surface_update does; FB_EINVAL when there is no stress of the current mesh.  One copy of
+ * 4 n_vertices bytes leaves the device. */
+int fb_fem_surface_stress(fb_fem_t h, float* von_mises);
+/* Medians of `reps` HIP-event timings of fb_fem_stress(flags) and of fb_fem_surface_stress, copies included; either pointer may be
+ * NULL.  Leaves the handle as a fb_fem_stress(flags) call does. */
+int fb_fem_time_stress(fb_fem_t h, int reps, int flags, double* seconds_elements, double* seconds_surface);
+
 /* ---- inspection entry points (what the parity tests compare against the oracle) ---- */
 int fb_fem_num_nodes(fb_fem_t h);   /* global */
 int fb_fem_num_tets(fb_fem_t h);    /* local (all for an unsharded handle) */
