@@ -5,19 +5,15 @@
 #include <cstring>
 #include <vector>
 
-#include <rocprim/rocprim.hpp>
-
-#include "common.h"
 #include "delta.h"
+#include "device_prims.hip.h"
 #include "fem_plan.h"
+#include "launch.hip.h"
 
 namespace fb {
 namespace {
 
-constexpr int kB = 256;
-
 inline int pad4(int x) { return (x + 3) & ~3; }
-inline dim3 grid_for(long long n) { return dim3((unsigned)std::max<long long>(1, (n + kB - 1) / kB)); }
 
 __global__ __launch_bounds__(kB) void k_delta_mark(int n_removed, const int* __restrict__ removed, int n_changed, const int* __restrict__ changed, unsigned char* __restrict__ estate) {
   const int i = blockIdx.x * kB + threadIdx.x;
@@ -535,12 +531,6 @@ __global__ __launch_bounds__(kB) void k_max_width(int n_slices, const int* __res
   if ((threadIdx.x & 63) == 0 && w > 0) atomicMax(out, w);
 }
 
-int bits_of(long long n) {
-  int b = 1;
-  while ((1LL << b) < n) b++;
-  return b;
-}
-
 // the 16 pairs of every changed and added element, ascending in the new element id (changed ones keep an id below every added one), then
 // the markers of the new nodes; key = new row << 32 | new column
 __global__ __launch_bounds__(kB) void k_delta_new_pairs(int n_changed, int n_added, int n_new_nodes, int n_kept, int n_nodes_old, const int* __restrict__ changed_ids,
@@ -609,46 +599,31 @@ static int delta_mark(hipStream_t s, int n_tets_old, MeshDelta& D, PlanWorkspace
   const int n_removed = D.n_removed, n_changed = D.n_changed;
   FB_TRY(D.estate.reserve((size_t)n_tets_old + 1));
   FB_HIP(hipMemsetAsync(D.estate.p, 0, (size_t)n_tets_old + 1, s));
-  if (n_removed + n_changed) {
-    hipLaunchKernelGGL(k_delta_mark, grid_for(n_removed + n_changed), dim3(kB), 0, s, n_removed, D.removed, n_changed, D.changed_ids, D.estate.p);
-    FB_HIP(hipGetLastError());
-  }
+  if (n_removed + n_changed) FB_TRY(launch_1d(k_delta_mark, n_removed + n_changed, s, n_removed, D.removed, n_changed, D.changed_ids, D.estate.p));
   FB_TRY(D.pos.reserve((size_t)n_tets_old + 1));
   const auto stays = rocprim::make_transform_iterator(static_cast<const unsigned char*>(D.estate.p), Stays());
-  size_t bytes = 0;
-  FB_HIP(rocprim::exclusive_scan(nullptr, bytes, stays, D.pos.p, 0, (size_t)n_tets_old, rocprim::plus<int>(), s));
-  FB_TRY(W.temp.reserve(std::max<size_t>(bytes, 16)));
-  FB_HIP(rocprim::exclusive_scan(W.temp.p, bytes, stays, D.pos.p, 0, (size_t)n_tets_old, rocprim::plus<int>(), s));
-  return FB_OK;
+  return exclusive_scan(W.temp, s, stays, D.pos.p, 0, (size_t)n_tets_old);
 }
 
 int delta_relabel_nodes(hipStream_t s, MeshDelta& D, int n_nodes, const int* map) {
   // (changed_nodes and added lie back to back in the staging buffer)
   const int n = D.n_changed + D.n_added;
   if (n == 0) return FB_OK;
-  hipLaunchKernelGGL(k_delta_relabel, grid_for(n), dim3(kB), 0, s, n, D.changed_nodes, n_nodes, map);
-  FB_HIP(hipGetLastError());
-  return FB_OK;
+  return launch_1d(k_delta_relabel, n, s, n, D.changed_nodes, n_nodes, map);
 }
 
 int delta_tets(hipStream_t s, const MeshDelta& D, const int4* tets_old, const int* imap, int4* tets_new) {
-  hipLaunchKernelGGL(k_delta_tets, grid_for(D.n_tets_old), dim3(kB), 0, s, D.n_tets_old, tets_old, D.estate.p, D.pos.p, imap, D.n_changed, D.changed_ids, D.changed_nodes, tets_new);
-  FB_HIP(hipGetLastError());
+  FB_TRY(launch_1d(k_delta_tets, D.n_tets_old, s, D.n_tets_old, tets_old, D.estate.p, D.pos.p, imap, D.n_changed, D.changed_ids, D.changed_nodes, tets_new));
   if (D.n_added) FB_HIP(hipMemcpyAsync(tets_new + D.n_kept, D.added, sizeof(int4) * (size_t)D.n_added, hipMemcpyDeviceToDevice, s));
   return FB_OK;
 }
 
 int delta_element_bytes(hipStream_t s, const MeshDelta& D, const unsigned char* ids_old, unsigned char* ids_new, int n_parents, const int* parents, const int* piece_off,
                         const int* piece_cnt) {
-  if (D.n_tets_old > 0) {
-    hipLaunchKernelGGL(k_delta_bytes, grid_for(D.n_tets_old), dim3(kB), 0, s, D.n_tets_old, D.estate.p, D.pos.p, ids_old, ids_new);
-    FB_HIP(hipGetLastError());
-  }
+  if (D.n_tets_old > 0) FB_TRY(launch_1d(k_delta_bytes, D.n_tets_old, s, D.n_tets_old, D.estate.p, D.pos.p, ids_old, ids_new));
   if (D.n_added) FB_HIP(hipMemsetAsync(ids_new + D.n_kept, 0, (size_t)D.n_added, s));
-  if (D.n_added && n_parents > 0) {
-    hipLaunchKernelGGL(k_delta_piece_bytes, grid_for(n_parents), dim3(kB), 0, s, n_parents, parents, piece_off, piece_cnt, D.n_tets_old, D.n_added, ids_old, ids_new + D.n_kept);
-    FB_HIP(hipGetLastError());
-  }
+  if (D.n_added && n_parents > 0)
+    FB_TRY(launch_1d(k_delta_piece_bytes, n_parents, s, n_parents, parents, piece_off, piece_cnt, D.n_tets_old, D.n_added, ids_old, ids_new + D.n_kept));
   return FB_OK;
 }
 
@@ -665,47 +640,34 @@ int delta_node_order(hipStream_t s, MeshDelta& D, int n_old, const SlabKeyGeom& 
   FB_TRY(D.nv.reserve((size_t)std::max(1, n_new)));
   FB_TRY(D.nvs.reserve((size_t)std::max(1, n_new)));
   if (n_new) {
-    hipLaunchKernelGGL(k_delta_keys, grid_for(n_new), dim3(kB), 0, s, n_new, D.new_xyz.p, g, D.nk.p, D.nv.p);
-    FB_HIP(hipGetLastError());
+    FB_TRY(launch_1d(k_delta_keys, n_new, s, n_new, D.new_xyz.p, g, D.nk.p, D.nv.p));
     unsigned key_bits = (unsigned)(g.bits[0] + g.bits[1] + g.bits[2]);
     if (n_windows > 0) {  // the order has the second stage: keys_old are its keys, and the new nodes get theirs
       FB_TRY(D.new_count.reserve((size_t)n_new));
       FB_HIP(hipMemsetAsync(D.new_count.p, 0, sizeof(int) * (size_t)n_new, s));
       const int n_el = D.n_changed + D.n_added;   // (changed_nodes and added lie back to back, still in the caller's ids)
-      if (n_el) hipLaunchKernelGGL(k_delta_new_counts, grid_for(n_el), dim3(kB), 0, s, n_el, D.changed_nodes, n_old, D.new_count.p);
-      hipLaunchKernelGGL(k_delta_sigma_keys, grid_for(n_new), dim3(kB), 0, s, n_new, D.new_count.p, n_windows, win_keys, D.nk.p);
-      FB_HIP(hipGetLastError());
+      if (n_el) FB_TRY(launch_1d(k_delta_new_counts, n_el, s, n_el, D.changed_nodes, n_old, D.new_count.p));
+      FB_TRY(launch_1d(k_delta_sigma_keys, n_new, s, n_new, D.new_count.p, n_windows, win_keys, D.nk.p));
       key_bits = 10;
       while ((1LL << (key_bits - 10)) < n_windows) key_bits++;
     }
-    size_t bytes = 0;
-    FB_HIP(rocprim::radix_sort_pairs(nullptr, bytes, D.nk.p, D.nks.p, D.nv.p, D.nvs.p, (size_t)n_new, 0u, key_bits, s));
-    FB_TRY(W.temp.reserve(std::max<size_t>(bytes, 16)));
-    FB_HIP(rocprim::radix_sort_pairs(W.temp.p, bytes, D.nk.p, D.nks.p, D.nv.p, D.nvs.p, (size_t)n_new, 0u, key_bits, s));
+    FB_TRY(sort_pairs(W.temp, s, D.nk.p, D.nks.p, D.nv.p, D.nvs.p, (size_t)n_new, key_bits));
   }
-  hipLaunchKernelGGL(k_delta_imap, grid_for(n_old), dim3(kB), 0, s, n_old, keys_old, n_new, D.nks.p, old_of_new_old, D.imap.p, D.node_keys.p, old_of_new.p, new_of_old.p);
-  FB_HIP(hipGetLastError());
-  if (n_new) {
-    hipLaunchKernelGGL(k_delta_newint, grid_for(n_new), dim3(kB), 0, s, n_new, D.nks.p, D.nvs.p, n_old, keys_old, D.newint.p, D.node_keys.p, old_of_new.p, new_of_old.p);
-    FB_HIP(hipGetLastError());
-  }
+  FB_TRY(launch_1d(k_delta_imap, n_old, s, n_old, keys_old, n_new, D.nks.p, old_of_new_old, D.imap.p, D.node_keys.p, old_of_new.p, new_of_old.p));
+  if (n_new) FB_TRY(launch_1d(k_delta_newint, n_new, s, n_new, D.nks.p, D.nvs.p, n_old, keys_old, D.newint.p, D.node_keys.p, old_of_new.p, new_of_old.p));
   D.mapped = true;
   return FB_OK;
 }
 
 int delta_positions(hipStream_t s, const MeshDelta& D, int n_old, const double* x0_old, double* x0_new) {
-  hipLaunchKernelGGL(k_delta_positions, grid_for(3LL * (n_old + D.n_new_nodes)), dim3(kB), 0, s, n_old, D.n_new_nodes, x0_old, D.new_xyz.p, D.mapped ? D.imap.p : nullptr,
-                     D.mapped ? D.newint.p : nullptr, x0_new);
-  FB_HIP(hipGetLastError());
-  return FB_OK;
+  return launch_1d(k_delta_positions, 3LL * (n_old + D.n_new_nodes), s, n_old, D.n_new_nodes, x0_old, D.new_xyz.p, D.mapped ? D.imap.p : nullptr, D.mapped ? D.newint.p : nullptr,
+                   x0_new);
 }
 
 int delta_reserve(hipStream_t s, MeshDelta& D, PlanWorkspace& W, long long n_fresh) {
   const size_t n = (size_t)std::max<long long>(1, n_fresh);
   FB_TRY(D.nk.reserve(n)); FB_TRY(D.nks.reserve(n)); FB_TRY(D.nv.reserve(n)); FB_TRY(D.nvs.reserve(n));
-  size_t bytes = 0;
-  FB_HIP(rocprim::radix_sort_pairs(nullptr, bytes, D.nk.p, D.nks.p, D.nv.p, D.nvs.p, n, 0u, 64u, s));
-  return W.temp.reserve(std::max<size_t>(bytes, 16));
+  return sort_pairs(W.temp, s, D.nk.p, D.nks.p, D.nv.p, D.nvs.p, n, 64u, /*run=*/false);
 }
 
 int delta_plan(hipStream_t s, MeshDelta& D, const OldPlanArrays& O, const int4* tets_old, const int4* tets_new, int n_new, DevicePlan& out, PlanWorkspace& W) {
@@ -719,22 +681,17 @@ int delta_plan(hipStream_t s, MeshDelta& D, const OldPlanArrays& O, const int4* 
   FB_TRY(D.nv.reserve((size_t)std::max<long long>(1, n_fresh)));
   FB_TRY(D.nvs.reserve((size_t)std::max<long long>(1, n_fresh)));
   if (n_fresh > 0) {
-    hipLaunchKernelGGL(k_delta_new_pairs, grid_for(n_fresh), dim3(kB), 0, s, D.n_changed, D.n_added, D.n_new_nodes, D.n_kept, n_old, D.changed_ids, D.pos.p, tets_new,
-                       D.mapped ? D.newint.p : nullptr, D.nk.p, D.nv.p);
-    FB_HIP(hipGetLastError());
-    const unsigned key_bits = 32u + (unsigned)bits_of(n_new);
-    size_t bytes = 0;
-    FB_HIP(rocprim::radix_sort_pairs(nullptr, bytes, D.nk.p, D.nks.p, D.nv.p, D.nvs.p, (size_t)n_fresh, 0u, key_bits, s));
-    FB_TRY(W.temp.reserve(std::max<size_t>(bytes, 16)));
-    FB_HIP(rocprim::radix_sort_pairs(W.temp.p, bytes, D.nk.p, D.nks.p, D.nv.p, D.nvs.p, (size_t)n_fresh, 0u, key_bits, s));
+    FB_TRY(launch_1d(k_delta_new_pairs, n_fresh, s, D.n_changed, D.n_added, D.n_new_nodes, D.n_kept, n_old, D.changed_ids, D.pos.p, tets_new, D.mapped ? D.newint.p : nullptr,
+                     D.nk.p, D.nv.p));
+    FB_TRY(sort_pairs(W.temp, s, D.nk.p, D.nks.p, D.nv.p, D.nvs.p, (size_t)n_fresh, 32u + (unsigned)bits_of(n_new)));
   }
   // 2. element ids, row map, touched rows
   FB_TRY(D.newid.reserve((size_t)D.n_tets_old + 1));
-  hipLaunchKernelGGL(k_newid, grid_for(D.n_tets_old), dim3(kB), 0, s, D.n_tets_old, D.estate.p, D.pos.p, D.newid.p);
+  FB_TRY(launch_1d(k_newid, D.n_tets_old, s, D.n_tets_old, D.estate.p, D.pos.p, D.newid.p));
   const bool mapped = D.mapped && D.n_new_nodes > 0;
   if (mapped) {
     FB_TRY(D.oldrow.reserve((size_t)n_new));
-    hipLaunchKernelGGL(k_oldrow, grid_for(n_new), dim3(kB), 0, s, n_old, D.n_new_nodes, D.imap.p, D.newint.p, D.oldrow.p);
+    FB_TRY(launch_1d(k_oldrow, n_new, s, n_old, D.n_new_nodes, D.imap.p, D.newint.p, D.oldrow.p));
   }
   // one buffer, one fill: the number of touched rows | a word per row | an int2 per row (its fresh entries) | the list of touched rows
   const size_t tw = ((size_t)n_new + 4) & ~(size_t)1;
@@ -744,25 +701,20 @@ int delta_plan(hipStream_t s, MeshDelta& D, const OldPlanArrays& O, const int4* 
   int2* frow = reinterpret_cast<int2*>(D.touched.p + 2 + tw);
   int* tlist = reinterpret_cast<int*>(D.touched.p) + 2 + tw + 2 * (size_t)n_new + 2;
   const int n_gone = D.n_removed + D.n_changed;
-  if (n_fresh + n_gone > 0) {
-    hipLaunchKernelGGL(k_touch, grid_for(n_fresh + 4LL * n_gone), dim3(kB), 0, s, (int)n_fresh, D.nks.p, n_gone, D.removed, D.n_removed, D.changed_ids, tets_old,
-                       mapped ? D.imap.p : nullptr, touched, frow, tlist, reinterpret_cast<int*>(D.touched.p));
-  }
-  FB_HIP(hipGetLastError());
+  if (n_fresh + n_gone > 0)
+    FB_TRY(launch_1d(k_touch, n_fresh + 4LL * n_gone, s, (int)n_fresh, D.nks.p, n_gone, D.removed, D.n_removed, D.changed_ids, tets_old, mapped ? D.imap.p : nullptr, touched, frow,
+                     tlist, reinterpret_cast<int*>(D.touched.p)));
   OldPlan C = {O.bptr, O.bcol, O.ucnt, O.slice_off, O.slot_coff, O.contrib, n_old};
   FreshPairs F = {D.nks.p, D.nvs.p, (int)n_fresh, frow};
   RowMaps M = {mapped ? D.oldrow.p : nullptr, mapped ? D.imap.p : nullptr, D.newid.p, touched, n_old, tlist, reinterpret_cast<const int*>(D.touched.p)};
   const dim3 touched_grid(1024);  // (4,096 wavefronts take the touched rows from the list in turn)
   // 3. the pattern: row lengths, their scan, the blocks
   FB_TRY(D.len.reserve((size_t)n_new + 1));
-  hipLaunchKernelGGL(k_row_len, grid_for(n_new + 1), dim3(kB), 0, s, n_new, C, M, D.len.p);
+  FB_TRY(launch_1d(k_row_len, n_new + 1, s, n_new, C, M, D.len.p));
   hipLaunchKernelGGL(k_row_len_touched, touched_grid, dim3(kB), 0, s, C, F, M, D.len.p);
   FB_HIP(hipGetLastError());
   FB_TRY(out.bptr->alloc((size_t)n_new + 1));
-  size_t bytes = 0;
-  FB_HIP(rocprim::exclusive_scan(nullptr, bytes, D.len.p, out.bptr->p, 0, (size_t)n_new + 1, rocprim::plus<int>(), s));
-  FB_TRY(W.temp.reserve(std::max<size_t>(bytes, 16)));
-  FB_HIP(rocprim::exclusive_scan(W.temp.p, bytes, D.len.p, out.bptr->p, 0, (size_t)n_new + 1, rocprim::plus<int>(), s));
+  FB_TRY(exclusive_scan(W.temp, s, D.len.p, out.bptr->p, 0, (size_t)n_new + 1));
   int nb = 0;
   FB_TRY(out.bptr->download(&nb, 1, s, (size_t)n_new));
   out.n_blocks = nb;
@@ -770,7 +722,7 @@ int delta_plan(hipStream_t s, MeshDelta& D, const OldPlanArrays& O, const int4* 
   FB_TRY(out.blk_slot->alloc((size_t)std::max(1, nb)));
   FB_TRY(out.ucnt_keep->alloc((size_t)std::max(1, nb)));
   FB_TRY(D.src.reserve((size_t)std::max(1, nb)));
-  hipLaunchKernelGGL(k_row_blocks, dim3((unsigned)(((n_new + 63) / 64 + kB / 64 - 1) / (kB / 64))), dim3(kB), 0, s, n_new, C, M, out.bptr->p, out.bcol->p, out.ucnt_keep->p, D.src.p);
+  FB_TRY(launch_waves(k_row_blocks, (n_new + 63) / 64, s, n_new, C, M, out.bptr->p, out.bcol->p, out.ucnt_keep->p, D.src.p));
   hipLaunchKernelGGL(k_row_blocks_touched, touched_grid, dim3(kB), 0, s, C, F, M, out.bptr->p, out.bcol->p, out.ucnt_keep->p, D.src.p);
   FB_HIP(hipGetLastError());
   // 4. SELL layout, slot table, list heights and offsets: the second half of the builder, on the new pattern
@@ -778,9 +730,8 @@ int delta_plan(hipStream_t s, MeshDelta& D, const OldPlanArrays& O, const int4* 
   // 5. the contribution table from the old one
   FB_TRY(out.contrib->alloc(std::max<size_t>(1, (size_t)out.n_crows * kSliceRows)));
   FB_TRY(D.slot_slice.reserve((size_t)std::max(1, out.n_slots)));
-  hipLaunchKernelGGL(k_slot_slices, dim3((unsigned)std::max(1, (out.n_slices + kB / 64 - 1) / (kB / 64))), dim3(kB), 0, s, out.n_slices, out.slice_off->p, D.slot_slice.p);
-  hipLaunchKernelGGL(k_table_plain, dim3((unsigned)std::max(1, (out.n_slots + kB / 64 - 1) / (kB / 64))), dim3(kB), 0, s, n_new, out.n_slots, C, M, out.slice_off->p, D.slot_slice.p,
-                     out.slot_coff->p, out.contrib->p);
+  FB_TRY(launch_waves(k_slot_slices, out.n_slices, s, out.n_slices, out.slice_off->p, D.slot_slice.p));
+  FB_TRY(launch_waves(k_table_plain, out.n_slots, s, n_new, out.n_slots, C, M, out.slice_off->p, D.slot_slice.p, out.slot_coff->p, out.contrib->p));
   hipLaunchKernelGGL(k_table_touched, touched_grid, dim3(kB), 0, s, n_new, C, F, M, out.bptr->p, out.bcol->p, out.ucnt_keep->p, D.src.p, out.slice_off->p, out.slot_coff->p,
                      out.contrib->p);
   FB_HIP(hipGetLastError());

@@ -21,11 +21,11 @@
 
 #include "fem_handle.h"
 #include "haptic.h"
+#include "launch.hip.h"
 
 namespace fb {
 namespace {
 
-constexpr int kB = 256;
 constexpr int kWaves = kB / 64;
 inline int blocks_for(int n) { return std::max(1, ceil_div(n, kB)); }
 
@@ -289,20 +289,17 @@ int haptic_spread(hipStream_t s, HapticWork& H, int n_nodes, int n_tets, const i
   const double* d_f3 = reinterpret_cast<const double*>(H.args.p);
   const double* d_mag = d_f3 + 3 * (size_t)n;
   const int* d_ids = reinterpret_cast<const int*>(H.args.p + sizeof(double) * n_dbl);
-  hipLaunchKernelGGL(k_hap_direct, dim3(blocks_for(n)), dim3(kB), 0, s, n, d_ids, d_f3, new_of_old, n_nodes, fext);
-  FB_HIP(hipGetLastError());
+  FB_TRY(launch_1d(k_hap_direct, n, s, n, d_ids, d_f3, new_of_old, n_nodes, fext));
   if (size <= 1 || n_tets <= 0) return FB_OK;
   for (int base = 0; base < n; base += kHapticBatch) {  // ascending: the order of every node's additions
     const int nb = std::min(kHapticBatch, n - base);
     FB_HIP(hipMemsetAsync(H.level.p, 0xFF, (size_t)nb * n_nodes, s));
-    hipLaunchKernelGGL(k_hap_seed, dim3(blocks_for(nb)), dim3(kB), 0, s, nb, d_ids + base, new_of_old, n_nodes, H.level.p);
-    FB_HIP(hipGetLastError());
+    FB_TRY(launch_1d(k_hap_seed, nb, s, nb, d_ids + base, new_of_old, n_nodes, H.level.p));
     for (int j = 1; j < size; j++) {
       hipLaunchKernelGGL(k_hap_ring, dim3(blocks_for(n_tets), nb), dim3(kB), 0, s, n_tets, tets, n_nodes, j, H.level.p);
       FB_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_hap_apply, dim3(blocks_for(n_nodes)), dim3(kB), 0, s, n_nodes, nb, size, H.level.p, d_f3 + 3 * (size_t)base, d_mag, fext);
-    FB_HIP(hipGetLastError());
+    FB_TRY(launch_1d(k_hap_apply, n_nodes, s, n_nodes, nb, size, H.level.p, d_f3 + 3 * (size_t)base, d_mag, fext));
   }
   return FB_OK;
 }

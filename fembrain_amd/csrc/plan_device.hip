@@ -23,16 +23,13 @@
 #include <chrono>
 #include <cstring>
 
-#include <rocprim/rocprim.hpp>
-
-#include "common.h"
+#include "device_prims.hip.h"
 #include "fem_plan.h"
+#include "launch.hip.h"
 #include "plan_device.h"
 
 namespace fb {
 namespace {
-
-constexpr int kB = 256;
 
 // rows [0, n_rows) of local ids are matrix rows; a pair whose row is a halo node gets the row value n_rows and so sorts behind
 // every real pair.  The column part of the key is the GLOBAL id (node_lo + c for an owned column, halo[c - n_rows] otherwise;
@@ -486,15 +483,11 @@ int device_partition(hipStream_t s, int n_tets, DevBuf<int4>& tets, int n_global
   FB_HIP(hipMemcpyAsync(W.splits.p, splits.data(), sizeof(int) * (n_ranks + 1), hipMemcpyHostToDevice, s));
   FB_HIP(hipMemsetAsync(W.nodeflag.p, 0, (size_t)n_global, s));
   FB_HIP(hipMemsetAsync(W.sendmask.p, 0, sizeof(unsigned long long) * (size_t)n_owned, s));
-  hipLaunchKernelGGL(k_part_mark, dim3((n_tets + kB - 1) / kB), dim3(kB), 0, s, n_tets, tets.p, n_global, node_lo, n_owned, W.splits.p, n_ranks, W.nodeflag.p,
-                     W.sendmask.p, W.keep.p, d_cnt);
-  FB_HIP(hipGetLastError());
+  FB_TRY(launch_1d(k_part_mark, n_tets, s, n_tets, tets.p, n_global, node_lo, n_owned, W.splits.p, n_ranks, W.nodeflag.p, W.sendmask.p, W.keep.p, d_cnt));
   // halo = the marked nodes, ascending
   int* d_count = W.picked.p + std::max(n_global, n_owned);
-  size_t bytes = 0;
-  FB_HIP(rocprim::select(nullptr, bytes, rocprim::counting_iterator<int>(0), W.nodeflag.p, W.picked.p, d_count, (size_t)n_global, s));
-  FB_TRY(W.temp.reserve(std::max<size_t>(bytes, 16)));
-  FB_HIP(rocprim::select(W.temp.p, bytes, rocprim::counting_iterator<int>(0), W.nodeflag.p, W.picked.p, d_count, (size_t)n_global, s));
+  const rocprim::counting_iterator<int> ids(0);
+  FB_TRY(select_flagged(W.temp, s, ids, W.nodeflag.p, W.picked.p, d_count, (size_t)n_global));
   int n_halo = 0;
   FB_HIP(hipMemcpyAsync(&cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, s));
   FB_HIP(hipMemcpyAsync(&n_halo, d_count, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -514,14 +507,8 @@ int device_partition(hipStream_t s, int n_tets, DevBuf<int4>& tets, int n_global
     FB_TRY(W.tetsel.reserve((size_t)out.n_kept));
     FB_TRY(W.idsel.reserve((size_t)out.n_kept + 4));
     int* d_n = W.idsel.p + out.n_kept;
-    bytes = 0;
-    FB_HIP(rocprim::select(nullptr, bytes, tets.p, W.keep.p, W.tetsel.p, d_n, (size_t)n_tets, s));
-    FB_TRY(W.temp.reserve(std::max<size_t>(bytes, 16)));
-    FB_HIP(rocprim::select(W.temp.p, bytes, tets.p, W.keep.p, W.tetsel.p, d_n, (size_t)n_tets, s));
-    bytes = 0;
-    FB_HIP(rocprim::select(nullptr, bytes, rocprim::counting_iterator<int>(0), W.keep.p, W.idsel.p, d_n, (size_t)n_tets, s));
-    FB_TRY(W.temp.reserve(std::max<size_t>(bytes, 16)));
-    FB_HIP(rocprim::select(W.temp.p, bytes, rocprim::counting_iterator<int>(0), W.keep.p, W.idsel.p, d_n, (size_t)n_tets, s));
+    FB_TRY(select_flagged(W.temp, s, tets.p, W.keep.p, W.tetsel.p, d_n, (size_t)n_tets));
+    FB_TRY(select_flagged(W.temp, s, ids, W.keep.p, W.idsel.p, d_n, (size_t)n_tets));
     out.tet_global.resize((size_t)out.n_kept);
     FB_HIP(hipMemcpyAsync(out.tet_global.data(), W.idsel.p, sizeof(int) * (size_t)out.n_kept, hipMemcpyDeviceToHost, s));
     FB_HIP(hipStreamSynchronize(s));
@@ -532,8 +519,7 @@ int device_partition(hipStream_t s, int n_tets, DevBuf<int4>& tets, int n_global
   out.halo.resize((size_t)n_halo);
   if (n_halo) FB_HIP(hipMemcpyAsync(out.halo.data(), W.picked.p, sizeof(int) * (size_t)n_halo, hipMemcpyDeviceToHost, s));
   // local numbering of the elements while the halo list is still in W.picked
-  hipLaunchKernelGGL(k_part_local, dim3((n_tets + kB - 1) / kB), dim3(kB), 0, s, n_tets, d_tets, node_lo, n_owned, W.picked.p, n_halo);
-  FB_HIP(hipGetLastError());
+  FB_TRY(launch_1d(k_part_local, n_tets, s, n_tets, d_tets, node_lo, n_owned, W.picked.p, n_halo));
   FB_HIP(hipStreamSynchronize(s));
   // send lists: the neighbours are the owners of the halo nodes (a rank that wants my nodes owns nodes of the same elements)
   out.send_off.assign((size_t)n_ranks + 1, 0);
@@ -548,10 +534,7 @@ int device_partition(hipStream_t s, int n_tets, DevBuf<int4>& tets, int n_global
   for (int q = 0; q < n_ranks; q++) {
     if (neighbour[q]) {
       WantedBy pred = {W.sendmask.p, q};
-      size_t b2 = 0;
-      FB_HIP(rocprim::select(nullptr, b2, rocprim::counting_iterator<int>(0), W.picked.p, d_count, (size_t)n_owned, pred, s));
-      FB_TRY(W.temp.reserve(std::max<size_t>(b2, 16)));
-      FB_HIP(rocprim::select(W.temp.p, b2, rocprim::counting_iterator<int>(0), W.picked.p, d_count, (size_t)n_owned, pred, s));
+      FB_TRY(select_if(W.temp, s, ids, W.picked.p, d_count, (size_t)n_owned, pred));
       int n_send = 0;
       FB_HIP(hipMemcpyAsync(&n_send, d_count, sizeof(int), hipMemcpyDeviceToHost, s));
       FB_HIP(hipStreamSynchronize(s));
@@ -569,21 +552,14 @@ int build_incidence_device(hipStream_t s, int n_slices, int n_owned, const int* 
                            const uint32_t* contrib, const int4* tets, DevBuf<int>& inc_off, DevBuf<uint32_t>& inc, DevBuf<uint32_t>& inc_slot, PlanWorkspace& W, bool ascending_columns) {
   FB_TRY(W.width.reserve((size_t)n_slices + 1));
   FB_HIP(hipMemsetAsync(W.width.p, 0, sizeof(int) * ((size_t)n_slices + 1), s));
-  const dim3 sg((unsigned)((n_slices + kB / 64 - 1) / (kB / 64)));
-  hipLaunchKernelGGL(k_inc_heights, sg, dim3(kB), 0, s, n_slices, n_owned, slice_off, colidx, slot_coff, slot_ccnt, contrib, W.width.p);
-  FB_HIP(hipGetLastError());
+  FB_TRY(launch_waves(k_inc_heights, n_slices, s, n_slices, n_owned, slice_off, colidx, slot_coff, slot_ccnt, contrib, W.width.p));
   FB_TRY(inc_off.alloc((size_t)n_slices + 1));
-  size_t bytes = 0;
-  FB_HIP(rocprim::exclusive_scan(nullptr, bytes, W.width.p, inc_off.p, 0, (size_t)n_slices + 1, rocprim::plus<int>(), s));
-  FB_TRY(W.temp.reserve(std::max<size_t>(bytes, 16)));
-  FB_HIP(rocprim::exclusive_scan(W.temp.p, bytes, W.width.p, inc_off.p, 0, (size_t)n_slices + 1, rocprim::plus<int>(), s));
+  FB_TRY(exclusive_scan(W.temp, s, W.width.p, inc_off.p, 0, (size_t)n_slices + 1));
   int rows = 0;
   FB_TRY(inc_off.download(&rows, 1, s, (size_t)n_slices));
   FB_TRY(inc.alloc(std::max<size_t>(1, (size_t)rows * 64)));
   FB_TRY(inc_slot.alloc(std::max<size_t>(1, (size_t)rows * 64)));
-  hipLaunchKernelGGL(k_inc_fill, sg, dim3(kB), 0, s, n_slices, n_owned, slice_off, colidx, slot_coff, slot_ccnt, contrib, tets, inc_off.p, inc.p, inc_slot.p, ascending_columns ? 1 : 0);
-  FB_HIP(hipGetLastError());
-  return FB_OK;
+  return launch_waves(k_inc_fill, n_slices, s, n_slices, n_owned, slice_off, colidx, slot_coff, slot_ccnt, contrib, tets, inc_off.p, inc.p, inc_slot.p, ascending_columns ? 1 : 0);
 }
 
 static int plan_from_sorted(hipStream_t s, int n_nodes, long long n_pairs, long long n_valid, bool narrow, int cb32, int span, const PairGeom& geom, const PlanShard* shard,
@@ -596,7 +572,6 @@ int build_plan_device(hipStream_t s, int n_nodes_local, int n_tets, const int4* 
   if (n_pairs >= (1LL << 31)) return fail(FB_EINVAL, "mesh too large for the device plan builder (%lld pairs)", n_pairs);
   DevBuf<unsigned long long>&keys = W.keys, &keys_s = W.keys_s;
   DevBuf<uint32_t>&vals = W.vals, &vals_s = W.vals_s;
-  DevBuf<char>& temp = W.temp;
   FB_TRY(W.flags.reserve(2));
   FB_TRY(keys.reserve((size_t)n_pairs));
   FB_TRY(keys_s.reserve((size_t)n_pairs));
@@ -604,17 +579,14 @@ int build_plan_device(hipStream_t s, int n_nodes_local, int n_tets, const int4* 
   FB_TRY(vals_s.reserve((size_t)n_pairs));
   PairGeom geom;
   geom.n_rows = n_nodes; geom.node_lo = shard ? shard->node_lo : 0; geom.halo = shard ? shard->d_halo : nullptr;
-  geom.col_bits = 1;
-  while ((1LL << geom.col_bits) < (shard ? shard->n_global : n_nodes)) geom.col_bits++;
-  int row_bits = 1;
-  while ((1LL << row_bits) < (long long)n_nodes + (shard ? 1 : 0)) row_bits++;  // a shard needs the row value n_rows for the dropped pairs
+  geom.col_bits = bits_of(shard ? shard->n_global : n_nodes);
+  const int row_bits = bits_of((long long)n_nodes + (shard ? 1 : 0));  // a shard needs the row value n_rows for the dropped pairs
   if (row_bits + geom.col_bits > 63) return fail(FB_EINVAL, "mesh too large for the device plan builder's sort key");
   const long long n_valid = shard ? shard->n_pairs : n_pairs;  // pairs that belong to a row
   // 32-bit keys where the mesh is banded enough (see k_plan_pairs32)
   int cb32 = 1;
   while (span >= 0 && cb32 < 31 && (1LL << cb32) < 2LL * span + 1) cb32++;
-  int rb32 = 1;
-  while ((1LL << rb32) < (long long)n_nodes) rb32++;
+  const int rb32 = bits_of(n_nodes);
   const bool narrow = !shard && span >= 0 && span < n_nodes && rb32 + cb32 <= 32 && !(getenv("FEMBRAIN_PLAN_KEYS64") && atoi(getenv("FEMBRAIN_PLAN_KEYS64")) != 0);
   const int init[2] = {0x7fffffff, 0};  // [0] lowest tet with a bad node id, [1] "a column difference does not fit 16 bits"
   const int none = init[0];
@@ -622,25 +594,16 @@ int build_plan_device(hipStream_t s, int n_nodes_local, int n_tets, const int4* 
   struct { int* p; } bad = {W.flags.p};
   unsigned int* keys32 = reinterpret_cast<unsigned int*>(keys.p);
   unsigned int* keys32_s = reinterpret_cast<unsigned int*>(keys_s.p);
-  if (narrow) hipLaunchKernelGGL(k_plan_pairs32, dim3((unsigned)((n_pairs + kB - 1) / kB)), dim3(kB), 0, s, n_tets, n_nodes_local, cb32, span, d_tets, keys32, vals.p, bad.p);
-  else hipLaunchKernelGGL(k_plan_pairs, dim3((unsigned)((n_pairs + kB - 1) / kB)), dim3(kB), 0, s, n_tets, n_nodes_local, geom, d_tets, keys.p, vals.p, bad.p);
-  FB_HIP(hipGetLastError());
+  if (narrow) FB_TRY(launch_1d(k_plan_pairs32, n_pairs, s, n_tets, n_nodes_local, cb32, span, d_tets, keys32, vals.p, bad.p));
+  else FB_TRY(launch_1d(k_plan_pairs, n_pairs, s, n_tets, n_nodes_local, geom, d_tets, keys.p, vals.p, bad.p));
   int first_bad = none;
   FB_HIP(hipMemcpyAsync(&first_bad, bad.p, sizeof(int), hipMemcpyDeviceToHost, s));
   FB_HIP(hipStreamSynchronize(s));
   D.first_bad_tet = first_bad == none ? -1 : first_bad;
   if (D.first_bad_tet >= 0) return fail(FB_EINVAL, "tet %d references a node outside [0,%d)", D.first_bad_tet, n_nodes_local);
-  size_t bytes = 0;
   const unsigned key_bits = narrow ? (unsigned)(rb32 + cb32) : (unsigned)(row_bits + geom.col_bits);
-  if (narrow) {
-    FB_HIP(rocprim::radix_sort_pairs(nullptr, bytes, keys32, keys32_s, vals.p, vals_s.p, (size_t)n_pairs, 0u, key_bits, s));
-    FB_TRY(temp.reserve(std::max<size_t>(bytes, 16)));
-    FB_HIP(rocprim::radix_sort_pairs(temp.p, bytes, keys32, keys32_s, vals.p, vals_s.p, (size_t)n_pairs, 0u, key_bits, s));
-  } else {
-    FB_HIP(rocprim::radix_sort_pairs(nullptr, bytes, keys.p, keys_s.p, vals.p, vals_s.p, (size_t)n_pairs, 0u, key_bits, s));
-    FB_TRY(temp.reserve(std::max<size_t>(bytes, 16)));
-    FB_HIP(rocprim::radix_sort_pairs(temp.p, bytes, keys.p, keys_s.p, vals.p, vals_s.p, (size_t)n_pairs, 0u, key_bits, s));
-  }
+  if (narrow) FB_TRY(sort_pairs(W.temp, s, keys32, keys32_s, vals.p, vals_s.p, (size_t)n_pairs, key_bits));
+  else FB_TRY(sort_pairs(W.temp, s, keys.p, keys_s.p, vals.p, vals_s.p, (size_t)n_pairs, key_bits));
   return plan_from_sorted(s, n_nodes, n_pairs, n_valid, narrow, cb32, span, geom, shard, D, W);
 }
 
@@ -650,9 +613,7 @@ static int plan_from_sorted(hipStream_t s, int n_nodes, long long n_pairs, long 
   DevBuf<unsigned long long>&keys_s = W.keys_s, &ukeys = W.ukeys;
   DevBuf<uint32_t>& vals_s = W.vals_s;
   DevBuf<unsigned int>&ucnt = W.ucnt, &cstart = W.cstart, &nruns = W.nruns;
-  DevBuf<char>& temp = W.temp;
   unsigned int* keys32_s = reinterpret_cast<unsigned int*>(keys_s.p);
-  size_t bytes = 0;
   static const bool timing = getenv("FEMBRAIN_TIMING") && atoi(getenv("FEMBRAIN_TIMING")) >= 2;  // development aid: the stages, each synchronised
   const auto t0 = std::chrono::steady_clock::now();
   auto lap = [&](const char* what) {
@@ -665,36 +626,21 @@ static int plan_from_sorted(hipStream_t s, int n_nodes, long long n_pairs, long 
   FB_TRY(ucnt.reserve((size_t)n_pairs));
   FB_TRY(nruns.reserve(1));
   unsigned int* ukeys32 = reinterpret_cast<unsigned int*>(ukeys.p);
-  if (narrow) {
-    bytes = 0;  // blocks = runs of equal keys
-    FB_HIP(rocprim::run_length_encode(nullptr, bytes, keys32_s, (unsigned int)n_valid, ukeys32, ucnt.p, nruns.p, s));
-    FB_TRY(temp.reserve(std::max<size_t>(bytes, 16)));
-    FB_HIP(rocprim::run_length_encode(temp.p, bytes, keys32_s, (unsigned int)n_valid, ukeys32, ucnt.p, nruns.p, s));
-  } else {
-    bytes = 0;  // blocks = runs of equal keys
-    FB_HIP(rocprim::run_length_encode(nullptr, bytes, keys_s.p, (unsigned int)n_valid, ukeys.p, ucnt.p, nruns.p, s));
-    FB_TRY(temp.reserve(std::max<size_t>(bytes, 16)));
-    FB_HIP(rocprim::run_length_encode(temp.p, bytes, keys_s.p, (unsigned int)n_valid, ukeys.p, ucnt.p, nruns.p, s));
-  }
+  // blocks = runs of equal keys
+  if (narrow) FB_TRY(run_length_encode(W.temp, s, keys32_s, (unsigned int)n_valid, ukeys32, ucnt.p, nruns.p));
+  else FB_TRY(run_length_encode(W.temp, s, keys_s.p, (unsigned int)n_valid, ukeys.p, ucnt.p, nruns.p));
   unsigned int nb = 0;
   FB_TRY(nruns.download(&nb, 1, s));
   lap("run-length encoding");
   D.n_blocks = (int)nb;
   FB_TRY(cstart.reserve((size_t)nb));
-  bytes = 0;
-  FB_HIP(rocprim::exclusive_scan(nullptr, bytes, ucnt.p, cstart.p, 0u, (size_t)nb, rocprim::plus<unsigned int>(), s));
-  FB_TRY(temp.reserve(std::max<size_t>(bytes, 16)));
-  FB_HIP(rocprim::exclusive_scan(temp.p, bytes, ucnt.p, cstart.p, 0u, (size_t)nb, rocprim::plus<unsigned int>(), s));
+  FB_TRY(exclusive_scan(W.temp, s, ucnt.p, cstart.p, 0u, (size_t)nb));
   FB_TRY(D.bptr->alloc((size_t)n_nodes + 1));
   FB_TRY(D.bcol->alloc((size_t)nb));
   FB_TRY(D.blk_slot->alloc((size_t)nb));
-  if (narrow)
-    hipLaunchKernelGGL(k_plan_rows32, dim3((unsigned)((std::max<long long>(nb, n_nodes + 1) + kB - 1) / kB)), dim3(kB), 0, s, n_nodes, (int)nb, cb32, span, ukeys32, D.bptr->p,
-                       D.bcol->p);
-  else
-    hipLaunchKernelGGL(k_plan_rows, dim3((unsigned)((std::max<long long>(nb, n_nodes + 1) + kB - 1) / kB)), dim3(kB), 0, s, n_nodes, (int)nb, geom, shard ? shard->n_halo : 0, ukeys.p,
-                       D.bptr->p, D.bcol->p);
-  FB_HIP(hipGetLastError());
+  const long long n_rows_or_blocks = std::max<long long>(nb, n_nodes + 1);
+  if (narrow) FB_TRY(launch_1d(k_plan_rows32, n_rows_or_blocks, s, n_nodes, (int)nb, cb32, span, ukeys32, D.bptr->p, D.bcol->p));
+  else FB_TRY(launch_1d(k_plan_rows, n_rows_or_blocks, s, n_nodes, (int)nb, geom, shard ? shard->n_halo : 0, ukeys.p, D.bptr->p, D.bcol->p));
   lap("block rows");
   if (D.ucnt_keep) {  // (the pairs of every block, kept with the pattern: fb_fem_resync_delta updates the plan from the plan, delta.hip)
     FB_TRY(D.ucnt_keep->alloc((size_t)nb));
@@ -704,18 +650,17 @@ static int plan_from_sorted(hipStream_t s, int n_nodes, long long n_pairs, long 
   lap("SELL layout and slot offsets");
   FB_TRY(D.contrib->alloc(std::max<size_t>(1, (size_t)D.n_crows * kSliceRows)));
   const int n_slices = D.n_slices;
-  const dim3 sg((unsigned)((n_slices + kB / 64 - 1) / (kB / 64)));
   const bool direct = getenv("FEMBRAIN_PLAN_CONTRIB") && !strcmp(getenv("FEMBRAIN_PLAN_CONTRIB"), "direct");  // development aid: the round-1 kernel
   if (direct) {
-    hipLaunchKernelGGL(k_plan_contrib, sg, dim3(kB), 0, s, n_nodes, n_slices, D.bptr->p, D.bcol->p, ucnt.p, cstart.p, vals_s.p, D.slice_off->p, D.slot_coff->p,
-                       D.slot_ccnt->p, D.contrib->p);
+    FB_TRY(launch_waves(k_plan_contrib, n_slices, s, n_nodes, n_slices, D.bptr->p, D.bcol->p, ucnt.p, cstart.p, vals_s.p, D.slice_off->p, D.slot_coff->p, D.slot_ccnt->p,
+                        D.contrib->p));
   } else {
     constexpr int kSegCap = 10240;  // words: 40 KB of LDS per workgroup, four workgroups per CU
     FB_HIP(hipFuncSetAttribute((const void*)k_plan_contrib_lds, hipFuncAttributeMaxDynamicSharedMemorySize, kSegCap * (int)sizeof(uint32_t)));
     hipLaunchKernelGGL(k_plan_contrib_lds, dim3((unsigned)std::max(1, n_slices)), dim3(kB), kSegCap * sizeof(uint32_t), s, n_nodes, n_slices, D.bptr->p, D.bcol->p, ucnt.p, cstart.p,
                        vals_s.p, D.slice_off->p, D.slot_coff->p, D.slot_ccnt->p, D.contrib->p, kSegCap);
+    FB_HIP(hipGetLastError());
   }
-  FB_HIP(hipGetLastError());
   // (no wait here: the workspace and the plan's buffers outlive the kernel; the caller's next stages queue behind it)
   lap("contribution table");
   return FB_OK;
@@ -725,22 +670,15 @@ static int plan_from_sorted(hipStream_t s, int n_nodes, long long n_pairs, long 
 // includes its marker): slice_off, colidx, blk_slot, coldelta, slot_ccnt, slot_coff; n_slices, n_slots, n_crows, max_width, deltas_fit16.
 int plan_layout_from_csr(hipStream_t s, int n_nodes, const unsigned int* ucnt, bool shard, DevicePlan& D, PlanWorkspace& W) {
   DevBuf<int>& width = W.width;
-  DevBuf<char>& temp = W.temp;
-  size_t bytes = 0;
   FB_TRY(W.flags.reserve(2));
   // SELL-64
   const int n_slices = (n_nodes + kSliceRows - 1) / kSliceRows;
   D.n_slices = n_slices;
-  const dim3 sg((unsigned)((n_slices + kB / 64 - 1) / (kB / 64)));
   FB_TRY(width.reserve((size_t)n_slices + 1));
   FB_HIP(hipMemsetAsync(width.p, 0, sizeof(int) * ((size_t)n_slices + 1), s));
-  hipLaunchKernelGGL(k_plan_widths, sg, dim3(kB), 0, s, n_nodes, n_slices, D.bptr->p, width.p);
-  FB_HIP(hipGetLastError());
+  FB_TRY(launch_waves(k_plan_widths, n_slices, s, n_nodes, n_slices, D.bptr->p, width.p));
   FB_TRY(D.slice_off->alloc((size_t)n_slices + 1));
-  bytes = 0;
-  FB_HIP(rocprim::exclusive_scan(nullptr, bytes, width.p, D.slice_off->p, 0, (size_t)n_slices + 1, rocprim::plus<int>(), s));
-  FB_TRY(temp.reserve(std::max<size_t>(bytes, 16)));
-  FB_HIP(rocprim::exclusive_scan(temp.p, bytes, width.p, D.slice_off->p, 0, (size_t)n_slices + 1, rocprim::plus<int>(), s));
+  FB_TRY(exclusive_scan(W.temp, s, width.p, D.slice_off->p, 0, (size_t)n_slices + 1));
   D.slice_off_host.resize((size_t)n_slices + 1);
   FB_TRY(D.slice_off->download(D.slice_off_host.data(), (size_t)n_slices + 1, s));
   D.n_slots = D.slice_off_host[n_slices];
@@ -752,13 +690,9 @@ int plan_layout_from_csr(hipStream_t s, int n_nodes, const unsigned int* ucnt, b
   if (shard && D.halo_base) FB_TRY(D.halo_base->alloc((size_t)std::max(1, n_slices)));
   struct { int* p; } wide = {W.flags.p + 1};
   FB_HIP(hipMemsetAsync(wide.p, 0, sizeof(int), s));
-  hipLaunchKernelGGL(k_plan_sell, sg, dim3(kB), 0, s, n_nodes, n_slices, D.bptr->p, D.bcol->p, ucnt, D.slice_off->p, D.colidx->p, D.blk_slot->p,
-                     D.slot_ccnt->p, D.coldelta->p, wide.p, (shard && D.halo_base) ? D.halo_base->p : nullptr);
-  FB_HIP(hipGetLastError());
-  bytes = 0;
-  FB_HIP(rocprim::exclusive_scan(nullptr, bytes, D.slot_ccnt->p, D.slot_coff->p, 0, (size_t)D.n_slots + 1, rocprim::plus<int>(), s));
-  FB_TRY(temp.reserve(std::max<size_t>(bytes, 16)));
-  FB_HIP(rocprim::exclusive_scan(temp.p, bytes, D.slot_ccnt->p, D.slot_coff->p, 0, (size_t)D.n_slots + 1, rocprim::plus<int>(), s));
+  FB_TRY(launch_waves(k_plan_sell, n_slices, s, n_nodes, n_slices, D.bptr->p, D.bcol->p, ucnt, D.slice_off->p, D.colidx->p, D.blk_slot->p, D.slot_ccnt->p, D.coldelta->p, wide.p,
+                      (shard && D.halo_base) ? D.halo_base->p : nullptr));
+  FB_TRY(exclusive_scan(W.temp, s, D.slot_ccnt->p, D.slot_coff->p, 0, (size_t)D.n_slots + 1));
   int crows = 0, w = 0;  // (one wait for both)
   FB_HIP(hipMemcpyAsync(&w, wide.p, sizeof(int), hipMemcpyDeviceToHost, s));
   FB_HIP(hipMemcpyAsync(&crows, D.slot_coff->p + D.n_slots, sizeof(int), hipMemcpyDeviceToHost, s));

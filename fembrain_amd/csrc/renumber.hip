@@ -7,14 +7,13 @@
 #include <cmath>
 #include <numeric>
 
-#include <rocprim/rocprim.hpp>
-
+#include "device_prims.hip.h"
+#include "launch.hip.h"
 #include "renumber.h"
 
 namespace fb {
 namespace {
 
-constexpr int kB = 256;
 constexpr int kBoxBlocks = 64;
 
 __device__ __forceinline__ double wave_min_d(double v) {
@@ -172,12 +171,6 @@ bool sigma_wanted(int n_nodes, long long padded, long long used) {
   return n_nodes >= kRenumberMinNodes && padded > 0 && 10 * (padded - used) > padded;  // (small meshes are all surface, and no one waits for them)
 }
 
-int bits_for(long long cells) {  // bits that hold the cell indices 0 .. cells - 1
-  int b = 1;
-  while ((1LL << b) < cells) b++;
-  return b;
-}
-
 }  // namespace
 
 bool slab_key_geometry(int n_nodes, const double lo[3], const double hi[3], SlabKeyGeom* out) {
@@ -201,7 +194,7 @@ bool slab_key_geometry(int n_nodes, const double lo[3], const double hi[3], Slab
   for (;;) {
     int total = 0;
     for (int a = 0; a < 3; a++) {
-      out->bits[a] = bits_for((long long)(ext[ax[a]] / h + 0.5) + 2);
+      out->bits[a] = bits_of((long long)(ext[ax[a]] / h + 0.5) + 2);
       total += out->bits[a];
     }
     if (total <= 62) break;
@@ -257,14 +250,8 @@ int renumber_build(hipStream_t s, int mode, int n_nodes, int n_tets, const int4*
   FB_TRY(W.keys_s.reserve((size_t)n_nodes));
   FB_TRY(W.vals.reserve((size_t)n_nodes));
   FB_TRY(W.vals_s.reserve((size_t)n_nodes));
-  const dim3 ng((unsigned)((n_nodes + kB - 1) / kB));
-  hipLaunchKernelGGL(k_slab_keys, ng, dim3(kB), 0, s, n_nodes, d_xyz, g, W.keys.p, W.vals.p);
-  FB_HIP(hipGetLastError());
-  const unsigned key_bits = (unsigned)(g.bits[0] + g.bits[1] + g.bits[2]);
-  size_t bytes = 0;
-  FB_HIP(rocprim::radix_sort_pairs(nullptr, bytes, W.keys.p, W.keys_s.p, W.vals.p, W.vals_s.p, (size_t)n_nodes, 0u, key_bits, s));
-  FB_TRY(W.temp.reserve(std::max<size_t>(bytes, 16)));
-  FB_HIP(rocprim::radix_sort_pairs(W.temp.p, bytes, W.keys.p, W.keys_s.p, W.vals.p, W.vals_s.p, (size_t)n_nodes, 0u, key_bits, s));
+  FB_TRY(launch_1d(k_slab_keys, n_nodes, s, n_nodes, d_xyz, g, W.keys.p, W.vals.p));
+  FB_TRY(sort_pairs(W.temp, s, W.keys.p, W.keys_s.p, W.vals.p, W.vals_s.p, (size_t)n_nodes, (unsigned)(g.bits[0] + g.bits[1] + g.bits[2])));
   // second stage (renumber.h: sigma_window): would the slab order pad the matrix by more than a tenth?
   R.sigma = false;
   R.n_windows = 0;
@@ -272,11 +259,10 @@ int renumber_build(hipStream_t s, int mode, int n_nodes, int n_tets, const int4*
     const int n_slices = (n_nodes + 63) / 64;
     FB_TRY(R.d_count.alloc((size_t)n_nodes));
     FB_TRY(R.d_count.zero(s));
-    hipLaunchKernelGGL(k_incident_count, dim3((unsigned)((n_tets + kB - 1) / kB)), dim3(kB), 0, s, n_tets, d_tets, n_nodes, R.d_count.p);
+    FB_TRY(launch_1d(k_incident_count, n_tets, s, n_tets, d_tets, n_nodes, R.d_count.p));
     FB_TRY(W.temp.reserve(sizeof(int2) * (size_t)n_slices));
     int2* d_sc = reinterpret_cast<int2*>(W.temp.p);
-    hipLaunchKernelGGL(k_slice_counts, dim3((unsigned)((n_slices + kB / 64 - 1) / (kB / 64))), dim3(kB), 0, s, n_nodes, W.vals_s.p, R.d_count.p, d_sc);
-    FB_HIP(hipGetLastError());
+    FB_TRY(launch_waves(k_slice_counts, n_slices, s, n_nodes, W.vals_s.p, R.d_count.p, d_sc));
     std::vector<int2> sc((size_t)n_slices);
     FB_HIP(hipMemcpyAsync(sc.data(), d_sc, sizeof(int2) * (size_t)n_slices, hipMemcpyDeviceToHost, s));
     FB_HIP(hipStreamSynchronize(s));
@@ -286,22 +272,17 @@ int renumber_build(hipStream_t s, int mode, int n_nodes, int n_tets, const int4*
       R.window = sigma_window(n_nodes);
       R.n_windows = (n_nodes + R.window - 1) / R.window;
       FB_TRY(R.d_win_keys.alloc((size_t)R.n_windows));
-      hipLaunchKernelGGL(k_window_keys, dim3((unsigned)((R.n_windows + kB - 1) / kB)), dim3(kB), 0, s, R.n_windows, R.window, W.keys_s.p, R.d_win_keys.p);
-      hipLaunchKernelGGL(k_sigma_keys, ng, dim3(kB), 0, s, n_nodes, R.window, W.vals_s.p, R.d_count.p, W.keys.p, W.vals.p);
-      FB_HIP(hipGetLastError());
+      FB_TRY(launch_1d(k_window_keys, R.n_windows, s, R.n_windows, R.window, W.keys_s.p, R.d_win_keys.p));
+      FB_TRY(launch_1d(k_sigma_keys, n_nodes, s, n_nodes, R.window, W.vals_s.p, R.d_count.p, W.keys.p, W.vals.p));
       unsigned bits2 = 10;
       while ((1LL << (bits2 - 10)) < R.n_windows) bits2++;
-      bytes = 0;
-      FB_HIP(rocprim::radix_sort_pairs(nullptr, bytes, W.keys.p, W.keys_s.p, W.vals.p, W.vals_s.p, (size_t)n_nodes, 0u, bits2, s));
-      FB_TRY(W.temp.reserve(std::max<size_t>(bytes, 16)));
-      FB_HIP(rocprim::radix_sort_pairs(W.temp.p, bytes, W.keys.p, W.keys_s.p, W.vals.p, W.vals_s.p, (size_t)n_nodes, 0u, bits2, s));
+      FB_TRY(sort_pairs(W.temp, s, W.keys.p, W.keys_s.p, W.vals.p, W.vals_s.p, (size_t)n_nodes, bits2));
       R.sigma = true;
     }
   }
   FB_TRY(R.d_old_of_new.alloc((size_t)n_nodes));
   FB_TRY(R.d_new_of_old.alloc((size_t)n_nodes));
-  hipLaunchKernelGGL(k_invert, ng, dim3(kB), 0, s, n_nodes, W.vals_s.p, R.d_old_of_new.p, R.d_new_of_old.p);
-  FB_HIP(hipGetLastError());
+  FB_TRY(launch_1d(k_invert, n_nodes, s, n_nodes, W.vals_s.p, R.d_old_of_new.p, R.d_new_of_old.p));
   FB_TRY(tet_span_device(s, n_tets, d_tets, n_nodes, R.d_new_of_old.p, W, &R.span_after, &R.mean_after));
   // AUTO keeps the new order only if the elements get a quarter narrower ON AVERAGE (the widest one may be an outlier -- a sliver on the
   // hull of a Delaunay mesh joins nodes a body apart in any order); ON keeps it
@@ -351,35 +332,27 @@ int device_constraint_masks(hipStream_t s, int n_nodes, int n_fixed, const int* 
   if (n_fixed > 0) {
     FB_TRY(stage.reserve((size_t)n_fixed));
     FB_HIP(hipMemcpyAsync(stage.p, fixed_dofs, sizeof(int) * (size_t)n_fixed, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_fix_dofs, dim3((unsigned)((n_fixed + kB - 1) / kB)), dim3(kB), 0, s, n_fixed, stage.p, d_new_of_old, dofmask.p);
-    FB_HIP(hipGetLastError());
+    FB_TRY(launch_1d(k_fix_dofs, n_fixed, s, n_fixed, stage.p, d_new_of_old, dofmask.p));
   }
-  hipLaunchKernelGGL(k_node_masks, dim3((unsigned)((n_nodes + kB - 1) / kB)), dim3(kB), 0, s, n_nodes, dofmask.p, nodemask.p);
-  FB_HIP(hipGetLastError());
+  FB_TRY(launch_1d(k_node_masks, n_nodes, s, n_nodes, dofmask.p, nodemask.p));
   FB_HIP(hipStreamSynchronize(s));  // (the caller's list may go away)
   return FB_OK;
 }
 
 int relabel_tets(hipStream_t s, int n_tets, int4* d_tets, int n_nodes, const int* d_new_of_old) {
-  hipLaunchKernelGGL(k_relabel, dim3((unsigned)((n_tets + kB - 1) / kB)), dim3(kB), 0, s, n_tets, d_tets, n_nodes, d_new_of_old);
-  FB_HIP(hipGetLastError());
-  return FB_OK;
+  return launch_1d(k_relabel, n_tets, s, n_tets, d_tets, n_nodes, d_new_of_old);
 }
 
 int gather_nodes(hipStream_t s, int n, int width, const double* src, const int* map, double* dst) {
   const long long total = (long long)n * width;
   if (total <= 0) return FB_OK;
-  hipLaunchKernelGGL(k_gather_nodes, dim3((unsigned)((total + kB - 1) / kB)), dim3(kB), 0, s, (long long)n, width, src, map, dst);
-  FB_HIP(hipGetLastError());
-  return FB_OK;
+  return launch_1d(k_gather_nodes, total, s, n, width, src, map, dst);
 }
 
 int scatter_nodes(hipStream_t s, int n, int width, const double* src, const int* map, double* dst) {
   const long long total = (long long)n * width;
   if (total <= 0) return FB_OK;
-  hipLaunchKernelGGL(k_scatter_nodes, dim3((unsigned)((total + kB - 1) / kB)), dim3(kB), 0, s, (long long)n, width, src, map, dst);
-  FB_HIP(hipGetLastError());
-  return FB_OK;
+  return launch_1d(k_scatter_nodes, total, s, n, width, src, map, dst);
 }
 
 int host_slab_order(int n_nodes, const double* xyz, int n_tets, const int* tets, std::vector<int>& old_of_new, int* span_before, int* span_after, double* mean_before,

@@ -6,16 +6,12 @@
 #include <cstring>
 #include <vector>
 
-#include <rocprim/rocprim.hpp>
-
-#include "common.h"
+#include "device_prims.hip.h"
+#include "launch.hip.h"
 #include "subdivide.h"
 
 namespace fb {
 namespace {
-
-constexpr int kB = 256;
-inline dim3 grid_for(long long n) { return dim3((unsigned)std::max<long long>(1, (n + kB - 1) / kB)); }
 
 // EPSILON is a float constant (base/MathBase.h:92) that IntersectRayTriangle compares a double against
 constexpr double kCutEps = (double)0.0001f;
@@ -383,8 +379,7 @@ int cut_classify(hipStream_t s, CutWork& C, int n_tets, const int4* tets, const 
   FB_TRY(C.counts.reserve(8));
   FB_TRY(C.cut_tets.reserve((size_t)std::max(1, n_tets / 16)));
   FB_HIP(hipMemsetAsync(C.counts.p, 0, 8 * sizeof(int), s));
-  hipLaunchKernelGGL(k_cut_codes, grid_for(n_tets), dim3(kB), 0, s, n_tets, tets, caller_of, x0, q, C.n_quads, C.quads.p, C.code.p, C.counts.p);
-  FB_HIP(hipGetLastError());
+  FB_TRY(launch_1d(k_cut_codes, n_tets, s, n_tets, tets, caller_of, x0, q, C.n_quads, C.quads.p, C.code.p, C.counts.p));
   int h[4];
   FB_HIP(hipMemcpyAsync(h, C.counts.p, sizeof(h), hipMemcpyDeviceToHost, s));
   FB_HIP(hipStreamSynchronize(s));
@@ -394,11 +389,7 @@ int cut_classify(hipStream_t s, CutWork& C, int n_tets, const int4* tets, const 
   FB_TRY(C.cut_tets.reserve((size_t)C.n_cut));
   const auto flags = rocprim::make_transform_iterator(static_cast<const unsigned char*>(C.code.p), IsCut());
   rocprim::counting_iterator<int> ids(0);
-  size_t bytes = 0;
-  FB_HIP(rocprim::select(nullptr, bytes, ids, flags, C.cut_tets.p, C.counts.p + 5, (size_t)n_tets, s));
-  FB_TRY(W.temp.reserve(std::max<size_t>(bytes, 16)));
-  FB_HIP(rocprim::select(W.temp.p, bytes, ids, flags, C.cut_tets.p, C.counts.p + 5, (size_t)n_tets, s));
-  return FB_OK;
+  return select_flagged(W.temp, s, ids, flags, C.cut_tets.p, C.counts.p + 5, (size_t)n_tets);
 }
 
 int cut_read_unhandled(hipStream_t s, CutWork& C, PlanWorkspace& W) {
@@ -408,10 +399,7 @@ int cut_read_unhandled(hipStream_t s, CutWork& C, PlanWorkspace& W) {
   FB_TRY(C.sel.reserve((size_t)C.n_unhandled));
   const auto flags = rocprim::make_transform_iterator(static_cast<const unsigned char*>(C.code.p), Unhandled());
   rocprim::counting_iterator<int> ids(0);
-  size_t bytes = 0;
-  FB_HIP(rocprim::select(nullptr, bytes, ids, flags, C.sel.p, C.counts.p + 6, (size_t)C.n_tets, s));
-  FB_TRY(W.temp.reserve(std::max<size_t>(bytes, 16)));
-  FB_HIP(rocprim::select(W.temp.p, bytes, ids, flags, C.sel.p, C.counts.p + 6, (size_t)C.n_tets, s));
+  FB_TRY(select_flagged(W.temp, s, ids, flags, C.sel.p, C.counts.p + 6, (size_t)C.n_tets));
   const int n = std::min(C.n_unhandled, kCutUnhandledIds);
   C.unhandled_ids.resize(n);
   std::vector<unsigned char> all((size_t)C.n_tets);
@@ -432,21 +420,13 @@ int cut_emit(hipStream_t s, CutWork& C, int n_nodes, const int4* tets, const int
   FB_TRY(C.head.reserve(ne)); FB_TRY(C.hpos.reserve(ne));
   FB_TRY(C.piece_off.reserve((size_t)m + 1));
   FB_TRY(C.pcount.reserve((size_t)m + 1));
-  hipLaunchKernelGGL(k_cut_edges, grid_for(m), dim3(kB), 0, s, m, C.cut_tets.p, tets, caller_of, x0, q, C.n_quads, C.quads.p, C.code.p, C.ekeys.p, C.et.p, C.pcount.p);
-  FB_HIP(hipGetLastError());
-  size_t bytes = 0, b2 = 0, b3 = 0;
-  FB_HIP(rocprim::radix_sort_pairs(nullptr, bytes, C.ekeys.p, C.ekeys_s.p, C.et.p, C.et_s.p, ne, 0u, 64u, s));
-  FB_HIP(rocprim::exclusive_scan(nullptr, b2, C.head.p, C.hpos.p, 0, ne, rocprim::plus<int>(), s));
-  FB_HIP(rocprim::exclusive_scan(nullptr, b3, C.pcount.p, C.piece_off.p, 0, (size_t)m, rocprim::plus<int>(), s));
-  FB_TRY(W.temp.reserve(std::max<size_t>(std::max(bytes, std::max(b2, b3)), 16)));
-  FB_HIP(rocprim::radix_sort_pairs(W.temp.p, bytes, C.ekeys.p, C.ekeys_s.p, C.et.p, C.et_s.p, ne, 0u, 64u, s));
-  hipLaunchKernelGGL(k_cut_heads, grid_for((long long)ne), dim3(kB), 0, s, (long long)ne, C.ekeys_s.p, C.head.p);
-  FB_HIP(hipGetLastError());
-  FB_HIP(rocprim::exclusive_scan(W.temp.p, b2, C.head.p, C.hpos.p, 0, ne, rocprim::plus<int>(), s));
+  FB_TRY(launch_1d(k_cut_edges, m, s, m, C.cut_tets.p, tets, caller_of, x0, q, C.n_quads, C.quads.p, C.code.p, C.ekeys.p, C.et.p, C.pcount.p));
+  FB_TRY(sort_pairs(W.temp, s, C.ekeys.p, C.ekeys_s.p, C.et.p, C.et_s.p, ne, 64u));
+  FB_TRY(launch_1d(k_cut_heads, (long long)ne, s, ne, C.ekeys_s.p, C.head.p));
+  FB_TRY(exclusive_scan(W.temp, s, C.head.p, C.hpos.p, 0, ne));
   FB_TRY(C.ukeys.reserve(ne)); FB_TRY(C.ut.reserve(ne));
-  hipLaunchKernelGGL(k_cut_unique, grid_for((long long)ne), dim3(kB), 0, s, (long long)ne, C.ekeys_s.p, C.et_s.p, C.head.p, C.hpos.p, C.ukeys.p, C.ut.p, C.counts.p + 4);
-  FB_HIP(hipGetLastError());
-  FB_HIP(rocprim::exclusive_scan(W.temp.p, b3, C.pcount.p, C.piece_off.p, 0, (size_t)m, rocprim::plus<int>(), s));
+  FB_TRY(launch_1d(k_cut_unique, (long long)ne, s, ne, C.ekeys_s.p, C.et_s.p, C.head.p, C.hpos.p, C.ukeys.p, C.ut.p, C.counts.p + 4));
+  FB_TRY(exclusive_scan(W.temp, s, C.pcount.p, C.piece_off.p, 0, (size_t)m));
   FB_HIP(hipMemcpyAsync(&C.n_edges, C.counts.p + 4, sizeof(int), hipMemcpyDeviceToHost, s));
   FB_HIP(hipStreamSynchronize(s));
   C.n_added = 4 * C.n_a + 6 * C.n_b;
@@ -455,22 +435,17 @@ int cut_emit(hipStream_t s, CutWork& C, int n_nodes, const int4* tets, const int
   FB_TRY(C.added.reserve((size_t)std::max(1, C.n_added)));
   FB_TRY(C.ratio.reserve(2 * ((size_t)std::max(1, C.n_added) + 1)));  // ratios, their minimum, absolute volumes, their minimum
   const int carry = C.mode == FB_CUT_CARRY ? 1 : 0;
-  hipLaunchKernelGGL(k_cut_nodes, grid_for(C.n_edges), dim3(kB), 0, s, C.n_edges, C.ukeys.p, C.ut.p, internal_of, x0, q, carry, C.frac.p, C.new_xyz.p);
-  FB_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_cut_pieces, grid_for(m), dim3(kB), 0, s, m, C.cut_tets.p, tets, caller_of, internal_of, x0, q, carry, C.code.p, C.piece_off.p, n_nodes, C.n_edges,
-                     C.ukeys.p, C.new_xyz.p, C.added.p, C.ratio.p, C.n_added + 1);
-  FB_HIP(hipGetLastError());
+  FB_TRY(launch_1d(k_cut_nodes, C.n_edges, s, C.n_edges, C.ukeys.p, C.ut.p, internal_of, x0, q, carry, C.frac.p, C.new_xyz.p));
+  FB_TRY(launch_1d(k_cut_pieces, m, s, m, C.cut_tets.p, tets, caller_of, internal_of, x0, q, carry, C.code.p, C.piece_off.p, n_nodes, C.n_edges, C.ukeys.p, C.new_xyz.p, C.added.p,
+                   C.ratio.p, C.n_added + 1));
   // the smallest piece-to-parent volume ratio (read back with the result)
   double* out = C.ratio.p + C.n_added;
-  size_t b4 = 0;
-  FB_HIP(rocprim::reduce(nullptr, b4, C.ratio.p, out, 1e300, (size_t)C.n_added, rocprim::minimum<double>(), s));
-  FB_TRY(W.temp.reserve(std::max<size_t>(b4, 16)));
-  FB_HIP(rocprim::reduce(W.temp.p, b4, C.ratio.p, out, 1e300, (size_t)C.n_added, rocprim::minimum<double>(), s));
+  FB_TRY(min_reduce(W.temp, s, C.ratio.p, out, (size_t)C.n_added));
   FB_HIP(hipMemcpyAsync(&C.min_ratio, out, sizeof(double), hipMemcpyDeviceToHost, s));
   // ... and the smallest piece volume itself: what the fp32 records have to hold (fb_fem_cut refuses a cut they cannot)
   const double* vol = C.ratio.p + C.n_added + 1;
   double* vout = C.ratio.p + 2 * (size_t)C.n_added + 1;
-  FB_HIP(rocprim::reduce(W.temp.p, b4, vol, vout, 1e300, (size_t)C.n_added, rocprim::minimum<double>(), s));
+  FB_TRY(min_reduce(W.temp, s, vol, vout, (size_t)C.n_added));
   FB_HIP(hipMemcpyAsync(&C.min_volume, vout, sizeof(double), hipMemcpyDeviceToHost, s));
   FB_HIP(hipStreamSynchronize(s));
   return FB_OK;
@@ -478,16 +453,12 @@ int cut_emit(hipStream_t s, CutWork& C, int n_nodes, const int4* tets, const int
 
 int cut_interpolate(hipStream_t s, const CutWork& C, int n_nodes, double* v) {
   if (C.n_edges == 0) return FB_OK;
-  hipLaunchKernelGGL(k_cut_interp, grid_for(C.n_edges), dim3(kB), 0, s, C.n_edges, C.ukeys.p, C.frac.p, n_nodes, v);
-  FB_HIP(hipGetLastError());
-  return FB_OK;
+  return launch_1d(k_cut_interp, C.n_edges, s, C.n_edges, C.ukeys.p, C.frac.p, n_nodes, v);
 }
 
 int cut_bake(hipStream_t s, long long n3, double* x0, const double* q) {
   if (n3 == 0) return FB_OK;
-  hipLaunchKernelGGL(k_cut_bake, grid_for(n3), dim3(kB), 0, s, n3, x0, q);
-  FB_HIP(hipGetLastError());
-  return FB_OK;
+  return launch_1d(k_cut_bake, n3, s, n3, x0, q);
 }
 
 }  // namespace fb

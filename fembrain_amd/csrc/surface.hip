@@ -16,16 +16,12 @@
 #include <cstring>
 #include <vector>
 
-#include <rocprim/rocprim.hpp>
-
-#include "common.h"
+#include "device_prims.hip.h"
+#include "launch.hip.h"
 #include "surface.h"
 
 namespace fb {
 namespace {
-
-constexpr int kB = 256;
-inline dim3 grid_for(long long n) { return dim3((unsigned)std::max<long long>(1, (n + kB - 1) / kB)); }
 
 __device__ __forceinline__ int tet_node(const int4& t, int k) { return k == 0 ? t.x : k == 1 ? t.y : k == 2 ? t.z : t.w; }
 
@@ -274,12 +270,6 @@ __global__ __launch_bounds__(kB) void k_box_final(int n_part, const float* __res
   }
 }
 
-int bits_of(long long n) {  // bits that hold every id in [0, n)
-  int b = 1;
-  while ((1LL << b) < n) b++;
-  return b;
-}
-
 }  // namespace
 
 int surface_build(hipStream_t s, SurfaceWork& S, int n_nodes, int n_tets, const int4* tets, const double* x0, const int* caller_of, const int* internal_of,
@@ -293,37 +283,24 @@ int surface_build(hipStream_t s, SurfaceWork& S, int n_nodes, int n_tets, const 
   FB_TRY(W.keys.reserve(ne)); FB_TRY(W.keys_s.reserve(ne)); FB_TRY(W.vals.reserve(ne)); FB_TRY(W.vals_s.reserve(ne));
   FB_TRY(S.flag.alloc(ne));
   FB_TRY(S.counts.alloc(2));
-  hipLaunchKernelGGL(k_face_keys, grid_for(n_tets), dim3(kB), 0, s, n_tets, tets, x0, caller_of, wide ? 0 : nb, W.keys.p, W.vals.p);
-  FB_HIP(hipGetLastError());
+  FB_TRY(launch_1d(k_face_keys, n_tets, s, n_tets, tets, x0, caller_of, wide ? 0 : nb, W.keys.p, W.vals.p));
   const unsigned long long* keys_sorted = W.keys_s.p;
   const uint32_t* pay_sorted = W.vals_s.p;
-  size_t bytes = 0;
   if (!wide) {
-    FB_HIP(rocprim::radix_sort_pairs(nullptr, bytes, W.keys.p, W.keys_s.p, W.vals.p, W.vals_s.p, ne, 0u, (unsigned)(3 * nb), s));
-    FB_TRY(W.temp.reserve(std::max<size_t>(bytes, 16)));
-    FB_HIP(rocprim::radix_sort_pairs(W.temp.p, bytes, W.keys.p, W.keys_s.p, W.vals.p, W.vals_s.p, ne, 0u, (unsigned)(3 * nb), s));
+    FB_TRY(sort_pairs(W.temp, s, W.keys.p, W.keys_s.p, W.vals.p, W.vals_s.p, ne, (unsigned)(3 * nb)));
   } else {
     // two stable passes: by the largest id, then by smallest << 32 | middle
-    size_t b2 = 0;
-    FB_HIP(rocprim::radix_sort_pairs(nullptr, bytes, W.keys.p, W.keys_s.p, W.vals.p, W.vals_s.p, ne, 0u, (unsigned)nb, s));
-    FB_HIP(rocprim::radix_sort_pairs(nullptr, b2, W.keys.p, W.keys_s.p, W.vals.p, W.vals_s.p, ne, 0u, (unsigned)(32 + nb), s));
-    FB_TRY(W.temp.reserve(std::max<size_t>(std::max(bytes, b2), 16)));
-    FB_HIP(rocprim::radix_sort_pairs(W.temp.p, bytes, W.keys.p, W.keys_s.p, W.vals.p, W.vals_s.p, ne, 0u, (unsigned)nb, s));
-    hipLaunchKernelGGL(k_face_keys_ab, grid_for((long long)ne), dim3(kB), 0, s, (long long)ne, tets, caller_of, W.vals_s.p, W.keys_s.p);
-    FB_HIP(hipGetLastError());
-    FB_HIP(rocprim::radix_sort_pairs(W.temp.p, b2, W.keys_s.p, W.keys.p, W.vals_s.p, W.vals.p, ne, 0u, (unsigned)(32 + nb), s));
+    FB_TRY(sort_pairs(W.temp, s, W.keys.p, W.keys_s.p, W.vals.p, W.vals_s.p, ne, (unsigned)nb));
+    FB_TRY(launch_1d(k_face_keys_ab, (long long)ne, s, ne, tets, caller_of, W.vals_s.p, W.keys_s.p));
+    FB_TRY(sort_pairs(W.temp, s, W.keys_s.p, W.keys.p, W.vals_s.p, W.vals.p, ne, (unsigned)(32 + nb)));
     keys_sorted = W.keys.p;
     pay_sorted = W.vals.p;
     FB_TRY(S.csort.alloc(ne));
-    hipLaunchKernelGGL(k_face_largest, grid_for((long long)ne), dim3(kB), 0, s, (long long)ne, tets, caller_of, pay_sorted, S.csort.p);
-    FB_HIP(hipGetLastError());
+    FB_TRY(launch_1d(k_face_largest, (long long)ne, s, ne, tets, caller_of, pay_sorted, S.csort.p));
   }
-  hipLaunchKernelGGL(k_face_ends, grid_for((long long)ne), dim3(kB), 0, s, (long long)ne, keys_sorted, wide ? S.csort.p : nullptr, S.flag.p);
-  FB_HIP(hipGetLastError());
+  FB_TRY(launch_1d(k_face_ends, (long long)ne, s, ne, keys_sorted, wide ? S.csort.p : nullptr, S.flag.p));
   FB_TRY(S.sel.alloc(ne));  // (a mesh of separate elements keeps every face)
-  FB_HIP(rocprim::select(nullptr, bytes, pay_sorted, S.flag.p, S.sel.p, S.counts.p, ne, s));
-  FB_TRY(W.temp.reserve(std::max<size_t>(bytes, 16)));
-  FB_HIP(rocprim::select(W.temp.p, bytes, pay_sorted, S.flag.p, S.sel.p, S.counts.p, ne, s));
+  FB_TRY(select_flagged(W.temp, s, pay_sorted, S.flag.p, S.sel.p, S.counts.p, ne));
   int nf = 0;
   FB_HIP(hipMemcpyAsync(&nf, S.counts.p, sizeof(int), hipMemcpyDeviceToHost, s));
   FB_HIP(hipStreamSynchronize(s));  // the first host wait
@@ -341,17 +318,10 @@ int surface_build(hipStream_t s, SurfaceWork& S, int n_nodes, int n_tets, const 
   FB_TRY(S.out.alloc((size_t)6 * nv_max + 6));  // (the rest box of this build sits in the last six)
   FB_TRY(S.part.alloc((size_t)6 * std::max(1, ceil_div(nv_max, kB))));
   FB_TRY(S.bitmap.zero(s));
-  if (nf) {
-    hipLaunchKernelGGL(k_face_emit, grid_for(nf), dim3(kB), 0, s, nf, tets, caller_of, S.sel.p, S.faces.p, S.faces_int.p, S.face_tets.p, S.bitmap.p);
-    FB_HIP(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_word_counts, grid_for(n_words + 1), dim3(kB), 0, s, n_words, S.bitmap.p, S.word_cnt.p);
-  FB_HIP(hipGetLastError());
-  FB_HIP(rocprim::exclusive_scan(nullptr, bytes, S.word_cnt.p, S.word_off.p, 0, (size_t)n_words + 1, rocprim::plus<int>(), s));
-  FB_TRY(W.temp.reserve(std::max<size_t>(bytes, 16)));
-  FB_HIP(rocprim::exclusive_scan(W.temp.p, bytes, S.word_cnt.p, S.word_off.p, 0, (size_t)n_words + 1, rocprim::plus<int>(), s));
-  hipLaunchKernelGGL(k_vertex_ids, grid_for(n_words), dim3(kB), 0, s, n_words, S.bitmap.p, S.word_off.p, internal_of, S.vertex_ids.p, S.vnode.p, S.counts.p);
-  FB_HIP(hipGetLastError());
+  if (nf) FB_TRY(launch_1d(k_face_emit, nf, s, nf, tets, caller_of, S.sel.p, S.faces.p, S.faces_int.p, S.face_tets.p, S.bitmap.p));
+  FB_TRY(launch_1d(k_word_counts, n_words + 1, s, n_words, S.bitmap.p, S.word_cnt.p));
+  FB_TRY(exclusive_scan(W.temp, s, S.word_cnt.p, S.word_off.p, 0, (size_t)n_words + 1));
+  FB_TRY(launch_1d(k_vertex_ids, n_words, s, n_words, S.bitmap.p, S.word_off.p, internal_of, S.vertex_ids.p, S.vnode.p, S.counts.p));
   if (nf) {
     // incidence: the corners sorted stably by compact vertex keep their ascending face order
     // (the face sort's arrays are free again: the surviving payloads are in S.sel)
@@ -359,14 +329,9 @@ int surface_build(hipStream_t s, SurfaceWork& S, int n_nodes, int n_tets, const 
     uint32_t* ck = reinterpret_cast<uint32_t*>(W.keys.p);
     uint32_t* ck_s = reinterpret_cast<uint32_t*>(W.keys_s.p);
     uint32_t* cv = W.vals.p;
-    hipLaunchKernelGGL(k_corner_keys, grid_for(nc), dim3(kB), 0, s, nc, S.faces.p, S.bitmap.p, S.word_off.p, ck, cv);
-    FB_HIP(hipGetLastError());
-    const unsigned vb = (unsigned)bits_of(nv_max);
-    FB_HIP(rocprim::radix_sort_pairs(nullptr, bytes, ck, ck_s, cv, S.inc.p, (size_t)nc, 0u, vb, s));
-    FB_TRY(W.temp.reserve(std::max<size_t>(bytes, 16)));
-    FB_HIP(rocprim::radix_sort_pairs(W.temp.p, bytes, ck, ck_s, cv, S.inc.p, (size_t)nc, 0u, vb, s));
-    hipLaunchKernelGGL(k_corner_heads, grid_for(nc), dim3(kB), 0, s, nc, ck_s, S.counts.p, S.inc_off.p);
-    FB_HIP(hipGetLastError());
+    FB_TRY(launch_1d(k_corner_keys, nc, s, nc, S.faces.p, S.bitmap.p, S.word_off.p, ck, cv));
+    FB_TRY(sort_pairs(W.temp, s, ck, ck_s, cv, S.inc.p, (size_t)nc, (unsigned)bits_of(nv_max)));
+    FB_TRY(launch_1d(k_corner_heads, nc, s, nc, ck_s, S.counts.p, S.inc_off.p));
   }
   // the rest box: the grid covers the most vertices there can be and the kernel reads the count on the device, so the count and the box
   // leave together in the second (and last) host wait
