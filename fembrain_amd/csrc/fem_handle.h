@@ -1,6 +1,6 @@
-// The FEM handle (fb_fem_t of include/fembrain_hip.h) and what the units that work on it share: fem.hip (life cycle, assembly,
-// the two-launch solver, the C ABI), fem_persist.hip (the persistent solver's host side), haptic.hip (the probe's entry points) and
-// stress.hip (element stress and strain).
+// The FEM handle (fb_fem_t of include/fembrain_hip.h) and what the units that work on it share: fem.hip (assembly, the two-launch
+// solver, the steps and the rest of the C ABI), fem_build.hip (life cycle: plan build, creation, re-sync, cut), fem_persist.hip (the
+// persistent solver's host side), haptic.hip (the probe's entry points) and stress.hip (element stress and strain).
 // Internal: not installed, included by these units only.
 #pragma once
 #include "comm.h"
@@ -136,7 +136,7 @@ struct AsmKernels { const void *warp = nullptr, *rows = nullptr, *wide = nullptr
 
 }  // namespace fb
 
-using namespace fb;  // (both units do; the handle's members are fb's types)
+using namespace fb;  // (the units do; the handle's members are fb's types)
 
 struct fb_fem_s {
   fb_fem_params prm;
@@ -205,6 +205,9 @@ struct fb_fem_s {
   bool mass_valid = false;           // h->mblk holds the mass entries of the current rest data (k_mass_blocks)
   fb::HostKnobs knobs;               // as the last plan build read them
   fb::AsmKernels asm_k;              // the assembly kernels of this plan
+  // Per mesh generation -- begin_mesh_generation (fem_build.hip) is the one place that resets them, for build(), its host-builder fallback
+  // and fb_fem_resync_delta: ren, l2c, order_sum, x0_ready, masks_ready, caller_pattern, csr_ready, span_stale (all below), surf.valid and
+  // stress.valid (above); batch_graph is dropped with them.  (fb_fem_resync_delta keeps ren, and csr_ready while it decides, and says so.)
   // locality renumbering behind the ABI (renumber.h): the handle works in its own node order, ids are mapped on the way in and out
   Renumbering ren;
   DevBuf<double> xyz_in;               // the caller-order rest positions the order was derived from
@@ -263,6 +266,8 @@ struct fb_fem_s {
 
 namespace fb {
 
+inline bool has_material_map(const fb_fem_s* h) { return h->mat_ids.p != nullptr; }  // (none: nothing allocated, the kernels' uniform instantiations)
+
 inline SellView sell_view(const fb_fem_s* h) {
   SellView sv;
   sv.slice_off = h->slice_off.p; sv.colidx = h->colidx.p; sv.n_slices = h->plan.n_slices; sv.n_owned = h->plan.n_owned;
@@ -291,10 +296,42 @@ struct ZeroBatch {   // (fem.hip, next to its kernel)
   int flush();
 };
 
+// The timing entry points' common sequence: ev[0], `body` reps times, ev[1], wait, seconds per repetition.  Warm-up calls stay with the caller.
+template <typename Body>
+int timed_reps(fb_fem_s* h, int reps, Body body, double* seconds_per_rep) {
+  FB_HIP(hipEventRecord(h->ev[0], h->stream));
+  for (int r = 0; r < reps; r++) FB_TRY(body());
+  FB_HIP(hipEventRecord(h->ev[1], h->stream));
+  FB_HIP(hipStreamSynchronize(h->stream));
+  float ms = 0;
+  FB_HIP(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+  *seconds_per_rep = ms * 1e-3 / reps;
+  return FB_OK;
+}
+// ... each repetition timed and waited for on its own: the median (fb_fem_time_surface, fb_fem_time_stress)
+template <typename Body>
+int timed_median(fb_fem_s* h, int reps, Body body, double* seconds) {
+  std::vector<double> t((size_t)reps);
+  for (double& x : t) FB_TRY(timed_reps(h, 1, body, &x));
+  std::sort(t.begin(), t.end());
+  *seconds = t[t.size() / 2];
+  return FB_OK;
+}
+
 // fem.hip
 int assemble_system(fb_fem_s* h);
 int handle_slack_now(const fb_fem_s* h);   // the slack rule of this handle's allocations at its current mesh (SlackScope)
 int surface_current(fb_fem_s* h);          // builds the surface where it is stale (fb_fem_surface_update's first step)
+// ... and what fem_build.hip builds a handle with
+int handle_slack(const fb_fem_s* h, int n_nodes, int n_tets);  // the slack rule at a mesh of this size
+int renumber_mode(const fb_fem_s* h);      // FB_RENUMBER_* of this handle
+HostKnobs read_host_knobs();
+int upload_masks(fb_fem_s* h);             // the plan's constraint mask to the device (host-built plans, sharded handles)
+int upload_plan(fb_fem_s* h, const double* xyz_global, const float* xyz_device = nullptr, const double* xyz_device64 = nullptr);  // everything per plan
+int launch_rest(fb_fem_s* h, int* first_flat = nullptr);
+void drop_graph(fb_fem_s* h);
+int widen_positions(hipStream_t s, long long n, const float* in, double* out);  // float positions handed over on the device -> doubles
+int download_owned(fb_fem_s* h, const DevBuf<double>& src, double* g);          // owned part of a device vector -> its place in a global-length host vector
 
 // fem_persist.hip
 bool auto_matrix_f64(const fb_fem_s* h, int n_nodes, int n_ranks);

@@ -720,14 +720,10 @@ int fb_fem_time_persist(fb_fem_t h, int reps, int n_iters, double* seconds_per_l
   if (!h->system_valid) FB_TRY(assemble_system(h));
   double total = 0.0;
   for (int r = -1; r < reps; r++) {  // r = -1: warm-up
-    float ms = 0;
-    // a solve of the current right-hand side with a tolerance it cannot reach, cut after n_iters iterations
-    FB_HIP(hipEventRecord(h->ev[0], h->stream));
-    FB_TRY(launch_pipe(h, h->rhs.p, 1, n_iters, 1e-30, 1 << 30));
-    FB_HIP(hipEventRecord(h->ev[1], h->stream));
-    FB_HIP(hipStreamSynchronize(h->stream));
-    FB_HIP(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    if (r >= 0) total += ms * 1e-3;
+    double t = 0.0;
+    // a solve of the current right-hand side with a tolerance it cannot reach, cut after n_iters iterations; each launch is timed and waited for
+    FB_TRY(timed_reps(h, 1, [&] { return launch_pipe(h, h->rhs.p, 1, n_iters, 1e-30, 1 << 30); }, &t));
+    if (r >= 0) total += t;
   }
   unsigned int err = 0;
   FB_HIP(hipMemcpy(&err, h->ps.pipe_flags.p + h->ps.persist_blocks + h->ps.pipe_flag_extra + 4, sizeof err, hipMemcpyDeviceToHost));

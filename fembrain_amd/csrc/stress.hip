@@ -352,32 +352,7 @@ int fb_fem_time_stress(fb_fem_t h, int reps, int flags, double* seconds_elements
   FB_TRY(surface_current(h));
   std::vector<float> host((size_t)std::max(h->surf.n_vertices, 1));
   FB_TRY(run_surface_stress(h, host.data()));
-  hipEvent_t e0, e1;
-  FB_HIP(hipEventCreate(&e0));
-  if (hipEventCreate(&e1) != hipSuccess) {
-    (void)hipEventDestroy(e0);
-    return fail(FB_EDEVICE, "hipEventCreate failed");
-  }
-  int rc = FB_OK;
-  auto median = [](std::vector<double>& v) { std::sort(v.begin(), v.end()); return v[v.size() / 2]; };
-  for (int what = 0; what < 2 && rc == FB_OK; what++) {
-    double* dst = what == 0 ? seconds_elements : seconds_surface;
-    if (!dst) continue;
-    std::vector<double> t;
-    for (int r = 0; r < reps && rc == FB_OK; r++) {
-      if (hipEventRecord(e0, h->stream) != hipSuccess) { rc = fail(FB_EDEVICE, "hipEventRecord failed"); break; }
-      rc = what == 0 ? run_stress(h, flags, &info) : run_surface_stress(h, host.data());
-      if (rc != FB_OK) break;
-      float ms = 0;
-      if (hipEventRecord(e1, h->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) {
-        rc = fail(FB_EDEVICE, "timing events failed");
-        break;
-      }
-      t.push_back(ms * 1e-3);
-    }
-    if (rc == FB_OK) *dst = median(t);
-  }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  return rc;
+  if (seconds_elements) FB_TRY(timed_median(h, reps, [&] { return run_stress(h, flags, &info); }, seconds_elements));
+  if (seconds_surface) FB_TRY(timed_median(h, reps, [&] { return run_surface_stress(h, host.data()); }, seconds_surface));
+  return FB_OK;
 }

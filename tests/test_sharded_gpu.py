@@ -211,6 +211,89 @@ def test_renumbered_shards_of_a_scrambled_cube_are_slabs_with_two_neighbours(gpu
     g.close()
 
 
+def _other_plane_dofs(v, fixed):
+    """list B of the constraint tests: the face of the cube opposite the constrained one, in the caller's ids, ascending"""
+    from fembrain_amd.meshgen import fixed_vertices_to_dofs
+    a = v[np.unique(np.asarray(fixed) // 3)]
+    axis = int(np.argmin(np.ptp(a, axis=0)))   # the constrained face is flat along it
+    far = v[:, axis].max() if a[0, axis] == v[:, axis].min() else v[:, axis].min()
+    return fixed_vertices_to_dofs(np.nonzero(v[:, axis] == far)[0])
+
+
+def _set_constraints_worker(rank, world, shm_name, n, q, set_later):
+    try:
+        from fembrain_amd import lib as fl
+        from fembrain_amd.fem import FemIntegrator
+        L = fl.lib()
+        comm = C.c_void_p()
+        fl.check(L.fb_comm_create_local(C.byref(comm), rank, world, shm_name.encode(), 8 << 20, 0))
+        v, t, fixed_a = _scrambled_cube(n)
+        fixed_b = _other_plane_dofs(v, fixed_a)
+        assert len(fixed_b) == len(fixed_a) and not np.intersect1d(fixed_a, fixed_b).size and (np.diff(fixed_b) > 0).all()
+        g = FemIntegrator(v, t, fixed_a if set_later else fixed_b, shard=(world, rank, None, comm), renumber=fl.FB_RENUMBER_ON)
+        assert g.renumbering()[0]
+        f = np.zeros(g.r)
+        f[1::3] = -10000.0
+        f[0::3] = 300.0 * np.sin(v[:, 2] * 7.0)
+        refusals = []
+        if set_later:
+            g.set_constrained_dofs(fixed_b)
+        its = []
+        for bad in (np.append(fixed_b, 3 * len(v)).astype(np.int32), np.ascontiguousarray(fixed_b[::-1])):
+            if set_later:   # (rank-local: a refused list leaves the handle as it was, and the step that follows is the reference's)
+                try:
+                    g.set_constrained_dofs(bad)
+                    refusals.append(None)
+                except fl.FbError as e:
+                    refusals.append(str(e))
+            g.set_external_forces(f)
+            its.append(g.do_timestep())
+        dofs = _own_dofs(g)
+        q.put((rank, set_later, its, dofs, g.get_q_state()[0][dofs].copy(), refusals))
+        g.close()
+        L.fb_comm_destroy(comm)
+    except Exception as e:
+        import traceback
+        q.put((rank, set_later, "EXC " + repr(e) + traceback.format_exc(), None, None, None))
+        q.close()
+        q.join_thread()
+        os._exit(1)
+
+
+def test_constrained_dofs_set_on_a_renumbered_shard_equal_those_it_was_created_with(gpu):
+    """fb_fem_set_constrained_dofs on a renumbered shard takes the list in the caller's ids, checks it, maps it to internal ids and sorts it
+    again -- the steps creation takes.  Two ranks under FB_RENUMBER_ON on the scrambled 10^3 cube, created with the plane i = 0 constrained
+    and then given the opposite face, step twice to the bits of two ranks created with that face: each rank's owned DOFs of q.  A list with
+    an id out of range and a descending one are refused with the messages creation has, before each of the two steps, which stay the
+    reference's."""
+    import multiprocessing as mp
+    world, n = 2, 10
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_set_constraints_worker, args=(r, world, "/fembrain_test_%d_setfix_%d" % (os.getpid(), later), n, q, bool(later)))
+             for later in (0, 1) for r in range(world)]
+    for p in procs:
+        p.start()
+    res = {}
+    try:
+        for _ in procs:
+            r = q.get(timeout=120)
+            assert r[3] is not None, r
+            res[(r[0], r[1])] = r
+    finally:
+        for p in procs:
+            p.join(timeout=30)
+            if p.is_alive():
+                p.kill()
+    for rank in range(world):
+        _, _, its_c, dofs_c, q_c, _ = res[(rank, False)]
+        _, _, its_s, dofs_s, q_s, refusals = res[(rank, True)]
+        assert "out of range" in refusals[0] and "strictly ascending" in refusals[1], refusals
+        assert its_s == its_c and its_c[0] > 0, (its_s, its_c)
+        assert np.array_equal(dofs_s, dofs_c) and np.abs(q_c).max() > 0
+        assert np.array_equal(q_s, q_c), (rank, np.abs(q_s - q_c).max())
+
+
 def test_renumbered_shards_refuse_ranks_that_hold_different_meshes(gpu):
     """the internal order is derived per rank; ranks that were not given the same whole mesh derive different orders, and creation
     fails on every rank alike instead of solving a scrambled system"""
@@ -649,6 +732,78 @@ def test_a_failed_collective_resync_fails_on_every_rank_instead_of_hanging(gpu):
         assert msg is not None and not msg.startswith("EXC"), res[rank]
         assert ("rest volume" in msg) if rank == world - 1 else ("failed on rank %d" % (world - 1) in msg), (rank, msg)
         assert poisoned is not None and "unusable after a failed" in poisoned, (rank, poisoned)
+        assert it0 > 0 and it1 == it0, (rank, it0, it1)
+
+
+def _bad_create_worker(rank, world, shm_name, q):
+    try:
+        from fembrain_amd import lib as fl
+        from fembrain_amd.fem import FemIntegrator
+        L = fl.lib()
+        comm = C.c_void_p()
+        fl.check(L.fb_comm_create_local(C.byref(comm), rank, world, shm_name.encode(), 8 << 20, 0))
+        v, t, fixed, splits = _mesh(10, world)
+
+        def step_of_a_new_handle():
+            g = FemIntegrator(v, t, fixed, shard=(world, rank, splits, comm))
+            g.set_uniform_force(1, -3000.0)
+            it = g.do_timestep()
+            g.close()
+            return it
+        it0 = step_of_a_new_handle()   # (before anything has failed on this communicator)
+        # the mesh of the LAST rank has a flat element among its own (every rank passes its own elements: per-rank ingest)
+        own = ((t >= splits[rank]) & (t < splits[rank + 1])).any(axis=1)
+        t_mine = t[own].copy()
+        v_mine = v.copy()
+        if rank == world - 1:
+            e = t_mine[len(t_mine) // 2]
+            v_mine[e[3]] = v_mine[e[0]]
+        msg = None
+        try:
+            FemIntegrator(v_mine, t_mine, fixed, shard=(world, rank, splits, comm)).close()
+        except fl.FbError as e:
+            msg = str(e)
+        it1 = step_of_a_new_handle()
+        q.put((rank, msg, it0, it1))
+        L.fb_comm_destroy(comm)
+    except Exception as e:
+        import traceback
+        q.put((rank, "EXC " + repr(e) + traceback.format_exc(), 0, 0))
+        q.close()
+        q.join_thread()
+        os._exit(1)
+
+
+def test_a_failed_collective_creation_fails_on_every_rank_instead_of_hanging(gpu):
+    """fb_fem_create_sharded is collective, its plan build is not: one rank's mesh has a flat element.  The ranks agree on the outcome
+    before the collective attach of the peer inboxes: the bad rank reports its element, the healthy rank reports that rank --
+    within the call, not after a communicator time-out --, no handle is made, and a good creation on the same communicator afterwards
+    steps like the one before the failure."""
+    import multiprocessing as mp
+    import time
+    world = 2
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    name = "/fembrain_test_%d_badcreate" % os.getpid()
+    procs = [ctx.Process(target=_bad_create_worker, args=(r, world, name, q)) for r in range(world)]
+    t0 = time.time()
+    for p in procs:
+        p.start()
+    res = {}
+    try:
+        for _ in range(world):
+            r = q.get(timeout=120)
+            res[r[0]] = r
+    finally:
+        for p in procs:
+            p.join(timeout=30)
+            if p.is_alive():
+                p.kill()
+    assert time.time() - t0 < 100
+    for rank in range(world):
+        _, msg, it0, it1 = res[rank]
+        assert msg is not None and not msg.startswith("EXC"), res[rank]
+        assert ("rest volume" in msg) if rank == world - 1 else ("failed on rank %d" % (world - 1) in msg), (rank, msg)
         assert it0 > 0 and it1 == it0, (rank, it0, it1)
 
 
