@@ -49,7 +49,7 @@ struct LapTimer {
 enum { kKeepOrder = 1, kKeepCsr = 2 };
 void begin_mesh_generation(fb_fem_s* h, int keep = 0) {
   drop_graph(h);
-  h->surf.valid = h->stress.valid = false;  // (fb_fem_surface; fb_fem_read_stress / fb_fem_surface_stress)
+  h->surf.valid = h->stress.valid = h->parts.valid = false;  // (fb_fem_surface; fb_fem_read_stress / fb_fem_surface_stress; fb_fem_parts)
   if (!(keep & kKeepCsr)) h->csr_ready = false;
   if (!(keep & kKeepOrder)) h->ren.clear();
   h->l2c.clear();
@@ -666,8 +666,9 @@ int resync_delta_rebuild(fb_fem_s* h, int n_old, int n_new, int n_fixed, const i
 }
 
 // device_src: removed / added / new_xyz are device arrays (fb_fem_cut; no element changed in place)
+// force_rebuild: the full builder whatever there is to merge into (refresh_node_order)
 int resync_delta(fb_fem_s* h, int n_removed, const int* removed, int n_changed, const int* changed_ids, const int* changed_nodes, int n_added, const int* added,
-                 int n_new_nodes, const double* new_xyz, int n_fixed, const int* fixed, bool device_src = false) {
+                 int n_new_nodes, const double* new_xyz, int n_fixed, const int* fixed, bool device_src = false, bool force_rebuild = false) {
   const LapTimer lap("delta re-sync");
   hipStream_t s = h->stream;
   MeshDelta& D = h->delta;
@@ -691,7 +692,7 @@ int resync_delta(fb_fem_s* h, int n_removed, const int* removed, int n_changed, 
   }
   lap("change uploaded");
   const char* env = getenv("FEMBRAIN_RESYNC_DELTA");
-  bool merge = h->csr_ready && !(env && !strcmp(env, "rebuild"));
+  bool merge = h->csr_ready && !force_rebuild && !(env && !strcmp(env, "rebuild"));
   // A renumbered handle keeps the order it has while nodes are added -- new nodes are merged in, old ones stay where they are although
   // the cut has changed how many elements sit on them, so rows of unlike length come to share a slice and the matrix pads.  Measured at
   // 1.1M tets (tools/probe_resync_delta.py): 9 % more nodes merged in, 42.5 us per PCG iteration against 30.6 in a fresh order -- 26 ms per
@@ -798,6 +799,48 @@ int prewarm_delta(fb_fem_s* h, int n_fixed, const int* fixed) {
 }
 
 }  // namespace
+
+extern "C++" {
+namespace fb {  // for parts.hip
+// The rest positions of a renumbered handle have moved (fb_fem_split_parts): its node order was derived from the old ones, and so were the
+// keys later cuts merge their new nodes by.  The handle is built again from its own mesh on the device -- the full builder of
+// fb_fem_resync_delta with an empty change, which derives the order a new handle of the moved mesh would get -- and q, qvel, (qaccel) and
+// the external forces are carried across in the caller's order, as FB_CUT_CARRY carries the state.  The labels of the parts hold the
+// caller's ids and the element order, which do not change: they stay valid (PartsWork's arrays in the internal order are the build's own
+// scratch, see parts.h).  Called for a handle with an active renumbering only -- which an unsharded handle has from build_plan_on_device
+// alone, so its plan is device-built.  fb_fem_resync_path reports the rebuild (FB_RESYNC_DELTA_REBUILT).  A failure inside the rebuild
+// leaves the handle poisoned like any failed re-sync.
+int refresh_node_order(fb_fem_s* h) {
+  if (!h->ren.active || !h->device_plan) return fail(FB_EINVAL, "refresh_node_order: the handle has no internal node order");
+  hipStream_t s = h->stream;
+  const int n = h->plan.n_global;
+  const size_t len = (size_t)3 * n;
+  const bool newmark = h->prm.integrator == FB_INTEGRATOR_NEWMARK;
+  DevBuf<double>* vec[4] = {&h->q, &h->qvel, &h->fext, &h->qacc};
+  const int n_vec = newmark ? 4 : 3;
+  FB_TRY(h->carry.reserve(len * n_vec));
+  for (int v = 0; v < n_vec; v++) {
+    double* dst = h->carry.p + len * v;
+    FB_TRY(gather_nodes(s, n, 3, vec[v]->p, h->ren.d_new_of_old.p, dst));
+  }
+  const std::vector<int> fixed = h->fixed_caller;
+  const bool labels = h->parts.valid;
+  FB_HIP(hipStreamSynchronize(s));
+  ResyncScope scope(h);
+  FB_TRY(resync_delta(h, 0, nullptr, 0, nullptr, nullptr, 0, nullptr, 0, nullptr, (int)fixed.size(), fixed.data(), false, true));
+  for (int v = 0; v < n_vec; v++) {
+    const double* src = h->carry.p + len * v;
+    // (the builder may have decided against an order for the moved mesh: FB_RENUMBER_AUTO)
+    if (h->ren.active) FB_TRY(gather_nodes(s, n, 3, src, h->ren.d_old_of_new.p, vec[v]->p));
+    else FB_HIP(hipMemcpyAsync(vec[v]->p, src, sizeof(double) * len, hipMemcpyDeviceToDevice, s));
+  }
+  FB_HIP(hipStreamSynchronize(s));
+  h->parts.valid = labels;
+  scope.commit();
+  return FB_OK;
+}
+}  // namespace fb
+}  // extern "C++"
 
 int fb_fem_resync_delta(fb_fem_t h, int n_removed, const int* removed, int n_changed, const int* changed_ids, const int* changed_nodes, int n_added,
                         const int* added_tets, int n_new_nodes, const double* new_xyz, int n_fixed_dofs, const int* fixed_dofs) {

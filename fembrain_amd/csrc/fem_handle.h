@@ -1,6 +1,6 @@
 // The FEM handle (fb_fem_t of include/fembrain_hip.h) and what the units that work on it share: fem.hip (assembly, the two-launch
 // solver, the steps and the rest of the C ABI), fem_build.hip (life cycle: plan build, creation, re-sync, cut), fem_persist.hip (the
-// persistent solver's host side), haptic.hip (the probe's entry points) and stress.hip (element stress and strain).
+// persistent solver's host side), haptic.hip (the probe's entry points), stress.hip (element stress and strain) and parts.hip (disjoint parts).
 // Internal: not installed, included by these units only.
 #pragma once
 #include "comm.h"
@@ -14,6 +14,7 @@
 #include "surface.h"
 #include "haptic.h"
 #include "stress.h"
+#include "parts.h"
 
 namespace fb {
 
@@ -183,6 +184,7 @@ struct fb_fem_s {
   DevBuf<double> carry;   // fb_fem_cut, FB_CUT_CARRY: the state in the caller's order across the re-sync
   SurfaceWork surf;       // fb_fem_surface: the boundary of the current mesh (surface.h); empty until somebody asks
   StressWork stress;      // fb_fem_stress: von Mises, energy density, J (and tensors) per element of the last call (stress.h); empty until somebody asks
+  PartsWork parts;        // fb_fem_parts: face-connected parts of the current mesh (parts.h); empty until somebody asks
   HapticWork hap;         // fb_fem_add_haptic_forces / pick / volume: level array and scratch (haptic.h); empty until somebody asks
   std::vector<int> fixed_caller;  // the constrained DOFs in the caller's numbering (unsharded): what fb_fem_cut keeps
   DevBuf<int4> tets_next, tets_caller;   // (the element list being built; swapped with `tets`)
@@ -206,8 +208,8 @@ struct fb_fem_s {
   fb::HostKnobs knobs;               // as the last plan build read them
   fb::AsmKernels asm_k;              // the assembly kernels of this plan
   // Per mesh generation -- begin_mesh_generation (fem_build.hip) is the one place that resets them, for build(), its host-builder fallback
-  // and fb_fem_resync_delta: ren, l2c, order_sum, x0_ready, masks_ready, caller_pattern, csr_ready, span_stale (all below), surf.valid and
-  // stress.valid (above); batch_graph is dropped with them.  (fb_fem_resync_delta keeps ren, and csr_ready while it decides, and says so.)
+  // and fb_fem_resync_delta: ren, l2c, order_sum, x0_ready, masks_ready, caller_pattern, csr_ready, span_stale (all below), surf.valid,
+  // stress.valid and parts.valid (above); batch_graph is dropped with them.  (fb_fem_resync_delta keeps ren, and csr_ready while it decides, and says so.)
   // locality renumbering behind the ABI (renumber.h): the handle works in its own node order, ids are mapped on the way in and out
   Renumbering ren;
   DevBuf<double> xyz_in;               // the caller-order rest positions the order was derived from
@@ -322,6 +324,8 @@ int timed_median(fb_fem_s* h, int reps, Body body, double* seconds) {
 int assemble_system(fb_fem_s* h);
 int handle_slack_now(const fb_fem_s* h);   // the slack rule of this handle's allocations at its current mesh (SlackScope)
 int surface_current(fb_fem_s* h);          // builds the surface where it is stale (fb_fem_surface_update's first step)
+// fem_build.hip
+int refresh_node_order(fb_fem_s* h);      // a renumbered handle whose rest positions moved: built again in the order a new handle would get, state and forces carried
 // ... and what fem_build.hip builds a handle with
 int handle_slack(const fb_fem_s* h, int n_nodes, int n_tets);  // the slack rule at a mesh of this size
 int renumber_mode(const fb_fem_s* h);      // FB_RENUMBER_* of this handle

@@ -245,6 +245,67 @@ class FemIntegrator:
         _l.check(self._L.fb_fem_time_surface(self.h, reps, C.byref(b), C.byref(u)))
         return b.value, u.value
 
+    # -- disjoint parts of the (cut) mesh on the device (fb_fem_parts / split_parts / read_part; unsharded handles) --
+    def parts(self):
+        """The face-connected parts of the mesh the device holds (fb_fem_parts; VolMesh::get_disjoint_parts): dict of n_parts,
+        n_builds, largest_part, n_shared_nodes (nodes of more than one part) and n_unused_nodes.  Labelled on the device, and again
+        only after the mesh has changed."""
+        info = _l.PartsInfo()
+        _l.check(self._L.fb_fem_parts(self.h, C.byref(info)))
+        return {name: getattr(info, name) for name, _ in _l.PartsInfo._fields_}
+
+    def element_parts(self):
+        """(n_tets,) int32: the part of every element, ``read_mesh``'s element order; parts ascend with their smallest element"""
+        out = np.zeros(int(self._L.fb_fem_num_tets(self.h)), np.int32)
+        _l.check(self._L.fb_fem_read_parts(self.h, _l.iptr(out), None, None, None, None, None))
+        return out
+
+    def node_parts(self):
+        """(n_nodes,) int32: the lowest part whose elements use the node (caller ids), -1 for a node no element uses"""
+        out = np.zeros(int(self._L.fb_fem_num_nodes(self.h)), np.int32)
+        _l.check(self._L.fb_fem_read_parts(self.h, None, _l.iptr(out), None, None, None, None))
+        return out
+
+    def part_table(self):
+        """Per part: dict of elements, nodes (a shared node counts in each of its parts), first_element (n_parts,) int32 and volume
+        (n_parts,) float64, the rest volume of the part's elements summed in a fixed order"""
+        n = self.parts()["n_parts"]
+        el, nd, fe, vol = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n)
+        _l.check(self._L.fb_fem_read_parts(self.h, None, None, _l.iptr(el), _l.iptr(nd), _l.iptr(fe), _l.dptr(vol)))
+        return dict(elements=el, nodes=nd, first_element=fe, volume=vol)
+
+    def split_parts(self, quad, dist, track=True):
+        """``CuttableMesh::splitParts(sweptquad, dist)`` on the rest positions (fb_fem_split_parts): the parts wholly in front of the
+        quad's plane move by +shift, those wholly behind by -shift, straddling parts stay.  Returns the dict of n_front_parts,
+        n_back_parts, n_straddling_parts, n_nodes_moved and shift (3,).  With track, ``self.verts`` follows."""
+        qd = np.ascontiguousarray(quad, dtype=np.float64).reshape(-1)
+        if qd.size != 12:
+            raise ValueError("a quad is four xyz points")
+        info = _l.SplitInfo()
+        _l.check(self._L.fb_fem_split_parts(self.h, _l.dptr(qd), float(dist), C.byref(info)))
+        if track:
+            self.verts = self.read_mesh()[0]
+        return dict(n_front_parts=int(info.n_front_parts), n_back_parts=int(info.n_back_parts), n_straddling_parts=int(info.n_straddling_parts),
+                    n_nodes_moved=int(info.n_nodes_moved), shift=np.array(list(info.shift)))
+
+    def read_part(self, k):
+        """Part ``k`` as a mesh of its own (fb_fem_read_part; one iteration of ``convertDisjointPartsToMeshes``): (element_ids (m,),
+        node_ids (n,) caller ids in order of first use, rest_xyz (n, 3), tets_local (m, 4)) -- what a second ``FemIntegrator`` is made of"""
+        n = self.parts()["n_parts"]
+        if not 0 <= int(k) < n:
+            _l.check(self._L.fb_fem_read_part(self.h, int(k), None, None, None, None))
+        t = self.part_table()
+        m, nn = int(t["elements"][k]), int(t["nodes"][k])
+        ids, nodes, xyz, tl = np.zeros(m, np.int32), np.zeros(nn, np.int32), np.zeros((nn, 3)), np.zeros((m, 4), np.int32)
+        _l.check(self._L.fb_fem_read_part(self.h, int(k), _l.iptr(ids), _l.iptr(nodes), _l.dptr(xyz), _l.iptr(tl)))
+        return ids, nodes, xyz, tl
+
+    def time_parts(self, reps=20):
+        """(seconds per labelling, seconds per split): medians of ``reps`` HIP-event timings each (fb_fem_time_parts)"""
+        a, b = C.c_double(0), C.c_double(0)
+        _l.check(self._L.fb_fem_time_parts(self.h, reps, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def resync_path(self):
         """FB_RESYNC_* of the handle's last (re-)build"""
         return int(self._L.fb_fem_resync_path(self.h))
@@ -699,6 +760,18 @@ class Deformable:
         info, delta = self.integrator.cut(strip, mode=mode)
         self.dof, self._pattern = self.integrator.r, None
         return info, delta
+
+    def parts(self):
+        """``FemIntegrator.parts``: the disjoint parts of the (cut) body, counted on the device"""
+        return self.integrator.parts()
+
+    def split_parts(self, quad, dist):
+        """``FemIntegrator.split_parts``: the parts on either side of the quad's plane pushed apart by ``dist`` each"""
+        return self.integrator.split_parts(quad, dist)
+
+    def read_part(self, k):
+        """``FemIntegrator.read_part``: part ``k`` as a mesh of its own"""
+        return self.integrator.read_part(k)
 
     def _positions(self):
         it = self.integrator

@@ -63,6 +63,14 @@ class SurfaceInfo(C.Structure):
     _fields_ = [("n_faces", C.c_int), ("n_vertices", C.c_int), ("n_builds", C.c_int), ("aabb_lo", C.c_float * 3), ("aabb_hi", C.c_float * 3)]
 
 
+class PartsInfo(C.Structure):
+    _fields_ = [("n_parts", C.c_int), ("n_builds", C.c_int), ("largest_part", C.c_int), ("n_shared_nodes", C.c_int), ("n_unused_nodes", C.c_int)]
+
+
+class SplitInfo(C.Structure):
+    _fields_ = [("n_front_parts", C.c_int), ("n_back_parts", C.c_int), ("n_straddling_parts", C.c_int), ("n_nodes_moved", C.c_int), ("shift", C.c_double * 3)]
+
+
 class StressInfo(C.Structure):
     _fields_ = [("n_elements", C.c_int), ("flags", C.c_int), ("max_von_mises", C.c_double), ("max_element", C.c_int), ("min_J", C.c_double),
                 ("min_J_element", C.c_int), ("n_inverted", C.c_int), ("energy", C.c_double)]
@@ -137,6 +145,12 @@ def lib():
         "fb_fem_read_surface": (C.c_int, [vp, _ip, _ip, _ip]),
         "fb_fem_surface_update": (C.c_int, [vp, _fp, _fp, C.POINTER(SurfaceInfo)]),
         "fb_fem_time_surface": (C.c_int, [vp, C.c_int, _dp, _dp]),
+        "fb_fem_parts": (C.c_int, [vp, C.POINTER(PartsInfo)]),
+        "fb_fem_read_parts": (C.c_int, [vp, _ip, _ip, _ip, _ip, _ip, _dp]),
+        "fb_fem_split_parts": (C.c_int, [vp, _dp, C.c_double, C.POINTER(SplitInfo)]),
+        "fb_fem_read_part": (C.c_int, [vp, C.c_int, _ip, _ip, _dp, _ip]),
+        "fb_fem_time_parts": (C.c_int, [vp, C.c_int, _dp, _dp]),
+        "fb_fem_parts_wide": (C.c_int, [vp]),
         "fb_fem_rebuild_elements": (C.c_int, [vp]),
         "fb_fem_set_external_forces": (C.c_int, [vp, _dp]),
         "fb_fem_add_external_forces": (C.c_int, [vp, _dp]),

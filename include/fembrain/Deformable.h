@@ -207,6 +207,9 @@ class HipIntegrator {
     elements.resize(4 * (size_t)fb_fem_num_tets(h_));
     check(fb_fem_read_mesh(h_, rest.data(), elements.data()));
   }
+  // fb_fem_parts / fb_fem_split_parts: the disjoint parts of the device's mesh, and the parts on either side of a quad pushed apart
+  void Parts(fb_fem_parts_info* out) { check(fb_fem_parts(h_, out)); }
+  void SplitParts(const double quad[12], double dist, fb_fem_split_info* out) { check(fb_fem_split_parts(h_, quad, dist, out)); }
   fb_fem_t handle() const { return h_; }
   static void check(int rc) {
     if (rc != FB_OK) throw std::runtime_error(std::string("fembrain_hip: ") + fb_last_error());
@@ -413,6 +416,49 @@ class Deformable {
     m_restVolume = -1.0;
     surfaceChanged();
     return r.n_removed;
+  }
+  // VolMesh::get_disjoint_parts (VolMesh.cpp:915-965), counted and labelled on the device (fb_fem_parts): the face-connected parts of
+  // the mesh the handle holds, in ascending order of their smallest cell.
+  int countDisjointParts() {
+    if (!m_lpIntegrator) syncForceModel();
+    fb_fem_parts_info info;
+    m_lpIntegrator->Parts(&info);
+    return info.n_parts;
+  }
+  // ... and the reference's signature and grouping: cells ascending inside a part.  Returns the number of parts.
+  int getDisjointParts(std::vector<std::vector<U32> >& cellgroups) {
+    const int n = countDisjointParts();
+    std::vector<int> part((size_t)fb_fem_num_tets(m_lpIntegrator->handle()));
+    HipIntegrator::check(fb_fem_read_parts(m_lpIntegrator->handle(), part.data(), nullptr, nullptr, nullptr, nullptr, nullptr));
+    cellgroups.assign((size_t)n, std::vector<U32>());
+    for (size_t e = 0; e < part.size(); e++) cellgroups[(size_t)part[e]].push_back((U32)e);
+    return n;
+  }
+  // CuttableMesh::splitParts(sweptquad, dist) (CuttableMesh.cpp:553-626) on the rest shape (fb_fem_split_parts): the parts wholly in front
+  // of the quad move by + normal * dist, those wholly behind by - normal * dist.  The host copy of the rest positions follows.
+  bool splitParts(const vec3d sweptquad[4], double dist) {
+    if (!m_lpIntegrator) syncForceModel();
+    double quad[12];
+    for (int i = 0; i < 4; i++) { quad[3 * i] = sweptquad[i].x; quad[3 * i + 1] = sweptquad[i].y; quad[3 * i + 2] = sweptquad[i].z; }
+    fb_fem_split_info info;
+    m_lpIntegrator->SplitParts(quad, dist, &info);
+    m_lpIntegrator->ReadMesh(m_rest, m_elements);
+    m_restVolume = -1.0;
+    surfaceChanged();
+    return true;
+  }
+  // One iteration of CuttableMesh::convertDisjointPartsToMeshes' loop (CuttableMesh.cpp:644-689; fb_fem_read_part): part `part` as the
+  // flat node and cell arrays a CuttableMesh (or a second Deformable) is made of, nodes in order of first use.  Nothing is deleted here.
+  void readPart(int part, std::vector<double>& xyz, std::vector<U32>& cells) {
+    const int n = countDisjointParts();
+    if (part < 0 || part >= n) throw std::runtime_error("fembrain_hip: readPart: no such part");
+    std::vector<int> el((size_t)n), nd((size_t)n);
+    fb_fem_t h = m_lpIntegrator->handle();
+    HipIntegrator::check(fb_fem_read_parts(h, nullptr, nullptr, el.data(), nd.data(), nullptr, nullptr));
+    xyz.resize(3 * (size_t)nd[(size_t)part]);
+    std::vector<int> local(4 * (size_t)el[(size_t)part]);
+    HipIntegrator::check(fb_fem_read_part(h, part, nullptr, nullptr, xyz.data(), local.data()));
+    cells.assign(local.begin(), local.end());
   }
   void setMesh(int numVertices, const double* rest, int numElements, const int* elements) {
     m_rest.assign(rest, rest + 3 * (size_t)numVertices);

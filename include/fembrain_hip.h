@@ -301,6 +301,64 @@ int fb_fem_surface_update(fb_fem_t h, float* xyz, float* normals, fb_fem_surface
  * pointer may be NULL.  The build's figure includes its two host waits. */
 int fb_fem_time_surface(fb_fem_t h, int reps, double* seconds_build, double* seconds_update);
 
+/* ---- Disjoint parts of the (cut) mesh, on the device ----
+ * What the reference does after every completed cut: VolMesh::get_disjoint_parts (src/deformable/VolMesh.cpp:915-965) counts the parts,
+ * CuttableMesh::splitParts (src/deformable/CuttableMesh.cpp:553-626) pushes the parts on either side of the swept quad apart, and
+ * convertDisjointPartsToMeshes (:628-698) makes a mesh of each.  Unsharded handles only (FB_EINVAL otherwise), device- or host-built plan
+ * alike.  A handle that never asks allocates and launches nothing.
+ *
+ * Two elements are adjacent exactly when they share a face (an equal sorted triple of node ids); an edge or a node in common does not
+ * connect, and a face that three or more elements carry connects all of them.  Parts are numbered in ascending order of their smallest
+ * element id (the order get_disjoint_parts produces).  Elements are in fb_fem_read_mesh's order, node ids are the CALLER's, also on a
+ * renumbered handle.
+ * Staleness as for the surface: creation, fb_fem_resync, fb_fem_resync_delta and a fb_fem_cut that returns FB_CUT_DONE make the labels
+ * stale; a step, a state change, a cut that changes nothing and fb_fem_split_parts do not.  Every call below labels first when stale
+ * (n_builds counts the labellings of this handle). */
+typedef struct fb_fem_parts_info {
+  int n_parts;          /* face-connected components of the element list */
+  int n_builds;         /* labellings this handle has run */
+  int largest_part;     /* index of the part with the most elements (lowest index of equals) */
+  int n_shared_nodes;   /* nodes used by elements of more than one part (parts touching at a node or an edge only) */
+  int n_unused_nodes;   /* nodes no element uses */
+} fb_fem_parts_info;
+int fb_fem_parts(fb_fem_t h, fb_fem_parts_info* out);
+/* element_part[fb_fem_num_tets]; node_part[fb_fem_num_nodes]: the lowest part whose elements use the node, -1 for a node no element
+ * uses; per part: part_elements[n_parts], part_nodes[n_parts] (nodes the part uses: a shared node counts in each of its parts),
+ * part_first_element[n_parts] (its smallest element id), part_volume[n_parts] (the sum of the rest volumes |det| / 6 of its elements in
+ * fp64, in a fixed order that depends on the element counts alone: the same bits from call to call; within part_elements[k] 2^-52
+ * relative of any other order of summation).  Any pointer may be NULL. */
+int fb_fem_read_parts(fb_fem_t h, int* element_part, int* node_part, int* part_elements, int* part_nodes, int* part_first_element, double* part_volume);
+/* CuttableMesh::splitParts(sweptquad, dist) on the REST positions.  n = normalised (q1 - q0) x (q2 - q0), c = the mean of the four
+ * points; an element is in front when dot(centroid(x0 + q) - c, n) > 0 (the centroid: a quarter of the sum of its four current
+ * positions, fp64).  A part whose elements are all in front is a front part, one with none in front a back part, every other part
+ * straddles and is left alone.  Every node a front part uses gets + shift, every node a back part uses - shift (shift = n * dist, computed
+ * once and returned), a node of both gets both and stays: one fp64 add per coordinate.  The reference moves `pos`, which its
+ * syncForceModel bakes into the rest shape; after a FB_CUT_BAKE cut q is zero and the two coincide.
+ * q, qvel, qaccel and the external forces are untouched; the element rest data are made again as by fb_fem_rebuild_elements; surface and
+ * stress become stale; the labels stay valid (part_volume is summed again).  Later re-syncs and cuts start from the moved positions.
+ * A handle that works in an internal node order (fb_fem_renumbering) derived that order from the old positions: it is built again from its
+ * own mesh on the device, in the order a handle created from fb_fem_read_mesh's arrays would get, with q, qvel, qaccel and the external
+ * forces carried across -- the cost of a full fb_fem_resync_delta rebuild, once per split; fb_fem_resync_path then reports
+ * FB_RESYNC_DELTA_REBUILT.  (Such a handle always has a device-built plan: a host-built plan keeps the caller's order.)  Should that
+ * rebuild fail, the positions have moved already and the handle is unusable until a full fb_fem_resync, as after any failed re-sync.
+ * FB_EINVAL with nothing changed: a quad whose first three points span no plane, a coordinate or a dist that is not finite. */
+typedef struct fb_fem_split_info {
+  int n_front_parts, n_back_parts, n_straddling_parts;
+  int n_nodes_moved;       /* nodes whose rest position changed */
+  double shift[3];         /* the unit normal times dist: what was added to front nodes and subtracted from back nodes */
+} fb_fem_split_info;
+int fb_fem_split_parts(fb_fem_t h, const double quad_xyz[12], double dist, fb_fem_split_info* out);
+/* One part as a mesh of its own (one iteration of convertDisjointPartsToMeshes' loop; nothing is deleted from the handle):
+ * element_ids[part_elements[part]] ascending; node_ids[part_nodes[part]] the caller ids of its nodes in order of first use when those
+ * elements are walked in ascending order, corners 0..3 (the order the reference's mapNodes assigns); rest_xyz[3 part_nodes] their rest
+ * positions; tets_local[4 part_elements] the elements in that local numbering.  Pointers may be NULL.  Only the part's arrays leave the
+ * device.  FB_EINVAL for a part outside [0, n_parts). */
+int fb_fem_read_part(fb_fem_t h, int part, int* element_ids, int* node_ids, double* rest_xyz, int* tets_local);
+/* Device time of `reps` forced labellings (host waits included) and of `reps` splits (HIP events on the handle's stream around each;
+ * the medians).  The timed split runs a split's device work -- classification against the plane x = 0, node marks, the pass over the
+ * nodes, the element rest data, the volumes -- with a zero shift and without its stores: nothing moves.  Either pointer may be NULL. */
+int fb_fem_time_parts(fb_fem_t h, int reps, double* seconds_label, double* seconds_split);
+
 
 /* Per-element rest-state rebuild on the device (M^-1 rows / volume, corotationalLinearFEM.cpp:66-90 and
  * tetMesh.cpp:184-188) -- the per-step "K0 rebuild" of BASELINE config 4. */

@@ -50,6 +50,11 @@ int fb_comm_create_local(struct fb_comm_s** out, int rank, int n_ranks, const ch
  * order -- the barrier pair every collective of the transport is made of. */
 int fb_comm_test_allgather(struct fb_comm_s* c, const void* mine, void* all, size_t bytes);
 
+/* Host-only: 1 when the handle's last labelling of its parts (fb_fem_parts) sorted the faces in two passes (more than 2^21 nodes, or
+ * FEMBRAIN_PARTS_WIDE_KEYS=1), 0 when in one, -1 when it has not labelled yet. */
+struct fb_fem_s;
+int fb_fem_parts_wide(struct fb_fem_s* h);
+
 /* Host-only: compiles a BlobTree (operator walk order, slot allocation, expansion of instanced subtrees) exactly as
  * fb_poly_create does and reports the number of evaluation steps and of per-point value slots; needs no device.
  * Lets the CPU suite check every reference model's tree, including the instanced ones. */
