@@ -115,6 +115,50 @@ struct DevBuf {
 
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// ---- the timing entry points' common sequences, for any handle with a `stream` and events `ev` of its own (fb_fem_s, fb_poly_s); warm-up calls
+// stay with the caller.  ev[0], `body` reps times, ev[1], wait, seconds per repetition
+template <typename Handle, typename Body>
+int timed_reps(Handle* h, int reps, Body body, double* seconds_per_rep) {
+  FB_HIP(hipEventRecord(h->ev[0], h->stream));
+  for (int r = 0; r < reps; r++) FB_TRY(body());
+  FB_HIP(hipEventRecord(h->ev[1], h->stream));
+  FB_HIP(hipStreamSynchronize(h->stream));
+  float ms = 0;
+  FB_HIP(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+  *seconds_per_rep = ms * 1e-3 / reps;
+  return FB_OK;
+}
+// ... each repetition timed and waited for on its own: the median (fb_fem_time_surface, fb_fem_time_stress)
+template <typename Handle, typename Body>
+int timed_median(Handle* h, int reps, Body body, double* seconds) {
+  std::vector<double> t((size_t)reps);
+  for (double& x : t) FB_TRY(timed_reps(h, 1, body, &x));
+  std::sort(t.begin(), t.end());
+  *seconds = t[t.size() / 2];
+  return FB_OK;
+}
+// ... a pipeline timed stage by stage.  Per repetition: ev[k] before stage(k) for k < n_stages, ev[n_stages] after the last, wait; seconds[i] is
+// the time from ev[pairs[i][0]] to ev[pairs[i][1]], per repetition
+template <int n_stages, typename Handle, typename Stage, size_t NP>
+int timed_stages(Handle* h, int reps, Stage stage, const int (&pairs)[NP][2], double* seconds) {
+  static_assert(sizeof(Handle::ev) / sizeof(hipEvent_t) > n_stages, "an event before every stage and one after the last");
+  std::fill(seconds, seconds + NP, 0.0);
+  for (int r = 0; r < reps; r++) {
+    for (int k = 0; k < n_stages; k++) {
+      FB_HIP(hipEventRecord(h->ev[k], h->stream));
+      FB_TRY(stage(k));
+    }
+    FB_HIP(hipEventRecord(h->ev[n_stages], h->stream));
+    FB_HIP(hipStreamSynchronize(h->stream));
+    for (size_t i = 0; i < NP; i++) {
+      float ms = 0;
+      FB_HIP(hipEventElapsedTime(&ms, h->ev[pairs[i][0]], h->ev[pairs[i][1]]));
+      seconds[i] += ms * 1e-3 / reps;
+    }
+  }
+  return FB_OK;
+}
+
 // the tet mesh a polygonizer handle holds on its device after fb_poly_tetrahedralize (poly.hip -> fem.hip hand-off):
 // positions 3 floats per vertex, elements 4 vertex ids per tet; the handle's stream has been synchronised
 // (xyz64: the positions as doubles instead -- the handle's own device copy, fb_fem_resync_delta)

@@ -298,28 +298,6 @@ struct ZeroBatch {   // (fem.hip, next to its kernel)
   int flush();
 };
 
-// The timing entry points' common sequence: ev[0], `body` reps times, ev[1], wait, seconds per repetition.  Warm-up calls stay with the caller.
-template <typename Body>
-int timed_reps(fb_fem_s* h, int reps, Body body, double* seconds_per_rep) {
-  FB_HIP(hipEventRecord(h->ev[0], h->stream));
-  for (int r = 0; r < reps; r++) FB_TRY(body());
-  FB_HIP(hipEventRecord(h->ev[1], h->stream));
-  FB_HIP(hipStreamSynchronize(h->stream));
-  float ms = 0;
-  FB_HIP(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-  *seconds_per_rep = ms * 1e-3 / reps;
-  return FB_OK;
-}
-// ... each repetition timed and waited for on its own: the median (fb_fem_time_surface, fb_fem_time_stress)
-template <typename Body>
-int timed_median(fb_fem_s* h, int reps, Body body, double* seconds) {
-  std::vector<double> t((size_t)reps);
-  for (double& x : t) FB_TRY(timed_reps(h, 1, body, &x));
-  std::sort(t.begin(), t.end());
-  *seconds = t[t.size() / 2];
-  return FB_OK;
-}
-
 // fem.hip
 int assemble_system(fb_fem_s* h);
 int handle_slack_now(const fb_fem_s* h);   // the slack rule of this handle's allocations at its current mesh (SlackScope)

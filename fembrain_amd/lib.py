@@ -86,17 +86,26 @@ class PolyCounts(C.Structure):
 def source_sha256(part=None):
     """Hash of the kernel sources (csrc/*.hip, *.h, *.cpp).  A profile under profiles/ records it; bench.py reports PMC traffic
     from that profile only while the kernels are still the ones that were profiled.  part = "fem": everything but the field / cutting
-    translation units (poly.hip, cut.hip); "poly": poly.hip and the shared headers it includes -- so that an edit of one half does not
-    retire the other half's profile."""
+    units (poly*, cut.hip); "poly": the polygonizer's units (poly.hip, poly_device.hip.h, poly_compile.cpp, poly_program.h: poly*) and the
+    shared headers of csrc/ they include, found by following their #include "..." lines -- so that an edit of one half does not retire
+    the other half's profile."""
     import hashlib
+    import re
     h = hashlib.sha256()
     d = os.path.join(_HERE, "csrc")
-    for name in sorted(os.listdir(d)):
-        if not name.endswith((".hip", ".h", ".cpp")):
+    names = sorted(n for n in os.listdir(d) if n.endswith((".hip", ".h", ".cpp")))
+    if part == "poly":
+        todo, included = [n for n in names if n.startswith("poly")], set()
+        while todo:
+            name = todo.pop()
+            if name not in included and name in names:
+                included.add(name)
+                todo += re.findall(r'^#include "([^"/]+)"', open(os.path.join(d, name)).read(), re.M)
+    for name in names:
+        poly = name.startswith("poly")
+        if part == "fem" and (poly or name == "cut.hip"):
             continue
-        if part == "fem" and name in ("poly.hip", "cut.hip"):
-            continue
-        if part == "poly" and name not in ("poly.hip", "common.h"):
+        if part == "poly" and name not in included:
             continue
         h.update(name.encode())
         h.update(open(os.path.join(d, name), "rb").read())

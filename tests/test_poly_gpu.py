@@ -328,6 +328,31 @@ def test_surface_on_ragged_and_empty_grids(gpu):
     assert xyz.shape == (0, 3) and tri.shape == (0, 3)
 
 
+@pytest.mark.parametrize("name,lower,cell,dims", [("nested", (-1.12, -0.35, -0.4), 0.035, (64, 19, 23)), ("sphere", (-1.08, -0.6, -0.51), 0.06, (37, 21, 18))])
+def test_timing_entry_points_leave_the_results_as_they_were(gpu, name, lower, cell, dims):
+    """fb_poly_time_pipeline, _stages, _grid and _surface run the pipeline's launches again on the handle's own buffers: afterwards the grid,
+    the classification, the counts, the tet mesh and the surface read what they read before, bit for bit.  `nested` on rows of 64 points runs
+    the culled sweep and k_classify<ROWS64>, the sphere on rows of 37 the unculled sweep and the kernel that loads the masks.
+    Times: finite and positive; the four stage times are differences of the five events whose ends the staged total spans, so their sum is
+    the total but for fp32 rounding -- each of the five passes through a few fp32 roundings (2^-24 relative each), 2^-20 of the total in all."""
+    blob = sphere_blob() if name == "sphere" else _trees()[name]
+    g = GpuPoly(blob)
+    lower = np.array(lower, np.float32)
+    assert g.sweep_grid(lower, cell, dims) == dims
+    own = OrcPoly(blob).sweep_grid(lower, cell, dims)
+    before = _assert_pipeline_on_device_grid(blob, g, own)
+    grid = g.read_grid()
+    times = list(g.time_pipeline(2)) + list(g.time_stages(2)) + [g.time_grid(2), g.time_surface(2)]
+    assert np.isfinite(times).all() and min(times) > 0
+    stages = times[2:7]
+    assert sum(stages[:4]) <= stages[4] * (1 + 2.0 ** -20)
+    assert times[0] <= times[1]  # the sweep is the first part of the pipeline
+    assert np.array_equal(g.read_grid(), grid)
+    after = pi.assert_pipeline_equals(g, pi.oracle_on_grid(blob, g.lower, g.cellsize, g.dims, grid), pi.normals_tol(blob, np.array_equal(grid, own)))
+    pi.assert_runs_identical(before, after)
+    g.close()
+
+
 def test_apply_fem_displacements(gpu):
     from fembrain_amd import lib as fl
     from fembrain_amd.poly import MESH_SURFACE, MESH_TET
