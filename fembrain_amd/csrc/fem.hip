@@ -1160,6 +1160,24 @@ extern "C++" {
 namespace fb {  // for stress.hip
 int handle_slack_now(const fb_fem_s* h) { return handle_slack(h, h->plan.n_global, h->plan.n_tets); }
 int surface_current(fb_fem_s* h) { return surface_ready(h, false); }
+// for detach.hip: what fb_fem_set_internal_force_scaling, fb_fem_set_materials and fb_fem_set_element_materials leave in a handle, from
+// src's values and an id array filled on the device.  As there, the table and the kernels first and the map last: a failure leaves no map.
+int inherit_materials(fb_fem_s* h, const fb_fem_s* src, DevBuf<unsigned char>* ids) {
+  const double scale_before = h->force_scale;
+  h->force_scale = src->force_scale;  // (the device table is made under it)
+  if (ids) {
+    int rc = upload_material_table(h, (int)src->mat_E.size(), src->mat_E.data(), src->mat_nu.data(), src->mat_rho.data());
+    if (rc == FB_OK) rc = resolve_asm_kernels(h, true);
+    if (rc != FB_OK) { h->force_scale = scale_before; return rc; }  // (the host side as it was)
+    h->mat_ids.swap(*ids);
+    h->mat_hi = src->mat_hi;  // (an upper bound of the ids in use, as in src)
+  }
+  h->mat_E = src->mat_E; h->mat_nu = src->mat_nu; h->mat_rho = src->mat_rho;
+  lame_of(h->prm.E * h->force_scale, h->prm.nu, &h->lambda, &h->mu);
+  h->system_valid = false;
+  h->mass_valid = false;
+  return FB_OK;
+}
 }  // namespace fb
 }  // extern "C++"
 

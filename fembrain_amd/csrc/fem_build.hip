@@ -687,7 +687,8 @@ int resync_delta(fb_fem_s* h, int n_removed, const int* removed, int n_changed, 
     // the element map through the change, on the device: kept and changed elements keep their material in order, the pieces of a cut
     // inherit their parent's (k_cut_pieces' cut_tets / piece_off), other added elements get 0.  Swapped in when the re-sync is complete.
     FB_TRY(h->mat_ids_next.alloc((size_t)std::max(1, nt_new)));
-    if (device_src) FB_TRY(delta_element_bytes(s, D, h->mat_ids.p, h->mat_ids_next.p, h->cut.n_cut, h->cut.cut_tets.p, h->cut.piece_off.p, h->cut.pcount.p));
+    // (device_src with nothing added: a part's elements taken out, remove_elements_device -- no cut stands behind it)
+    if (device_src && n_added) FB_TRY(delta_element_bytes(s, D, h->mat_ids.p, h->mat_ids_next.p, h->cut.n_cut, h->cut.cut_tets.p, h->cut.piece_off.p, h->cut.pcount.p));
     else FB_TRY(delta_element_bytes(s, D, h->mat_ids.p, h->mat_ids_next.p));
   }
   lap("change uploaded");
@@ -798,6 +799,38 @@ int prewarm_delta(fb_fem_s* h, int n_fixed, const int* fixed) {
   return FB_OK;
 }
 
+// A delta re-sync that only takes elements out (n_removed ascending ids in a DEVICE list; none: the empty change) with q, qvel, (qaccel)
+// and the external forces carried across it: a re-sync leaves the vectors zero, and the rebuilt path gives a renumbered handle a new
+// order, so they go out in the caller's order before it and come back in the order it left.  force_rebuild: the full builder whatever
+// there is to merge into.  The list is copied on the handle's stream by the re-sync's first step.  A failure inside the re-sync leaves
+// the handle poisoned like any failed re-sync.
+int resync_delta_carrying(fb_fem_s* h, int n_removed, const int* d_removed, bool force_rebuild) {
+  hipStream_t s = h->stream;
+  const int n = h->plan.n_global;
+  const size_t len = (size_t)3 * n;
+  DevBuf<double>* vec[4] = {&h->q, &h->qvel, &h->fext, &h->qacc};
+  const int n_vec = h->prm.integrator == FB_INTEGRATOR_NEWMARK ? 4 : 3;
+  FB_TRY(h->carry.reserve(len * n_vec));
+  for (int v = 0; v < n_vec; v++) {
+    double* dst = h->carry.p + len * v;
+    if (h->ren.active) FB_TRY(gather_nodes(s, n, 3, vec[v]->p, h->ren.d_new_of_old.p, dst));
+    else FB_HIP(hipMemcpyAsync(dst, vec[v]->p, sizeof(double) * len, hipMemcpyDeviceToDevice, s));
+  }
+  const std::vector<int> fixed = h->fixed_caller;
+  FB_HIP(hipStreamSynchronize(s));
+  ResyncScope scope(h);
+  FB_TRY(resync_delta(h, n_removed, d_removed, 0, nullptr, nullptr, 0, nullptr, 0, nullptr, (int)fixed.size(), fixed.data(), n_removed > 0, force_rebuild));
+  for (int v = 0; v < n_vec; v++) {
+    const double* src = h->carry.p + len * v;
+    // (the builder may have decided against an order for the new mesh: FB_RENUMBER_AUTO)
+    if (h->ren.active) FB_TRY(gather_nodes(s, n, 3, src, h->ren.d_old_of_new.p, vec[v]->p));
+    else FB_HIP(hipMemcpyAsync(vec[v]->p, src, sizeof(double) * len, hipMemcpyDeviceToDevice, s));
+  }
+  FB_HIP(hipStreamSynchronize(s));
+  scope.commit();
+  return FB_OK;
+}
+
 }  // namespace
 
 extern "C++" {
@@ -812,33 +845,23 @@ namespace fb {  // for parts.hip
 // leaves the handle poisoned like any failed re-sync.
 int refresh_node_order(fb_fem_s* h) {
   if (!h->ren.active || !h->device_plan) return fail(FB_EINVAL, "refresh_node_order: the handle has no internal node order");
-  hipStream_t s = h->stream;
-  const int n = h->plan.n_global;
-  const size_t len = (size_t)3 * n;
-  const bool newmark = h->prm.integrator == FB_INTEGRATOR_NEWMARK;
-  DevBuf<double>* vec[4] = {&h->q, &h->qvel, &h->fext, &h->qacc};
-  const int n_vec = newmark ? 4 : 3;
-  FB_TRY(h->carry.reserve(len * n_vec));
-  for (int v = 0; v < n_vec; v++) {
-    double* dst = h->carry.p + len * v;
-    FB_TRY(gather_nodes(s, n, 3, vec[v]->p, h->ren.d_new_of_old.p, dst));
-  }
-  const std::vector<int> fixed = h->fixed_caller;
   const bool labels = h->parts.valid;
-  FB_HIP(hipStreamSynchronize(s));
-  ResyncScope scope(h);
-  FB_TRY(resync_delta(h, 0, nullptr, 0, nullptr, nullptr, 0, nullptr, 0, nullptr, (int)fixed.size(), fixed.data(), false, true));
-  for (int v = 0; v < n_vec; v++) {
-    const double* src = h->carry.p + len * v;
-    // (the builder may have decided against an order for the moved mesh: FB_RENUMBER_AUTO)
-    if (h->ren.active) FB_TRY(gather_nodes(s, n, 3, src, h->ren.d_old_of_new.p, vec[v]->p));
-    else FB_HIP(hipMemcpyAsync(vec[v]->p, src, sizeof(double) * len, hipMemcpyDeviceToDevice, s));
-  }
-  FB_HIP(hipStreamSynchronize(s));
+  FB_TRY(resync_delta_carrying(h, 0, nullptr, true));
   h->parts.valid = labels;
-  scope.commit();
   return FB_OK;
 }
+
+// for detach.hip: the piece of fb_fem_detach_part.  dm's arrays belong to another handle of the same device; the new handle's own stream
+// copies them, so whoever wrote them has been waited for, and creation ends with a wait for the new stream (the rest-state check).
+int create_from_device_mesh(fb_fem_t* out, const DeviceTetMesh& dm, int n_fixed, const int* fixed, const fb_fem_params* params) {
+  return create_common(out, dm.n_vertices, nullptr, dm.n_tets, nullptr, n_fixed, fixed, params, 1, 0, nullptr, nullptr, &dm);
+}
+
+// ... and the removal of its elements from the parent: fb_fem_resync_delta's device-fed removal (the order of the rest is kept, no node
+// goes: the nodes only the removed elements used get identity rows).  A re-sync leaves the vectors zero, so q, qvel, (qaccel) and the
+// external forces are carried across in the caller's order, as refresh_node_order carries them -- the change may take either path of the
+// delta re-sync, and the rebuilt one gives a renumbered handle a new order.
+int remove_elements_device(fb_fem_s* h, int n_removed, const int* d_removed) { return resync_delta_carrying(h, n_removed, d_removed, false); }
 }  // namespace fb
 }  // extern "C++"
 
@@ -890,6 +913,7 @@ int fb_fem_set_constrained_dofs(fb_fem_t h, int n_fixed_dofs, const int* fixed_d
   } else {
     FB_TRY(plan_set_constraints(h->plan, n_fixed_dofs, fixed_dofs));
     FB_TRY(upload_masks(h));
+    if (h->plan.n_ranks == 1) h->fixed_caller.assign(fixed_dofs, fixed_dofs + n_fixed_dofs);  // (fb_fem_read_constrained_dofs)
   }
   h->system_valid = false;
   return FB_OK;

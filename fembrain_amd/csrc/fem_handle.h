@@ -1,6 +1,7 @@
 // The FEM handle (fb_fem_t of include/fembrain_hip.h) and what the units that work on it share: fem.hip (assembly, the two-launch
 // solver, the steps and the rest of the C ABI), fem_build.hip (life cycle: plan build, creation, re-sync, cut), fem_persist.hip (the
-// persistent solver's host side), haptic.hip (the probe's entry points), stress.hip (element stress and strain) and parts.hip (disjoint parts).
+// persistent solver's host side), haptic.hip (the probe's entry points), stress.hip (element stress and strain), parts.hip (disjoint parts)
+// and detach.hip (a part into a handle of its own).
 // Internal: not installed, included by these units only.
 #pragma once
 #include "comm.h"
@@ -15,6 +16,7 @@
 #include "haptic.h"
 #include "stress.h"
 #include "parts.h"
+#include "detach.h"
 
 namespace fb {
 
@@ -185,6 +187,7 @@ struct fb_fem_s {
   SurfaceWork surf;       // fb_fem_surface: the boundary of the current mesh (surface.h); empty until somebody asks
   StressWork stress;      // fb_fem_stress: von Mises, energy density, J (and tensors) per element of the last call (stress.h); empty until somebody asks
   PartsWork parts;        // fb_fem_parts: face-connected parts of the current mesh (parts.h); empty until somebody asks
+  DetachWork detach;      // fb_fem_detach_part: the constrained DOFs of the part being detached (detach.h); empty until somebody asks
   HapticWork hap;         // fb_fem_add_haptic_forces / pick / volume: level array and scratch (haptic.h); empty until somebody asks
   std::vector<int> fixed_caller;  // the constrained DOFs in the caller's numbering (unsharded): what fb_fem_cut keeps
   DevBuf<int4> tets_next, tets_caller;   // (the element list being built; swapped with `tets`)
@@ -304,6 +307,10 @@ int handle_slack_now(const fb_fem_s* h);   // the slack rule of this handle's al
 int surface_current(fb_fem_s* h);          // builds the surface where it is stale (fb_fem_surface_update's first step)
 // fem_build.hip
 int refresh_node_order(fb_fem_s* h);      // a renumbered handle whose rest positions moved: built again in the order a new handle would get, state and forces carried
+// an unsharded handle from a mesh on its device (fp64 positions, local ids), on a stream of its own: fb_fem_create without the host hop
+int create_from_device_mesh(fb_fem_t* out, const DeviceTetMesh& dm, int n_fixed, const int* fixed, const fb_fem_params* params);
+// fb_fem_resync_delta(removed = the ascending device list) with q, qvel, (qaccel) and the external forces carried; a failure poisons the handle
+int remove_elements_device(fb_fem_s* h, int n_removed, const int* d_removed);
 // ... and what fem_build.hip builds a handle with
 int handle_slack(const fb_fem_s* h, int n_nodes, int n_tets);  // the slack rule at a mesh of this size
 int renumber_mode(const fb_fem_s* h);      // FB_RENUMBER_* of this handle
@@ -314,6 +321,11 @@ int launch_rest(fb_fem_s* h, int* first_flat = nullptr);
 void drop_graph(fb_fem_s* h);
 int widen_positions(hipStream_t s, long long n, const float* in, double* out);  // float positions handed over on the device -> doubles
 int download_owned(fb_fem_s* h, const DevBuf<double>& src, double* g);          // owned part of a device vector -> its place in a global-length host vector
+// the material side of a handle made from elements of `src`: force scaling and table, and -- ids non-null -- the filled element map (swapped in)
+int inherit_materials(fb_fem_s* h, const fb_fem_s* src, DevBuf<unsigned char>* ids);
+
+// parts.hip
+PartsMesh parts_mesh(fb_fem_s* h);         // the handle's arrays the calls of parts.h work on
 
 // fem_persist.hip
 bool auto_matrix_f64(const fb_fem_s* h, int n_nodes, int n_ranks);

@@ -625,8 +625,7 @@ int parts_extract(hipStream_t s, PartsWork& P, const PartsMesh& M, int part, int
 
 // ---- the C ABI ----
 
-namespace {
-
+namespace fb {  // (for detach.hip too)
 PartsMesh parts_mesh(fb_fem_s* h) {
   PartsMesh M;
   M.n_nodes = h->plan.n_global; M.n_tets = h->plan.n_tets;
@@ -634,6 +633,9 @@ PartsMesh parts_mesh(fb_fem_s* h) {
   M.caller_of = h->ren.active ? h->ren.d_old_of_new.p : nullptr;
   return M;
 }
+}  // namespace fb
+
+namespace {
 
 int parts_ready(fb_fem_s* h, const char* who, bool force) {
   if (h->plan.n_ranks > 1) return fail(FB_EINVAL, "%s is for unsharded handles", who);

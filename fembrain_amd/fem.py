@@ -300,6 +300,44 @@ class FemIntegrator:
         _l.check(self._L.fb_fem_read_part(self.h, int(k), _l.iptr(ids), _l.iptr(nodes), _l.dptr(xyz), _l.iptr(tl)))
         return ids, nodes, xyz, tl
 
+    def detach_part(self, k, remove=False, track=True):
+        """Part ``k`` as a ``FemIntegrator`` of its own, made on the device (fb_fem_detach_part; ``convertDisjointPartsToMeshes``): the
+        piece's mesh is ``read_part(k)``'s, and it takes over this handle's parameters, the state and external forces of its nodes, its
+        elements' materials and the constrained DOFs on its nodes.  ``remove`` erases the part's elements from this handle (state and
+        forces carried, node count unchanged; ``self.tets`` follows).  Returns (piece, element_ids, node_ids); ``piece.detach_info`` is
+        the dict of the fb_fem_detach_info fields.  With track, ``piece.verts`` / ``piece.tets`` are read back for the caller's
+        convenience (track=False: nothing but the two id arrays leaves the device -- timing runs)."""
+        n = self.parts()["n_parts"]
+        flags = _l.FB_DETACH_REMOVE if remove else _l.FB_DETACH_KEEP
+        out = C.c_void_p()
+        if not 0 <= int(k) < n or (remove and n < 2):  # (refused: nothing to size the arrays by)
+            _l.check(self._L.fb_fem_detach_part(self.h, int(k), flags, C.byref(out), None, None, None))
+        t = self.part_table()
+        ids, nodes = np.zeros(int(t["elements"][k]), np.int32), np.zeros(int(t["nodes"][k]), np.int32)
+        info = _l.DetachInfo()
+        _l.check(self._L.fb_fem_detach_part(self.h, int(k), flags, C.byref(out), _l.iptr(ids), _l.iptr(nodes), C.byref(info)))
+        piece = FemIntegrator.__new__(FemIntegrator)
+        piece._L, piece.h = self._L, out
+        piece.verts, piece.tets = piece.read_mesh() if track else (None, None)
+        piece.n_nodes, piece.n_tets_global = int(info.n_nodes), int(info.n_elements)
+        piece.r = 3 * piece.n_nodes
+        piece.node_lo, piece.node_hi = 0, piece.n_nodes
+        piece.params = _l.FemParams.from_buffer_copy(self.params)
+        piece.last = _l.StepInfo()
+        piece.detach_info = {name: getattr(info, name) for name, _ in _l.DetachInfo._fields_}
+        if remove:
+            self.tets = self.read_mesh()[1] if track and self.tets is not None else None
+            self.n_tets_global = int(info.parent_elements_left)
+        return piece, ids, nodes
+
+    def constrained_dofs(self):
+        """The constrained DOFs of the handle in the caller's ids, ascending (fb_fem_read_constrained_dofs): the list a later
+        ``resync_delta`` of this handle is to be given"""
+        n = int(self._L.fb_fem_num_constrained_dofs(self.h))
+        out = np.zeros(max(n, 0), np.int32)
+        _l.check(self._L.fb_fem_read_constrained_dofs(self.h, _l.iptr(out)))
+        return out
+
     def time_parts(self, reps=20):
         """(seconds per labelling, seconds per split): medians of ``reps`` HIP-event timings each (fb_fem_time_parts)"""
         a, b = C.c_double(0), C.c_double(0)

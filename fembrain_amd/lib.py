@@ -21,6 +21,7 @@ FB_INTEGRATOR_VOLUME_CONSERVING, FB_INTEGRATOR_NEWMARK = 0, 1
 FB_RENUMBER_AUTO, FB_RENUMBER_ON, FB_RENUMBER_OFF = 0, 1, -1
 FB_RESYNC_FULL, FB_RESYNC_DELTA_MERGED, FB_RESYNC_DELTA_REBUILT = 0, 1, 2
 FB_CUT_BAKE, FB_CUT_CARRY = 0, 1
+FB_DETACH_KEEP, FB_DETACH_REMOVE = 0, 1  # fb_fem_detach_part flags
 FB_CUT_NOTHING, FB_CUT_DONE, FB_CUT_UNHANDLED, FB_CUT_DRY = 0, 1, 2, 3
 FB_CUT_UNHANDLED_IDS = 64  # unhandled element ids fb_fem_read_cut returns at most (subdivide.h kCutUnhandledIds)
 FB_HAPTIC_MAX_SOURCES = 256  # sources fb_fem_add_haptic_forces takes in one call
@@ -69,6 +70,11 @@ class PartsInfo(C.Structure):
 
 class SplitInfo(C.Structure):
     _fields_ = [("n_front_parts", C.c_int), ("n_back_parts", C.c_int), ("n_straddling_parts", C.c_int), ("n_nodes_moved", C.c_int), ("shift", C.c_double * 3)]
+
+
+class DetachInfo(C.Structure):
+    _fields_ = [("part", C.c_int), ("n_elements", C.c_int), ("n_nodes", C.c_int), ("n_fixed_dofs", C.c_int), ("n_materials", C.c_int),
+                ("parent_elements_left", C.c_int), ("parent_resync_path", C.c_int)]
 
 
 class StressInfo(C.Structure):
@@ -160,6 +166,9 @@ def lib():
         "fb_fem_read_part": (C.c_int, [vp, C.c_int, _ip, _ip, _dp, _ip]),
         "fb_fem_time_parts": (C.c_int, [vp, C.c_int, _dp, _dp]),
         "fb_fem_parts_wide": (C.c_int, [vp]),
+        "fb_fem_detach_part": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(vp), _ip, _ip, C.POINTER(DetachInfo)]),
+        "fb_fem_num_constrained_dofs": (C.c_int, [vp]),
+        "fb_fem_read_constrained_dofs": (C.c_int, [vp, _ip]),
         "fb_fem_rebuild_elements": (C.c_int, [vp]),
         "fb_fem_set_external_forces": (C.c_int, [vp, _dp]),
         "fb_fem_add_external_forces": (C.c_int, [vp, _dp]),

@@ -70,6 +70,13 @@ class HipIntegrator {
     r_ = 3 * fb_fem_num_nodes(h_);
     std::memset(&info_, 0, sizeof info_);
   }
+  // a handle made by the library itself (fb_fem_detach_part) is adopted: this object owns it from here on.  params: the parameters the
+  // handle was made with (the parent's, as its setters have left them), the host mirror GetTimestep and the damping setters work from
+  HipIntegrator(fb_fem_t adopted, const fb_fem_params& params) : r_(0), h_(adopted), prm_(params) {
+    if (!adopted) throw std::invalid_argument("null FEM handle");
+    r_ = 3 * fb_fem_num_nodes(adopted);
+    std::memset(&info_, 0, sizeof info_);
+  }
   ~HipIntegrator() { fb_fem_destroy(h_); }
   HipIntegrator(const HipIntegrator&) = delete;
   HipIntegrator& operator=(const HipIntegrator&) = delete;
@@ -210,6 +217,19 @@ class HipIntegrator {
   // fb_fem_parts / fb_fem_split_parts: the disjoint parts of the device's mesh, and the parts on either side of a quad pushed apart
   void Parts(fb_fem_parts_info* out) { check(fb_fem_parts(h_, out)); }
   void SplitParts(const double quad[12], double dist, fb_fem_split_info* out) { check(fb_fem_split_parts(h_, quad, dist, out)); }
+  // fb_fem_detach_part: part `part` as an integrator of its own, made on the device with the parameters of this one and the state, forces,
+  // materials and constraints of its nodes and elements; FB_DETACH_REMOVE erases its elements here.  The caller deletes the returned integrator.
+  HipIntegrator* DetachPart(int part, int flags, fb_fem_detach_info* out = nullptr) {
+    fb_fem_t piece = nullptr;
+    check(fb_fem_detach_part(h_, part, flags, &piece, nullptr, nullptr, out));
+    if (flags == FB_DETACH_REMOVE) { mass_.clear(); bptr_.clear(); bcol_.clear(); }
+    try { return new HipIntegrator(piece, prm_); } catch (...) { fb_fem_destroy(piece); throw; }
+  }
+  // the constrained DOFs as the handle holds them (caller ids, ascending)
+  void ReadConstrainedDofs(std::vector<int>& dofs) {
+    dofs.assign((size_t)std::max(0, fb_fem_num_constrained_dofs(h_)), 0);
+    check(fb_fem_read_constrained_dofs(h_, dofs.data()));
+  }
   fb_fem_t handle() const { return h_; }
   static void check(int rc) {
     if (rc != FB_OK) throw std::runtime_error(std::string("fembrain_hip: ") + fb_last_error());
@@ -460,6 +480,42 @@ class Deformable {
     HipIntegrator::check(fb_fem_read_part(h, part, nullptr, nullptr, xyz.data(), local.data()));
     cells.assign(local.begin(), local.end());
   }
+  // One part as a body of its own, made on the device (fb_fem_detach_part): the new Deformable owns a handle whose mesh is readPart's,
+  // with the displacement, velocity, external forces, materials and fixed vertices the part had in this body; it takes over this body's
+  // gravity, floor and haptic settings.  remove: the part's cells are erased from this body (its nodes stay, no cell uses them; state
+  // and forces carried; the host copy of the mesh follows).  The caller deletes the returned body.
+  Deformable* detachPart(int part, bool remove) {
+    const int n = countDisjointParts();
+    if (part < 0 || part >= n) throw std::runtime_error("fembrain_hip: detachPart: no such part");
+    if (remove && n < 2) throw std::runtime_error("fembrain_hip: detachPart: the body has one part");
+    HipIntegrator* in = m_lpIntegrator->DetachPart(part, remove ? FB_DETACH_REMOVE : FB_DETACH_KEEP);
+    if (remove) {  // (first: the device has changed whatever happens to the piece below)
+      try { m_lpIntegrator->ReadMesh(m_rest, m_elements); } catch (...) { delete in; throw; }
+      m_bptr.clear(); m_bcol.clear();
+      m_restVolume = -1.0;
+      surfaceChanged();
+    }
+    try { return new Deformable(in, *this); } catch (...) { delete in; throw; }
+  }
+  // CuttableMesh::convertDisjointPartsToMeshes (CuttableMesh.cpp:628-698): every part becomes a body of its own and its cells are erased
+  // from this one.  With fewer than two parts nothing happens and 0 is returned, as in the reference.  Otherwise parts n-1 ... 1 are
+  // detached with removal (the labels are made again after each; the parts before the removed one keep their indices, which follow
+  // their smallest cells), this body is left with part 0, `meshes` receives the n - 1 new bodies in ascending part order (the caller
+  // deletes them), and n -- the number of bodies there are now -- is returned.  Should a detachPart throw on the way, the bodies made
+  // so far are handed over all the same (their cells are gone from this body: they are the only copy) and the exception goes on.
+  int convertDisjointPartsToMeshes(std::vector<Deformable*>& meshes) {
+    const int n = countDisjointParts();
+    if (n < 2) return 0;
+    std::vector<Deformable*> made;
+    try {
+      for (int p = n - 1; p >= 1; p--) made.push_back(detachPart(p, true));
+    } catch (...) {
+      meshes.insert(meshes.end(), made.rbegin(), made.rend());
+      throw;
+    }
+    meshes.insert(meshes.end(), made.rbegin(), made.rend());
+    return n;
+  }
   void setMesh(int numVertices, const double* rest, int numElements, const int* elements) {
     m_rest.assign(rest, rest + 3 * (size_t)numVertices);
     m_elements.assign(elements, elements + 4 * (size_t)numElements);
@@ -671,6 +727,21 @@ class Deformable {
   }
 
  private:
+  // the body of a detached part (detachPart): the integrator is adopted, mesh and fixed vertices are read from it, the settings are `from`'s
+  Deformable(HipIntegrator* adopted, const Deformable& from) : m_device(from.m_device) {
+    init();
+    m_bApplyGravity = from.m_bApplyGravity; m_hasFloor = from.m_hasFloor; m_floorY = from.m_floorY;
+    m_hapticForceNeighorhoodSize = from.m_hapticForceNeighorhoodSize; m_boxCapacity = from.m_boxCapacity;
+    m_dampingMassCoeff = from.m_dampingMassCoeff; m_dampingStiffnessCoeff = from.m_dampingStiffnessCoeff; m_timeStep = from.m_timeStep;
+    adopted->ReadMesh(m_rest, m_elements);
+    adopted->ReadConstrainedDofs(m_vFixedDofs);
+    for (size_t i = 0; i < m_vFixedDofs.size(); i++)
+      if (m_vFixedVertices.empty() || m_vFixedVertices.back() != m_vFixedDofs[i] / 3) m_vFixedVertices.push_back(m_vFixedDofs[i] / 3);
+    m_dof = (U32)m_rest.size();
+    m_q.assign(m_dof, 0.0); m_qVel.assign(m_dof, 0.0); m_arrExtForces.assign(m_dof, 0.0);
+    adopted->GetqState(m_q.data(), m_qVel.data(), nullptr);
+    m_lpIntegrator = adopted;  // (last: nothing above may leave a half-made body that owns it)
+  }
   void surfaceChanged();  // the surface mesh, if there is one, re-reads its topology at the next access (SurfaceMesh.h)
   double volumeOf(const std::vector<double>& q, double* arrStore = nullptr, U32 count = 0) const {
     const U32 m = (U32)(m_elements.size() / 4);

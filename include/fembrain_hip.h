@@ -359,6 +359,40 @@ int fb_fem_read_part(fb_fem_t h, int part, int* element_ids, int* node_ids, doub
  * nodes, the element rest data, the volumes -- with a zero shift and without its stores: nothing moves.  Either pointer may be NULL. */
 int fb_fem_time_parts(fb_fem_t h, int reps, double* seconds_label, double* seconds_split);
 
+/* ---- A part detached into a handle of its own, on the device ----
+ * What convertDisjointPartsToMeshes (src/deformable/CuttableMesh.cpp:628-698) does with every part: the part becomes a body of its own,
+ * and (FB_DETACH_REMOVE) its cells are erased from the original.  *out is a new handle on h's device, with a stream of its own, whose mesh
+ * is exactly fb_fem_read_part(h, part, ...)'s arrays -- element order, nodes in order of first use, local ids, fp64 rest positions --
+ * built by the device plan builder from the device copy; the piece decides its own node order and matrix width as any new handle does.
+ * It inherits: h's current fb_fem_params (expect_cuts included: it can be cut again) with the timestep, damping, CG and Newmark settings
+ * and the internal-force scaling set since creation; q, qvel, (qaccel on a Newmark handle) and the external forces of its nodes; the
+ * material table, and -- where h has an element map -- the ids of its elements (a handle without a map gives a piece without one); every
+ * constrained DOF of h on a node the part uses, ascending in the piece's ids (fb_fem_read_constrained_dofs).  A node that several parts
+ * share is a node of each piece.  Only counts and the constrained-DOF list cross the bus.
+ * element_ids / node_ids (either may be NULL): the arrays fb_fem_read_part returns.
+ * FB_DETACH_REMOVE: afterwards the part's elements are erased from h as by fb_fem_resync_delta(removed = element_ids): the order of the
+ * rest is kept, the node count does not change (the part's own nodes stay as nodes no element uses: identity rows), q, qvel, qaccel and the
+ * external forces are carried, the element map follows; labels, surface and stress become stale.  fb_fem_resync_path(h) reports the path.
+ * The piece is built first.  If anything fails before the removal begins the piece is destroyed, h is untouched and *out is NULL; a
+ * failure inside the removal leaves h unusable like any failed delta re-sync, and the piece is destroyed as well.
+ * FB_EINVAL before anything changes: a sharded handle, a host-built plan, a part outside [0, n_parts), out NULL, unknown flags,
+ * FB_DETACH_REMOVE on a handle with one part (a handle cannot be left without elements). */
+#define FB_DETACH_KEEP   0  /* the parent is left as it is */
+#define FB_DETACH_REMOVE 1  /* the part's elements are erased from the parent */
+typedef struct fb_fem_detach_info {
+  int part, n_elements, n_nodes;   /* of the piece */
+  int n_fixed_dofs;                /* constrained DOFs the piece inherited */
+  int n_materials;                 /* entries of the material table it inherited (1: no map) */
+  int parent_elements_left;        /* fb_fem_num_tets(parent) afterwards */
+  int parent_resync_path;          /* FB_RESYNC_* of the parent's removal, -1 with KEEP */
+} fb_fem_detach_info;
+int fb_fem_detach_part(fb_fem_t h, int part, int flags, fb_fem_t* out, int* element_ids, int* node_ids, fb_fem_detach_info* info);
+/* The constrained DOFs of an unsharded handle in the caller's ids, ascending: what fb_fem_create, the last re-sync or
+ * fb_fem_set_constrained_dofs set, what a cut keeps, what a detached piece inherited -- "the whole constrained-DOF list" that
+ * fb_fem_resync_delta takes.  FB_EINVAL for a sharded handle (-1 from the count). */
+int fb_fem_num_constrained_dofs(fb_fem_t h);
+int fb_fem_read_constrained_dofs(fb_fem_t h, int* dofs);
+
 
 /* Per-element rest-state rebuild on the device (M^-1 rows / volume, corotationalLinearFEM.cpp:66-90 and
  * tetMesh.cpp:184-188) -- the per-step "K0 rebuild" of BASELINE config 4. */
