@@ -164,5 +164,8 @@ int timed_stages(Handle* h, int reps, Stage stage, const int (&pairs)[NP][2], do
 // (xyz64: the positions as doubles instead -- the handle's own device copy, fb_fem_resync_delta)
 struct DeviceTetMesh { int device, n_vertices, n_tets; const float* xyz; const uint4* tets; const double* xyz64 = nullptr; };
 int poly_device_tetmesh(fb_poly_t h, DeviceTetMesh* out);
+// ... and its marching-cubes surface after fb_poly_surface (poly.hip -> embed.hip hand-off): positions 3 floats per vertex, 3 vertex ids per triangle
+struct DeviceSurface { int device, n_vertices, n_triangles; const float* xyz; const unsigned int* indices; };
+int poly_device_surface(fb_poly_t h, DeviceSurface* out);
 
 }  // namespace fb

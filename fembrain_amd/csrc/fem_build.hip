@@ -50,6 +50,7 @@ enum { kKeepOrder = 1, kKeepCsr = 2 };
 void begin_mesh_generation(fb_fem_s* h, int keep = 0) {
   drop_graph(h);
   h->surf.valid = h->stress.valid = h->parts.valid = false;  // (fb_fem_surface; fb_fem_read_stress / fb_fem_surface_stress; fb_fem_parts)
+  embed_mesh_changed(h->embed, keep != 0 || h->map_from_delta);  // (fb_fem_embed: a change in place, or its full rebuild, is followed by resync_delta)
   if (!(keep & kKeepCsr)) h->csr_ready = false;
   if (!(keep & kKeepOrder)) h->ren.clear();
   h->l2c.clear();
@@ -667,8 +668,8 @@ int resync_delta_rebuild(fb_fem_s* h, int n_old, int n_new, int n_fixed, const i
 
 // device_src: removed / added / new_xyz are device arrays (fb_fem_cut; no element changed in place)
 // force_rebuild: the full builder whatever there is to merge into (refresh_node_order)
-int resync_delta(fb_fem_s* h, int n_removed, const int* removed, int n_changed, const int* changed_ids, const int* changed_nodes, int n_added, const int* added,
-                 int n_new_nodes, const double* new_xyz, int n_fixed, const int* fixed, bool device_src = false, bool force_rebuild = false) {
+int resync_delta_apply(fb_fem_s* h, int n_removed, const int* removed, int n_changed, const int* changed_ids, const int* changed_nodes, int n_added, const int* added,
+                       int n_new_nodes, const double* new_xyz, int n_fixed, const int* fixed, bool device_src, bool force_rebuild) {
   const LapTimer lap("delta re-sync");
   hipStream_t s = h->stream;
   MeshDelta& D = h->delta;
@@ -780,6 +781,22 @@ int resync_delta(fb_fem_s* h, int n_removed, const int* removed, int n_changed, 
   lap("per-step arrays");
   FB_TRY(rest_state_checked(h));
   lap("rest state");
+  return FB_OK;
+}
+
+// ... and every live embedding carried across it, in the same call: MeshDelta and CutWork are scratch the next change overwrites.
+// (device_src with elements added: fb_fem_cut stands behind the change, as for the element map above)
+int resync_delta(fb_fem_s* h, int n_removed, const int* removed, int n_changed, const int* changed_ids, const int* changed_nodes, int n_added, const int* added,
+                 int n_new_nodes, const double* new_xyz, int n_fixed, const int* fixed, bool device_src = false, bool force_rebuild = false) {
+  FB_TRY(resync_delta_apply(h, n_removed, removed, n_changed, changed_ids, changed_nodes, n_added, added, n_new_nodes, new_xyz, n_fixed, fixed, device_src, force_rebuild));
+  if (!h->embed.n_live) return FB_OK;
+  const CutWork* cut = device_src && n_added ? &h->cut : nullptr;
+  EmbedMesh M;
+  M.n_nodes = h->plan.n_global; M.n_tets = h->plan.n_tets; M.tets = h->tets.p; M.x0 = h->x0.p;
+  M.caller_of = h->ren.active ? h->ren.d_old_of_new.p : nullptr;
+  M.internal_of = h->ren.active ? h->ren.d_new_of_old.p : nullptr;
+  for (Embedding& E : h->embed.slot)
+    if (E.live) FB_TRY(embed_follow(h->stream, h->embed, E, M, h->delta, cut, cut && cut->mode == FB_CUT_BAKE));
   return FB_OK;
 }
 

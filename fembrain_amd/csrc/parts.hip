@@ -713,6 +713,7 @@ int fb_fem_split_parts(fb_fem_t h, const double quad_xyz[12], double dist, fb_fe
   // from its own mesh, which is what makes it the handle a caller would create from fb_fem_read_mesh's arrays; state and forces are carried.
   h->system_valid = false;
   h->surf.valid = h->stress.valid = false;
+  h->embed.grid.valid = false;  // (fb_fem_embed: bindings hold, ids and weights; a later search needs a grid over the moved positions)
   if (h->ren.active) FB_TRY(refresh_node_order(h));  // (an unsharded handle with an internal order has a device-built plan: the host builder works in the caller's order)
   else FB_TRY(launch_rest(h));
   FB_TRY(parts_volumes(h->stream, h->parts, parts_mesh(h)));

@@ -328,6 +328,14 @@ int poly_device_tetmesh(fb_poly_t h, DeviceTetMesh* out) {
   out->xyz = h->tv.p; out->tets = h->tt.p;
   return FB_OK;
 }
+int poly_device_surface(fb_poly_t h, DeviceSurface* out) {
+  CHECK_POLY(h);
+  if (!h->surfaced) return fail(FB_EINVAL, "run fb_poly_surface first");
+  FB_HIP(hipStreamSynchronize(h->stream));
+  out->device = h->device; out->n_vertices = h->counts.n_surface_vertices; out->n_triangles = h->counts.n_surface_indices / 3;
+  out->xyz = h->sv.p; out->indices = h->si.p;
+  return FB_OK;
+}
 }  // namespace fb
 
 extern "C" {

@@ -16,6 +16,7 @@
 #include <cstring>
 #include <vector>
 
+#include "box_reduce.hip.h"
 #include "device_prims.hip.h"
 #include "launch.hip.h"
 #include "surface.h"
@@ -191,18 +192,8 @@ __global__ __launch_bounds__(kB) void k_corner_heads(int n_corners, const uint32
   if (j == 0) inc_off[counts[1]] = n_corners;
 }
 
-__device__ __forceinline__ void box_merge(float* lo, float* hi) {  // over the wavefront
-#pragma unroll
-  for (int k = 0; k < 3; k++)
-    for (int d = 32; d >= 1; d >>= 1) {
-      lo[k] = fminf(lo[k], __shfl_xor(lo[k], d));
-      hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], d));
-    }
-}
-
 // A thread per surface vertex.  NORMALS = false: positions and box only (the rest box of fb_fem_surface, q == nullptr).
-// The box goes to a per-workgroup partial; k_box_final folds the partials (a second, single-workgroup launch: no counter to reset, and
-// min / max are exact in any order).
+// The box goes to a per-workgroup partial; k_box_final folds the partials (box_reduce.hip.h).
 template <bool NORMALS>
 __global__ __launch_bounds__(kB) void k_surface_update(int n_max, const int* __restrict__ n_dev, const int* __restrict__ vnode, const int* __restrict__ inc_off, const uint32_t* __restrict__ inc,
                                                        const int* __restrict__ faces_int, const double* __restrict__ x0, const double* __restrict__ q,
@@ -240,34 +231,7 @@ __global__ __launch_bounds__(kB) void k_surface_update(int n_max, const int* __r
       for (int k = 0; k < 3; k++) normals[3 * (size_t)v + k] = len > 0.0 ? (float)(sum[k] / len) : 0.0f;
     }
   }
-  box_merge(lo, hi);
-  __shared__ float sh[kB / 64][6];
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0)
-    for (int k = 0; k < 3; k++) { sh[wave][k] = lo[k]; sh[wave][3 + k] = hi[k]; }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    float r = sh[0][threadIdx.x];
-    for (int w = 1; w < kB / 64; w++) r = threadIdx.x < 3 ? fminf(r, sh[w][threadIdx.x]) : fmaxf(r, sh[w][threadIdx.x]);
-    part[6 * (size_t)blockIdx.x + threadIdx.x] = r;
-  }
-}
-
-__global__ __launch_bounds__(kB) void k_box_final(int n_part, const float* __restrict__ part, float* __restrict__ box) {
-  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-  for (int b = threadIdx.x; b < n_part; b += kB)
-    for (int k = 0; k < 3; k++) { lo[k] = fminf(lo[k], part[6 * (size_t)b + k]); hi[k] = fmaxf(hi[k], part[6 * (size_t)b + 3 + k]); }
-  box_merge(lo, hi);
-  __shared__ float sh[kB / 64][6];
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0)
-    for (int k = 0; k < 3; k++) { sh[wave][k] = lo[k]; sh[wave][3 + k] = hi[k]; }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    float r = sh[0][threadIdx.x];
-    for (int w = 1; w < kB / 64; w++) r = threadIdx.x < 3 ? fminf(r, sh[w][threadIdx.x]) : fmaxf(r, sh[w][threadIdx.x]);
-    box[threadIdx.x] = r;
-  }
+  box_workgroup(lo, hi, part + 6 * (size_t)blockIdx.x);
 }
 
 }  // namespace

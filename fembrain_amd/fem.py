@@ -56,6 +56,7 @@ class FemIntegrator:
                 sp = np.array([self.n_nodes * i // n_ranks for i in range(n_ranks + 1)], dtype=np.int32)
             self.node_lo, self.node_hi = int(sp[rank]), int(sp[rank + 1])
         self.last = _l.StepInfo()
+        self._embed_n = {}  # points of every live embedding, by id
 
     @classmethod
     def from_poly(cls, poly, fixed_dofs=(), E=1e7, nu=0.46, rho=1000.0, timestep=0.0333, damping_mass=0.0, damping_stiffness=0.01,
@@ -82,6 +83,7 @@ class FemIntegrator:
         self.node_lo, self.node_hi = 0, self.n_nodes
         _l.check(L.fb_fem_create_from_poly(C.byref(self.h), poly.h, len(fd), _l.iptr(fd), C.byref(p)))
         self.last = _l.StepInfo()
+        self._embed_n = {}  # points of every live embedding, by id
         return self
 
     # -- life cycle --
@@ -245,6 +247,79 @@ class FemIntegrator:
         _l.check(self._L.fb_fem_time_surface(self.h, reps, C.byref(b), C.byref(u)))
         return b.value, u.value
 
+    # -- embedded point sets: the drawn mesh bound to the tets and moved on the device (fb_fem_embed; unsharded handles) --
+    @staticmethod
+    def _embed_info(info):
+        return dict(id=int(info.id), n_points=int(info.n_points), n_triangles=int(info.n_triangles), n_external=int(info.n_external),
+                    n_zeroed=int(info.n_zeroed), n_locates=int(info.n_locates), n_rebound=int(info.n_rebound), grid=tuple(info.grid),
+                    n_wide=int(info.n_wide), aabb=np.array([list(info.aabb_lo), list(info.aabb_hi)], np.float32))
+
+    def _embed_points(self, eid):
+        if eid not in self._embed_n:
+            _l.check(self._L.fb_fem_read_embedding(self.h, int(eid), None, None, None, None))  # (the library's refusal and its text)
+            raise ValueError("no embedding %r was made through this object" % (eid,))
+        return self._embed_n[eid]
+
+    def embed(self, points, triangles=None, zero_threshold=0.0, info=False):
+        """Bind ``points`` (n, 3) in the rest frame, optionally with ``triangles`` (m, 3) over them, to the elements of the mesh the
+        device holds (fb_fem_embed; VolumetricMesh::generateInterpolationWeights): the id of the embedding, with ``info`` also the
+        dict of counts (n_external, n_zeroed, grid, n_wide, ...) and the box of the bound points in the rest shape."""
+        pts = _l.as_f64(points)
+        if pts.size % 3:
+            raise ValueError("points: (n, 3)")
+        tri = None if triangles is None else _l.as_i32(triangles)
+        if tri is not None and tri.size % 3:
+            raise ValueError("triangles: (m, 3)")
+        prm = _l.EmbedParams(float(zero_threshold))
+        eid, out = C.c_int(-1), _l.EmbedInfo()
+        _l.check(self._L.fb_fem_embed(self.h, pts.size // 3, _l.dptr(pts), 0 if tri is None else tri.size // 3, _l.iptr(tri),
+                                      C.byref(prm), C.byref(eid), C.byref(out)))
+        self._embed_n[eid.value] = pts.size // 3  # (point count per id: sizes of the read-backs)
+        return (eid.value, self._embed_info(out)) if info else eid.value
+
+    def embed_from_poly(self, poly, zero_threshold=0.0, info=False):
+        """The current marching-cubes surface of a GpuPoly (after ``surface()``) as an embedding, handed over on the device
+        (fb_fem_embed_from_poly): the same as ``embed(*poly.read_surface()[::2])`` without the host copy"""
+        prm = _l.EmbedParams(float(zero_threshold))
+        eid, out = C.c_int(-1), _l.EmbedInfo()
+        _l.check(self._L.fb_fem_embed_from_poly(self.h, poly.h, C.byref(prm), C.byref(eid), C.byref(out)))
+        self._embed_n[eid.value] = int(out.n_points)
+        return (eid.value, self._embed_info(out)) if info else eid.value
+
+    def embedding(self, eid):
+        """dict of elements (n,), vertices (n, 4) in the caller's numbering, weights (n, 4) and rest_xyz (n, 3) of embedding ``eid``
+        (fb_fem_read_embedding); after a fb_fem_resync the points are searched again first"""
+        n = self._embed_points(eid)
+        el, vt, w, xyz = np.zeros(n, np.int32), np.zeros((n, 4), np.int32), np.zeros((n, 4)), np.zeros((n, 3))
+        _l.check(self._L.fb_fem_read_embedding(self.h, eid, _l.iptr(el), _l.iptr(vt), _l.dptr(w), _l.dptr(xyz)))
+        return dict(elements=el, vertices=vt, weights=w, rest_xyz=xyz)
+
+    def embed_update(self, eid, positions=True, normals=True):
+        """(xyz (n, 3) float32, normals (n, 3) float32, info dict) of the embedded points at the current state (fb_fem_embed_update);
+        ``positions`` / ``normals`` False: that array is not copied out (None)"""
+        n = self._embed_points(eid)
+        xyz = np.zeros((n, 3), np.float32) if positions else None
+        nrm = np.zeros((n, 3), np.float32) if normals else None
+        out = _l.EmbedInfo()
+        _l.check(self._L.fb_fem_embed_update(self.h, eid, _l.fptr(xyz), _l.fptr(nrm), C.byref(out)))
+        return xyz, nrm, self._embed_info(out)
+
+    def embed_release(self, eid):
+        _l.check(self._L.fb_fem_embed_release(self.h, eid))
+        self._embed_n.pop(eid, None)
+
+    def time_embed(self, eid, reps=20):
+        """(seconds per full search, seconds per update): medians of ``reps`` HIP-event timings each (fb_fem_time_embed)"""
+        a, b = C.c_double(0), C.c_double(0)
+        _l.check(self._L.fb_fem_time_embed(self.h, eid, reps, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def time_embed_search(self, eid, reps=20):
+        """(grid build, search through the grid, external pass with weights and counts): seconds, medians of ``reps`` (fb_fem_time_embed_search)"""
+        out = np.zeros(3)
+        _l.check(self._L.fb_fem_time_embed_search(self.h, eid, reps, _l.dptr(out)))
+        return tuple(float(x) for x in out)
+
     # -- disjoint parts of the (cut) mesh on the device (fb_fem_parts / split_parts / read_part; unsharded handles) --
     def parts(self):
         """The face-connected parts of the mesh the device holds (fb_fem_parts; VolMesh::get_disjoint_parts): dict of n_parts,
@@ -324,6 +399,7 @@ class FemIntegrator:
         piece.node_lo, piece.node_hi = 0, piece.n_nodes
         piece.params = _l.FemParams.from_buffer_copy(self.params)
         piece.last = _l.StepInfo()
+        piece._embed_n = {}
         piece.detach_info = {name: getattr(info, name) for name, _ in _l.DetachInfo._fields_}
         if remove:
             self.tets = self.read_mesh()[1] if track and self.tets is not None else None
@@ -777,6 +853,15 @@ class Deformable:
     def surface_mesh(self, update=False):
         """What the host draws: ``FemIntegrator.surface()``, or with ``update`` ``FemIntegrator.surface_update()``"""
         return self.integrator.surface_update() if update else self.integrator.surface()
+
+    def embed(self, points, triangles=None, zero_threshold=0.0):
+        """``FemIntegrator.embed``: the mesh the host draws instead of the boundary triangles, bound to the tets on the device -- what
+        replaces the receiver of ``Deformable::setDeformCallback``"""
+        return self.integrator.embed(points, triangles, zero_threshold)
+
+    def embedded_mesh(self, eid):
+        """``FemIntegrator.embed_update``: (xyz, normals, info) of embedding ``eid`` at the current state"""
+        return self.integrator.embed_update(eid)
 
     def stress(self, world=False, tensors=False):
         """``FemIntegrator.stress``: stress and strain of every element on the device, the summary returned"""

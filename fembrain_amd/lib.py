@@ -64,6 +64,16 @@ class SurfaceInfo(C.Structure):
     _fields_ = [("n_faces", C.c_int), ("n_vertices", C.c_int), ("n_builds", C.c_int), ("aabb_lo", C.c_float * 3), ("aabb_hi", C.c_float * 3)]
 
 
+class EmbedParams(C.Structure):
+    _fields_ = [("zero_threshold", C.c_double)]
+
+
+class EmbedInfo(C.Structure):
+    _fields_ = [("id", C.c_int), ("n_points", C.c_int), ("n_triangles", C.c_int), ("n_external", C.c_int), ("n_zeroed", C.c_int),
+                ("n_locates", C.c_int), ("n_rebound", C.c_int), ("grid", C.c_int * 3), ("n_wide", C.c_int),
+                ("aabb_lo", C.c_float * 3), ("aabb_hi", C.c_float * 3)]
+
+
 class PartsInfo(C.Structure):
     _fields_ = [("n_parts", C.c_int), ("n_builds", C.c_int), ("largest_part", C.c_int), ("n_shared_nodes", C.c_int), ("n_unused_nodes", C.c_int)]
 
@@ -160,6 +170,13 @@ def lib():
         "fb_fem_read_surface": (C.c_int, [vp, _ip, _ip, _ip]),
         "fb_fem_surface_update": (C.c_int, [vp, _fp, _fp, C.POINTER(SurfaceInfo)]),
         "fb_fem_time_surface": (C.c_int, [vp, C.c_int, _dp, _dp]),
+        "fb_fem_embed": (C.c_int, [vp, C.c_int, _dp, C.c_int, _ip, C.POINTER(EmbedParams), _ip, C.POINTER(EmbedInfo)]),
+        "fb_fem_embed_from_poly": (C.c_int, [vp, vp, C.POINTER(EmbedParams), _ip, C.POINTER(EmbedInfo)]),
+        "fb_fem_read_embedding": (C.c_int, [vp, C.c_int, _ip, _ip, _dp, _dp]),
+        "fb_fem_embed_update": (C.c_int, [vp, C.c_int, _fp, _fp, C.POINTER(EmbedInfo)]),
+        "fb_fem_embed_release": (C.c_int, [vp, C.c_int]),
+        "fb_fem_time_embed": (C.c_int, [vp, C.c_int, C.c_int, _dp, _dp]),
+        "fb_fem_time_embed_search": (C.c_int, [vp, C.c_int, C.c_int, _dp]),
         "fb_fem_parts": (C.c_int, [vp, C.POINTER(PartsInfo)]),
         "fb_fem_read_parts": (C.c_int, [vp, _ip, _ip, _ip, _ip, _ip, _dp]),
         "fb_fem_split_parts": (C.c_int, [vp, _dp, C.c_double, C.POINTER(SplitInfo)]),

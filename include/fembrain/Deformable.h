@@ -8,6 +8,7 @@
 //   PS::FEM::Deformable     <-> class Deformable (reference src/deformable/Deformable.h:63-235): same method names,
 //                               argument meaning and callback type; timestep() follows Deformable.cpp:318-420.
 //   PS::FEM::SurfaceMesh    <-> class SurfaceMesh (SurfaceMesh.h, included at the end of this file): what the host draws.
+//   PS::FEM::EmbeddedMesh   (EmbeddedMesh.h, included at the end of this file): a finer drawn mesh bound to the tets, moved on the device.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -308,6 +309,7 @@ class HipCGSolver {
 };
 
 class SurfaceMesh;
+class EmbeddedMesh;
 
 class Deformable {
  public:
@@ -322,6 +324,10 @@ class Deformable {
   // What the host draws (the reference's Deformable IS an SGMesh; its surface is getSurfMesh()): the boundary triangles of the mesh the
   // device holds, built and kept current there (SurfaceMesh.h).  Owned by the Deformable, created at the first call.
   SurfaceMesh* surfaceMesh();
+  // The mesh the host draws instead (the marching-cubes surface, an organ mesh), bound to the tets and moved with them on the device:
+  // what replaces the receiver of setDeformCallback (EmbeddedMesh.h).  xyz: 3 doubles per point in the rest frame; triangles: 3 point
+  // indices each, may be empty.  Owned by the Deformable; the binding follows cut, syncForceModel(Delta) and detached parts by itself.
+  EmbeddedMesh* embed(const std::vector<double>& xyz, const std::vector<int>& triangles = std::vector<int>(), double zeroThreshold = 0.0);
 
   // Deformable::timestep (Deformable.cpp:318-420)
   void timestep() {
@@ -743,6 +749,7 @@ class Deformable {
     m_lpIntegrator = adopted;  // (last: nothing above may leave a half-made body that owns it)
   }
   void surfaceChanged();  // the surface mesh, if there is one, re-reads its topology at the next access (SurfaceMesh.h)
+  void releaseEmbedded();  // deletes the embedded meshes, before the integrator they live on (EmbeddedMesh.h)
   double volumeOf(const std::vector<double>& q, double* arrStore = nullptr, U32 count = 0) const {
     const U32 m = (U32)(m_elements.size() / 4);
     const bool store = arrStore != nullptr && count == m;
@@ -773,6 +780,7 @@ class Deformable {
   std::vector<double> m_q, m_qVel, m_arrExtForces, m_hapticStage, m_boxStage;
   HipIntegrator* m_lpIntegrator;
   SurfaceMesh* m_lpSurface;
+  std::vector<EmbeddedMesh*> m_vEmbedded;
   FOnApplyDeformations m_fOnDeform;
   U32 m_dof, m_ctCollided, m_ctTimeStep;
   int m_idxPulledVertex, m_device, m_hapticForceNeighorhoodSize, m_boxCapacity;
@@ -784,4 +792,5 @@ class Deformable {
 }  // namespace FEM
 }  // namespace PS
 
+#include "EmbeddedMesh.h"  // class EmbeddedMesh and the members of Deformable that need it (before SurfaceMesh.h: ~Deformable deletes both)
 #include "SurfaceMesh.h"  // class SurfaceMesh and the members of Deformable that need it

@@ -117,6 +117,7 @@ class SurfaceMesh {
 
 // the members of Deformable that need the class above (Deformable.h declares them)
 inline Deformable::~Deformable() {
+  releaseEmbedded();
   delete m_lpSurface;
   delete m_lpIntegrator;
 }

@@ -301,6 +301,73 @@ int fb_fem_surface_update(fb_fem_t h, float* xyz, float* normals, fb_fem_surface
  * pointer may be NULL.  The build's figure includes its two host waits. */
 int fb_fem_time_surface(fb_fem_t h, int reps, double* seconds_build, double* seconds_update);
 
+/* ---- Embedded point sets: what is drawn instead of the boundary triangles ----
+ * The reference draws a finer mesh than the tets (the marching-cubes surface, an organ mesh) and moves it with them through
+ * Deformable::setDeformCallback; the binding is VolumetricMesh::generateInterpolationWeights with TetMesh::computeBarycentricWeights
+ * (src/3rdparty/vegafem/volumetricMesh/volumetricMesh.cpp:971-1134, tetMesh.cpp:233-305), a linear scan of all elements per point.  Here
+ * a set of points, optionally with triangles, is bound on the device through a uniform grid over the rest box, and its current
+ * positions, normals and box come out of x0 + q there.  Unsharded handles only (FB_EINVAL otherwise).  A handle that never embeds
+ * allocates and launches nothing.
+ *
+ * Binding, in fp64 on the handle's rest positions: w_i = D_i / D_0, D_0 = TetMesh::getTetDeterminant of the element's four vertices, D_i
+ * the same with vertex i replaced by the point.  An element contains the point when all four w_i >= 0; the point binds to the
+ * lowest-numbered containing element.  A point no element contains is EXTERNAL: it binds to the element whose centre (the mean of the
+ * four vertices) is closest, distance sqrt(dx^2 + dy^2 + dz^2) compared with < in ascending element order; its weights are still
+ * D_i / D_0, some negative.  zero_threshold > 0: a point farther than that from every vertex of its element gets four zero weights
+ * (counted in n_zeroed; its vertices are still the element's -- the reference leaves them uninitialised).  Elements are numbered as
+ * in fb_fem_read_mesh, node ids are the CALLER's, also on a renumbered handle.  A point on a face, an edge or a node shared by several
+ * elements is in each of them up to rounding: which of those the device picks may differ from a CPU evaluation of the same rule.
+ *
+ * Up to 8 embeddings live on a handle; id is a slot number and a released slot is reused.  FB_EINVAL before anything is uploaded:
+ * n_points <= 0, a coordinate that is not finite, a triangle index outside [0, n_points), an id without an embedding, a ninth embedding.
+ *
+ * Mesh changes.  Each point keeps its location in the handle's CURRENT rest shape (fb_fem_read_embedding's rest_xyz: the point as given,
+ * later sum w_i x0_i); that is what any later search looks for.
+ *  - A change of the mesh in place -- a fb_fem_cut that returns FB_CUT_DONE, fb_fem_resync_delta, fb_fem_detach_part with
+ *    FB_DETACH_REMOVE -- is applied to every embedding in the same call.  A point in a kept element gets the element's new number and
+ *    keeps its weights bit for bit.  A point in an element a cut subdivided is bound again among that parent's pieces: its location is
+ *    sum w_i x0_i over the parent's nodes in the rest shape after the cut, the lowest-numbered piece that contains it wins, else the piece
+ *    with the closest centre, and the weights are that piece's, new nodes included (a point whose weights were zeroed keeps four zeros and
+ *    its location).  A point in any other removed or changed element becomes an ORPHAN.  FB_CUT_BAKE moves the rest shape under every
+ *    point, so rest_xyz is refreshed for all (zeroed points excepted).  A point outside the body stays with the element it has.
+ *  - fb_fem_resync (a new mesh) orphans every point; rest_xyz stands as it was.
+ *  - Orphans are searched again by the rule above, in the mesh the handle then holds, when the embedding is next read or updated.  The
+ *    grid is built once per mesh generation and only if somebody needs it.  n_locates counts the searches; n_rebound the points that cuts
+ *    re-bound, orphans that were searched, and points a search after fb_fem_resync moved to an element with another number.
+ *  - fb_fem_split_parts keeps elements and weights (rest_xyz of the moved points is not refreshed).
+ *  - An orphan has no binding to refresh rest_xyz through: if a FB_CUT_BAKE cut or fb_fem_split_parts moves the rest shape before the
+ *    orphan has been searched (no read or update in between), it is searched where it stood in the OLD rest shape.  Read or update the
+ *    embedding between such changes.
+ * fb_fem_detach_part does not copy embeddings to the new handle. */
+typedef struct fb_fem_embed_params { double zero_threshold; /* <= 0: off */ } fb_fem_embed_params;
+typedef struct fb_fem_embed_info {
+  int id, n_points, n_triangles;
+  int n_external, n_zeroed;
+  int n_locates;      /* full searches run for this embedding */
+  int n_rebound;      /* points that changed element through mesh changes since creation */
+  int grid[3], n_wide;/* the search grid; elements kept in the overflow list (their box covers more than 64 cells) */
+  float aabb_lo[3], aabb_hi[3];
+} fb_fem_embed_info;
+/* xyz[3 n_points] in the handle's rest frame; triangles[3 n_triangles] index the points (n_triangles may be 0); p may be NULL.  out (may
+ * be NULL): the counts, and the box of the bound points in the rest shape. */
+int fb_fem_embed(fb_fem_t h, int n_points, const double* xyz, int n_triangles, const int* triangles, const fb_fem_embed_params* p, int* id, fb_fem_embed_info* out);
+/* (fb_fem_embed_from_poly, the same from a polygonizer's surface on the device, stands beside fb_fem_create_from_poly below) */
+/* elements[n], vertices4[4 n] (caller ids), weights4[4 n], rest_xyz[3 n]; any pointer may be NULL */
+int fb_fem_read_embedding(fb_fem_t h, int id, int* elements, int* vertices4, double* weights4, double* rest_xyz);
+/* The current state of the points: xyz[3 n] = (float) of the fp64 sum ((w0 p0 + w1 p1) + w2 p2) + w3 p3 with p_i = x0_i + q_i;
+ * normals[3 n] by fb_fem_surface_update's rule over the embedding's own triangles at those fp64 positions (zero where a point has no
+ * triangle); out->aabb_lo/hi: min / max of xyz.  Pointers may be NULL.  One copy of 24 n + 24 bytes leaves the device. */
+int fb_fem_embed_update(fb_fem_t h, int id, float* xyz, float* normals, fb_fem_embed_info* out);
+int fb_fem_embed_release(fb_fem_t h, int id);
+/* Medians of `reps` HIP-event timings of a full search (grid build, every point, the external pass; host waits included) and of an
+ * update with its copy.  Either pointer may be NULL.  The search runs on a scratch copy of the points' rest_xyz: the binding, its counts
+ * and n_locates are left as they are. */
+int fb_fem_time_embed(fb_fem_t h, int id, int reps, double* seconds_locate, double* seconds_update);
+/* ... the search by phase: seconds3[0] the grid build (with its two host waits), [1] the search of every point through the grid and the
+ * overflow list with the compaction of the points without an element (and the host wait for their number), [2] the external pass
+ * (closest centre), the weights and the counts.  Each the median of `reps`; fb_fem_time_embed's seconds_locate is their sum. */
+int fb_fem_time_embed_search(fb_fem_t h, int id, int reps, double seconds3[3]);
+
 /* ---- Disjoint parts of the (cut) mesh, on the device ----
  * What the reference does after every completed cut: VolMesh::get_disjoint_parts (src/deformable/VolMesh.cpp:915-965) counts the parts,
  * CuttableMesh::splitParts (src/deformable/CuttableMesh.cpp:553-626) pushes the parts on either side of the swept quad apart, and
@@ -807,6 +874,10 @@ int fb_poly_time_stages(fb_poly_t h, int reps, double seconds[5]);
  * layout / contribution lists built on the device.  Same result as fb_fem_create on fb_poly_read_tetmesh's arrays.
  * params->device must be the polygonizer's device.  The constrained DOFs come from the host as for fb_fem_create. */
 int fb_fem_create_from_poly(fb_fem_t* out, fb_poly_t poly, int n_fixed_dofs, const int* fixed_dofs, const fb_fem_params* params);
+/* The current fb_poly_surface of `poly` as an embedding of h (fb_fem_embed), without a host copy: its vertices widened to double, and its
+ * triangles.  poly must live on the handle's device and have a surface (FB_EINVAL otherwise).  Bit for bit what fb_fem_embed makes of
+ * fb_poly_read_surface's arrays. */
+int fb_fem_embed_from_poly(fb_fem_t h, fb_poly_t poly, const fb_fem_embed_params* p, int* id, fb_fem_embed_info* out);
 
 /* ---- multi-GPU field path: z-slabs of one grid ---------------------------------------------------------------------
  * The grid's point planes are dealt to the ranks in contiguous runs.  A rank that owns planes [p0, p1) (and the cell layers

@@ -1,0 +1,101 @@
+"""fb_fem_embed / fb_fem_embed_update at size, on one GPU.
+
+    python tools/probe_embed.py [--out profiles/embed_probe.json] [--reps 10] [--n 56] [--cell 0.01]
+
+The n^3 cantilever (56: 998,250 tets) with the marching-cubes surface of sphere.blob, polygonized at --cell, scaled into it.  The
+polygonizer takes no cell below 0.01, which is a 102^3 grid over the sphere's box and 38,958 vertices: the 256^3 grid and 250 k vertices
+one would like to measure are out of its reach, and the probe says which surface it got.  Measured: the full search by phase -- grid
+build, search through the grid, external pass with weights and counts (HIP events inside fb_fem_time_embed_search, on a scratch copy
+of the points; medians of --reps) -- and the update with its copy (fb_fem_time_embed); the same after a cut through mid-span; and the
+eager re-bind inside fb_fem_cut: wall clock of a FIRST cut and of a SECOND cut (another blade, the handle warm) on a handle with the
+embedding live and on a twin without.  FEMBRAIN_TIMING=1 prints the laps of the re-sync inside the cut."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from fembrain_amd import lib as fl  # noqa: E402
+from fembrain_amd.blobtree import sphere_blob  # noqa: E402
+from fembrain_amd.fem import FemIntegrator  # noqa: E402
+from fembrain_amd.meshgen import cube_fixed_plane_i0, fixed_vertices_to_dofs, truth_cube  # noqa: E402
+from fembrain_amd.poly import GpuPoly  # noqa: E402
+import cutref as cr  # noqa: E402
+
+
+def mid_blade(v, frac=0.5):
+    xs = np.unique(v[:, 0])
+    k = int(len(xs) * frac)
+    p = np.array([0.5 * (xs[k - 1] + xs[k]), 0.5 * (v[:, 1].min() + v[:, 1].max()), 0.5 * (v[:, 2].min() + v[:, 2].max())])
+    return cr.plane_strip(p, (1.0, 0.013, 0.007), half=20.0)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "embed_probe.json"))
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--n", type=int, default=56)
+    ap.add_argument("--cell", type=float, default=0.01)
+    a = ap.parse_args()
+    v, t = truth_cube(a.n, a.n, a.n, 0.1)
+    v = np.asarray(v, np.float64).reshape(-1, 3)
+    fixed = fixed_vertices_to_dofs(cube_fixed_plane_i0(a.n, a.n))
+    # the drawn surface: the sphere, 90 % of the body's width, about its centre
+    poly = GpuPoly(sphere_blob())
+    box = poly.sweep(a.cell)
+    poly.classify()
+    poly.surface()
+    sx, _, st = poly.read_surface()
+    lo, hi = v.min(0), v.max(0)
+    r = np.abs(sx).max()
+    pts = 0.5 * (lo + hi) + sx.astype(np.float64) * (0.45 * (hi - lo).min() / r)
+    tri = st.astype(np.int32)
+    poly.close()
+    rows = []
+
+    def row(name, g, eid, **extra):
+        info = g.embed_update(eid)[2]
+        loc, upd = g.time_embed(eid, a.reps)
+        phases = g.time_embed_search(eid, a.reps)
+        out = dict(case=name, n_tets=int(g.num_tets()), n_points=info["n_points"], n_triangles=info["n_triangles"], grid=list(info["grid"]), n_wide=info["n_wide"],
+                   n_external=info["n_external"], n_rebound=info["n_rebound"], seconds_locate=loc, seconds_grid_build=phases[0],
+                   seconds_search=phases[1], seconds_external_pass=phases[2], seconds_update=upd,
+                   bytes_out_update=24 * info["n_points"] + 24, **extra)
+        print(json.dumps(out), flush=True)
+        rows.append(out)
+
+    g = FemIntegrator(v, t, fixed, expect_cuts=True)
+    t0 = time.perf_counter()
+    eid = g.embed(pts, tri)
+    first = time.perf_counter() - t0
+    row("cube%d" % a.n, g, eid, first_embed_wall_s=first, sweep_dims=[int(x) for x in box] if box is not None else None)
+    def two_cuts(h):
+        out = []
+        for frac in (0.5, 0.75):
+            t0 = time.perf_counter()
+            info, _ = h.cut(mid_blade(v, frac), mode="carry", track=False)
+            out.append(time.perf_counter() - t0)
+            assert info["status"] == fl.FB_CUT_DONE, info
+        return out
+
+    with_e = two_cuts(g)
+    row("cube%d_after_cuts" % a.n, g, eid)
+    g.close()
+    g = FemIntegrator(v, t, fixed, expect_cuts=True)
+    without = two_cuts(g)
+    g.close()
+    rows.append(dict(case="cube%d_cuts" % a.n, first_cut_wall_s_with_embedding=with_e[0], first_cut_wall_s_without=without[0],
+                     second_cut_wall_s_with_embedding=with_e[1], second_cut_wall_s_without=without[1]))
+    print(json.dumps(rows[-1]), flush=True)
+    with open(a.out, "w") as fh:
+        json.dump(dict(tool="tools/probe_embed.py", reps=a.reps, timer="HIP events inside fb_fem_time_embed / fb_fem_time_embed_search (medians); time.perf_counter around fb_fem_cut", rows=rows), fh, indent=1)
+        fh.write("\n")
+
+
+if __name__ == "__main__":
+    main()
