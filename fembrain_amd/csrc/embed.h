@@ -67,7 +67,23 @@ struct Embedding {
   DevBuf<float> out;               // [6 n + 6] xyz, normals, box of the last update
   DevBuf<float> part;              // per-workgroup boxes
   std::vector<float> host;         // staging of `out`
+  // The transpose of the binding (embed_touch.hip): nothing of it exists before the first fb_fem_embed_add_forces; it is stale whenever the
+  // binding changes (a search, embed_follow, a release) and built again by the next add.
+  bool tr_valid = false;
+  int tr_builds = 0, tr_longest = 0, tr_touched = 0;  // builds since creation | longest run | nodes with a run, of the last build
+  DevBuf<uint32_t> tr_corner;      // [4 n] corners 4 p + k grouped by internal node, ascending inside a group
+  DevBuf<int> tr_lo, tr_hi;        // [n_nodes] the node's run in tr_corner (both 0: none)
+  DevBuf<int> tr_nodes;            // [tr_touched] the nodes with a run, ascending
+  DevBuf<unsigned char> tr_flag;   // [n_nodes] the node has a run (what tr_nodes is compacted from)
+  DevBuf<double> f_stage;          // [3 n] the force on every point of the running add
+  DevBuf<unsigned char> f_mask;    // [n] the points of the running add's list; zero between calls
   void release_all();
+};
+
+// what a pick on an embedding brings back in one copy: ray (t, u, v, the hit, the triangle) | point (dist2 in t, the point, its id)
+struct EmbedPick {
+  double t, u, v, xyz[3];
+  int index, pad;
 };
 
 struct EmbedWork {
@@ -78,6 +94,13 @@ struct EmbedWork {
   DevBuf<double> close_d;  // [chunks][such points] the closest centre of every chunk of the element list: its distance
   DevBuf<int> close_e;     // ... and its element
   DevBuf<int> counts;    // [0] such points, [1] external, [2] zeroed, [3] changed element
+  // embed_touch.hip; empty until one of its entry points is called
+  DevBuf<unsigned char> touch_args;  // one upload per add with a list: forces3[3 n] | ids[n]
+  DevBuf<int> tr_stats;              // [0] nodes with a run, [1] the longest run of the table being built
+  DevBuf<double> pick_d;             // per-workgroup minima of a pick ...
+  DevBuf<int> pick_i;                // ... and their triangles / points
+  DevBuf<EmbedPick> pick_out;
+  DevBuf<float> vm_out;              // [n] fb_fem_embed_stress
 };
 
 // The grid of the mesh: count, scan, emit, one stable sort by cell.  Two host waits (the mesh box; pairs and overflow length).
@@ -101,5 +124,19 @@ void embed_mesh_changed(EmbedWork& EW, bool in_place);
 // in the new rest shape), else the piece with the closest centre; in any other removed or changed element an orphan.  bake: the rest
 // shape moved under every point (FB_CUT_BAKE), loc is refreshed.  One launch and a count per embedding.
 int embed_follow(hipStream_t s, EmbedWork& EW, Embedding& E, const EmbedMesh& M, const MeshDelta& D, const CutWork* C, bool bake);
+
+// ---- embed_touch.hip: the way back from the drawn points to the tets ----
+// The transposed table of E's binding: one stable sort of the 4 n corners by internal node, the runs, the nodes that have one.  One host wait.
+int embed_table_build(hipStream_t s, EmbedWork& EW, Embedding& E, int n_nodes, PlanWorkspace& W);
+// fext[3 v + c] += w * f for the corners of the points in `ids` (strictly ascending, validated by the caller; null: every point, n = n_points),
+// per node in table order, the value of fext first.  The table must be valid.
+int embed_scatter(hipStream_t s, EmbedWork& EW, Embedding& E, int n_nodes, int n, const int* ids, const double* forces3, double* fext);
+// E.cur at the state q, as embed_update forms it
+int embed_positions(hipStream_t s, Embedding& E, int n_nodes, const double* x0, const double* q);
+// the nearest hit of the ray on E's triangles at E.cur (index -1: none) | the point of E.cur closest to wpos
+int embed_pick_ray(hipStream_t s, EmbedWork& EW, Embedding& E, const double origin[3], const double dir[3], double t_max, EmbedPick* out);
+int embed_pick_point(hipStream_t s, EmbedWork& EW, Embedding& E, const double wpos[3], EmbedPick* out);
+// per point (float) vm[element of the point]
+int embed_stress(hipStream_t s, EmbedWork& EW, const Embedding& E, int n_elements, const double* vm, float* per_point);
 
 }  // namespace fb

@@ -517,8 +517,10 @@ GridDev grid_dev(const EmbedGrid& G) {
 void Embedding::release_all() {
   loc.release(); w.release(); elem.release(); elem_old.release(); vert.release(); vert_int.release(); ext.release(); zeroed.release(); need.release(); changed.release(); orphan.release();
   tris.release(); inc.release(); inc_lo.release(); inc_hi.release(); cur.release(); out.release(); part.release();
+  tr_corner.release(); tr_lo.release(); tr_hi.release(); tr_nodes.release(); tr_flag.release(); f_stage.release(); f_mask.release();
   host.clear(); host.shrink_to_fit();
-  live = orphan_all = lost = false;
+  live = orphan_all = lost = tr_valid = false;
+  tr_builds = tr_longest = tr_touched = 0;
   n_points = n_triangles = n_external = n_zeroed = n_locates = n_rebound = n_orphans = 0;
 }
 
@@ -646,6 +648,7 @@ int embed_locate_finish(hipStream_t s, EmbedWork& EW, Embedding& E, const EmbedM
   E.n_locates++;
   E.orphan_all = false;
   E.n_orphans = 0;
+  E.tr_valid = false;  // (the transposed table is of the binding before)
   return FB_OK;
 }
 
@@ -692,6 +695,7 @@ void embed_mesh_changed(EmbedWork& EW, bool in_place) {
 
 int embed_follow(hipStream_t s, EmbedWork& EW, Embedding& E, const EmbedMesh& M, const MeshDelta& D, const CutWork* C, bool bake) {
   const int n = E.n_points;
+  E.tr_valid = false;  // (internal ids and elements change under the transposed table)
   if (E.orphan_all) { E.lost = false; return FB_OK; }  // (no binding to carry: every point is searched in whatever mesh is there when it is read)
   if (!E.orphan.p) {
     FB_TRY(E.orphan.alloc((size_t)n));
@@ -727,8 +731,10 @@ EmbedMesh mesh_of(const fb_fem_s* h) {
   return M;
 }
 
+}  // namespace
+
 // the embedding of a slot, searched again where the mesh under it was replaced
-int embedding_current(fb_fem_s* h, int id, Embedding** out) {
+int fb::embedding_current(fb_fem_s* h, int id, Embedding** out) {
   if (h->plan.n_ranks > 1) return fail(FB_EINVAL, "fb_fem_embed is for unsharded handles");
   if (id < 0 || id >= kEmbedSlots || !h->embed.slot[id].live) return fail(FB_EINVAL, "no embedding %d", id);
   Embedding& E = h->embed.slot[id];
@@ -743,6 +749,8 @@ int embedding_current(fb_fem_s* h, int id, Embedding** out) {
   *out = &E;
   return FB_OK;
 }
+
+namespace {
 
 int free_slot(fb_fem_s* h, int* slot) {
   for (int k = 0; k < kEmbedSlots; k++)

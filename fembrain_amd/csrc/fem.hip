@@ -1248,6 +1248,12 @@ int fb_fem_set_external_forces_zero(fb_fem_t h) {
   return h->fext.zero(h->stream);
 }
 
+int fb_fem_get_external_forces(fb_fem_t h, double* f) {
+  CHECK_HANDLE(h);
+  if (!f) return fail(FB_EINVAL, "null force vector");
+  return download_owned(h, h->fext, f);
+}
+
 int fb_fem_set_uniform_force(fb_fem_t h, int axis, double value) {
   CHECK_HANDLE(h);
   if (axis < 0 || axis > 2) return fail(FB_EINVAL, "axis %d", axis);

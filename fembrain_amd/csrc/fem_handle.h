@@ -1,7 +1,7 @@
 // The FEM handle (fb_fem_t of include/fembrain_hip.h) and what the units that work on it share: fem.hip (assembly, the two-launch
 // solver, the steps and the rest of the C ABI), fem_build.hip (life cycle: plan build, creation, re-sync, cut), fem_persist.hip (the
 // persistent solver's host side), haptic.hip (the probe's entry points), stress.hip (element stress and strain), parts.hip (disjoint parts),
-// detach.hip (a part into a handle of its own) and embed.hip (point sets bound to the elements).
+// detach.hip (a part into a handle of its own), embed.hip (point sets bound to the elements) and embed_touch.hip (forces, picks and stress on them).
 // Internal: not installed, included by these units only.
 #pragma once
 #include "comm.h"
@@ -325,6 +325,11 @@ int widen_positions(hipStream_t s, long long n, const float* in, double* out);  
 int download_owned(fb_fem_s* h, const DevBuf<double>& src, double* g);          // owned part of a device vector -> its place in a global-length host vector
 // the material side of a handle made from elements of `src`: force scaling and table, and -- ids non-null -- the filled element map (swapped in)
 int inherit_materials(fb_fem_s* h, const fb_fem_s* src, DevBuf<unsigned char>* ids);
+
+// stress.hip: FB_EINVAL with who's name unless h holds a fb_fem_stress of its current mesh
+int stress_current(const fb_fem_s* h, const char* who);
+// embed.hip: the embedding of a slot, its orphans searched first (FB_EINVAL: a sharded handle, no such embedding)
+int embedding_current(fb_fem_s* h, int id, Embedding** out);
 
 // parts.hip
 PartsMesh parts_mesh(fb_fem_s* h);         // the handle's arrays the calls of parts.h work on

@@ -22,6 +22,7 @@
 #include "fem_handle.h"
 #include "haptic.h"
 #include "launch.hip.h"
+#include "pick_reduce.hip.h"
 
 namespace fb {
 namespace {
@@ -94,23 +95,7 @@ __global__ __launch_bounds__(kB) void k_hap_apply(int n_nodes, int nb, int size,
 
 // ---- pick ----
 
-__device__ __forceinline__ bool closer(double d, int i, double bd, int bi) { return d < bd || (d == bd && i < bi); }
-
-// (d, caller id) minimum over the workgroup, lexicographic; valid in thread 0
-__device__ __forceinline__ void pick_reduce(double& d, int& i) {
-  for (int o = 32; o >= 1; o >>= 1) {
-    const double od = __shfl_xor(d, o);
-    const int oi = __shfl_xor(i, o);
-    if (closer(od, oi, d, i)) { d = od; i = oi; }
-  }
-  __shared__ double sd[kWaves];
-  __shared__ int si[kWaves];
-  if ((threadIdx.x & 63) == 0) { sd[threadIdx.x >> 6] = d; si[threadIdx.x >> 6] = i; }
-  __syncthreads();
-  if (threadIdx.x == 0)
-    for (int w = 1; w < kWaves; w++)
-      if (closer(sd[w], si[w], d, i)) { d = sd[w]; i = si[w]; }
-}
+// (closer / pick_reduce, the (d, caller id) minimum over the workgroup: pick_reduce.hip.h)
 
 __device__ __forceinline__ void node_position(int i, const int* __restrict__ new_of_old, int n_nodes, const double* __restrict__ x0, const double* __restrict__ q, double p[3],
                                               bool* ok) {

@@ -274,14 +274,14 @@ int stress_surface(hipStream_t s, StressWork& S, int n_vertices, int n_faces, co
 
 // ---- the C ABI ----
 
-namespace {
-
-int stress_current(const fb_fem_s* h, const char* who) {
+int fb::stress_current(const fb_fem_s* h, const char* who) {
   if (h->plan.n_ranks > 1) return fail(FB_EINVAL, "%s is for unsharded handles", who);
   if (!h->stress.valid || h->stress.n_elements != h->plan.n_tets)
     return fail(FB_EINVAL, "%s: no fb_fem_stress of the current mesh (none yet, or the mesh has changed since)", who);
   return FB_OK;
 }
+
+namespace {
 
 int run_stress(fb_fem_s* h, int flags, fb_fem_stress_info* out) {
   StressArgs a;

@@ -308,6 +308,50 @@ class FemIntegrator:
         _l.check(self._L.fb_fem_embed_release(self.h, eid))
         self._embed_n.pop(eid, None)
 
+    # -- the way back from an embedding: forces on drawn points, picks, stress per point (fb_fem_embed_add_forces / pick_ray / ...) --
+    def embed_add_forces(self, eid, forces, point_ids=None):
+        """The transpose of embedding ``eid``, added into the current external force vector (fb_fem_embed_add_forces): ``forces[s]``
+        on point ``point_ids[s]`` (strictly ascending; None: ``forces`` (n_points, 3) on every point) goes to the four nodes of the
+        point's element by its weights -- bit for bit ``for p, k, c: fext[3 v + c] += w[p, k] * f[p, c]`` over ``embedding(eid)``."""
+        n_points = self._embed_points(eid)
+        ids = None if point_ids is None else _l.as_i32(point_ids)
+        n = n_points if ids is None else len(ids)
+        f = _l.as_f64(forces, 3 * n)
+        _l.check(self._L.fb_fem_embed_add_forces(self.h, int(eid), n, _l.iptr(ids), _l.dptr(f)))
+
+    def embed_forces_info(self, eid):
+        """dict of n_table_builds (transposed tables built for embedding ``eid``), longest_run (most corners of one node) and
+        n_nodes_touched (nodes with a corner) of the last one (fb_fem_embed_forces_info)"""
+        a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+        _l.check(self._L.fb_fem_embed_forces_info(self.h, int(eid), C.byref(a), C.byref(b), C.byref(c)))
+        return dict(n_table_builds=a.value, longest_run=b.value, n_nodes_touched=c.value)
+
+    def embed_pick_ray(self, eid, origin, direction, t_max=np.inf):
+        """The nearest hit of the ray ``origin + t direction``, 0 <= t <= t_max, on the triangles of embedding ``eid`` at the current
+        state (fb_fem_embed_pick_ray): dict of triangle (-1: a miss), t, bary (u, v) -- the hit is (1-u-v) a + u b + v c -- and xyz"""
+        self._embed_points(eid)
+        o, d = _l.as_f64(origin, 3), _l.as_f64(direction, 3)
+        tri, t, bary, xyz = C.c_int(-1), C.c_double(0), np.zeros(2), np.zeros(3)
+        _l.check(self._L.fb_fem_embed_pick_ray(self.h, int(eid), _l.dptr(o), _l.dptr(d), float(t_max), C.byref(tri), C.byref(t), _l.dptr(bary), _l.dptr(xyz)))
+        return dict(triangle=tri.value, t=t.value, bary=bary, xyz=xyz)
+
+    def embed_pick_point(self, eid, wpos):
+        """(index, position (3,), squared distance) of the point of embedding ``eid`` closest to ``wpos`` at the current state; of
+        equal distances the lowest id (fb_fem_embed_pick_point)"""
+        self._embed_points(eid)
+        w = _l.as_f64(wpos, 3)
+        idx, xyz, d2 = C.c_int(-1), np.zeros(3), C.c_double(0)
+        _l.check(self._L.fb_fem_embed_pick_point(self.h, int(eid), _l.dptr(w), C.byref(idx), _l.dptr(xyz), C.byref(d2)))
+        return idx.value, xyz, d2.value
+
+    def embed_stress(self, eid):
+        """(n_points,) float32: the von Mises stress of the element each point of embedding ``eid`` is bound to, from the last
+        ``stress()`` (fb_fem_embed_stress) -- the colour to draw on ``embed_update()``'s points"""
+        n = self._embed_points(eid)
+        vm = np.zeros(n, np.float32)
+        _l.check(self._L.fb_fem_embed_stress(self.h, int(eid), _l.fptr(vm)))
+        return vm
+
     def time_embed(self, eid, reps=20):
         """(seconds per full search, seconds per update): medians of ``reps`` HIP-event timings each (fb_fem_time_embed)"""
         a, b = C.c_double(0), C.c_double(0)
@@ -439,6 +483,12 @@ class FemIntegrator:
 
     def set_uniform_force(self, axis, value):
         _l.check(self._L.fb_fem_set_uniform_force(self.h, axis, value))
+
+    def external_forces(self):
+        """The external force vector the next step will read, (3 n_nodes,) in the caller's node order (fb_fem_get_external_forces)"""
+        f = np.zeros(3 * int(self._L.fb_fem_num_nodes(self.h)))
+        _l.check(self._L.fb_fem_get_external_forces(self.h, _l.dptr(f)))
+        return f
 
     def do_timestep(self):
         """Returns the PCG iteration count; raises FbError(FB_ESOLVER) when the solve fails."""
@@ -786,6 +836,7 @@ class Deformable:
         self._pattern = None
         self.haptic_on_device = bool(haptic_on_device) and kw.get("shard") is None
         self.on_deform = None  # FOnApplyDeformations(dof, q), Deformable.h:46
+        self._embed_tris = {}  # triangles of the embeddings made through embed()
 
     def set_deform_callback(self, fn):
         self.on_deform = fn
@@ -857,11 +908,52 @@ class Deformable:
     def embed(self, points, triangles=None, zero_threshold=0.0):
         """``FemIntegrator.embed``: the mesh the host draws instead of the boundary triangles, bound to the tets on the device -- what
         replaces the receiver of ``Deformable::setDeformCallback``"""
-        return self.integrator.embed(points, triangles, zero_threshold)
+        eid = self.integrator.embed(points, triangles, zero_threshold)
+        self._embed_tris[eid] = None if triangles is None else np.array(triangles, np.int32).reshape(-1, 3)  # (touch_embedded: the hit triangle's points)
+        return eid
 
     def embedded_mesh(self, eid):
         """``FemIntegrator.embed_update``: (xyz, normals, info) of embedding ``eid`` at the current state"""
         return self.integrator.embed_update(eid)
+
+    def embed_add_forces(self, eid, forces, point_ids=None):
+        """``FemIntegrator.embed_add_forces``: forces on drawn points, added to the nodes' external forces through the binding"""
+        self.integrator.embed_add_forces(eid, forces, point_ids)
+
+    def embed_pick_ray(self, eid, origin, direction, t_max=np.inf):
+        """``FemIntegrator.embed_pick_ray``: the nearest hit of a ray on the drawn triangles at the current state"""
+        return self.integrator.embed_pick_ray(eid, origin, direction, t_max)
+
+    def embed_pick_point(self, eid, wpos):
+        """``FemIntegrator.embed_pick_point``: the drawn point closest to ``wpos``"""
+        return self.integrator.embed_pick_point(eid, wpos)
+
+    def embed_stress(self, eid):
+        """``FemIntegrator.embed_stress``: the per-point scalar to draw on ``embedded_mesh(eid)``"""
+        return self.integrator.embed_stress(eid)
+
+    def external_forces(self):
+        """``FemIntegrator.external_forces``"""
+        return self.integrator.external_forces()
+
+    def touch_embedded(self, eid, origin, direction, force, triangles=None):
+        """A click on the drawn mesh: the ray's nearest hit on embedding ``eid``, and ``force`` shared among the hit triangle's three
+        points by the hit's barycentrics (1-u-v, u, v), added to the external forces (``embed_add_forces`` with the three ids
+        ascending).  ``triangles``: the (m, 3) array the embedding was made with (kept by ``embed`` when made through this object).
+        Returns the hit (``embed_pick_ray``'s dict, with ``point_ids`` and ``forces`` as they were added); nothing is added on a miss."""
+        hit = self.integrator.embed_pick_ray(eid, origin, direction)
+        if hit["triangle"] < 0:
+            return hit
+        tri = self._embed_tris.get(eid) if triangles is None else np.asarray(triangles, np.int32).reshape(-1, 3)
+        if tri is None:
+            raise ValueError("embedding %r was not made with triangles through this object: pass them" % (eid,))
+        u, v = hit["bary"]
+        ids = tri[hit["triangle"]].astype(np.int32)
+        f = np.array([1.0 - u - v, u, v])[:, None] * np.asarray(force, np.float64).reshape(1, 3)
+        order = np.argsort(ids, kind="stable")  # (three different points: a triangle that names one twice has no area and is never hit)
+        hit["point_ids"], hit["forces"] = ids[order], f[order]
+        self.integrator.embed_add_forces(eid, hit["forces"], hit["point_ids"])
+        return hit
 
     def stress(self, world=False, tensors=False):
         """``FemIntegrator.stress``: stress and strain of every element on the device, the summary returned"""

@@ -177,6 +177,11 @@ def lib():
         "fb_fem_embed_release": (C.c_int, [vp, C.c_int]),
         "fb_fem_time_embed": (C.c_int, [vp, C.c_int, C.c_int, _dp, _dp]),
         "fb_fem_time_embed_search": (C.c_int, [vp, C.c_int, C.c_int, _dp]),
+        "fb_fem_embed_add_forces": (C.c_int, [vp, C.c_int, C.c_int, _ip, _dp]),
+        "fb_fem_embed_forces_info": (C.c_int, [vp, C.c_int, _ip, _ip, _ip]),
+        "fb_fem_embed_pick_ray": (C.c_int, [vp, C.c_int, _dp, _dp, C.c_double, _ip, _dp, _dp, _dp]),
+        "fb_fem_embed_pick_point": (C.c_int, [vp, C.c_int, _dp, _ip, _dp, _dp]),
+        "fb_fem_embed_stress": (C.c_int, [vp, C.c_int, _fp]),
         "fb_fem_parts": (C.c_int, [vp, C.POINTER(PartsInfo)]),
         "fb_fem_read_parts": (C.c_int, [vp, _ip, _ip, _ip, _ip, _ip, _dp]),
         "fb_fem_split_parts": (C.c_int, [vp, _dp, C.c_double, C.POINTER(SplitInfo)]),
@@ -190,6 +195,7 @@ def lib():
         "fb_fem_set_external_forces": (C.c_int, [vp, _dp]),
         "fb_fem_add_external_forces": (C.c_int, [vp, _dp]),
         "fb_fem_set_external_forces_zero": (C.c_int, [vp]),
+        "fb_fem_get_external_forces": (C.c_int, [vp, _dp]),
         "fb_fem_set_uniform_force": (C.c_int, [vp, C.c_int, C.c_double]),
         "fb_fem_step": (C.c_int, [vp, C.POINTER(StepInfo)]),
         "fb_fem_get_state": (C.c_int, [vp, _dp, _dp, _dp]),

@@ -190,6 +190,24 @@ class HipIntegrator {
     vonMises.assign((size_t)info.n_vertices, 0.0f);
     check(fb_fem_surface_stress(h_, vonMises.data()));
   }
+  // The way back from an embedding (fembrain_hip.h; EmbeddedMesh wraps these per mesh): forces on drawn points added to the nodes through
+  // the binding (pointIds strictly ascending; null: every point, n = the embedding's points), picks on the drawn mesh at the current
+  // state, and the von Mises stress of every point's element from the last ComputeStress.
+  void EmbedAddForces(int id, int n, const int* pointIds, const double* forces3) { check(fb_fem_embed_add_forces(h_, id, n, pointIds, forces3)); }
+  // returns the hit triangle, -1 for a miss; t, bary (u, v) and xyz may be null
+  int EmbedPickRay(int id, const double origin[3], const double dir[3], double tMax, double* t, double bary[2], double xyz[3]) {
+    int triangle = -1;
+    check(fb_fem_embed_pick_ray(h_, id, origin, dir, tMax, &triangle, t, bary, xyz));
+    return triangle;
+  }
+  int EmbedPickPoint(int id, const double wpos[3], double xyz[3], double* dist2 = nullptr) {
+    int index = -1;
+    check(fb_fem_embed_pick_point(h_, id, wpos, &index, xyz, dist2));
+    return index;
+  }
+  void EmbedStress(int id, float* perPoint) { check(fb_fem_embed_stress(h_, id, perPoint)); }
+  // the external forces the next step will read, Getr() doubles in the caller's node order
+  void GetExternalForces(double* f) { check(fb_fem_get_external_forces(h_, f)); }
   void RebuildElements() { check(fb_fem_rebuild_elements(h_)); }
   void Resync(int numVertices, const double* rest, int numElements, const int* elements, int nFixed, const int* fixed) {
     mass_.clear(); bptr_.clear(); bcol_.clear();
@@ -328,6 +346,16 @@ class Deformable {
   // what replaces the receiver of setDeformCallback (EmbeddedMesh.h).  xyz: 3 doubles per point in the rest frame; triangles: 3 point
   // indices each, may be empty.  Owned by the Deformable; the binding follows cut, syncForceModel(Delta) and detached parts by itself.
   EmbeddedMesh* embed(const std::vector<double>& xyz, const std::vector<int>& triangles = std::vector<int>(), double zeroThreshold = 0.0);
+  // A click on an embedded mesh that pulls (EmbeddedMesh::touch): the nearest hit of the ray on its triangles at the current state, and
+  // `force` shared among the hit triangle's three points by the hit's barycentrics, added to the external forces on the device.  Returns
+  // the hit triangle, -1 for a miss (nothing is added).  The forces act in the next DoTimestep of the integrator; timestep() itself
+  // sets the external forces anew (gravity, the probe) before it steps.
+  int touchEmbedded(EmbeddedMesh* mesh, const vec3d& origin, const vec3d& dir, const vec3d& force);
+  // the external forces the next integrator step will read, 3 doubles per node
+  void externalForces(std::vector<double>& f) {
+    f.assign((size_t)m_lpIntegrator->Getr(), 0.0);
+    m_lpIntegrator->GetExternalForces(f.data());
+  }
 
   // Deformable::timestep (Deformable.cpp:318-420)
   void timestep() {

@@ -7,7 +7,14 @@
 // The binding follows Deformable::cut, syncForceModelDelta, syncForceModel and the removal of a detached part by itself (fembrain_hip.h,
 // "Mesh changes"); the points and triangles of the drawn mesh never change.  Made by Deformable::embed, which owns it, or directly over an
 // integrator that outlives it.
+//
+// The way back runs on the device too (fb_fem_embed_add_forces / fb_fem_embed_pick_ray / fb_fem_embed_pick_point / fb_fem_embed_stress):
+// addForces pushes on drawn points, pickRay / pickPoint click on the drawn mesh, touch does both, applyStress colours it.  The reference
+// has none of these: its probe talks to nodes and its drawn surface only receives.
 #pragma once
+#include <limits>
+#include <stdexcept>
+#include <utility>
 #include <vector>
 
 #include "Deformable.h"
@@ -56,12 +63,83 @@ class EmbeddedMesh {
     HipIntegrator::check(fb_fem_read_embedding(m_lpIntegrator->handle(), m_id, elements.data(), vertices4.data(), weights4.data(), restXYZ.data()));
   }
 
+  // ---- the way back: the drawn mesh touched, clicked and coloured (fb_fem_embed_add_forces / pick_ray / pick_point / embed_stress) ----
+  // forces[s] on point pointIds[s] (strictly ascending), added to the external forces of the four nodes of the point's element by its
+  // weights -- bit for bit the host loop over readBinding
+  void addForces(const std::vector<int>& pointIds, const std::vector<vec3d>& forces) {
+    if (pointIds.size() != forces.size()) throw std::invalid_argument("EmbeddedMesh::addForces: one force per point id");
+    stage(forces);
+    m_lpIntegrator->EmbedAddForces(m_id, (int)pointIds.size(), pointIds.data(), m_forceStage.data());
+  }
+  // ... one force on every point
+  void addForces(const std::vector<vec3d>& forces) {
+    if (forces.size() != (size_t)m_info.n_points) throw std::invalid_argument("EmbeddedMesh::addForces: one force per point");
+    stage(forces);
+    m_lpIntegrator->EmbedAddForces(m_id, (int)forces.size(), nullptr, m_forceStage.data());
+  }
+  // what a click on the drawn mesh finds
+  struct RayHit {
+    int triangle;  // -1: a miss
+    double t, u, v;  // origin + t dir = (1-u-v) a + u b + v c
+    vec3d point;
+    RayHit() : triangle(-1), t(0.0), u(0.0), v(0.0) {}
+  };
+  // the nearest hit of the ray on the triangles at the current state; tMax < 0: unbounded
+  RayHit pickRay(const vec3d& origin, const vec3d& dir, double tMax = -1.0) {
+    const double o[3] = {origin.x, origin.y, origin.z}, d[3] = {dir.x, dir.y, dir.z};
+    double bary[2] = {0.0, 0.0}, p[3] = {0.0, 0.0, 0.0};
+    RayHit hit;
+    hit.triangle = m_lpIntegrator->EmbedPickRay(m_id, o, d, tMax < 0.0 ? std::numeric_limits<double>::infinity() : tMax, &hit.t, bary, p);
+    hit.u = bary[0]; hit.v = bary[1];
+    hit.point = vec3d(p[0], p[1], p[2]);
+    return hit;
+  }
+  // the point closest to wpos at the current state (of equal distances the lowest index), its fp64 position in `vertex`
+  int pickPoint(const vec3d& wpos, vec3d& vertex) {
+    const double w[3] = {wpos.x, wpos.y, wpos.z};
+    double p[3] = {0.0, 0.0, 0.0};
+    const int best = m_lpIntegrator->EmbedPickPoint(m_id, w, p);
+    if (best >= 0) vertex = vec3d(p[0], p[1], p[2]);
+    return best;
+  }
+  // a click that pulls: the ray's nearest hit, and `force` shared among the hit triangle's three points by (1-u-v, u, v)
+  RayHit touch(const vec3d& origin, const vec3d& dir, const vec3d& force) {
+    const RayHit hit = pickRay(origin, dir);
+    if (hit.triangle < 0) return hit;
+    const double share[3] = {1.0 - hit.u - hit.v, hit.u, hit.v};
+    int order[3] = {0, 1, 2};
+    const int* f = &m_triangles[3 * (size_t)hit.triangle];
+    for (int a = 0; a < 3; a++)  // ascending point ids
+      for (int b = a + 1; b < 3; b++)
+        if (f[order[b]] < f[order[a]]) std::swap(order[a], order[b]);
+    std::vector<int> ids(3);
+    std::vector<vec3d> forces(3);
+    for (int k = 0; k < 3; k++) {
+      ids[k] = f[order[k]];
+      forces[k] = vec3d(share[order[k]] * force.x, share[order[k]] * force.y, share[order[k]] * force.z);
+    }
+    addForces(ids, forces);
+    return hit;
+  }
+  // the colour of the drawn mesh: per point the von Mises stress of its element, from the last Deformable::computeStress
+  void applyStress() {
+    m_stress.assign((size_t)m_info.n_points, 0.0f);
+    m_lpIntegrator->EmbedStress(m_id, m_stress.data());
+  }
+  float stressAt(U32 idx) const { return m_stress[idx]; }
+  const std::vector<float>& stress() const { return m_stress; }
+
  private:
+  void stage(const std::vector<vec3d>& forces) {
+    m_forceStage.resize(3 * forces.size());
+    for (size_t i = 0; i < forces.size(); i++) { m_forceStage[3 * i] = forces[i].x; m_forceStage[3 * i + 1] = forces[i].y; m_forceStage[3 * i + 2] = forces[i].z; }
+  }
   HipIntegrator* m_lpIntegrator;  // not owned
   int m_id;
   fb_fem_embed_info m_info;
   std::vector<int> m_triangles;
-  std::vector<float> m_xyz, m_normals;
+  std::vector<float> m_xyz, m_normals, m_stress;
+  std::vector<double> m_forceStage;
 };
 
 // the members of Deformable that need the class above (Deformable.h declares them)
@@ -69,6 +147,9 @@ inline EmbeddedMesh* Deformable::embed(const std::vector<double>& xyz, const std
   if (!m_lpIntegrator) syncForceModel();
   m_vEmbedded.push_back(new EmbeddedMesh(m_lpIntegrator, xyz, triangles, zeroThreshold));
   return m_vEmbedded.back();
+}
+inline int Deformable::touchEmbedded(EmbeddedMesh* mesh, const vec3d& origin, const vec3d& dir, const vec3d& force) {
+  return mesh->touch(origin, dir, force).triangle;
 }
 inline void Deformable::releaseEmbedded() {
   for (size_t i = 0; i < m_vEmbedded.size(); i++) delete m_vEmbedded[i];

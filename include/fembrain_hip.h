@@ -368,6 +368,45 @@ int fb_fem_time_embed(fb_fem_t h, int id, int reps, double* seconds_locate, doub
  * (closest centre), the weights and the counts.  Each the median of `reps`; fb_fem_time_embed's seconds_locate is their sum. */
 int fb_fem_time_embed_search(fb_fem_t h, int id, int reps, double seconds3[3]);
 
+/* ---- The way back: touching, picking and colouring what an embedding draws ----
+ * fb_fem_embed sends data outward, from the tets to the drawn points.  These calls go the other way, on the device, so that a host which
+ * draws an embedding can push on it, click on it and colour it without reading the binding back (52 bytes per point), scattering on the
+ * host and uploading a 3*n_nodes force vector per touch.  The reference has neither: its probe talks to nodes, and its drawn surface only
+ * receives Deformable::setDeformCallback.  Unsharded handles only (FB_EINVAL otherwise); ids are the caller's, also on a renumbered
+ * handle; points that wait for a search (after fb_fem_resync, orphans of a change in place) are searched first, as fb_fem_embed_update
+ * does.  A handle that never calls these allocates and launches nothing extra.
+ *
+ * fb_fem_embed_add_forces is the transpose of the embedding, ADDED into the current external force vector (set gravity or zero first).
+ * With the binding fb_fem_read_embedding returns, the result is bit for bit this loop:
+ *     for s = 0 .. n-1 (p = point_ids[s], strictly ascending), k = 0 .. 3 (v = vertices4[4 p + k]), c = 0 .. 2:
+ *         fext[3 v + c] = fext[3 v + c] + weights4[4 p + k] * forces3[3 s + c]
+ * one fp64 multiply and one fp64 add per addition, the value fext holds being the start of each node's sequential sum.  point_ids NULL:
+ * every point (n must be n_points, forces3 is [3 n_points]).  External points and points with zeroed weights take part with the weights
+ * they have.  n == 0 is a no-op.  FB_EINVAL before anything is launched or changed: an id outside [0, n_points), a list that is not
+ * strictly ascending, NULL forces3 with n > 0, a force that is not finite, an id without a live embedding.  Mechanism: the 4 n_points
+ * corners are sorted once, stably, by node (the transposed table); a wavefront per node that has corners forms the products of 64 corners
+ * at a time and adds them in order.  No floating-point atomics, one path for short and long lists: the same bits from call to call.  The
+ * table is built by the first call and kept until the binding changes (a search, a change of the mesh in place, a release); the time of
+ * a dense add is bounded below by the node with the most corners (longest_run sequential additions). */
+int fb_fem_embed_add_forces(fb_fem_t h, int id, int n, const int* point_ids, const double* forces3);
+/* Of embedding id: transposed tables built since its creation; of the last of them the most corners of one node and the nodes that have
+ * a corner (zeros before the first fb_fem_embed_add_forces).  Any pointer may be NULL. */
+int fb_fem_embed_forces_info(fb_fem_t h, int id, int* n_table_builds, int* longest_run, int* n_nodes_touched);
+/* The nearest hit of the ray origin + t dir, 0 <= t <= t_max (dir need not be a unit vector; t_max may be INFINITY), on the embedding's
+ * triangles at the current state: the fp64 positions fb_fem_embed_update forms, recomputed here.  Per triangle (a, b, c) Moeller-Trumbore
+ * in fp64 with e1 = b - a, e2 = c - a: P = dir x e2, det = e1 . P (a triangle with det == 0 is skipped; both sides are hit), T = origin - a,
+ * u = (T . P) / det, Q = T x e1, v = (dir . Q) / det, t = (e2 . Q) / det; a hit when u >= 0, v >= 0, u + v <= 1 and 0 <= t <= t_max.  Of all hits
+ * the smallest t, of equal t the lowest triangle.  *triangle = -1 (and FB_OK) for a miss or an embedding without triangles; bary = (u, v),
+ * the hit is (1-u-v) a + u b + v c; xyz = origin + t dir.  Output pointers may be NULL.  FB_EINVAL: a zero or non-finite dir, a
+ * non-finite origin, t_max not a number.  One copy of 56 bytes leaves the device. */
+int fb_fem_embed_pick_ray(fb_fem_t h, int id, const double origin[3], const double dir[3], double t_max, int* triangle, double* t, double bary[2], double xyz[3]);
+/* fb_fem_pick_vertex over the embedded points at the current state: the point with the smallest d = dx*dx + dy*dy + dz*dz, of equal d
+ * the lowest id; xyz its fp64 position.  Output pointers may be NULL.  One copy of 56 bytes leaves the device. */
+int fb_fem_embed_pick_point(fb_fem_t h, int id, const double wpos[3], int* index, double xyz[3], double* dist2);
+/* per_point[n_points]: (float) of the von Mises stress of the element each point is bound to, from the last fb_fem_stress.  FB_EINVAL
+ * when there is no stress of the current mesh, by fb_fem_surface_stress's rule.  One copy of 4 n_points bytes leaves the device. */
+int fb_fem_embed_stress(fb_fem_t h, int id, float* per_point);
+
 /* ---- Disjoint parts of the (cut) mesh, on the device ----
  * What the reference does after every completed cut: VolMesh::get_disjoint_parts (src/deformable/VolMesh.cpp:915-965) counts the parts,
  * CuttableMesh::splitParts (src/deformable/CuttableMesh.cpp:553-626) pushes the parts on either side of the swept quad apart, and
@@ -470,6 +509,10 @@ int fb_fem_rebuild_elements(fb_fem_t h);
 int fb_fem_set_external_forces(fb_fem_t h, const double* f);
 int fb_fem_add_external_forces(fb_fem_t h, const double* f);
 int fb_fem_set_external_forces_zero(fb_fem_t h);
+/* The external force vector the next step will read -- whatever the calls above, fb_fem_set_uniform_force, fb_fem_add_haptic_forces and
+ * fb_fem_embed_add_forces have left in it -- as 3*n_nodes doubles in the caller's node order (a sharded handle fills its owned range,
+ * as fb_fem_get_state does). */
+int fb_fem_get_external_forces(fb_fem_t h, double* f);
 /* constant force on one axis of every node, generated on the device: axis 1, value -10000 is the gravity
  * load of Deformable::timestep (Deformable.cpp:331-338) */
 int fb_fem_set_uniform_force(fb_fem_t h, int axis, double value);

@@ -8,7 +8,13 @@ one would like to measure are out of its reach, and the probe says which surface
 build, search through the grid, external pass with weights and counts (HIP events inside fb_fem_time_embed_search, on a scratch copy
 of the points; medians of --reps) -- and the update with its copy (fb_fem_time_embed); the same after a cut through mid-span; and the
 eager re-bind inside fb_fem_cut: wall clock of a FIRST cut and of a SECOND cut (another blade, the handle warm) on a handle with the
-embedding live and on a twin without.  FEMBRAIN_TIMING=1 prints the laps of the re-sync inside the cut."""
+embedding live and on a twin without.  FEMBRAIN_TIMING=1 prints the laps of the re-sync inside the cut.
+
+The way back (fb_fem_embed_add_forces / pick_ray / pick_point / embed_stress), before the cuts, each the median of --reps wall-clock
+timings of the call followed by a device synchronise, every shape warmed first: the first add of a fresh embedding (table build +
+dense add; one sample per spare slot), a dense add, a 3-point add, a ray pick, a point pick, embed_stress -- and, in the same run, the
+host route they replace: fb_fem_read_embedding + np.add.at + fb_fem_set_external_forces, and a numpy Moeller-Trumbore pass over the
+positions fb_fem_embed_update reads back."""
 import argparse
 import json
 import os
@@ -33,6 +39,91 @@ def mid_blade(v, frac=0.5):
     k = int(len(xs) * frac)
     p = np.array([0.5 * (xs[k - 1] + xs[k]), 0.5 * (v[:, 1].min() + v[:, 1].max()), 0.5 * (v[:, 2].min() + v[:, 2].max())])
     return cr.plane_strip(p, (1.0, 0.013, 0.007), half=20.0)
+
+
+def _median_wall(fn, reps, sync):
+    fn()
+    sync()
+    out = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        sync()
+        out.append(time.perf_counter() - t0)
+    return float(np.median(out))
+
+
+def touch_row(g, eid, pts, tri, reps):
+    """the calls that go from the drawn mesh back to the tets, and the host route they replace"""
+    import ctypes
+    hip = ctypes.CDLL("libamdhip64.so")
+    sync = hip.hipDeviceSynchronize
+    n = len(pts)
+    rng = np.random.default_rng(1)
+    f_all, f3 = rng.standard_normal((n, 3)), rng.standard_normal((3, 3))
+    ids3 = np.sort(tri[len(tri) // 2]).astype(np.int32)
+    g.set_uniform_force(1, -300.0)
+    # the first add of a fresh embedding builds its table: one sample per spare slot (the first of them also warms the sort's storage)
+    firsts = []
+    for _ in range(5):
+        e = g.embed(pts, tri)
+        sync()
+        t0 = time.perf_counter()
+        g.embed_add_forces(e, f_all)
+        sync()
+        firsts.append(time.perf_counter() - t0)
+        g.embed_release(e)
+    dense = _median_wall(lambda: g.embed_add_forces(eid, f_all), reps, sync)
+    three = _median_wall(lambda: g.embed_add_forces(eid, f3, ids3), reps, sync)
+    info = g.embed_forces_info(eid)
+    # a ray through the middle of the drawn surface, from outside the body
+    c = pts.mean(axis=0)
+    o, d = c + [0.03, 0.05, 10.0], np.array([0.0, 0.0, -1.0])
+    hit = g.embed_pick_ray(eid, o, d)
+    assert hit["triangle"] >= 0, hit
+    ray = _median_wall(lambda: g.embed_pick_ray(eid, o, d), reps, sync)
+    point = _median_wall(lambda: g.embed_pick_point(eid, c + [0.3, 0.1, 0.2]), reps, sync)
+    g.stress()
+    stress = _median_wall(lambda: g.embed_stress(eid), reps, sync)
+
+    # the host route: the binding comes back, the scatter runs on the host, a 3 n_nodes vector goes up
+    def host_add():
+        b = g.embedding(eid)
+        f = g.external_forces().reshape(-1, 3)
+        np.add.at(f, b["vertices"].ravel(), (b["weights"][:, :, None] * f_all[:, None, :]).reshape(-1, 3))
+        g.set_external_forces(f)
+
+    def host_add3():
+        b = g.embedding(eid)
+        f = g.external_forces().reshape(-1, 3)
+        np.add.at(f, b["vertices"][ids3].ravel(), (b["weights"][ids3][:, :, None] * f3[:, None, :]).reshape(-1, 3))
+        g.set_external_forces(f)
+
+    def host_ray():
+        p = g.embed_update(eid, normals=False)[0].astype(np.float64)
+        a, b, cc = p[tri[:, 0]], p[tri[:, 1]], p[tri[:, 2]]
+        e1, e2 = b - a, cc - a
+        pv = np.cross(d[None, :], e2)
+        det = (e1 * pv).sum(axis=1)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            tv = o[None, :] - a
+            u = (tv * pv).sum(axis=1) / det
+            qv = np.cross(tv, e1)
+            w = (qv * d[None, :]).sum(axis=1) / det
+            t = (e2 * qv).sum(axis=1) / det
+            ok = (det != 0) & (u >= 0) & (w >= 0) & (u + w <= 1) & (t >= 0)
+        k = np.nonzero(ok)[0]
+        return int(k[np.argmin(t[k])]) if len(k) else -1
+
+    assert host_ray() == hit["triangle"], (host_ray(), hit)
+    out = dict(case="touch", n_points=n, n_triangles=len(tri), n_nodes=g.r // 3, longest_run=info["longest_run"], n_nodes_touched=info["n_nodes_touched"],
+               seconds_first_add_samples=firsts, seconds_first_add=float(np.median(firsts[1:])), seconds_dense_add=dense, seconds_3_point_add=three,
+               seconds_pick_ray=ray, seconds_pick_point=point, seconds_embed_stress=stress,
+               host_seconds_dense_add=_median_wall(host_add, reps, sync), host_seconds_3_point_add=_median_wall(host_add3, reps, sync),
+               host_seconds_pick_ray=_median_wall(host_ray, reps, sync),
+               bytes_host_route_add=52 * n + 2 * 24 * (g.r // 3), bytes_dense_add=24 * n, bytes_3_point_add=3 * 28)
+    out["seconds_table_build"] = out["seconds_first_add"] - dense
+    return out
 
 
 def main():
@@ -74,6 +165,9 @@ def main():
     eid = g.embed(pts, tri)
     first = time.perf_counter() - t0
     row("cube%d" % a.n, g, eid, first_embed_wall_s=first, sweep_dims=[int(x) for x in box] if box is not None else None)
+    rows.append(touch_row(g, eid, pts, tri, a.reps))
+    print(json.dumps(rows[-1]), flush=True)
+
     def two_cuts(h):
         out = []
         for frac in (0.5, 0.75):
@@ -93,7 +187,7 @@ def main():
                      second_cut_wall_s_with_embedding=with_e[1], second_cut_wall_s_without=without[1]))
     print(json.dumps(rows[-1]), flush=True)
     with open(a.out, "w") as fh:
-        json.dump(dict(tool="tools/probe_embed.py", reps=a.reps, timer="HIP events inside fb_fem_time_embed / fb_fem_time_embed_search (medians); time.perf_counter around fb_fem_cut", rows=rows), fh, indent=1)
+        json.dump(dict(tool="tools/probe_embed.py", reps=a.reps, timer="HIP events inside fb_fem_time_embed / fb_fem_time_embed_search (medians); time.perf_counter around fb_fem_cut; the touch row: time.perf_counter around the call and a hipDeviceSynchronize (medians)", rows=rows), fh, indent=1)
         fh.write("\n")
 
 
