@@ -72,7 +72,8 @@ struct PersistState {
   // the LDS window of the one-row kernel (pcg_pipe_mirror.h; k_pipe_mirror_plan in setup_pipe_mirror), pipe_mir empty: none
   // (FEMBRAIN_PIPE_MIRROR=0, or another instantiation).  pipe_mir_stats: mirror layers, pool entries, fewest plain layers of a slice --
   // fetched when asked
-  int pipe_mir_got[3] = {0, 0, 0};
+  int pipe_mir_got[4] = {0, 0, 0, 0};  // (the fourth: register slots over all slices, fb_fem_persist_regs)
+  int pipe_regs = 0;                   // register slots per slice this plan's launches may hold (pcg_pipe_regs.hip.h): the kernel's, capped by FEMBRAIN_PIPE_REGS
   bool pipe_mir_pending = false;
 
   // per plan, released by reset_plan(): a plan that does not use one must not find the previous plan's
@@ -108,7 +109,8 @@ struct PersistState {
     persist = false;
     kernel = nullptr;
     pipe_mir.release(); pipe_mir_pending = false;  // (setup_pipe_mirror plans the window again where it applies)
-    pipe_mir_got[0] = pipe_mir_got[1] = pipe_mir_got[2] = 0;
+    pipe_mir_got[0] = pipe_mir_got[1] = pipe_mir_got[2] = pipe_mir_got[3] = 0;
+    pipe_regs = 0;
     shard_persist = false;
     persist_broken = false;
     pipe_stats_pending = false;

@@ -20,6 +20,7 @@ struct PipeKernel {
   int wmax, klt;        // wavefronts it is built for; most LDS slots per wavefront (the unroll bound of the loop over resident slots)
   bool timing, shard, bj, help, xyz;
   bool ahead;           // the run-ahead form: for launches with a service wavefront (pcg_pipe.hip.h)
+  int regs;             // register slots per slice it holds (pcg_pipe_regs.hip.h), 0: none
   const void* fn;
 };
 
@@ -30,12 +31,16 @@ namespace {
 // per CU; SHARD on a sharded handle (32-bit local column ids); TIMING: the development build with the phase clocks, for the 1M-tet
 // configuration, the small ones and the helpers'; BJ: the block preconditioner; HELP: the task table, which also carries XYZ.  Every
 // unsharded one-row kernel without the task table comes in two forms, one per launch form: with its barriers (as many slices as
-// wavefronts) and run-ahead (a service wavefront); the others keep their barriers with or without a service wavefront.
-#define FB_PIPE1F(C16, WMAX, KLT, TIMING, SHARD, BJ, HELP, XYZ, AHEAD) \
-  {1, C16, WMAX, KLT, TIMING, SHARD, BJ, HELP, XYZ, AHEAD, (const void*)k_pcg_pipe<float, C16, WMAX, KLT, TIMING, SHARD, BJ, HELP, XYZ, AHEAD>}
-#define FB_PIPE1(C16, WMAX, KLT, TIMING, SHARD, BJ, HELP, XYZ) FB_PIPE1F(C16, WMAX, KLT, TIMING, SHARD, BJ, HELP, XYZ, false)
-#define FB_PIPE1A(C16, WMAX, KLT, TIMING, BJ) FB_PIPE1F(C16, WMAX, KLT, TIMING, false, BJ, false, false, true)
-#define FB_PIPE2(C16, SHARD, XYZ) {2, C16, 12, kPipe2Klt, false, SHARD, false, false, XYZ, false, (const void*)k_pcg_pipe2<C16, SHARD, XYZ>}
+// wavefronts) and run-ahead (a service wavefront); the others keep their barriers with or without a service wavefront.  The run-ahead LDS-window
+// kernels of the plain Jacobi solver -- (12, 6) and (12, 7), the headline's -- come a second time with register slots (k_pcg_pipe_regs, REGS = 3);
+// FEMBRAIN_PIPE_REGS=0 launches the one without.
+#define FB_PIPE1F(C16, WMAX, KLT, TIMING, SHARD, BJ, HELP, XYZ, AHEAD, REGS) \
+  {1, C16, WMAX, KLT, TIMING, SHARD, BJ, HELP, XYZ, AHEAD, REGS, (const void*)k_pcg_pipe<float, C16, WMAX, KLT, TIMING, SHARD, BJ, HELP, XYZ, AHEAD, REGS>}
+#define FB_PIPE1(C16, WMAX, KLT, TIMING, SHARD, BJ, HELP, XYZ) FB_PIPE1F(C16, WMAX, KLT, TIMING, SHARD, BJ, HELP, XYZ, false, 0)
+#define FB_PIPE1A(C16, WMAX, KLT, TIMING, BJ) FB_PIPE1F(C16, WMAX, KLT, TIMING, false, BJ, false, false, true, 0)
+#define FB_PIPE1R(C16, KLT) \
+  {1, C16, 12, KLT, false, false, false, false, false, true, kPipeRegsMax, (const void*)k_pcg_pipe_regs<float, C16, 12, KLT, false, false, false, false, false, true, kPipeRegsMax>}
+#define FB_PIPE2(C16, SHARD, XYZ) {2, C16, 12, kPipe2Klt, false, SHARD, false, false, XYZ, false, 0, (const void*)k_pcg_pipe2<C16, SHARD, XYZ>}
 const PipeKernel kPipeKernels[] = {
     FB_PIPE1(true, 5, 16, false, false, false, false, false),  FB_PIPE1(false, 5, 16, false, false, false, false, false),
     FB_PIPE1(true, 8, 8, false, false, false, false, false),   FB_PIPE1(false, 8, 8, false, false, false, false, false),
@@ -56,10 +61,12 @@ const PipeKernel kPipeKernels[] = {
     FB_PIPE1A(true, 5, 16, true, false),   FB_PIPE1A(true, 8, 8, true, false),     FB_PIPE1A(false, 8, 8, true, false),
     FB_PIPE1A(true, 12, 6, true, false),   FB_PIPE1A(false, 12, 6, true, false),
     FB_PIPE1A(true, 8, 8, false, true),    FB_PIPE1A(false, 8, 8, false, true),    FB_PIPE1A(true, 12, 6, false, true),   FB_PIPE1A(false, 12, 6, false, true),
+    FB_PIPE1R(true, 6),  FB_PIPE1R(false, 6),  FB_PIPE1R(true, 7),  FB_PIPE1R(false, 7),
     FB_PIPE2(true, false, false),  FB_PIPE2(false, false, false),  FB_PIPE2(true, false, true),  FB_PIPE2(false, false, true),
     FB_PIPE2(false, true, false),
 };
 #undef FB_PIPE2
+#undef FB_PIPE1R
 #undef FB_PIPE1A
 #undef FB_PIPE1
 #undef FB_PIPE1F
@@ -96,6 +103,7 @@ PersistKnobs read_persist_knobs() {
   k.lds_cap = getenv("FEMBRAIN_PIPE_LDS_CAP") ? std::max(1, env_int("FEMBRAIN_PIPE_LDS_CAP", 1)) : 0;
   k.plain_stores = env_int("FEMBRAIN_PIPE_PLAIN_STORES", -1);
   k.mirror = env_int("FEMBRAIN_PIPE_MIRROR", 1) != 0;
+  k.regs = env_int("FEMBRAIN_PIPE_REGS", -1);
   k.verbose = getenv("FEMBRAIN_TIMING") != nullptr;
   return k;
 }
@@ -118,10 +126,14 @@ int resolve_pipe_kernel(fb_fem_s* h, const PersistKnobs& kn) {
   want.wmax = ps.pipe_wmax;
   want.ahead = want.rows == 1 && !want.shard && !want.help && pipe_has_service(ps);
   want.klt = want.rows == 2 ? kPipe2Klt : (want.wmax == 5 ? 16 : (want.wmax == 8 ? 8 : (klt7 ? 7 : 6)));
+  // register slots: the run-ahead LDS-window kernels of a handle that keeps its window; FEMBRAIN_PIPE_REGS caps them (0: the kernel without)
+  const bool regs_form = want.rows == 1 && want.wmax == 12 && want.ahead && !want.timing && !want.bj && !want.xyz && ps.pipe_mir_knob != 0 && kn.regs != 0;
+  want.regs = regs_form ? kPipeRegsMax : 0;
+  ps.pipe_regs = kn.regs < 0 ? want.regs : std::min(kn.regs, want.regs);
   ps.kernel = nullptr;
   for (const PipeKernel& k : kPipeKernels)
     if (k.rows == want.rows && k.c16 == want.c16 && k.wmax == want.wmax && k.klt == want.klt && k.timing == want.timing && k.shard == want.shard && k.bj == want.bj &&
-        k.help == want.help && k.xyz == want.xyz && k.ahead == want.ahead)
+        k.help == want.help && k.xyz == want.xyz && k.ahead == want.ahead && k.regs == want.regs)
       ps.kernel = &k;
   if (!ps.kernel) return fail(FB_EINVAL, "FEMBRAIN_PERSIST_TIMING is built for one row per lane: (12, 6) and (5, 16) with 16-bit column words, (8, 8)");
   return FB_OK;
@@ -196,7 +208,7 @@ int setup_pipe_mirror(fb_fem_s* h) {
   hipStream_t s = h->stream;
   const PipeKernel& K = *ps.kernel;
   ps.pipe_mir_pending = false;
-  ps.pipe_mir_got[0] = ps.pipe_mir_got[1] = ps.pipe_mir_got[2] = 0;
+  ps.pipe_mir_got[0] = ps.pipe_mir_got[1] = ps.pipe_mir_got[2] = ps.pipe_mir_got[3] = 0;
   if (ps.pipe_mir_knob == 0 || K.rows != 1 || K.wmax != 12 || K.shard || K.help || K.bj || ps.pipe_xyz || P.n_slices <= 0) {
     ps.pipe_mir.release(); ps.pipe_mir_addr.release(); ps.pipe_mir_wg.release(); ps.pipe_mir_pool.release();
     return FB_OK;
@@ -206,11 +218,12 @@ int setup_pipe_mirror(fb_fem_s* h) {
   FB_TRY(ps.pipe_mir_addr.alloc((size_t)P.n_slices * kMirMax * 64));
   FB_TRY(ps.pipe_mir_wg.alloc((size_t)nb));
   FB_TRY(ps.pipe_mir_pool.alloc((size_t)nb * kMirPoolMax));
-  FB_TRY(ps.pipe_mir_stats.alloc(3));
+  FB_TRY(ps.pipe_mir_stats.alloc(4));
   FB_HIP(hipMemsetAsync(ps.pipe_mir_stats.p, 0, 2 * sizeof(int), s));
+  FB_HIP(hipMemsetAsync(ps.pipe_mir_stats.p + 3, 0, sizeof(int), s));
   FB_HIP(hipMemsetAsync(ps.pipe_mir_stats.p + 2, 0x7f, sizeof(int), s));  // (a minimum)
   hipLaunchKernelGGL(k_pipe_mirror_plan, dim3(nb), dim3(64 * kMirWaves), 0, s, P.n_slices, P.n_owned, h->slice_off.p, h->colidx.p, ps.pipe_wg_first.p, K.klt,
-                     h->c16 ? 1 : 0, ps.pipe_mir.p, ps.pipe_mir_addr.p, ps.pipe_mir_pool.p, ps.pipe_mir_wg.p, ps.pipe_mir_stats.p);
+                     h->c16 ? 1 : 0, std::min(ps.pipe_regs, K.regs), ps.pipe_mir.p, ps.pipe_mir_addr.p, ps.pipe_mir_pool.p, ps.pipe_mir_wg.p, ps.pipe_mir_stats.p);
   FB_HIP(hipGetLastError());
   ps.pipe_mir_pending = true;
   return FB_OK;
@@ -689,7 +702,7 @@ int fb_fem_persist_helpers(fb_fem_t h) { return h && h->ps.persist ? h->ps.pipe_
 int fb_fem_persist_mirror(fb_fem_t h, int* mirror_layers, int* pool_entries, int* plain_slots) {
   if (!h) return fail(FB_EINVAL, "null FEM handle");
   if (h->ps.pipe_mir_pending) {
-    FB_TRY(h->ps.pipe_mir_stats.download(h->ps.pipe_mir_got, 3, h->stream));
+    FB_TRY(h->ps.pipe_mir_stats.download(h->ps.pipe_mir_got, 4, h->stream));
     h->ps.pipe_mir_pending = false;
   }
   const bool on = h->ps.persist && h->ps.pipe_mir.p;
@@ -697,6 +710,17 @@ int fb_fem_persist_mirror(fb_fem_t h, int* mirror_layers, int* pool_entries, int
   if (pool_entries) *pool_entries = on ? h->ps.pipe_mir_got[1] : 0;
   if (plain_slots) *plain_slots = on ? h->ps.pipe_mir_got[2] : 0;
   return on && h->ps.pipe_mir_got[0] > 0 ? 1 : 0;
+}
+
+int fb_fem_persist_regs(fb_fem_t h, int* slots_per_slice) {
+  if (!h) return fail(FB_EINVAL, "null FEM handle");
+  const bool on = h->ps.persist && h->ps.pipe_mir.p && h->ps.kernel && h->ps.kernel->regs > 0;
+  if (on && h->ps.pipe_mir_pending) {
+    FB_TRY(h->ps.pipe_mir_stats.download(h->ps.pipe_mir_got, 4, h->stream));
+    h->ps.pipe_mir_pending = false;
+  }
+  if (slots_per_slice) *slots_per_slice = on ? std::min(h->ps.pipe_regs, h->ps.kernel->regs) : 0;
+  return on ? h->ps.pipe_mir_got[3] : 0;
 }
 
 int fb_fem_persist_gather(fb_fem_t h, double* lines_planes, double* lines_records) {

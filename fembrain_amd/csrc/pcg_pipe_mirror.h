@@ -99,6 +99,19 @@ __host__ __device__ inline bool mir_wg_layout(MirWave* mw, int count, int klt, b
   return true;
 }
 
+// Register slots of a slice (pcg_pipe_regs.hip.h): of `regs` (what the instantiation holds and FEMBRAIN_PIPE_REGS allows) as many as the slice streams.
+// mir_reg_split: nb of them follow the plain layers -- as many as there are slots behind the window --, the other nf precede the mirror layers, so
+// streamed [0, a - nf) | register | mirror [a, a + m) | plain [a + m, a + m + p) | register | streamed [a + m + p + nb, width) partition the slice in slot order.
+__host__ __device__ inline int mir_reg_slots(const MirWave& w, int regs) {
+  const int behind = w.width - (w.a + w.m + w.p) > 0 ? w.width - (w.a + w.m + w.p) : 0, streamed = w.a + behind;
+  return regs < streamed ? (regs > 0 ? regs : 0) : streamed;
+}
+__host__ __device__ inline void mir_reg_split(const MirWave& w, int r, int* nf, int* nb) {
+  const int behind = w.width - (w.a + w.m + w.p) > 0 ? w.width - (w.a + w.m + w.p) : 0;
+  *nb = r < behind ? r : behind;
+  *nf = r - *nb < w.a ? r - *nb : w.a;
+}
+
 // byte offset of the pool (after the plain layers and the mirror tables)
 __host__ __device__ inline int mir_pool_at(const MirWave* mw, int count, bool c16) {
   int b = 0;

@@ -27,36 +27,36 @@ namespace fb {
 // one block row: the words are in v152, v153, v154; NEXT_AB / NEXT_C read the next row's into them as soon as they are consumed
 #define FBO_ROW(y, x0, x1, x2, NEXT_AB, NEXT_C)                            \
   "s_waitcnt lgkmcnt(0)\n\t"                                               \
-  "v_cvt_f64_f32_e32 v[120:121], v152\n\t"                                 \
-  "v_cvt_f64_f32_e32 v[122:123], v153\n\t"                                 \
+  "v_cvt_f64_f32_e32 " FBV_120_121 ", " FBV_152 "\n\t"                                 \
+  "v_cvt_f64_f32_e32 " FBV_122_123 ", " FBV_153 "\n\t"                                 \
   NEXT_AB                                                                  \
-  "v_mul_f64 v[120:121], " x0 ", v[120:121]\n\t"                           \
-  "v_mul_f64 v[122:123], " x1 ", v[122:123]\n\t"                           \
-  "v_add_f64 v[120:121], v[120:121], v[122:123]\n\t"                       \
-  "v_cvt_f64_f32_e32 v[122:123], v154\n\t"                                 \
+  "v_mul_f64 " FBV_120_121 ", " x0 ", " FBV_120_121 "\n\t"                           \
+  "v_mul_f64 " FBV_122_123 ", " x1 ", " FBV_122_123 "\n\t"                           \
+  "v_add_f64 " FBV_120_121 ", " FBV_120_121 ", " FBV_122_123 "\n\t"                       \
+  "v_cvt_f64_f32_e32 " FBV_122_123 ", " FBV_154 "\n\t"                                 \
   NEXT_C                                                                   \
-  "v_mul_f64 v[122:123], " x2 ", v[122:123]\n\t"                           \
-  "v_add_f64 v[120:121], v[120:121], v[122:123]\n\t"                       \
-  "v_add_f64 " y ", " y ", v[120:121]\n\t"
+  "v_mul_f64 " FBV_122_123 ", " x2 ", " FBV_122_123 "\n\t"                           \
+  "v_add_f64 " FBV_120_121 ", " FBV_120_121 ", " FBV_122_123 "\n\t"                       \
+  "v_add_f64 " y ", " y ", " FBV_120_121 "\n\t"
 // words o0, o1 (x 256 bytes) and o2 (bytes) of the block at LDS address A
-#define FBO_READ_AB(A, o0, o1) "ds_read2st64_b32 v[152:153], " A " offset0:" o0 " offset1:" o1 "\n\t"
-#define FBO_READ_C(A, o2) "ds_read_b32 v154, " A " offset:" o2 "\n\t"
+#define FBO_READ_AB(A, o0, o1) "ds_read2st64_b32 " FBV_152_153 ", " A " offset0:" o0 " offset1:" o1 "\n\t"
+#define FBO_READ_C(A, o2) "ds_read_b32 " FBV_154 ", " A " offset:" o2 "\n\t"
 // a plain layer: row a of the block is words 3a, 3a + 1, 3a + 2
 #define FBO_COMPUTE_PLAIN(x0, x1, x2, A)                                                               \
   FBO_ROW("%[y0]", x0, x1, x2, FBO_READ_AB(A, "3", "4"), FBO_READ_C(A, "1280"))                        \
   FBO_ROW("%[y1]", x0, x1, x2, FBO_READ_AB(A, "6", "7"), FBO_READ_C(A, "2048"))                        \
-  FBO_ROW("%[y2]", x0, x1, x2, "", "")
+  FBO_ROW("%[y2]", x0, x1, x2,,)
 #define FBO_FIRST_PLAIN(A) FBO_READ_AB(A, "0", "1") FBO_READ_C(A, "512")
 // a mirror layer: row a of the block is words a, a + 3, a + 6 of the partner's (the transpose)
 #define FBO_COMPUTE_MIR(x0, x1, x2, A)                                                                 \
   FBO_ROW("%[y0]", x0, x1, x2, FBO_READ_AB(A, "1", "4"), FBO_READ_C(A, "1792"))                        \
   FBO_ROW("%[y1]", x0, x1, x2, FBO_READ_AB(A, "2", "5"), FBO_READ_C(A, "2048"))                        \
-  FBO_ROW("%[y2]", x0, x1, x2, "", "")
+  FBO_ROW("%[y2]", x0, x1, x2,,)
 #define FBO_FIRST_MIR(A) FBO_READ_AB(A, "0", "3") FBO_READ_C(A, "1536")
 #define FBO_GATHER(x0, x1, x2)                                             \
-  "global_load_dwordx2 " x0 ", v122, %[spl0]\n\t"                          \
-  "global_load_dwordx2 " x1 ", v122, %[spl1]\n\t"                          \
-  "global_load_dwordx2 " x2 ", v122, %[spl2]\n\t"
+  "global_load_dwordx2 " x0 ", " FBV_122 ", %[spl0]\n\t"                          \
+  "global_load_dwordx2 " x1 ", " FBV_122 ", %[spl1]\n\t"                          \
+  "global_load_dwordx2 " x2 ", " FBV_122 ", %[spl2]\n\t"
 // The next layer's column and block address, then its gathers.  16-bit columns: a mirror layer's table word is (LDS word of the block) << 16 |
 // (column - row), a plain layer's column difference is a halfword behind the wavefront's values.  32-bit columns: the mirror table is 384 bytes
 // per layer (64 columns, then 64 halfword addresses), a plain layer's column is the tenth word of its slot.
@@ -64,36 +64,36 @@ namespace fb {
   "ds_read_b32 " A ", %[lmt]\n\t"                                          \
   "v_add_u32_e32 %[lmt], 0x100, %[lmt]\n\t"                                \
   "s_waitcnt lgkmcnt(0)\n\t"                                               \
-  "v_bfe_i32 v122, " A ", 0, 16\n\t"                                       \
-  "v_add_u32_e32 v122, %[row], v122\n\t"                                   \
-  "v_lshlrev_b32_e32 v122, 3, v122\n\t"                                    \
+  "v_bfe_i32 " FBV_122 ", " A ", 0, 16\n\t"                                       \
+  "v_add_u32_e32 " FBV_122 ", %[row], " FBV_122 "\n\t"                                   \
+  "v_lshlrev_b32_e32 " FBV_122 ", 3, " FBV_122 "\n\t"                                    \
   FBO_GATHER(x0, x1, x2)                                                   \
   "v_lshrrev_b32_e32 " A ", 16, " A "\n\t"                                 \
   "v_lshl_add_u32 " A ", " A ", 2, %[lmat]\n\t"
 #define FBO_ISSUE_PLAIN16(x0, x1, x2, A)                                   \
-  "ds_read_i16 v122, %[lcd]\n\t"                                           \
+  "ds_read_i16 " FBV_122 ", %[lcd]\n\t"                                           \
   "v_add_u32_e32 %[lcd], 0x80, %[lcd]\n\t"                                 \
   "v_mov_b32_e32 " A ", %[lres]\n\t"                                       \
   "v_add_u32_e32 %[lres], 0x900, %[lres]\n\t"                              \
   "s_waitcnt lgkmcnt(0)\n\t"                                               \
-  "v_add_u32_e32 v122, %[row], v122\n\t"                                   \
-  "v_lshlrev_b32_e32 v122, 3, v122\n\t"                                    \
+  "v_add_u32_e32 " FBV_122 ", %[row], " FBV_122 "\n\t"                                   \
+  "v_lshlrev_b32_e32 " FBV_122 ", 3, " FBV_122 "\n\t"                                    \
   FBO_GATHER(x0, x1, x2)
 #define FBO_ISSUE_MIR32(x0, x1, x2, A)                                     \
-  "ds_read_b32 v122, %[lmt]\n\t"                                           \
+  "ds_read_b32 " FBV_122 ", %[lmt]\n\t"                                           \
   "ds_read_u16 " A ", %[lmt2] offset:256\n\t"                              \
   "v_add_u32_e32 %[lmt], 0x180, %[lmt]\n\t"                                \
   "v_add_u32_e32 %[lmt2], 0x180, %[lmt2]\n\t"                              \
   "s_waitcnt lgkmcnt(0)\n\t"                                               \
-  "v_lshlrev_b32_e32 v122, 3, v122\n\t"                                    \
+  "v_lshlrev_b32_e32 " FBV_122 ", 3, " FBV_122 "\n\t"                                    \
   FBO_GATHER(x0, x1, x2)                                                   \
   "v_lshl_add_u32 " A ", " A ", 2, %[lmat]\n\t"
 #define FBO_ISSUE_PLAIN32(x0, x1, x2, A)                                   \
-  "ds_read_b32 v122, %[lres] offset:2304\n\t"                              \
+  "ds_read_b32 " FBV_122 ", %[lres] offset:2304\n\t"                              \
   "v_mov_b32_e32 " A ", %[lres]\n\t"                                       \
   "v_add_u32_e32 %[lres], 0xa00, %[lres]\n\t"                              \
   "s_waitcnt lgkmcnt(0)\n\t"                                               \
-  "v_lshlrev_b32_e32 v122, 3, v122\n\t"                                    \
+  "v_lshlrev_b32_e32 " FBV_122 ", 3, " FBV_122 "\n\t"                                    \
   FBO_GATHER(x0, x1, x2)
 // the next layer not yet issued, if there is one, into set J: mirror layers first (mi of them left), then plain ones (pi left); fl = slots in flight
 #define FBO_ISSUE(J, ISSUE_MIR, ISSUE_PLAIN, x0, x1, x2, A)                \
@@ -148,10 +148,10 @@ namespace fb {
   FBO_COMPUTE_PLAIN(x0, x1, x2, A)                                         \
   ".Lfbo_ci" J "_%=:\n\t"                                                  \
   FBO_ISSUE(J, ISSUE_MIR, ISSUE_PLAIN, x0, x1, x2, A)
-#define FBO_SET0 "v[124:125]", "v[126:127]", "v[128:129]", "v148"
-#define FBO_SET1 "v[130:131]", "v[132:133]", "v[134:135]", "v149"
-#define FBO_SET2 "v[136:137]", "v[138:139]", "v[140:141]", "v150"
-#define FBO_SET3 "v[142:143]", "v[144:145]", "v[146:147]", "v151"
+#define FBO_SET0 FBV_124_125, FBV_126_127, FBV_128_129, FBV_148
+#define FBO_SET1 FBV_130_131, FBV_132_133, FBV_134_135, FBV_149
+#define FBO_SET2 FBV_136_137, FBV_138_139, FBV_140_141, FBV_150
+#define FBO_SET3 FBV_142_143, FBV_144_145, FBV_146_147, FBV_151
 #define FBO_ISSUE_(J, ISSUE_MIR, ISSUE_PLAIN, SET) FBO_ISSUE(J, ISSUE_MIR, ISSUE_PLAIN, SET)
 #define FBO_SLOT_(J, ISSUE_MIR, ISSUE_PLAIN, SET) FBO_SLOT(J, ISSUE_MIR, ISSUE_PLAIN, SET)
 #define FBO_BODY(ISSUE_MIR, ISSUE_PLAIN)                                                                        \

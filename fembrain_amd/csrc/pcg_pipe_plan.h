@@ -76,6 +76,9 @@ struct PersistKnobs {
   int plain_stores = -1;
   // FEMBRAIN_PIPE_MIRROR=0: no LDS window (pcg_pipe_mirror.h).  Per HANDLE: what the first plan build read holds for its re-syncs
   bool mirror = true;
+  // FEMBRAIN_PIPE_REGS=0|2|3: streamed slots per slice whose values the run-ahead LDS-window kernels keep in registers for a launch
+  // (pcg_pipe_regs.hip.h).  Not set: as many as the instantiation holds, 3; 0: the kernel without
+  int regs = -1;
   // FEMBRAIN_TIMING (the library's): one line per decision on stderr
   bool verbose = false;
 };

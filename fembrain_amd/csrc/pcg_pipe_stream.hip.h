@@ -17,12 +17,14 @@
 //     y_a += (double)v[3a] * x0 + (double)v[3a+1] * x1 + (double)v[3a+2] * x2        (-ffp-contract=off: mul, mul, add, mul, add, add)
 // so a product has the bits of k_spmv's.
 // Registers: operands are allocated by the compiler; the 36 temporaries are v120..v155 (clobbers) -- a kernel using this has at
-// least 156 registers per lane, which every k_pcg_pipe instantiation needs for its state anyway.
+// least 156 registers per lane, which every k_pcg_pipe instantiation needs for its state anyway.  The text below calls them FBV_120..FBV_155
+// (pcg_pipe_temps.h): the instantiations with register slots expand the same loops over v64..v99 (pcg_pipe_regs.hip.h).
 // A product of the LDS-window kernels calls this twice, for the slots in front of the window and for those behind it; the on-chip run
 // between them is pcg_pipe_onchip.hip.h, which uses the same 36 temporaries and FBP_ROW's arithmetic.  Each of the three parts fills and
 // drains its own pipeline (vmcnt(0) at its end).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "pcg_pipe_temps.h"
 
 namespace fb {
 
@@ -38,49 +40,49 @@ namespace fb {
   "global_load_dword " r7 ", %[voff], %[svals] offset:1792\n\t"            \
   "global_load_dword " r8 ", %[voff], %[svals] offset:2048\n\t"            \
   "v_add_u32_e32 %[voff], 0x900, %[voff]\n\t"
-#define FBP_LOADV_A FBP_LOADV("v136", "v137", "v138", "v139", "v140", "v141", "v142", "v143", "v144")
-#define FBP_LOADV_B FBP_LOADV("v145", "v146", "v147", "v148", "v149", "v150", "v151", "v152", "v153")
+#define FBP_LOADV_A FBP_LOADV(FBV_136, FBV_137, FBV_138, FBV_139, FBV_140, FBV_141, FBV_142, FBV_143, FBV_144)
+#define FBP_LOADV_B FBP_LOADV(FBV_145, FBV_146, FBV_147, FBV_148, FBV_149, FBV_150, FBV_151, FBV_152, FBV_153)
 // column word: 16-bit difference to the row (C16) or the 32-bit column
 #define FBP_LOADC16(c) "global_load_sshort " c ", %[coff], %[scols]\n\t" "v_add_u32_e32 %[coff], 0x80, %[coff]\n\t"
 #define FBP_LOADC32(c) "global_load_dword " c ", %[coff], %[scols]\n\t" "v_add_u32_e32 %[coff], 0x100, %[coff]\n\t"
 // byte offset of the column in a plane (v122: a temporary of the arithmetic, free while loads are issued; the offset register is
 // read when a load is issued), then the three gathers
-#define FBP_GOFF16(c) "v_add_u32_e32 v122, %[row], " c "\n\t" "v_lshlrev_b32_e32 v122, 3, v122\n\t"
-#define FBP_GOFF32(c) "v_lshlrev_b32_e32 v122, 3, " c "\n\t"
+#define FBP_GOFF16(c) "v_add_u32_e32 " FBV_122 ", %[row], " c "\n\t" "v_lshlrev_b32_e32 " FBV_122 ", 3, " FBV_122 "\n\t"
+#define FBP_GOFF32(c) "v_lshlrev_b32_e32 " FBV_122 ", 3, " c "\n\t"
 // the same for a gathered vector stored node by node (x, y, z of a node side by side, 24 bytes apart; the three "planes" are then the
 // same array at +0, +8, +16 bytes): an irregular mesh's 64 columns of a slot lie in 64 different cache lines, and with planes in 3 x 64
-#define FBP_GOFF16X(c) "v_add_u32_e32 v122, %[row], " c "\n\t" "v_mul_u32_u24_e32 v122, 24, v122\n\t"
-#define FBP_GOFF32X(c) "v_mul_u32_u24_e32 v122, 24, " c "\n\t"
+#define FBP_GOFF16X(c) "v_add_u32_e32 " FBV_122 ", %[row], " c "\n\t" "v_mul_u32_u24_e32 " FBV_122 ", 24, " FBV_122 "\n\t"
+#define FBP_GOFF32X(c) "v_mul_u32_u24_e32 " FBV_122 ", 24, " c "\n\t"
 #define FBP_GATHER(g0, g1, g2)                                             \
-  "global_load_dwordx2 " g0 ", v122, %[spl0]\n\t"                          \
-  "global_load_dwordx2 " g1 ", v122, %[spl1]\n\t"                          \
-  "global_load_dwordx2 " g2 ", v122, %[spl2]\n\t"
-#define FBP_GATHER_A FBP_GATHER("v[124:125]", "v[126:127]", "v[128:129]")
-#define FBP_GATHER_B FBP_GATHER("v[130:131]", "v[132:133]", "v[134:135]")
+  "global_load_dwordx2 " g0 ", " FBV_122 ", %[spl0]\n\t"                          \
+  "global_load_dwordx2 " g1 ", " FBV_122 ", %[spl1]\n\t"                          \
+  "global_load_dwordx2 " g2 ", " FBV_122 ", %[spl2]\n\t"
+#define FBP_GATHER_A FBP_GATHER(FBV_124_125, FBV_126_127, FBV_128_129)
+#define FBP_GATHER_B FBP_GATHER(FBV_130_131, FBV_132_133, FBV_134_135)
 // node-by-node vector: x and y of the column in one 16-byte load, z in a second one (two loads per slot instead of three)
 #define FBP_GATHERX(g01, g2)                                               \
-  "global_load_dwordx4 " g01 ", v122, %[spl0]\n\t"                         \
-  "global_load_dwordx2 " g2 ", v122, %[spl0] offset:16\n\t"
-#define FBP_GATHERX_A FBP_GATHERX("v[124:127]", "v[128:129]")
-#define FBP_GATHERX_B FBP_GATHERX("v[130:133]", "v[134:135]")
+  "global_load_dwordx4 " g01 ", " FBV_122 ", %[spl0]\n\t"                         \
+  "global_load_dwordx2 " g2 ", " FBV_122 ", %[spl0] offset:16\n\t"
+#define FBP_GATHERX_A FBP_GATHERX(FBV_124_127, FBV_128_129)
+#define FBP_GATHERX_B FBP_GATHERX(FBV_130_133, FBV_134_135)
 #define FBP_ROW(y, a, b, c, x0, x1, x2)                                    \
-  "v_cvt_f64_f32_e32 v[120:121], " a "\n\t"                                \
-  "v_cvt_f64_f32_e32 v[122:123], " b "\n\t"                                \
-  "v_mul_f64 v[120:121], " x0 ", v[120:121]\n\t"                           \
-  "v_mul_f64 v[122:123], " x1 ", v[122:123]\n\t"                           \
-  "v_add_f64 v[120:121], v[120:121], v[122:123]\n\t"                       \
-  "v_cvt_f64_f32_e32 v[122:123], " c "\n\t"                                \
-  "v_mul_f64 v[122:123], " x2 ", v[122:123]\n\t"                           \
-  "v_add_f64 v[120:121], v[120:121], v[122:123]\n\t"                       \
-  "v_add_f64 " y ", " y ", v[120:121]\n\t"
+  "v_cvt_f64_f32_e32 " FBV_120_121 ", " a "\n\t"                                \
+  "v_cvt_f64_f32_e32 " FBV_122_123 ", " b "\n\t"                                \
+  "v_mul_f64 " FBV_120_121 ", " x0 ", " FBV_120_121 "\n\t"                           \
+  "v_mul_f64 " FBV_122_123 ", " x1 ", " FBV_122_123 "\n\t"                           \
+  "v_add_f64 " FBV_120_121 ", " FBV_120_121 ", " FBV_122_123 "\n\t"                       \
+  "v_cvt_f64_f32_e32 " FBV_122_123 ", " c "\n\t"                                \
+  "v_mul_f64 " FBV_122_123 ", " x2 ", " FBV_122_123 "\n\t"                           \
+  "v_add_f64 " FBV_120_121 ", " FBV_120_121 ", " FBV_122_123 "\n\t"                       \
+  "v_add_f64 " y ", " y ", " FBV_120_121 "\n\t"
 #define FBP_COMPUTE_A                                                                          \
-  FBP_ROW("%[y0]", "v136", "v137", "v138", "v[124:125]", "v[126:127]", "v[128:129]")           \
-  FBP_ROW("%[y1]", "v139", "v140", "v141", "v[124:125]", "v[126:127]", "v[128:129]")           \
-  FBP_ROW("%[y2]", "v142", "v143", "v144", "v[124:125]", "v[126:127]", "v[128:129]")
+  FBP_ROW("%[y0]", FBV_136, FBV_137, FBV_138, FBV_124_125, FBV_126_127, FBV_128_129)           \
+  FBP_ROW("%[y1]", FBV_139, FBV_140, FBV_141, FBV_124_125, FBV_126_127, FBV_128_129)           \
+  FBP_ROW("%[y2]", FBV_142, FBV_143, FBV_144, FBV_124_125, FBV_126_127, FBV_128_129)
 #define FBP_COMPUTE_B                                                                          \
-  FBP_ROW("%[y0]", "v145", "v146", "v147", "v[130:131]", "v[132:133]", "v[134:135]")           \
-  FBP_ROW("%[y1]", "v148", "v149", "v150", "v[130:131]", "v[132:133]", "v[134:135]")           \
-  FBP_ROW("%[y2]", "v151", "v152", "v153", "v[130:131]", "v[132:133]", "v[134:135]")
+  FBP_ROW("%[y0]", FBV_145, FBV_146, FBV_147, FBV_130_131, FBV_132_133, FBV_134_135)           \
+  FBP_ROW("%[y1]", FBV_148, FBV_149, FBV_150, FBV_130_131, FBV_132_133, FBV_134_135)           \
+  FBP_ROW("%[y2]", FBV_151, FBV_152, FBV_153, FBV_130_131, FBV_132_133, FBV_134_135)
 // One slot with two or more to follow / with one to follow / the last one; X = the set computed from, Y = the other set.
 // cX holds C(k) (consumed), cY holds C(k+1).
 // (W1..W4: the four counts above for three gathers per slot, "22" "13" "21" "12"; one less each with two)
@@ -95,10 +97,10 @@ namespace fb {
      memory instruction reading such a register needs 5 wait states, and the compiler does not look into this text */         \
   "s_nop 4\n\t"                                                                                                 \
   /* prologue: C(0) -> cA (v154), C(1) -> cB (v155) if it exists, V(0) -> A, G(0) -> A */                       \
-  LOADC("v154")                                                                                                 \
+  LOADC(FBV_154)                                                                                                 \
   "s_cmp_lt_i32 %[n], 2\n\t"                                                                                    \
   "s_cbranch_scc1 .Lfbp_one_%=\n\t"                                                                             \
-  LOADC("v155")                                                                                                 \
+  LOADC(FBV_155)                                                                                                 \
   FBP_LOADV_A                                                                                                   \
   "s_waitcnt vmcnt(10)\n\t"                                                                                     \
   "s_branch .Lfbp_g0_%=\n"                                                                                      \
@@ -106,23 +108,23 @@ namespace fb {
   FBP_LOADV_A                                                                                                   \
   "s_waitcnt vmcnt(9)\n"                                                                                        \
   ".Lfbp_g0_%=:\n\t"                                                                                            \
-  GOFF("v154") GATHER_A                                                                                     \
+  GOFF(FBV_154) GATHER_A                                                                                     \
   /* even slot: compute from A */                                                                               \
   ".Lfbp_even_%=:\n\t"                                                                                          \
   "s_cmp_lt_i32 %[n], 3\n\t"                                                                                    \
   "s_cbranch_scc1 .Lfbp_even_tail_%=\n\t"                                                                       \
-  FBP_FULL(LOADC, GOFF, "v154", "v155", FBP_LOADV_B, GATHER_B, FBP_COMPUTE_A, W1, W2)                               \
+  FBP_FULL(LOADC, GOFF, FBV_154, FBV_155, FBP_LOADV_B, GATHER_B, FBP_COMPUTE_A, W1, W2)                               \
   "s_sub_i32 %[n], %[n], 1\n\t"                                                                                 \
   /* odd slot: compute from B */                                                                                \
   "s_cmp_lt_i32 %[n], 3\n\t"                                                                                    \
   "s_cbranch_scc1 .Lfbp_odd_tail_%=\n\t"                                                                        \
-  FBP_FULL(LOADC, GOFF, "v155", "v154", FBP_LOADV_A, GATHER_A, FBP_COMPUTE_B, W1, W2)                               \
+  FBP_FULL(LOADC, GOFF, FBV_155, FBV_154, FBP_LOADV_A, GATHER_A, FBP_COMPUTE_B, W1, W2)                               \
   "s_sub_i32 %[n], %[n], 1\n\t"                                                                                 \
   "s_branch .Lfbp_even_%=\n"                                                                                    \
   ".Lfbp_even_tail_%=:\n\t"                                                                                     \
   "s_cmp_lt_i32 %[n], 2\n\t"                                                                                    \
   "s_cbranch_scc1 .Lfbp_even_last_%=\n\t"                                                                       \
-  FBP_PENULT(GOFF, "v155", FBP_LOADV_B, GATHER_B, FBP_COMPUTE_A, W3, W4)                                            \
+  FBP_PENULT(GOFF, FBV_155, FBP_LOADV_B, GATHER_B, FBP_COMPUTE_A, W3, W4)                                            \
   FBP_LAST(FBP_COMPUTE_B)                                                                                       \
   "s_branch .Lfbp_end_%=\n"                                                                                     \
   ".Lfbp_even_last_%=:\n\t"                                                                                     \
@@ -131,16 +133,16 @@ namespace fb {
   ".Lfbp_odd_tail_%=:\n\t"                                                                                      \
   "s_cmp_lt_i32 %[n], 2\n\t"                                                                                    \
   "s_cbranch_scc1 .Lfbp_odd_last_%=\n\t"                                                                        \
-  FBP_PENULT(GOFF, "v154", FBP_LOADV_A, GATHER_A, FBP_COMPUTE_B, W3, W4)                                            \
+  FBP_PENULT(GOFF, FBV_154, FBP_LOADV_A, GATHER_A, FBP_COMPUTE_B, W3, W4)                                            \
   FBP_LAST(FBP_COMPUTE_A)                                                                                       \
   "s_branch .Lfbp_end_%=\n"                                                                                     \
   ".Lfbp_odd_last_%=:\n\t"                                                                                      \
   FBP_LAST(FBP_COMPUTE_B)                                                                                       \
   ".Lfbp_end_%=:\n\t"
 #define FBP_CLOBBERS                                                                                                                   \
-  "memory", "scc", "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127", "v128", "v129", "v130", "v131", "v132", "v133",      \
-  "v134", "v135", "v136", "v137", "v138", "v139", "v140", "v141", "v142", "v143", "v144", "v145", "v146", "v147", "v148", "v149",      \
-  "v150", "v151", "v152", "v153", "v154", "v155"
+  "memory", "scc", FBV_120, FBV_121, FBV_122, FBV_123, FBV_124, FBV_125, FBV_126, FBV_127, FBV_128, FBV_129, FBV_130, FBV_131, FBV_132, FBV_133,      \
+  FBV_134, FBV_135, FBV_136, FBV_137, FBV_138, FBV_139, FBV_140, FBV_141, FBV_142, FBV_143, FBV_144, FBV_145, FBV_146, FBV_147, FBV_148, FBV_149,      \
+  FBV_150, FBV_151, FBV_152, FBV_153, FBV_154, FBV_155
 // clang-format on
 
 // n >= 1 slots (wave-uniform); voff = byte offset of the lane's first value of the first slot from `vals` (advances 2304 per
@@ -166,16 +168,16 @@ __device__ __forceinline__ void pipe_prefetch_values(int n, unsigned int voff, c
   asm volatile("s_nop 4\n\t"
                "s_cmp_lt_i32 %[n], 1\n\t"
                "s_cbranch_scc1 .Lfbp_pf_end_%=\n\t"
-               FBP_LOADV("v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127", "v128")
+               FBP_LOADV(FBV_120, FBV_121, FBV_122, FBV_123, FBV_124, FBV_125, FBV_126, FBV_127, FBV_128)
                "s_cmp_lt_i32 %[n], 2\n\t"
                "s_cbranch_scc1 .Lfbp_pf_wait_%=\n\t"
-               FBP_LOADV("v129", "v130", "v131", "v132", "v133", "v134", "v135", "v136", "v137")
+               FBP_LOADV(FBV_129, FBV_130, FBV_131, FBV_132, FBV_133, FBV_134, FBV_135, FBV_136, FBV_137)
                "s_cmp_lt_i32 %[n], 3\n\t"
                "s_cbranch_scc1 .Lfbp_pf_wait_%=\n\t"
-               FBP_LOADV("v138", "v139", "v140", "v141", "v142", "v143", "v144", "v145", "v146")
+               FBP_LOADV(FBV_138, FBV_139, FBV_140, FBV_141, FBV_142, FBV_143, FBV_144, FBV_145, FBV_146)
                "s_cmp_lt_i32 %[n], 4\n\t"
                "s_cbranch_scc1 .Lfbp_pf_wait_%=\n\t"
-               FBP_LOADV("v147", "v148", "v149", "v150", "v151", "v152", "v153", "v154", "v155")
+               FBP_LOADV(FBV_147, FBV_148, FBV_149, FBV_150, FBV_151, FBV_152, FBV_153, FBV_154, FBV_155)
                ".Lfbp_pf_wait_%=:\n\t"
                "s_waitcnt vmcnt(0)\n"
                ".Lfbp_pf_end_%=:\n\t"

@@ -17,6 +17,61 @@ struct fb_plan_s {
   fb::FemPlan plan;
 };
 
+namespace {
+
+// One workgroup of the host model of k_pipe_mirror_plan: the window of each of its slices (pipe_slices' deal).  Returns whether it keeps mirrors;
+// *pool = its pool entries.
+bool mirror_model_wg(const fb::FemPlan& P, int nb, int b, int c16, int klt, fb::MirWave* mw, int* first_out, int* count_out, int* pool) {
+  const int* so = P.slice_off.data();
+  const int* ci = P.colidx.data();
+  // (pipe_slices, pcg_pipe.hip.h)
+  const int xcd = b & 7, j = b >> 3, per = nb >> 3, chunk = (P.n_slices + 7) >> 3, lo_s = xcd * chunk;
+  int len = P.n_slices - lo_s;
+  len = len < 0 ? 0 : (len > chunk ? chunk : len);
+  const int base = len / per, rem = len - base * per;
+  const int first = lo_s + j * base + (j < rem ? j : rem);
+  const int count = std::min(base + (j < rem ? 1 : 0), fb::kMirWaves);
+  *first_out = first; *count_out = count < 0 ? 0 : count; *pool = 0;
+  if (count <= 0) return false;
+  const int lo = first * 64, hi = std::min((first + count) * 64, P.n_owned);
+  for (int w = 0; w < count; w++) {
+    const int sl = first + w, width = so[sl + 1] - so[sl];
+    int hist[256] = {0};
+    for (int l = 0; l < 64; l++) {
+      const int dk = fb::mir_lane_diag(so, ci, sl, l, P.n_owned);
+      if (dk >= 0 && dk < 256) hist[dk]++;
+    }
+    int d = -1, best = 0;
+    for (int k = 0; k < width && k < 256; k++)
+      if (hist[k] > best) { best = hist[k]; d = k; }
+    int m = 0;
+    if (d >= 0)
+      for (; m < fb::kMirMax && d - 1 - m >= 0; m++) {
+        int n = 0;
+        for (int l = 0; l < 64; l++) n += fb::mir_lane_lower(so, ci, sl, d - 1 - m, l, lo, hi) ? 1 : 0;
+        if (n < fb::kMirLanes) break;
+      }
+    mw[w].d = d; mw[w].m = m; mw[w].width = width;
+  }
+  auto misses = [&]() {
+    int e = 0;
+    for (int w = 0; w < count; w++)
+      for (int k = 0; k < mw[w].m; k++)
+        for (int l = 0; l < 64; l++) e += fb::mir_lane_addr(so, ci, first, mw, w, k, l, lo, hi, c16 != 0) < 0 ? 1 : 0;
+    return e;
+  };
+  bool ok = fb::mir_wg_layout(mw, count, klt, c16 != 0, 0, false);
+  int E = ok ? misses() : 0;
+  ok = ok && E <= fb::kMirPoolMax && fb::mir_wg_layout(mw, count, klt, c16 != 0, E, true);
+  if (ok) { E = misses(); ok = fb::mir_wg_gains(mw, count, klt, c16 != 0); }
+  if (!ok) { fb::mir_wg_plain(mw, count, klt, c16 != 0); E = 0; }
+  *pool = E;
+  return ok;
+}
+
+}  // namespace
+
+
 extern "C" {
 
 int fb_plan_create(fb_plan_t* out, int n_nodes, int n_tets, const int* tets, int n_fixed_dofs, const int* fixed_dofs, int n_ranks,
@@ -97,56 +152,36 @@ int fb_plan_shard_vote(int n_nodes, int n_tets, const int* tets, int n_ranks, in
 // out[1] = pool entries, out[2] = fewest plain layers of a slice, out[3] = workgroups that keep mirrors.
 int fb_plan_mirror_model(fb_plan_t p, int nb, int c16, int klt, int out[4]) {
   if (!p || !out || nb < 8 || (nb & 7) || (klt != 6 && klt != 7)) return fb::fail(FB_EINVAL, "bad argument");
-  const fb::FemPlan& P = p->plan;
-  const int* so = P.slice_off.data();
-  const int* ci = P.colidx.data();
   out[0] = out[1] = out[3] = 0;
   out[2] = 1 << 30;
   for (int b = 0; b < nb; b++) {
-    // (pipe_slices, pcg_pipe.hip.h)
-    const int xcd = b & 7, j = b >> 3, per = nb >> 3, chunk = (P.n_slices + 7) >> 3, lo_s = xcd * chunk;
-    int len = P.n_slices - lo_s;
-    len = len < 0 ? 0 : (len > chunk ? chunk : len);
-    const int base = len / per, rem = len - base * per;
-    const int first = lo_s + j * base + (j < rem ? j : rem);
-    const int count = std::min(base + (j < rem ? 1 : 0), fb::kMirWaves);
-    if (count <= 0) continue;
-    const int lo = first * 64, hi = std::min((first + count) * 64, P.n_owned);
     fb::MirWave mw[fb::kMirWaves];
-    for (int w = 0; w < count; w++) {
-      const int sl = first + w, width = so[sl + 1] - so[sl];
-      int hist[256] = {0};
-      for (int l = 0; l < 64; l++) {
-        const int dk = fb::mir_lane_diag(so, ci, sl, l, P.n_owned);
-        if (dk >= 0 && dk < 256) hist[dk]++;
-      }
-      int d = -1, best = 0;
-      for (int k = 0; k < width && k < 256; k++)
-        if (hist[k] > best) { best = hist[k]; d = k; }
-      int m = 0;
-      if (d >= 0)
-        for (; m < fb::kMirMax && d - 1 - m >= 0; m++) {
-          int n = 0;
-          for (int l = 0; l < 64; l++) n += fb::mir_lane_lower(so, ci, sl, d - 1 - m, l, lo, hi) ? 1 : 0;
-          if (n < fb::kMirLanes) break;
-        }
-      mw[w].d = d; mw[w].m = m; mw[w].width = width;
-    }
-    auto misses = [&]() {
-      int e = 0;
-      for (int w = 0; w < count; w++)
-        for (int k = 0; k < mw[w].m; k++)
-          for (int l = 0; l < 64; l++) e += fb::mir_lane_addr(so, ci, first, mw, w, k, l, lo, hi, c16 != 0) < 0 ? 1 : 0;
-      return e;
-    };
-    bool ok = fb::mir_wg_layout(mw, count, klt, c16 != 0, 0, false);
-    int E = ok ? misses() : 0;
-    ok = ok && E <= fb::kMirPoolMax && fb::mir_wg_layout(mw, count, klt, c16 != 0, E, true);
-    if (ok) { E = misses(); ok = fb::mir_wg_gains(mw, count, klt, c16 != 0); }
-    if (!ok) { fb::mir_wg_plain(mw, count, klt, c16 != 0); E = 0; }
+    int first = 0, count = 0, E = 0;
+    const bool ok = mirror_model_wg(p->plan, nb, b, c16, klt, mw, &first, &count, &E);
     for (int w = 0; w < count; w++) { out[0] += mw[w].m; out[2] = std::min(out[2], mw[w].p); }
     out[1] += E;
     out[3] += ok ? 1 : 0;
+  }
+  return FB_OK;
+}
+
+// The register slots that go with that window (pcg_pipe_regs.hip.h; mir_reg_slots / mir_reg_split as k_pipe_mirror_plan and the kernel apply them), per
+// slice: parts[slice][6] = slots streamed in front | register slots in front | mirror layers | plain layers (those the slice has) | register slots
+// behind | slots streamed behind -- in slot order, they add up to the slice's width.
+int fb_plan_regs_model(fb_plan_t p, int nb, int c16, int klt, int regs, int* parts) {
+  if (!p || !parts || nb < 8 || (nb & 7) || (klt != 6 && klt != 7) || regs < 0 || regs > 3) return fb::fail(FB_EINVAL, "bad argument");
+  for (int b = 0; b < nb; b++) {
+    fb::MirWave mw[fb::kMirWaves];
+    int first = 0, count = 0, E = 0;
+    mirror_model_wg(p->plan, nb, b, c16, klt, mw, &first, &count, &E);
+    for (int w = 0; w < count; w++) {
+      const fb::MirWave& q = mw[w];
+      int nf = 0, nbh = 0;
+      fb::mir_reg_split(q, fb::mir_reg_slots(q, regs), &nf, &nbh);
+      const int rest = std::max(q.width - q.a - q.m, 0), plain = std::min(q.p, rest);
+      int* o = parts + (size_t)6 * (first + w);
+      o[0] = q.a - nf; o[1] = nf; o[2] = q.m; o[3] = plain; o[4] = nbh; o[5] = rest - plain - nbh;
+    }
   }
   return FB_OK;
 }

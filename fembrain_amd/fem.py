@@ -738,6 +738,14 @@ class FemIntegrator:
             _l.check(on)
         return bool(on == 1), m.value, p.value, k.value
 
+    def persist_regs(self):
+        """(register slots a slice holds at most: 0, 2 or 3; register slots over all slices) -- fb_fem_persist_regs"""
+        r = C.c_int(0)
+        total = self._L.fb_fem_persist_regs(self.h, C.byref(r))
+        if total < 0:
+            _l.check(total)
+        return r.value, total
+
     def pcg_path(self):
         """What ran: dict(path = FB_PCG_PATH_* of the last solve, kernel = the persistent instantiation this handle launches or '',
         launches, fallbacks, max_producers)"""

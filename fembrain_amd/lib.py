@@ -261,6 +261,7 @@ def lib():
         "fb_plan_info": (C.c_int, [vp, _ip]),
         "fb_plan_get": (C.c_int, [vp, C.c_char_p, _ip, C.c_size_t]),
         "fb_plan_mirror_model": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, _ip]),
+        "fb_plan_regs_model": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, _ip]),
     }
     poly_sig = {
         "fb_fem_transport": (C.c_int, [vp]),
@@ -269,6 +270,7 @@ def lib():
         "fb_fem_persist_helpers": (C.c_int, [vp]),
         "fb_fem_persist_gather": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "fb_fem_persist_mirror": (C.c_int, [vp, _ip, _ip, _ip]),
+        "fb_fem_persist_regs": (C.c_int, [vp, _ip]),
         "fb_fem_renumbering": (C.c_int, [vp, _ip, _ip]),
         "fb_fem_owned_nodes": (C.c_int, [vp, _ip]),
         "fb_fem_halo_info": (C.c_int, [vp, _ip, _ip]),

@@ -761,6 +761,11 @@ int fb_fem_persist_gather(fb_fem_t h, double* lines_planes, double* lines_record
  * fewest plainly stored slots of any slice (never fewer than fb_fem_persist_info's lds_slots).  Returns 1 if some layer is mirrored, else 0
  * (0 / 0 / 0: no window -- other instantiations, FEMBRAIN_PIPE_MIRROR=0).  Any pointer may be NULL. */
 int fb_fem_persist_mirror(fb_fem_t h, int* mirror_layers, int* pool_entries, int* plain_slots);
+/* Register slots of the run-ahead LDS-window kernels (k_pcg_pipe (12, 6) / (12, 7) with a service wavefront, plain Jacobi): up to slots_per_slice
+ * streamed slots of every slice, those next to its LDS window, keep their matrix values in registers for a whole launch (filled at the head of
+ * every launch; the iterates do not change by a bit).  slots_per_slice (may be NULL) = what this handle's launches hold per slice at most: 3,
+ * or what FEMBRAIN_PIPE_REGS=0|2|3 said when the plan was built; a slice holds that many or as many as it streams.  Returns the register slots over all slices (0 / 0: another instantiation, no window, FEMBRAIN_PIPE_REGS=0), < 0: an error. */
+int fb_fem_persist_regs(fb_fem_t h, int* slots_per_slice);
 /* average device seconds of ONE persistent launch that starts a solve of the current system and is cut after n_iters
  * iterations (tolerance out of reach), HIP events on the handle's stream around the launch; the difference of two lengths
  * prices an iteration without the launch's fixed cost */

@@ -27,6 +27,10 @@ int fb_plan_get(fb_plan_t p, const char* name, int* out, size_t capacity);
  * dealt in equal numbers to nb workgroups: out[0] = mirror layers over all slices, out[1] = pool entries, out[2] = fewest plain layers of a
  * slice, out[3] = workgroups that keep mirrors.  c16: 16-bit column words; klt: the instantiation's bound (6 or 7). */
 int fb_plan_mirror_model(fb_plan_t p, int nb, int c16, int klt, int out[4]);
+/* ... and of the register slots that go with that window (fembrain_amd/csrc/pcg_pipe_regs.hip.h; regs = 0..3 slots per slice at most): for every slice
+ * parts[6 * slice + ...] = slots streamed in front | register slots in front | mirror layers | plain layers | register slots behind | slots
+ * streamed behind, in slot order.  parts holds 6 ints per slice of the plan. */
+int fb_plan_regs_model(fb_plan_t p, int nb, int c16, int klt, int regs, int* parts);
 
 /* Host restatement of the handle's internal node order (fembrain_amd/csrc/renumber.h: slab order of the rest positions): the caller id of
  * every internal id, and the widest element (largest id difference inside a tet) in the caller's and in that order */

@@ -55,11 +55,12 @@ def per_launch(path, pat):
     return [(float(r["Counter_Value"]), int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) for r in rows]
 
 
-pipe = [r for r in out if r["kernel"].replace(" ", "").startswith("k_pcg_pipe<float")]
+# (k_pcg_pipe_regs: the same kernel with register slots, fembrain_amd/csrc/pcg_pipe_regs.hip.h)
+pipe = [r for r in out if re.match(r"k_pcg_pipe(_regs)?<float", r["kernel"].replace(" ", ""))]
 if pipe:
     # ONE launch = one whole solve; launches differ in their iteration counts, so the counters are divided by the iterations the
     # same launches ran (bench.py wrote them, FEMBRAIN_BENCH_LAUNCH_LOG): bytes and time per PCG iteration
-    fl_, wl_ = per_launch(fetch, "k_pcg_pipe<float"), per_launch(write, "k_pcg_pipe<float")
+    fl_, wl_ = per_launch(fetch, pipe[0]["kernel"].replace(" ", "").split("<")[0] + "<float"), per_launch(write, pipe[0]["kernel"].replace(" ", "").split("<")[0] + "<float")
     fit = json.load(open(os.environ.get("FETCH_LAUNCHES", "gpurun_out/prof_fetch_launches.json")))["k_pcg_pipe_launch_iterations"]
     wit = json.load(open(os.environ.get("WRITE_LAUNCHES", "gpurun_out/prof_write_launches.json")))["k_pcg_pipe_launch_iterations"]
     assert len(fit) == len(fl_) and len(wit) == len(wl_), (len(fit), len(fl_), len(wit), len(wl_))
