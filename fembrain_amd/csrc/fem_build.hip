@@ -51,6 +51,7 @@ void begin_mesh_generation(fb_fem_s* h, int keep = 0) {
   drop_graph(h);
   h->surf.valid = h->stress.valid = h->parts.valid = false;  // (fb_fem_surface; fb_fem_read_stress / fb_fem_surface_stress; fb_fem_parts)
   embed_mesh_changed(h->embed, keep != 0 || h->map_from_delta);  // (fb_fem_embed: a change in place, or its full rebuild, is followed by resync_delta)
+  contact_mesh_changed(h->contact, keep != 0 || h->map_from_delta);  // (fb_fem_contact_move: the same two keep the session, a full re-sync clears it)
   if (!(keep & kKeepCsr)) h->csr_ready = false;
   if (!(keep & kKeepOrder)) h->ren.clear();
   h->l2c.clear();

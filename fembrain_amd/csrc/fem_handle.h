@@ -1,7 +1,7 @@
 // The FEM handle (fb_fem_t of include/fembrain_hip.h) and what the units that work on it share: fem.hip (assembly, the two-launch
 // solver, the steps and the rest of the C ABI), fem_build.hip (life cycle: plan build, creation, re-sync, cut), fem_persist.hip (the
 // persistent solver's host side), haptic.hip (the probe's entry points), stress.hip (element stress and strain), parts.hip (disjoint parts),
-// detach.hip (a part into a handle of its own), embed.hip (point sets bound to the elements) and embed_touch.hip (forces, picks and stress on them).
+// detach.hip (a part into a handle of its own), embed.hip (point sets bound to the elements), embed_touch.hip (forces, picks and stress on them) and contact.hip (the probe's box contact).
 // Internal: not installed, included by these units only.
 #pragma once
 #include "comm.h"
@@ -18,6 +18,7 @@
 #include "parts.h"
 #include "detach.h"
 #include "embed.h"
+#include "contact.h"
 
 namespace fb {
 
@@ -192,6 +193,7 @@ struct fb_fem_s {
   PartsWork parts;        // fb_fem_parts: face-connected parts of the current mesh (parts.h); empty until somebody asks
   DetachWork detach;      // fb_fem_detach_part: the constrained DOFs of the part being detached (detach.h); empty until somebody asks
   EmbedWork embed;        // fb_fem_embed: point sets bound to the elements, and their search grid (embed.h); empty until somebody asks
+  ContactWork contact;    // fb_fem_contact_move / apply: the probe's touched set, force list and spread records (contact.h); empty until somebody asks
   HapticWork hap;         // fb_fem_add_haptic_forces / pick / volume: level array and scratch (haptic.h); empty until somebody asks
   std::vector<int> fixed_caller;  // the constrained DOFs in the caller's numbering (unsharded): what fb_fem_cut keeps
   DevBuf<int4> tets_next, tets_caller;   // (the element list being built; swapped with `tets`)
@@ -215,7 +217,7 @@ struct fb_fem_s {
   fb::HostKnobs knobs;               // as the last plan build read them
   fb::AsmKernels asm_k;              // the assembly kernels of this plan
   // Per mesh generation -- begin_mesh_generation (fem_build.hip) is the one place that resets them, for build(), its host-builder fallback
-  // and fb_fem_resync_delta: ren, l2c, order_sum, x0_ready, masks_ready, caller_pattern, csr_ready, span_stale (all below), the embeddings' grid and bindings (embed_mesh_changed), surf.valid,
+  // and fb_fem_resync_delta: ren, l2c, order_sum, x0_ready, masks_ready, caller_pattern, csr_ready, span_stale (all below), the embeddings' grid and bindings (embed_mesh_changed), the contact session (contact_mesh_changed), surf.valid,
   // stress.valid and parts.valid (above); batch_graph is dropped with them.  (fb_fem_resync_delta keeps ren, and csr_ready while it decides, and says so.)
   // locality renumbering behind the ABI (renumber.h): the handle works in its own node order, ids are mapped on the way in and out
   Renumbering ren;

@@ -52,6 +52,10 @@ constexpr size_t kHapticArgBytes = sizeof(double) * (3 * (size_t)FB_HAPTIC_MAX_S
 // new_of_old: the renumbering's map (null: the caller's order is the internal one).  No host wait: the arguments leave through pinned staging.
 int haptic_spread(hipStream_t s, HapticWork& H, int n_nodes, int n_tets, const int4* tets, const int* new_of_old, int n, const int* ids, const double* forces3, int size,
                   double* fext);
+// ... the rings alone, of n sources already on the device (d_ids[n], d_f3[3 n], d_mag[size]; the sources' own nodes are the caller's to add):
+// the level-array passes in batches of kHapticBatch, for any n.  What haptic_spread ends with, and fb_fem_contact_apply's fallback.
+int haptic_spread_rings(hipStream_t s, HapticWork& H, int n_nodes, int n_tets, const int4* tets, const int* new_of_old, int n, const int* d_ids, const double* d_f3,
+                        const double* d_mag, int size, double* fext);
 int haptic_pick_vertex(hipStream_t s, HapticWork& H, int n_nodes, const double* x0, const double* q, const int* new_of_old, const double wpos[3], PickResult* out);
 int haptic_pick_box(hipStream_t s, HapticWork& H, int n_nodes, const double* x0, const double* q, const int* new_of_old, const double lo[3], const double hi[3], int capacity,
                     int* ids, double* xyz, int* n_found);

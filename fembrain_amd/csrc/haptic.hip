@@ -267,15 +267,19 @@ int haptic_spread(hipStream_t s, HapticWork& H, int n_nodes, int n_tets, const i
   for (int j = 1; j < size; j++) hd[3 * (size_t)n + j] = 1.0 * (size - j) / static_cast<double>(size);
   memcpy(H.args_pinned + sizeof(double) * n_dbl, ids, sizeof(int) * (size_t)n);
   FB_TRY(H.args.reserve(kHapticArgBytes));
-  const int nb_max = std::min(n, kHapticBatch);
-  if (size > 1) FB_TRY(H.level.reserve((size_t)nb_max * n_nodes));
   FB_HIP(hipMemcpyAsync(H.args.p, H.args_pinned, n_bytes, hipMemcpyHostToDevice, s));
   FB_HIP(hipEventRecord(H.args_ev, s));
   const double* d_f3 = reinterpret_cast<const double*>(H.args.p);
   const double* d_mag = d_f3 + 3 * (size_t)n;
   const int* d_ids = reinterpret_cast<const int*>(H.args.p + sizeof(double) * n_dbl);
   FB_TRY(launch_1d(k_hap_direct, n, s, n, d_ids, d_f3, new_of_old, n_nodes, fext));
-  if (size <= 1 || n_tets <= 0) return FB_OK;
+  return haptic_spread_rings(s, H, n_nodes, n_tets, tets, new_of_old, n, d_ids, d_f3, d_mag, size, fext);
+}
+
+int haptic_spread_rings(hipStream_t s, HapticWork& H, int n_nodes, int n_tets, const int4* tets, const int* new_of_old, int n, const int* d_ids, const double* d_f3,
+                        const double* d_mag, int size, double* fext) {
+  if (n <= 0 || size <= 1 || n_tets <= 0) return FB_OK;
+  FB_TRY(H.level.reserve((size_t)std::min(n, kHapticBatch) * n_nodes));
   for (int base = 0; base < n; base += kHapticBatch) {  // ascending: the order of every node's additions
     const int nb = std::min(kHapticBatch, n - base);
     FB_HIP(hipMemsetAsync(H.level.p, 0xFF, (size_t)nb * n_nodes, s));

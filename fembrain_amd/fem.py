@@ -618,6 +618,46 @@ class FemIntegrator:
         _l.check(self._L.fb_fem_volume(self.h, C.byref(t), _l.dptr(pe)))
         return (t.value, pe) if per_element else t.value
 
+    # -- the probe's box contact on the device (fb_fem_contact_move / apply; unsharded handles) --
+    @staticmethod
+    def _contact_info(c):
+        return dict(status=c.status, n_touched=c.n_touched, n_new=c.n_new, face=c.face, closest_node=c.closest_node, n_pushing=c.n_pushing,
+                    list_size=c.list_size, n_clears=c.n_clears, contact_dist=c.contact_dist, closest_point=np.array(c.closest_point[:], np.float64))
+
+    def contact_move(self, lo, hi, force_coeff):
+        """``AvatarProbe::onTranslate`` below its pick-mode branch, on the device: the tool box [lo, hi] against the tissue -- miss test,
+        touched set with first-touch positions, contact face, penalty forces.  The list stays on the device (``contact_apply`` spreads
+        it); the info dict comes back.  What ``ProbeContact.move`` computes on the host."""
+        lo, hi = _l.as_f64(lo, 3), _l.as_f64(hi, 3)
+        c = _l.ContactInfo()
+        _l.check(self._L.fb_fem_contact_move(self.h, _l.dptr(lo), _l.dptr(hi), float(force_coeff), C.byref(c)))
+        return self._contact_info(c)
+
+    def contact_info(self):
+        """The contact session's state without a move"""
+        c = _l.ContactInfo()
+        _l.check(self._L.fb_fem_contact_info_get(self.h, C.byref(c)))
+        return self._contact_info(c)
+
+    def contact_reset(self, keep_face=True):
+        """Clears the touched set and the force list; ``keep_face`` keeps the contact face (the reference's mouse-up), False is a new probe"""
+        _l.check(self._L.fb_fem_contact_reset(self.h, 1 if keep_face else 0))
+
+    def read_contact(self):
+        """(ids (k,), first-touch positions (k, 3), forces (k, 3)) of the stored list, ascending ids"""
+        k = self.contact_info()["list_size"]
+        ids, first, f = np.zeros(k, np.int32), np.zeros((k, 3)), np.zeros((k, 3))
+        if k:
+            _l.check(self._L.fb_fem_read_contact(self.h, _l.iptr(ids), _l.dptr(first), _l.dptr(f)))
+        return ids, first, f
+
+    def contact_apply(self, neighborhood_size):
+        """``Deformable::applyHapticForces`` on the stored contact list, added into the current external force vector; any number of
+        sources.  Returns dict(n_sources, n_pushing, path, n_targets, n_records)."""
+        c = _l.ContactSpreadInfo()
+        _l.check(self._L.fb_fem_contact_apply(self.h, int(neighborhood_size), C.byref(c)))
+        return dict(n_sources=c.n_sources, n_pushing=c.n_pushing, path=c.path, n_targets=c.n_targets, n_records=c.n_records)
+
     # -- element stress and strain on the device (fb_fem_stress / read_stress / surface_stress; unsharded handles) --
     def stress(self, world=False, tensors=False):
         """Stress and strain of every element at the current state, kept on the device (fb_fem_stress): the bracket of the corotational
@@ -820,6 +860,81 @@ def spread_haptic_forces(bptr, bcol, indices, forces, neighborhood_size, ext_for
     return ext_forces
 
 
+class ProbeContact:
+    """``AvatarProbe::onTranslate`` (reference src/deformable/AvatarProbe.cpp:124-265) below its pick-mode branch, on the host: the tool
+    box against the tissue, the hash of touched nodes with their first-touch positions (a dict keyed by node id, walked in sorted
+    order as the reference's std::map is), the contact face and the penalty forces.  What ``FemIntegrator.contact_move`` runs on
+    the device; field by field the same info."""
+
+    FACES = ("LEFT", "RIGHT", "BOTTOM", "TOP", "NEAR", "FAR")
+    NORMALS = np.array([[-1.0, 0, 0], [1.0, 0, 0], [0, -1.0, 0], [0, 1.0, 0], [0, 0, -1.0], [0, 0, 1.0]])
+
+    def __init__(self):
+        self.n_clears = 0
+        self.hash = {}
+        self.reset(keep_face=False)
+
+    def reset(self, keep_face=True):
+        self.hash = {}
+        self.ids, self.forces = np.zeros(0, np.int32), np.zeros((0, 3))
+        self._info = dict(status=_l.FB_CONTACT_MISS, n_touched=0, n_new=0, face=self._info["face"] if keep_face else -1, closest_node=-1, n_pushing=0,
+                          list_size=0, n_clears=self.n_clears, contact_dist=0.0, closest_point=np.zeros(3))
+
+    def clear(self):
+        """What a full re-sync does to the device session"""
+        self.n_clears += 1
+        self.reset(keep_face=False)
+
+    def info(self):
+        return dict(self._info, closest_point=self._info["closest_point"].copy())
+
+    def read(self):
+        """(ids, first-touch positions, forces) of the stored list"""
+        first = np.array([self.hash[int(i)] for i in self.ids], np.float64).reshape(-1, 3)
+        return self.ids.copy(), first, self.forces.copy()
+
+    def move(self, positions, lo, hi, force_coeff):
+        """positions: (n, 3) x0 + q of every node.  Returns the info dict."""
+        lo, hi = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
+        if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (lo <= hi).all() and np.isfinite(force_coeff)):
+            raise ValueError("bad tool box or force coefficient")
+        p = np.asarray(positions, np.float64).reshape(-1, 3)
+        # 1. AABB::intersect on the float boxes, strict
+        pf = p.astype(np.float32)
+        t_lo, t_hi = pf.min(axis=0), pf.max(axis=0)
+        if ((t_lo >= hi.astype(np.float32)) | (t_hi <= lo.astype(np.float32))).any():
+            self._info.update(status=_l.FB_CONTACT_MISS, n_new=0)
+            return self.info()
+        # 2. pickVertices, bounds included; a node already in the hash keeps its first position
+        inside = np.nonzero(((p >= lo) & (p <= hi)).all(axis=1))[0]
+        n_new = 0
+        for i in inside:
+            if int(i) not in self.hash:
+                self.hash[int(i)] = p[i].copy()
+                n_new += 1
+        if not self.hash:
+            self._info.update(status=_l.FB_CONTACT_EMPTY, n_new=0)
+            return self.info()
+        # 3. d(k, j) = (s_j - p_k) . n_j, the dot product summed left to right
+        ids = np.array(sorted(self.hash), np.int32)
+        first = np.array([self.hash[int(i)] for i in ids], np.float64).reshape(-1, 3)
+        s = np.array([lo, hi, lo, hi, lo, hi])
+        t = (s[None, :, :] - first[:, None, :]) * self.NORMALS[None, :, :]
+        d = (t[:, :, 0] + t[:, :, 1]) + t[:, :, 2]
+        face = self._info["face"]
+        if face < 0:
+            k, face = divmod(int(np.argmin(d)), 6)  # (the first of equal minima: nodes ascending, then faces)
+        else:
+            k = int(np.argmin(d[:, face]))
+        # 4. the forces
+        v = d[:, face] * float(force_coeff)
+        mag = np.where(v > 0.0, v, 0.0)
+        self.ids, self.forces = ids, self.NORMALS[face][None, :] * mag[:, None]
+        self._info.update(status=_l.FB_CONTACT_SET, n_touched=len(ids), n_new=n_new, face=face, closest_node=int(ids[k]), n_pushing=int((mag > 0.0).sum()),
+                          list_size=len(ids), contact_dist=float(d[k, face]), closest_point=first[k].copy())
+        return self.info()
+
+
 class Deformable:
     """Per-step driver of ``Deformable::timestep`` (reference src/deformable/Deformable.cpp:318-420) without the
     scene-graph / GL parts: external forces (gravity -10000 per y-DOF unless a collision happened in the previous
@@ -843,6 +958,8 @@ class Deformable:
         self.haptic_force_neighborhood_size = 5  # DEFAULT_FORCE_NEIGHBORHOOD_SIZE, Deformable.h:41
         self._pattern = None
         self.haptic_on_device = bool(haptic_on_device) and kw.get("shard") is None
+        self.probe = ProbeContact()  # the host route's contact session (probe_move)
+        self._contact_list = False   # the list set last is the device session's (probe_move on the device route), not haptic_indices
         self.on_deform = None  # FOnApplyDeformations(dof, q), Deformable.h:46
         self._embed_tris = {}  # triangles of the embeddings made through embed()
 
@@ -851,6 +968,33 @@ class Deformable:
 
     def haptic_set_current_forces(self, indices, forces):
         self.haptic_indices, self.haptic_forces = list(indices), [tuple(f) for f in forces]
+        self._contact_list = False  # (the list set last wins)
+
+    def probe_start(self):
+        """The probe's mouse-down without a picked node (AvatarProbe.cpp:108-109): haptics in progress"""
+        self.haptic_start(0)
+
+    def probe_move(self, lo, hi, force_coeff):
+        """``AvatarProbe::onTranslate`` with the tool box [lo, hi]: the contact session decides the touched nodes, the face and the forces,
+        and its list becomes the current haptic forces (every ``timestep`` spreads it).  On the device route nothing but the info comes
+        back; on the host route ``ProbeContact`` works on the positions read back.  Returns the info dict."""
+        if self.haptic_on_device:
+            info = self.integrator.contact_move(lo, hi, force_coeff)
+            if info["status"] == _l.FB_CONTACT_SET:
+                self.haptic_indices, self.haptic_forces, self._contact_list = [], [], True
+        else:
+            info = self.probe.move(self._positions(), lo, hi, force_coeff)
+            if info["status"] == _l.FB_CONTACT_SET:
+                self.haptic_set_current_forces(self.probe.ids, self.probe.forces)
+        return info
+
+    def probe_end(self):
+        """The probe's mouse-up (AvatarProbe.cpp:116-120): haptics end, the touched set is cleared, the face stays"""
+        self.haptic_end()
+        if self.haptic_on_device:
+            self.integrator.contact_reset(keep_face=True)
+        else:
+            self.probe.reset(keep_face=True)
 
     def set_haptic_force_radius(self, radius):
         self.haptic_force_neighborhood_size = int(radius)
@@ -864,11 +1008,18 @@ class Deformable:
     def haptic_end(self):
         self.haptic_in_progress = False
         self.haptic_indices, self.haptic_forces = [], []
+        self._contact_list = False
 
     def timestep(self):
         it = self.integrator
         apply_gravity = self.gravity and self.ct_collided == 0
-        if self.haptic_in_progress and self.haptic_indices and self.haptic_on_device and len(self.haptic_indices) <= _l.FB_HAPTIC_MAX_SOURCES:
+        if self.haptic_in_progress and self._contact_list:  # (the device session's list, any length)
+            if apply_gravity:
+                it.set_uniform_force(1, self.GRAVITY_FORCE)
+            else:
+                it.set_external_forces_to_zero()
+            it.contact_apply(self.haptic_force_neighborhood_size)
+        elif self.haptic_in_progress and self.haptic_indices and self.haptic_on_device and len(self.haptic_indices) <= _l.FB_HAPTIC_MAX_SOURCES:
             if apply_gravity:
                 it.set_uniform_force(1, self.GRAVITY_FORCE)
             else:

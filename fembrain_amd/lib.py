@@ -25,6 +25,8 @@ FB_DETACH_KEEP, FB_DETACH_REMOVE = 0, 1  # fb_fem_detach_part flags
 FB_CUT_NOTHING, FB_CUT_DONE, FB_CUT_UNHANDLED, FB_CUT_DRY = 0, 1, 2, 3
 FB_CUT_UNHANDLED_IDS = 64  # unhandled element ids fb_fem_read_cut returns at most (subdivide.h kCutUnhandledIds)
 FB_HAPTIC_MAX_SOURCES = 256  # sources fb_fem_add_haptic_forces takes in one call
+FB_CONTACT_MISS, FB_CONTACT_EMPTY, FB_CONTACT_SET = 0, 1, 2  # fb_fem_contact_info.status
+FB_CONTACT_SPREAD_RECORDS, FB_CONTACT_SPREAD_LEVELS = 0, 1  # fb_fem_contact_spread_info.path
 FB_MAX_MATERIALS = 256  # entries of a handle's material table (fb_fem_set_materials)
 FB_STRESS_WORLD, FB_STRESS_TENSORS = 1, 2  # fb_fem_stress flags
 
@@ -90,6 +92,15 @@ class DetachInfo(C.Structure):
 class StressInfo(C.Structure):
     _fields_ = [("n_elements", C.c_int), ("flags", C.c_int), ("max_von_mises", C.c_double), ("max_element", C.c_int), ("min_J", C.c_double),
                 ("min_J_element", C.c_int), ("n_inverted", C.c_int), ("energy", C.c_double)]
+
+
+class ContactInfo(C.Structure):
+    _fields_ = [("status", C.c_int), ("n_touched", C.c_int), ("n_new", C.c_int), ("face", C.c_int), ("closest_node", C.c_int), ("n_pushing", C.c_int),
+                ("list_size", C.c_int), ("n_clears", C.c_int), ("contact_dist", C.c_double), ("closest_point", C.c_double * 3)]
+
+
+class ContactSpreadInfo(C.Structure):
+    _fields_ = [("n_sources", C.c_int), ("n_pushing", C.c_int), ("path", C.c_int), ("n_targets", C.c_int), ("n_records", C.c_longlong)]
 
 
 class PolyCounts(C.Structure):
@@ -217,6 +228,11 @@ def lib():
         "fb_fem_pick_vertex": (C.c_int, [vp, _dp, _ip, _dp, _dp]),
         "fb_fem_pick_box": (C.c_int, [vp, _dp, _dp, C.c_int, _ip, _dp, _ip]),
         "fb_fem_volume": (C.c_int, [vp, _dp, _dp]),
+        "fb_fem_contact_move": (C.c_int, [vp, _dp, _dp, C.c_double, C.POINTER(ContactInfo)]),
+        "fb_fem_contact_info_get": (C.c_int, [vp, C.POINTER(ContactInfo)]),
+        "fb_fem_contact_reset": (C.c_int, [vp, C.c_int]),
+        "fb_fem_read_contact": (C.c_int, [vp, _ip, _dp, _dp]),
+        "fb_fem_contact_apply": (C.c_int, [vp, C.c_int, C.POINTER(ContactSpreadInfo)]),
         "fb_fem_stress": (C.c_int, [vp, C.c_int, C.POINTER(StressInfo)]),
         "fb_fem_read_stress": (C.c_int, [vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]),
         "fb_fem_surface_stress": (C.c_int, [vp, _fp]),

@@ -175,6 +175,30 @@ class HipIntegrator {
     check(fb_fem_volume(h_, &total, perElement));
     return total;
   }
+  // The probe's box contact on the device (fembrain_hip.h): AvatarProbe::onTranslate as a session of the handle -- touched set, face,
+  // penalty forces -- and the ring spread of its list, any number of sources.  Only the info structs come back.
+  fb_fem_contact_info ContactMove(const double lo[3], const double hi[3], double forceCoeff) {
+    fb_fem_contact_info info;
+    check(fb_fem_contact_move(h_, lo, hi, forceCoeff, &info));
+    return info;
+  }
+  fb_fem_contact_info ContactInfo() {
+    fb_fem_contact_info info;
+    check(fb_fem_contact_info_get(h_, &info));
+    return info;
+  }
+  void ContactReset(bool keepFace) { check(fb_fem_contact_reset(h_, keepFace ? 1 : 0)); }
+  // the stored list: ascending ids, first-touch positions and forces (3 doubles per entry), ContactInfo().list_size entries
+  void ReadContact(std::vector<int>& ids, std::vector<double>& firstXyz, std::vector<double>& forces3) {
+    const size_t n = (size_t)ContactInfo().list_size;
+    ids.assign(n, 0); firstXyz.assign(3 * n, 0.0); forces3.assign(3 * n, 0.0);
+    if (n) check(fb_fem_read_contact(h_, ids.data(), firstXyz.data(), forces3.data()));
+  }
+  fb_fem_contact_spread_info ContactApply(int neighbourhoodSize) {
+    fb_fem_contact_spread_info info;
+    check(fb_fem_contact_apply(h_, neighbourhoodSize, &info));
+    return info;
+  }
   // Element stress and strain on the device (fembrain_hip.h): von Mises stress, energy density and J of every element at the current
   // state stay on the device, `out` brings the summary.  flags: FB_STRESS_WORLD | FB_STRESS_TENSORS.
   void ComputeStress(int flags, fb_fem_stress_info* out) { check(fb_fem_stress(h_, flags, out)); }
@@ -361,7 +385,12 @@ class Deformable {
   void timestep() {
     if (m_lpIntegrator == nullptr) return;
     const bool applyGravity = m_bApplyGravity && (m_ctCollided == 0);
-    if (m_bHapticInProgress && !m_vHapticIndices.empty() && m_vHapticIndices.size() <= (size_t)FB_HAPTIC_MAX_SOURCES &&
+    if (m_bHapticInProgress && m_bContactList) {
+      // the probe's contact list, kept on the device by probeMove: any number of sources (fb_fem_contact_apply)
+      if (applyGravity) m_lpIntegrator->SetUniformForce(1, -10000.0);
+      else m_lpIntegrator->SetExternalForcesToZero();
+      m_lpIntegrator->ContactApply(m_hapticForceNeighorhoodSize);
+    } else if (m_bHapticInProgress && !m_vHapticIndices.empty() && m_vHapticIndices.size() <= (size_t)FB_HAPTIC_MAX_SOURCES &&
         m_vHapticForces.size() >= m_vHapticIndices.size()) {
       // the probe on the device: gravity or zero generated there, then the ring-spread forces added (fb_fem_add_haptic_forces)
       if (applyGravity) m_lpIntegrator->SetUniformForce(1, -10000.0);
@@ -630,9 +659,26 @@ class Deformable {
   void setHapticForceRadius(int radius) { m_hapticForceNeighorhoodSize = radius; }
   void setPulledVertex(int index) { m_idxPulledVertex = index; }
   bool hapticStart(int index) { m_idxPulledVertex = index; m_bHapticInProgress = true; m_vHapticIndices.clear(); return true; }
-  void hapticEnd() { m_bHapticInProgress = false; m_idxPulledVertex = -1; m_vHapticIndices.clear(); }
+  void hapticEnd() { m_bHapticInProgress = false; m_idxPulledVertex = -1; m_vHapticIndices.clear(); m_bContactList = false; }
   bool isHapticInProgress() const { return m_bHapticInProgress; }
-  void hapticSetCurrentForces(const std::vector<int>& indices, const std::vector<vec3d>& forces) { m_vHapticIndices = indices; m_vHapticForces = forces; }
+  // (the list set last wins: this one, or a probeMove's)
+  void hapticSetCurrentForces(const std::vector<int>& indices, const std::vector<vec3d>& forces) {
+    m_vHapticIndices = indices; m_vHapticForces = forces; m_bContactList = false;
+  }
+  // The probe's box contact (AvatarProbe::onTranslate below its pick-mode branch) as a session on the device.  probeStart: the probe's
+  // mouse-down without a picked node; probeMove: the tool box [lo, hi] against the tissue -- the session's list becomes the current haptic
+  // forces, spread by every timestep(), and only the info comes back; probeEnd: mouse-up, the touched set is cleared and the face stays.
+  bool probeStart() { return hapticStart(0); }
+  fb_fem_contact_info probeMove(const vec3d& lo, const vec3d& hi, double forceCoeff) {
+    const double l[3] = {lo.x, lo.y, lo.z}, h[3] = {hi.x, hi.y, hi.z};
+    const fb_fem_contact_info info = m_lpIntegrator->ContactMove(l, h, forceCoeff);
+    if (info.status == FB_CONTACT_SET) { m_vHapticIndices.clear(); m_vHapticForces.clear(); m_bContactList = true; }
+    return info;
+  }
+  void probeEnd() {
+    hapticEnd();
+    m_lpIntegrator->ContactReset(true);
+  }
   // the materials of the body's elements (HipIntegrator::SetMaterials / SetElementMaterials): E, nu, density equally long, 1..256 entries;
   // ids one per element of the current mesh from `first` on.  syncForceModel() from the whole mesh returns the ids to 0.
   void setMaterials(const std::vector<double>& E, const std::vector<double>& nu, const std::vector<double>& density) {
@@ -795,7 +841,7 @@ class Deformable {
     return vol;
   }
   void init() {  // Deformable::init (Deformable.cpp:85-124)
-    m_ctCollided = 0; m_fOnDeform = nullptr; m_idxPulledVertex = -1; m_bHapticInProgress = false;
+    m_ctCollided = 0; m_fOnDeform = nullptr; m_idxPulledVertex = -1; m_bHapticInProgress = false; m_bContactList = false;
     m_dampingMassCoeff = 0.0; m_dampingStiffnessCoeff = 0.01; m_timeStep = 0.0333; m_ctTimeStep = 0;
     m_hapticForceNeighorhoodSize = 5;  // DEFAULT_FORCE_NEIGHBORHOOD_SIZE, Deformable.h:41
     m_bApplyGravity = true;  // left uninitialised by the reference's init(); true is what its .sim files set
@@ -813,6 +859,7 @@ class Deformable {
   U32 m_dof, m_ctCollided, m_ctTimeStep;
   int m_idxPulledVertex, m_device, m_hapticForceNeighorhoodSize, m_boxCapacity;
   bool m_bHapticInProgress, m_bApplyGravity, m_hasFloor;
+  bool m_bContactList;  // the list set last is the device session's (probeMove), not m_vHapticIndices
   double m_dampingMassCoeff, m_dampingStiffnessCoeff, m_timeStep, m_floorY, m_restVolume;
   std::string m_strModelName;
 };

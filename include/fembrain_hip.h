@@ -594,7 +594,7 @@ int fb_fem_floor_collision(fb_fem_t h, double floor_y, double restitution, int* 
 /* ---- The haptic probe, on the device ----
  * What FemBrain's AvatarProbe drives every frame while the user touches the tissue: Deformable::applyHapticForces
  * (src/deformable/Deformable.cpp:634-706), pickVertex / pickVertices (:422-448) and computeVolume (:260-279).  The probe's own
- * contact logic (its box faces, its vertex hash) stays with the host.  Unsharded handles only (FB_EINVAL otherwise, as
+ * contact logic (its box faces, its vertex hash) is the next section's, fb_fem_contact_move.  Unsharded handles only (FB_EINVAL otherwise, as
  * fb_fem_read_mesh), device- or host-built plan alike; node ids are the CALLER's, also on a renumbered handle.  A handle that never
  * calls these allocates and launches nothing extra.
  *
@@ -620,6 +620,61 @@ int fb_fem_pick_box(fb_fem_t h, const double lo[3], const double hi[3], int capa
  * element order.  *total is their sum in a fixed tree that depends on the element count only (256 consecutive elements per leaf group):
  * the same bits from call to call, within n_tets * 2^-53 * total of any other order. */
 int fb_fem_volume(fb_fem_t h, double* total, double* per_element);
+
+/* ---- The probe's box contact, on the device ----
+ * AvatarProbe::onTranslate (src/deformable/AvatarProbe.cpp:124-265) below its pick-mode branch -- the path FemBrain runs every frame while
+ * the tool presses into tissue -- as a session kept on the device, and Deformable::applyHapticForces on the list it stores, for any
+ * number of sources.  Unsharded handles only (FB_EINVAL otherwise), device- or host-built plan alike; node ids are the CALLER's, also
+ * on a renumbered handle.  A handle that never calls these allocates and launches nothing extra.
+ *
+ * fb_fem_contact_move(lo, hi, coeff), every operation fp64 in the order written:
+ *  1. Miss test.  The tissue box is the min / max over all nodes of (float)(x0 + q) (VolMesh::displace -> computeNodalAABB; the expand(1.0)
+ *     of Deformable::syncForceModel is NOT reproduced: a tool within 1.0 of the tissue that the reference would let through is a miss
+ *     here), the tool box (float)lo, (float)hi.  AABB::intersect is strict: a miss on any axis with t_lo >= hi or t_hi <= lo.  Status
+ *     FB_CONTACT_MISS: the touched set, the face and the force list are unchanged.
+ *  2. Touched set.  Every node with lo <= x0 + q <= hi on all three axes (fb_fem_pick_box's rule, in doubles) enters the set with its
+ *     current position unless it is in it: a node keeps its first position, and never leaves on a move.  A set that is still empty:
+ *     FB_CONTACT_EMPTY, nothing else changes.
+ *  3. Face.  With s = {lo, hi, lo, hi, lo, hi} and n = {-x, +x, -y, +y, -z, +z} (LEFT RIGHT BOTTOM TOP NEAR FAR), d(k, j) = (s_j - p_k) . n_j
+ *     on the first-touch positions p_k.  While face < 0: the face is the j of the smallest d over the nodes ascending, then the faces
+ *     ascending (strict <: the first of equal minima wins); contact_dist is that d, closest_node / closest_point that node and its
+ *     first-touch position.  Otherwise the face stays, and contact_dist / closest_* are the minimum over the nodes ascending for it alone.
+ *  4. Force list.  One entry per touched node, ascending id: n_face * max(d(k, face) * force_coeff, 0); n_pushing counts the entries
+ *     greater than zero.  The list replaces the stored one and stays on the device: FB_CONTACT_SET.  Only the info struct comes back.
+ * After a MISS or EMPTY move the info keeps the last SET move's fields except status and n_new = 0.  A null lo or hi, lo[k] > hi[k], a
+ * non-finite box or coefficient: FB_EINVAL before anything is launched or changed.
+ *
+ * fb_fem_contact_reset clears the touched set and the list; keep_face != 0 keeps the face (the reference's mouse-up, m_hashVertices.clear():
+ * it never resets its face after the constructor), keep_face == 0 is a new probe.  fb_fem_read_contact: the touched set of the stored list,
+ * ascending ids[list_size], their first-touch positions first_xyz[3 list_size] and forces3[3 list_size]; any pointer may be NULL.
+ *
+ * fb_fem_contact_apply ADDS the stored list into the current external force vector as fb_fem_add_haptic_forces adds a list (set gravity or
+ * zero first): each force to its own node, then for the sources ascending mag_j * f_s to every node first reached in ring j = 1 .. size-1,
+ * every node receiving its additions in ascending source order, one fp64 multiply and one fp64 add per component -- the values of the host
+ * walk (the sign of a zero apart: zero forces are skipped).  No limit on the sources.  path says how: FB_CONTACT_SPREAD_RECORDS -- a
+ * wavefront per source walks its ball over the node adjacency and emits (target, source, ring) records, sorted and added per target
+ * (n_records of them, n_targets nodes) -- or, where a ball overflows its table or the records a budget, FB_CONTACT_SPREAD_LEVELS for the
+ * whole apply: fb_fem_add_haptic_forces' passes in batches of 32 sources, slow, the same numbers (n_targets -1; n_records what the walk
+ * counted, -1 if it did not finish).  n_sources is the list's length.  size outside [1, 255]: FB_EINVAL; an empty list: a no-op.
+ *
+ * The session is kept in the caller's numbering and survives steps, state changes, fb_fem_reset, fb_fem_cut and fb_fem_resync_delta (ids
+ * stay valid; appended nodes are untouched until a move finds them; the spread uses the current mesh's adjacency).  A full fb_fem_resync
+ * clears it (n_clears counts that); a detached part's handle starts without one. */
+#define FB_CONTACT_MISS  0   /* the boxes do not intersect: nothing changed */
+#define FB_CONTACT_EMPTY 1   /* they intersect, the touched set is (still) empty: nothing changed */
+#define FB_CONTACT_SET   2   /* the force list was replaced */
+typedef struct fb_fem_contact_info {
+  int status, n_touched, n_new, face /* -1, or 0..5 = LEFT RIGHT BOTTOM TOP NEAR FAR */, closest_node /* caller id or -1 */, n_pushing, list_size, n_clears;
+  double contact_dist, closest_point[3];
+} fb_fem_contact_info;
+int fb_fem_contact_move(fb_fem_t h, const double lo[3], const double hi[3], double force_coeff, fb_fem_contact_info* out);
+int fb_fem_contact_info_get(fb_fem_t h, fb_fem_contact_info* out);   /* the state without a move (all zero / -1 on a fresh handle) */
+int fb_fem_contact_reset(fb_fem_t h, int keep_face);
+int fb_fem_read_contact(fb_fem_t h, int* ids, double* first_xyz, double* forces3);
+#define FB_CONTACT_SPREAD_RECORDS 0
+#define FB_CONTACT_SPREAD_LEVELS  1
+typedef struct fb_fem_contact_spread_info { int n_sources, n_pushing, path, n_targets; long long n_records; } fb_fem_contact_spread_info;
+int fb_fem_contact_apply(fb_fem_t h, int neighbourhood_size, fb_fem_contact_spread_info* out);
 
 /* ---- Element stress and strain, on the device ----
  * The bracket of the corotational element force f_e,i = V R [lambda tr(H) I + mu (H + H^T)] b_i, which the assembly forms every step
