@@ -17,6 +17,7 @@ import cut_inputs as ci
 import cutref as cr
 import surface_inputs as si
 import surfref as sr
+from adversarial_inputs import scrambled as _scrambled
 from fembrain_amd import lib as fl
 from fembrain_amd.fem import Deformable, FemIntegrator
 from fembrain_amd.meshgen import fixed_vertices_to_dofs
@@ -66,16 +67,6 @@ def _update(g, s, x0):
     print("normals: max abs error %.3g over %d vertices, %d left out, smallest |sum| %.3g" % (err, ok.sum(), (~ok).sum(), length.min()))
     assert err <= NORMAL_TOL
     return xyz, nrm
-
-
-def _scrambled(v, t, fixed, seed=3):
-    """the same mesh with the caller's node ids permuted"""
-    perm = np.random.default_rng(seed).permutation(len(v))          # new id of old node
-    v2 = np.empty_like(v)
-    v2[perm] = v
-    t2 = np.ascontiguousarray(perm[t].astype(np.int32))
-    node, comp = np.asarray(fixed, np.int64) // 3, np.asarray(fixed, np.int64) % 3
-    return v2, t2, np.sort(3 * perm[node] + comp).astype(np.int32)
 
 
 @pytest.fixture(scope="module")
