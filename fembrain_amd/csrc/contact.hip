@@ -1,7 +1,7 @@
 // The probe's box contact on the device (contact.h), hand-written for gfx950: the contact session and a ring spread without a source limit.
 //
-// Move: the tissue's float box (box_reduce.hip.h), the box test with first-position capture per caller id, the compaction of the touched
-// flags into the ascending list, the lexicographic (d, node, face) minimum (the style of pick_reduce.hip.h) and the force pass.  Every
+// Move: the tissue's float box, the box test with first-position capture per caller id, the compaction of the touched flags into the
+// ascending list, the lexicographic (d, node, face) minimum and the force pass, all on the primitives of workgroup.hip.h.  Every
 // kernel decides "miss" and "empty" for itself from the box and the count left on the device by the kernels before it, so the host waits
 // once, for the info struct.  Counts and minima leave a workgroup as partials folded by a single-workgroup launch in a fixed order.
 //
@@ -23,16 +23,15 @@
 #include <cstring>
 #include <vector>
 
-#include "box_reduce.hip.h"
 #include "device_prims.hip.h"
 #include "fem_handle.h"
 #include "contact.h"
 #include "launch.hip.h"
+#include "mesh_device.hip.h"
+#include "workgroup.hip.h"
 
 namespace fb {
 namespace {
-
-constexpr int kWaves = kB / 64;
 
 struct Tool {
   double lo[3], hi[3];
@@ -55,36 +54,6 @@ __device__ __forceinline__ double face_dot(const Tool& T, const double p[3], int
   return (s[0] - p[0]) * n[0] + (s[1] - p[1]) * n[1] + (s[2] - p[2]) * n[2];
 }
 
-__device__ __forceinline__ bool ct_closer(double d, long long k, double bd, long long bk) { return d < bd || (d == bd && k < bk); }
-
-// (d, key) minimum over the workgroup, lexicographic; valid in thread 0
-__device__ __forceinline__ void ct_reduce(double& d, long long& k) {
-  for (int o = 32; o >= 1; o >>= 1) {
-    const double od = __shfl_xor(d, o);
-    const long long ok = __shfl_xor(k, o);
-    if (ct_closer(od, ok, d, k)) { d = od; k = ok; }
-  }
-  __shared__ double sd[kWaves];
-  __shared__ long long sk[kWaves];
-  if ((threadIdx.x & 63) == 0) { sd[threadIdx.x >> 6] = d; sk[threadIdx.x >> 6] = k; }
-  __syncthreads();
-  if (threadIdx.x == 0)
-    for (int w = 1; w < kWaves; w++)
-      if (ct_closer(sd[w], sk[w], d, k)) { d = sd[w]; k = sk[w]; }
-}
-
-// the workgroup's number of set flags; valid in thread 0
-__device__ __forceinline__ int count_reduce(bool flag) {
-  const unsigned long long m = __ballot(flag);
-  __shared__ int wc[kWaves];
-  if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = __popcll(m);
-  __syncthreads();
-  int c = 0;
-  for (int w = 0; w < kWaves; w++) c += wc[w];
-  __syncthreads();  // (wc is written again by the next call)
-  return c;
-}
-
 // ---- move ----
 
 // A thread per node (internal order; min and max are exact in any order): the box of (float)(x0 + q)
@@ -96,7 +65,7 @@ __global__ __launch_bounds__(kB) void k_ct_tissue_box(int n_nodes, const double*
 #pragma unroll
     for (int k = 0; k < 3; k++) lo[k] = hi[k] = (float)(x0[b + k] + q[b + k]);
   }
-  box_workgroup(lo, hi, part + 6 * (size_t)blockIdx.x);
+  wg_box(lo, hi, part + 6 * (size_t)blockIdx.x);
 }
 
 // A thread per caller id: a node inside the tool box enters the set with its current position unless it is in it; the workgroup's touched
@@ -109,40 +78,22 @@ __global__ __launch_bounds__(kB) void k_ct_mark(int n_nodes, const double* __res
   if (i < n_nodes) {
     in_set = touched[i] != 0;
     if (!miss && !in_set) {
-      const int node = new_of_old ? new_of_old[i] : i;
-      if ((unsigned)node < (unsigned)n_nodes) {
-        const size_t b = 3 * (size_t)node;
-        const double p[3] = {x0[b] + q[b], x0[b + 1] + q[b + 1], x0[b + 2] + q[b + 2]};
-        if (p[0] >= T.lo[0] && p[0] <= T.hi[0] && p[1] >= T.lo[1] && p[1] <= T.hi[1] && p[2] >= T.lo[2] && p[2] <= T.hi[2]) {
-          touched[i] = 1;
-          first[3 * (size_t)i] = p[0]; first[3 * (size_t)i + 1] = p[1]; first[3 * (size_t)i + 2] = p[2];
-          in_set = is_new = true;
-        }
+      double p[3];
+      bool ok;
+      node_position(i, new_of_old, n_nodes, x0, q, p, &ok);
+      if (ok && in_box(p, T.lo, T.hi)) {
+        touched[i] = 1;
+        first[3 * (size_t)i] = p[0]; first[3 * (size_t)i + 1] = p[1]; first[3 * (size_t)i + 2] = p[2];
+        in_set = is_new = true;
       }
     }
   }
-  const int c_set = count_reduce(in_set), c_new = count_reduce(is_new);
+  const int c_set = wg_count(in_set), c_new = wg_count(is_new);
   if (threadIdx.x == 0) { cnt[2 * (size_t)blockIdx.x] = c_set; cnt[2 * (size_t)blockIdx.x + 1] = c_new; }
 }
 
 // one workgroup: exclusive scan of the workgroups' touched counts; off[n] the total, off[n + 1] the new ones
-__global__ __launch_bounds__(kB) void k_ct_scan(int n, const int* __restrict__ cnt, int* __restrict__ off) {
-  const int per = (n + kB - 1) / kB;
-  const int lo = min((int)threadIdx.x * per, n), hi = min(lo + per, n);
-  int mine = 0, mine_new = 0;
-  for (int b = lo; b < hi; b++) { mine += cnt[2 * (size_t)b]; mine_new += cnt[2 * (size_t)b + 1]; }
-  __shared__ int sh[kB], sh_new[kB];
-  sh[threadIdx.x] = mine; sh_new[threadIdx.x] = mine_new;
-  __syncthreads();
-  int base = 0;
-  for (int t = 0; t < (int)threadIdx.x; t++) base += sh[t];
-  for (int b = lo; b < hi; b++) { off[b] = base; base += cnt[2 * (size_t)b]; }
-  if (threadIdx.x == kB - 1) {
-    int all_new = 0;
-    for (int t = 0; t < kB; t++) all_new += sh_new[t];
-    off[n] = base; off[n + 1] = all_new;
-  }
-}
+__global__ __launch_bounds__(kB) void k_ct_scan(int n, const int* __restrict__ cnt, int* __restrict__ off) { wg_scan_partials<2>(n, cnt, off); }
 
 // A thread per caller id: a touched node takes its place in the list, and brings its smallest d -- over the six faces ascending with a
 // strict <, or for the face that stands -- to the workgroup's (d, node, face) minimum
@@ -152,16 +103,12 @@ __global__ __launch_bounds__(kB) void k_ct_face(int n_nodes, int n_blocks, Tool 
   const int i = blockIdx.x * kB + threadIdx.x;
   const bool live = !ct_miss(box6, T) && off[n_blocks] > 0;
   const bool hit = live && i < n_nodes && touched[i] != 0;
-  const unsigned long long m = __ballot(hit);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __shared__ int wc[kWaves];
-  if (lane == 0) wc[wave] = __popcll(m);
-  __syncthreads();
+  int total;
+  const int rank = wg_rank(hit, &total);
   double d = INFINITY;
   long long key = LLONG_MAX;
   if (hit) {
-    int pos = off[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wave; w++) pos += wc[w];
+    const int pos = off[blockIdx.x] + rank;
     if (pos >= 0 && pos < n_nodes) ids[pos] = i;
     const double p[3] = {first[3 * (size_t)i], first[3 * (size_t)i + 1], first[3 * (size_t)i + 2]};
     if (face_in < 0) {
@@ -177,7 +124,7 @@ __global__ __launch_bounds__(kB) void k_ct_face(int n_nodes, int n_blocks, Tool 
       key = 8LL * i + face_in;
     }
   }
-  ct_reduce(d, key);
+  wg_best<long long, Lowest>(d, key);
   if (threadIdx.x == 0) { part_d[blockIdx.x] = d; part_k[blockIdx.x] = key; }
 }
 
@@ -187,9 +134,8 @@ __global__ __launch_bounds__(kB) void k_ct_final(int n_part, int n_nodes, Tool T
                                                  fb_fem_contact_info* __restrict__ res) {
   double d = INFINITY;
   long long key = LLONG_MAX;
-  for (int b = threadIdx.x; b < n_part; b += kB)
-    if (ct_closer(part_d[b], part_k[b], d, key)) { d = part_d[b]; key = part_k[b]; }
-  ct_reduce(d, key);
+  fold_best<long long, Lowest>(n_part, part_d, part_k, d, key);
+  wg_best<long long, Lowest>(d, key);
   if (threadIdx.x != 0) return;
   fb_fem_contact_info r;
   r.status = ct_miss(box6, T) ? FB_CONTACT_MISS : (off[n_part] > 0 ? FB_CONTACT_SET : FB_CONTACT_EMPTY);
@@ -226,20 +172,14 @@ __global__ __launch_bounds__(kB) void k_ct_force(int n_nodes, Tool T, double coe
       pushing = mag > 0.0;
     }
   }
-  const int c = count_reduce(pushing);
+  const int c = wg_count(pushing);
   if (threadIdx.x == 0) push_cnt[blockIdx.x] = c;
 }
 
 // one workgroup: the pushing entries of all workgroups, the list's length
 __global__ __launch_bounds__(kB) void k_ct_push_final(int n_part, const int* __restrict__ push_cnt, fb_fem_contact_info* __restrict__ res) {
-  int mine = 0;
-  for (int b = threadIdx.x; b < n_part; b += kB) mine += push_cnt[b];
-  __shared__ int sh[kB];
-  sh[threadIdx.x] = mine;
-  __syncthreads();
+  const int all = wg_sum(fold_sum(n_part, push_cnt));
   if (threadIdx.x != 0 || res->status != FB_CONTACT_SET) return;
-  int all = 0;
-  for (int t = 0; t < kB; t++) all += sh[t];
   res->n_pushing = all;
   res->list_size = res->n_touched;
 }
@@ -365,8 +305,6 @@ __global__ __launch_bounds__(kB) void k_ct_segments(long long n_rec, const unsig
 
 // ---- host ----
 
-inline int blocks_for(int n) { return std::max(1, ceil_div(n, kB)); }
-
 // `buf` covers n entries of `per` values: grown with its first n_old entries kept and the rest zero
 template <class T>
 int grow_keep(hipStream_t s, DevBuf<T>& buf, size_t n_old, size_t n, size_t per) {
@@ -406,7 +344,7 @@ int contact_move(fb_fem_s* h, const double lo[3], const double hi[3], double coe
   const int* noo = new_of_old_dev(h);
   const int face_in = C.info.face;
   FB_TRY(launch_1d(k_ct_tissue_box, n_nodes, s, n_nodes, h->x0.p, h->q.p, C.box_part.p));
-  FB_TRY(launch_grid(k_box_final, dim3(1), s, nblk, C.box_part.p, C.box6.p));
+  FB_TRY(launch_grid(k_box_final<float>, dim3(1), s, nblk, C.box_part.p, C.box6.p));
   FB_TRY(launch_1d(k_ct_mark, n_nodes, s, n_nodes, h->x0.p, h->q.p, noo, T, C.box6.p, C.touched.p, C.first.p, C.cnt.p));
   FB_TRY(launch_grid(k_ct_scan, dim3(1), s, nblk, C.cnt.p, C.off.p));
   FB_TRY(launch_1d(k_ct_face, n_nodes, s, n_nodes, nblk, T, C.box6.p, C.touched.p, C.first.p, C.off.p, face_in, C.ids.p, C.part_d.p, C.part_k.p));
@@ -484,9 +422,8 @@ int contact_apply(fb_fem_s* h, int size, fb_fem_contact_spread_info* out) {
       }
       const unsigned long long capacity = std::min(C.keys.n, C.rings.n);
       FB_TRY(C.walk.zero(s));
-      hipLaunchKernelGGL(k_ct_walk, dim3((unsigned)n), dim3(64), 0, s, n, C.ids.p, C.forces.p, noo, n_nodes, bptr, bcol, n_blocks, size, rank_bits, capacity, C.keys.p, C.rings.p,
-                         C.walk.p);
-      FB_HIP(hipGetLastError());
+      FB_TRY(launch_shape(k_ct_walk, dim3((unsigned)n), dim3(64), s, n, C.ids.p, C.forces.p, noo, n_nodes, bptr, bcol, n_blocks, size, rank_bits, capacity, C.keys.p, C.rings.p,
+                          C.walk.p));
       FB_TRY(C.walk.download(w, 2, s));
       if (w[1] != 0 || (long long)w[0] > budget) { records = false; break; }
       if (w[0] <= capacity) break;

@@ -22,18 +22,17 @@
 #include <cstring>
 #include <vector>
 
-#include "box_reduce.hip.h"
 #include "device_prims.hip.h"
 #include "embed.h"
 #include "fem_handle.h"
 #include "launch.hip.h"
+#include "mesh_device.hip.h"
+#include "workgroup.hip.h"
 
 namespace fb {
 namespace {
 
 constexpr int kWideTile = 64;  // overflow elements per LDS tile
-
-__device__ __forceinline__ int tet_node(const int4& t, int k) { return k == 0 ? t.x : k == 1 ? t.y : k == 2 ? t.z : t.w; }
 
 // the search grid as the kernels see it
 struct GridDev {
@@ -76,39 +75,13 @@ __device__ __forceinline__ void load_tet(const int4* __restrict__ tets, const do
   }
 }
 
-// ---- the mesh box (fp64) ----
-__device__ __forceinline__ void dbox_workgroup(double* lo, double* hi, double* __restrict__ out6) {
-#pragma unroll
-  for (int k = 0; k < 3; k++)
-    for (int d = 32; d >= 1; d >>= 1) {
-      lo[k] = fmin(lo[k], __shfl_xor(lo[k], d));
-      hi[k] = fmax(hi[k], __shfl_xor(hi[k], d));
-    }
-  __shared__ double sh[kB / 64][6];
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0)
-    for (int k = 0; k < 3; k++) { sh[wave][k] = lo[k]; sh[wave][3 + k] = hi[k]; }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    double r = sh[0][threadIdx.x];
-    for (int w = 1; w < kB / 64; w++) r = threadIdx.x < 3 ? fmin(r, sh[w][threadIdx.x]) : fmax(r, sh[w][threadIdx.x]);
-    out6[threadIdx.x] = r;
-  }
-}
-
+// ---- the mesh box (fp64; the partials are folded by k_box_final<double>) ----
 __global__ __launch_bounds__(kB) void k_node_box(int n_nodes, const double* __restrict__ x0, double* __restrict__ part) {
   const int i = blockIdx.x * kB + threadIdx.x;
   double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
   if (i < n_nodes)
     for (int k = 0; k < 3; k++) lo[k] = hi[k] = x0[3 * (size_t)i + k];
-  dbox_workgroup(lo, hi, part + 6 * (size_t)blockIdx.x);
-}
-
-__global__ __launch_bounds__(kB) void k_node_box_final(int n_part, const double* __restrict__ part, double* __restrict__ box) {
-  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-  for (int b = threadIdx.x; b < n_part; b += kB)
-    for (int k = 0; k < 3; k++) { lo[k] = fmin(lo[k], part[6 * (size_t)b + k]); hi[k] = fmax(hi[k], part[6 * (size_t)b + 3 + k]); }
-  dbox_workgroup(lo, hi, box);
+  wg_box(lo, hi, part + 6 * (size_t)blockIdx.x);
 }
 
 // ---- the grid ----
@@ -162,15 +135,7 @@ __global__ __launch_bounds__(kB) void k_grid_emit(int n_tets, GridDev g, const i
       }
 }
 
-// A thread per sorted entry: the first of a run of equal keys writes the run's start, the last its end (lo / hi zeroed before: an absent key has an empty run)
-__global__ __launch_bounds__(kB) void k_run_bounds(long long n, const uint32_t* __restrict__ keys_s, uint32_t n_keys, int* __restrict__ lo, int* __restrict__ hi) {
-  const long long j = (long long)blockIdx.x * kB + threadIdx.x;
-  if (j >= n) return;
-  const uint32_t k = keys_s[j];
-  if (k >= n_keys) return;
-  if (j == 0 || keys_s[j - 1] != k) lo[k] = (int)j;
-  if (j + 1 == n || keys_s[j + 1] != k) hi[k] = (int)(j + 1);
-}
+// (the cells' runs in the sorted pairs: k_run_bounds, mesh_device.hip.h)
 
 // ---- the search ----
 
@@ -185,8 +150,7 @@ __global__ __launch_bounds__(kB) void k_locate(int n, const unsigned char* __res
   if (active) {
     p[0] = loc[3 * (size_t)i]; p[1] = loc[3 * (size_t)i + 1]; p[2] = loc[3 * (size_t)i + 2];
     // outside the grid's box there is no cell: decided on the coordinates, before any index is formed
-    const bool inside = p[0] >= g.lo[0] && p[0] <= g.hi[0] && p[1] >= g.lo[1] && p[1] <= g.hi[1] && p[2] >= g.lo[2] && p[2] <= g.hi[2];
-    if (inside) {
+    if (in_box(p, g.lo, g.hi)) {
       const int c = (cell_of(g, 2, p[2]) * g.dim[1] + cell_of(g, 1, p[1])) * g.dim[0] + cell_of(g, 0, p[0]);
       const int j1 = g.cell_hi[c];
       for (int j = g.cell_lo[c]; j < j1; j++) {
@@ -418,17 +382,10 @@ __global__ __launch_bounds__(kB) void k_flag_sums(int n, const unsigned char* __
                                                   int* __restrict__ out3) {
   int s[3] = {0, 0, 0};
   for (int i = threadIdx.x; i < n; i += kB) { s[0] += a ? a[i] : 0; s[1] += b ? b[i] : 0; s[2] += c ? c[i] : 0; }
-  __shared__ int sh[kB / 64][3];
 #pragma unroll
-  for (int k = 0; k < 3; k++)
-    for (int d = 32; d >= 1; d >>= 1) s[k] += __shfl_xor(s[k], d);
-  if ((threadIdx.x & 63) == 0)
-    for (int k = 0; k < 3; k++) sh[threadIdx.x >> 6][k] = s[k];
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    int r = 0;
-    for (int w = 0; w < kB / 64; w++) r += sh[w][threadIdx.x];
-    out3[threadIdx.x] = r;
+  for (int k = 0; k < 3; k++) {
+    const int r = wg_sum(s[k]);
+    if (threadIdx.x == 0) out3[k] = r;
   }
 }
 
@@ -451,26 +408,17 @@ __global__ __launch_bounds__(kB) void k_embed_pos(int n, int n_nodes, const int*
   const int i = blockIdx.x * kB + threadIdx.x;
   float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
   if (i < n) {
-    double pk[4][3], w[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      int nd = vert_int[4 * (size_t)i + k];
-      if (nd < 0 || nd >= n_nodes) nd = 0;
-      const size_t b = 3 * (size_t)nd;
-      w[k] = w4[4 * (size_t)i + k];
-#pragma unroll
-      for (int c = 0; c < 3; c++) pk[k][c] = q ? x0[b + c] + q[b + c] : x0[b + c];
-    }
+    double s[3];
+    embed_point(i, n_nodes, vert_int, w4, x0, q, s);
 #pragma unroll
     for (int c = 0; c < 3; c++) {
-      const double s = ((w[0] * pk[0][c] + w[1] * pk[1][c]) + w[2] * pk[2][c]) + w[3] * pk[3][c];
-      cur[3 * (size_t)i + c] = s;
-      const float f = (float)s;
+      cur[3 * (size_t)i + c] = s[c];
+      const float f = (float)s[c];
       xyz[3 * (size_t)i + c] = f;
       lo[c] = hi[c] = f;
     }
   }
-  box_workgroup(lo, hi, part + 6 * (size_t)blockIdx.x);
+  wg_box(lo, hi, part + 6 * (size_t)blockIdx.x);
 }
 
 // A thread per point: the normalised fp64 sum of the unit normals of its triangles, ascending; zero where there is none
@@ -528,10 +476,10 @@ int embed_grid_build(hipStream_t s, EmbedGrid& G, const EmbedMesh& M, PlanWorksp
   G.valid = false;
   if (M.n_tets <= 0 || M.n_nodes <= 0) return fail(FB_EINVAL, "embedding: the mesh has no elements");
   // the box of the rest positions
-  const int nblk = std::max(1, ceil_div(M.n_nodes, kB));
+  const int nblk = blocks_for(M.n_nodes);
   FB_TRY(G.box_part.alloc((size_t)6 * nblk + 6));
   FB_TRY(launch_1d(k_node_box, M.n_nodes, s, M.n_nodes, M.x0, G.box_part.p));
-  FB_TRY(launch_grid(k_node_box_final, dim3(1), s, nblk, G.box_part.p, G.box_part.p + 6 * (size_t)nblk));
+  FB_TRY(launch_grid(k_box_final<double>, dim3(1), s, nblk, G.box_part.p, G.box_part.p + 6 * (size_t)nblk));
   double box[6];
   FB_TRY(G.box_part.download(box, 6, s, (size_t)6 * nblk));  // the first host wait
   double ext_max = 0.0;
@@ -590,7 +538,7 @@ int embed_grid_build(hipStream_t s, EmbedGrid& G, const EmbedMesh& M, PlanWorksp
     uint32_t* ck_s = reinterpret_cast<uint32_t*>(W.keys_s.p);
     FB_TRY(launch_1d(k_grid_emit, M.n_tets, s, M.n_tets, g, M.tets, M.x0, G.cnt.p, G.off.p, (long long)total, ck, W.vals.p));
     FB_TRY(sort_pairs(W.temp, s, ck, ck_s, W.vals.p, reinterpret_cast<uint32_t*>(G.cell_elem.p), (size_t)total, (unsigned)bits_of(n_cells)));
-    FB_TRY(launch_1d(k_run_bounds, (long long)total, s, total, ck_s, (uint32_t)n_cells, G.cell_lo.p, G.cell_hi.p));
+    FB_TRY(launch_1d(k_run_bounds<>, (long long)total, s, total, ck_s, (uint32_t)n_cells, G.cell_lo.p, G.cell_hi.p));
   }
   G.valid = true;
   G.n_builds++;
@@ -663,7 +611,7 @@ int embed_incidence(hipStream_t s, Embedding& E, PlanWorkspace& W) {
   FB_TRY(launch_1d(k_tri_corner_keys, nc, s, nc, n, E.tris.p, ck, W.vals.p));
   // the corners sorted stably by point keep their ascending triangle order
   FB_TRY(sort_pairs(W.temp, s, ck, ck_s, W.vals.p, E.inc.p, (size_t)nc, (unsigned)bits_of((long long)n + 1)));
-  return launch_1d(k_run_bounds, (long long)nc, s, nc, ck_s, (uint32_t)n, E.inc_lo.p, E.inc_hi.p);
+  return launch_1d(k_run_bounds<>, (long long)nc, s, nc, ck_s, (uint32_t)n, E.inc_lo.p, E.inc_hi.p);
 }
 
 int embed_update(hipStream_t s, Embedding& E, int n_nodes, const double* x0, const double* q, bool copy_out) {
@@ -675,7 +623,7 @@ int embed_update(hipStream_t s, Embedding& E, int n_nodes, const double* x0, con
   float* box = E.out.p + 6 * (size_t)n;
   FB_TRY(launch_1d(k_embed_pos, n, s, n, n_nodes, E.vert_int.p, E.w.p, x0, q, E.cur.p, xyz, E.part.p));
   FB_TRY(launch_1d(k_embed_normals, n, s, n, E.n_triangles, E.inc_lo.p, E.inc_hi.p, E.inc.p, E.tris.p, E.cur.p, nrm));
-  FB_TRY(launch_grid(k_box_final, dim3(1), s, nblk, E.part.p, box));
+  FB_TRY(launch_grid(k_box_final<float>, dim3(1), s, nblk, E.part.p, box));
   if (copy_out) {
     E.host.resize((size_t)6 * n + 6);
     FB_HIP(hipMemcpyAsync(E.host.data(), E.out.p, sizeof(float) * E.host.size(), hipMemcpyDeviceToHost, s));  // 24 n + 24 bytes

@@ -26,7 +26,8 @@
 #include "embed.h"
 #include "fem_handle.h"
 #include "launch.hip.h"
-#include "pick_reduce.hip.h"
+#include "mesh_device.hip.h"
+#include "workgroup.hip.h"
 
 namespace fb {
 namespace {
@@ -34,7 +35,7 @@ namespace {
 // ---- the transposed table ----
 
 // A thread per corner: its internal node as the sort key (a node outside [0, n_nodes) gets the key n_nodes: behind every run, where
-// k_table_bounds drops it), itself as the value
+// k_run_bounds drops it), itself as the value
 __global__ __launch_bounds__(kB) void k_table_keys(int n_corners, int n_nodes, const int* __restrict__ vert_int, uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
   const int j = blockIdx.x * kB + threadIdx.x;
   if (j >= n_corners) return;
@@ -43,15 +44,7 @@ __global__ __launch_bounds__(kB) void k_table_keys(int n_corners, int n_nodes, c
   vals[j] = (uint32_t)j;
 }
 
-// A thread per sorted corner: the first of a node's run writes its start, the last its end (lo / hi zeroed before)
-__global__ __launch_bounds__(kB) void k_table_bounds(int n, const uint32_t* __restrict__ keys_s, uint32_t n_nodes, int* __restrict__ lo, int* __restrict__ hi) {
-  const int j = blockIdx.x * kB + threadIdx.x;
-  if (j >= n) return;
-  const uint32_t k = keys_s[j];
-  if (k >= n_nodes) return;
-  if (j == 0 || keys_s[j - 1] != k) lo[k] = j;
-  if (j + 1 == n || keys_s[j + 1] != k) hi[k] = j + 1;
-}
+// (a node's run in the sorted corners: k_run_bounds, mesh_device.hip.h)
 
 // A thread per node: has it a run?
 __global__ __launch_bounds__(kB) void k_table_flags(int n_nodes, const int* __restrict__ lo, const int* __restrict__ hi, unsigned char* __restrict__ flag) {
@@ -63,14 +56,8 @@ __global__ __launch_bounds__(kB) void k_table_flags(int n_nodes, const int* __re
 __global__ __launch_bounds__(kB) void k_table_longest(int n_nodes, const int* __restrict__ lo, const int* __restrict__ hi, int* __restrict__ out) {
   int m = 0;
   for (int v = threadIdx.x; v < n_nodes; v += kB) m = max(m, hi[v] - lo[v]);
-  for (int d = 32; d >= 1; d >>= 1) m = max(m, __shfl_xor(m, d));
-  __shared__ int sh[kB / 64];
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < kB / 64; w++) m = max(m, sh[w]);
-    *out = m;
-  }
+  m = wg_max(m);
+  if (threadIdx.x == 0) *out = m;
 }
 
 // ---- the scatter ----
@@ -129,23 +116,11 @@ __global__ __launch_bounds__(kB) void k_scatter(int n_touched, const int* __rest
 
 // ---- positions ----
 
-// A thread per point: ((w0 p0 + w1 p1) + w2 p2) + w3 p3 with p = x0 + q, as k_embed_pos of embed.hip
+// A thread per point: embed_point at x0 + q, the fp64 positions k_embed_pos of embed.hip keeps
 __global__ __launch_bounds__(kB) void k_embed_cur(int n, int n_nodes, const int* __restrict__ vert_int, const double* __restrict__ w4, const double* __restrict__ x0,
                                                   const double* __restrict__ q, double* __restrict__ cur) {
   const int i = blockIdx.x * kB + threadIdx.x;
-  if (i >= n) return;
-  double pk[4][3], w[4];
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    int nd = vert_int[4 * (size_t)i + k];
-    if (nd < 0 || nd >= n_nodes) nd = 0;
-    const size_t b = 3 * (size_t)nd;
-    w[k] = w4[4 * (size_t)i + k];
-#pragma unroll
-    for (int c = 0; c < 3; c++) pk[k][c] = x0[b + c] + q[b + c];
-  }
-#pragma unroll
-  for (int c = 0; c < 3; c++) cur[3 * (size_t)i + c] = ((w[0] * pk[0][c] + w[1] * pk[1][c]) + w[2] * pk[2][c]) + w[3] * pk[3][c];
+  if (i < n) embed_point(i, n_nodes, vert_int, w4, x0, q, cur + 3 * (size_t)i);
 }
 
 // ---- the ray ----
@@ -184,7 +159,7 @@ __global__ __launch_bounds__(kB) void k_ray_part(int n_triangles, int n, const i
     double t, u, v;
     if (ray_triangle(r, tr, n, tris, cur, &t, &u, &v)) { d = t; bi = tr; }
   }
-  pick_reduce(d, bi);
+  wg_best<int, Lowest>(d, bi);
   if (threadIdx.x == 0) { part_d[blockIdx.x] = d; part_i[blockIdx.x] = bi; }
 }
 
@@ -193,9 +168,8 @@ __global__ __launch_bounds__(kB) void k_ray_final(int n_part, const double* __re
                                                   const int* __restrict__ tris, const double* __restrict__ cur, Ray r, EmbedPick* __restrict__ out) {
   double d = INFINITY;
   int bi = INT_MAX;
-  for (int b = threadIdx.x; b < n_part; b += kB)
-    if (closer(part_d[b], part_i[b], d, bi)) { d = part_d[b]; bi = part_i[b]; }
-  pick_reduce(d, bi);
+  fold_best<int, Lowest>(n_part, part_d, part_i, d, bi);
+  wg_best<int, Lowest>(d, bi);
   if (threadIdx.x == 0) {
     EmbedPick p;
     p.t = p.u = p.v = 0.0; p.xyz[0] = p.xyz[1] = p.xyz[2] = 0.0; p.index = -1; p.pad = 0;
@@ -220,7 +194,7 @@ __global__ __launch_bounds__(kB) void k_point_part(int n, const double* __restri
     d = dx * dx + dy * dy + dz * dz;
     bi = i;
   }
-  pick_reduce(d, bi);
+  wg_best<int, Lowest>(d, bi);
   if (threadIdx.x == 0) { part_d[blockIdx.x] = d; part_i[blockIdx.x] = bi; }
 }
 
@@ -228,9 +202,8 @@ __global__ __launch_bounds__(kB) void k_point_final(int n_part, const double* __
                                                     EmbedPick* __restrict__ out) {
   double d = INFINITY;
   int bi = INT_MAX;
-  for (int b = threadIdx.x; b < n_part; b += kB)
-    if (closer(part_d[b], part_i[b], d, bi)) { d = part_d[b]; bi = part_i[b]; }
-  pick_reduce(d, bi);
+  fold_best<int, Lowest>(n_part, part_d, part_i, d, bi);
+  wg_best<int, Lowest>(d, bi);
   if (threadIdx.x == 0) {
     EmbedPick p;
     p.t = d; p.u = p.v = 0.0; p.xyz[0] = p.xyz[1] = p.xyz[2] = 0.0; p.index = -1; p.pad = 0;
@@ -268,7 +241,7 @@ int embed_table_build(hipStream_t s, EmbedWork& EW, Embedding& E, int n_nodes, P
   FB_TRY(launch_1d(k_table_keys, nc, s, nc, n_nodes, E.vert_int.p, ck, W.vals.p));
   // the corners sorted stably by node keep their ascending order inside a node
   FB_TRY(sort_pairs(W.temp, s, ck, ck_s, W.vals.p, E.tr_corner.p, (size_t)nc, (unsigned)bits_of((long long)n_nodes + 1)));
-  FB_TRY(launch_1d(k_table_bounds, nc, s, nc, ck_s, (uint32_t)n_nodes, E.tr_lo.p, E.tr_hi.p));
+  FB_TRY(launch_1d(k_run_bounds<>, nc, s, nc, ck_s, (uint32_t)n_nodes, E.tr_lo.p, E.tr_hi.p));
   FB_TRY(launch_1d(k_table_flags, n_nodes, s, n_nodes, E.tr_lo.p, E.tr_hi.p, E.tr_flag.p));
   FB_TRY(select_flagged(W.temp, s, rocprim::counting_iterator<int>(0), E.tr_flag.p, E.tr_nodes.p, EW.tr_stats.p, (size_t)n_nodes));
   FB_TRY(launch_grid(k_table_longest, dim3(1), s, n_nodes, E.tr_lo.p, E.tr_hi.p, EW.tr_stats.p + 1));
@@ -322,21 +295,21 @@ int embed_pick_ray(hipStream_t s, EmbedWork& EW, Embedding& E, const double orig
   const int nt = E.n_triangles;
   out->t = out->u = out->v = 0.0; out->xyz[0] = out->xyz[1] = out->xyz[2] = 0.0; out->index = -1; out->pad = 0;
   if (nt <= 0) return FB_OK;
-  const int nblk = std::max(1, ceil_div(nt, kB));
+  const int nblk = blocks_for(nt);
   FB_TRY(EW.pick_d.reserve((size_t)nblk)); FB_TRY(EW.pick_i.reserve((size_t)nblk)); FB_TRY(EW.pick_out.reserve(1));
   Ray r;
   for (int k = 0; k < 3; k++) { r.o[k] = origin[k]; r.d[k] = dir[k]; }
   r.t_max = t_max;
-  FB_TRY(launch_grid(k_ray_part, dim3((unsigned)nblk), s, nt, E.n_points, E.tris.p, E.cur.p, r, EW.pick_d.p, EW.pick_i.p));
+  FB_TRY(launch_1d(k_ray_part, nt, s, nt, E.n_points, E.tris.p, E.cur.p, r, EW.pick_d.p, EW.pick_i.p));
   FB_TRY(launch_grid(k_ray_final, dim3(1), s, nblk, EW.pick_d.p, EW.pick_i.p, nt, E.n_points, E.tris.p, E.cur.p, r, EW.pick_out.p));
   return EW.pick_out.download(out, 1, s);
 }
 
 int embed_pick_point(hipStream_t s, EmbedWork& EW, Embedding& E, const double wpos[3], EmbedPick* out) {
   const int n = E.n_points;
-  const int nblk = std::max(1, ceil_div(n, kB));
+  const int nblk = blocks_for(n);
   FB_TRY(EW.pick_d.reserve((size_t)nblk)); FB_TRY(EW.pick_i.reserve((size_t)nblk)); FB_TRY(EW.pick_out.reserve(1));
-  FB_TRY(launch_grid(k_point_part, dim3((unsigned)nblk), s, n, E.cur.p, wpos[0], wpos[1], wpos[2], EW.pick_d.p, EW.pick_i.p));
+  FB_TRY(launch_1d(k_point_part, n, s, n, E.cur.p, wpos[0], wpos[1], wpos[2], EW.pick_d.p, EW.pick_i.p));
   FB_TRY(launch_grid(k_point_final, dim3(1), s, nblk, EW.pick_d.p, EW.pick_i.p, n, E.cur.p, EW.pick_out.p));
   return EW.pick_out.download(out, 1, s);
 }

@@ -10,7 +10,7 @@
 //
 // Pick / box / volume: one thread per caller id (gathering through the renumbering map, so ascending caller order needs no sort) or per
 // element; minima, counts and sums leave the workgroup as per-workgroup partials folded by a second, single-workgroup launch in a fixed
-// order -- no floating-point atomics, the same bits from call to call.
+// order (workgroup.hip.h) -- no floating-point atomics, the same bits from call to call.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -22,13 +22,11 @@
 #include "fem_handle.h"
 #include "haptic.h"
 #include "launch.hip.h"
-#include "pick_reduce.hip.h"
+#include "mesh_device.hip.h"
+#include "workgroup.hip.h"
 
 namespace fb {
 namespace {
-
-constexpr int kWaves = kB / 64;
-inline int blocks_for(int n) { return std::max(1, ceil_div(n, kB)); }
 
 // ---- spread ----
 
@@ -95,16 +93,7 @@ __global__ __launch_bounds__(kB) void k_hap_apply(int n_nodes, int nb, int size,
 
 // ---- pick ----
 
-// (closer / pick_reduce, the (d, caller id) minimum over the workgroup: pick_reduce.hip.h)
-
-__device__ __forceinline__ void node_position(int i, const int* __restrict__ new_of_old, int n_nodes, const double* __restrict__ x0, const double* __restrict__ q, double p[3],
-                                              bool* ok) {
-  const int node = new_of_old ? new_of_old[i] : i;
-  *ok = (unsigned)node < (unsigned)n_nodes;
-  if (!*ok) { p[0] = p[1] = p[2] = 0.0; return; }
-  const size_t b = 3 * (size_t)node;
-  p[0] = x0[b] + q[b]; p[1] = x0[b + 1] + q[b + 1]; p[2] = x0[b + 2] + q[b + 2];
-}
+// (the (d, caller id) minimum over the workgroup: wg_best<int, Lowest>; node_position: mesh_device.hip.h)
 
 // A thread per caller id: d = dx dx + dy dy + dz dz on x0 + q (VolMesh::findClosestVertex)
 __global__ __launch_bounds__(kB) void k_pick_part(int n_nodes, const double* __restrict__ x0, const double* __restrict__ q, const int* __restrict__ new_of_old, double wx,
@@ -122,7 +111,7 @@ __global__ __launch_bounds__(kB) void k_pick_part(int n_nodes, const double* __r
       bi = i;
     }
   }
-  pick_reduce(d, bi);
+  wg_best<int, Lowest>(d, bi);
   if (threadIdx.x == 0) { part_d[blockIdx.x] = d; part_i[blockIdx.x] = bi; }
 }
 
@@ -131,9 +120,8 @@ __global__ __launch_bounds__(kB) void k_pick_final(int n_part, const double* __r
                                                    const double* __restrict__ q, const int* __restrict__ new_of_old, PickResult* __restrict__ out) {
   double d = INFINITY;
   int bi = INT_MAX;
-  for (int b = threadIdx.x; b < n_part; b += kB)
-    if (closer(part_d[b], part_i[b], d, bi)) { d = part_d[b]; bi = part_i[b]; }
-  pick_reduce(d, bi);
+  fold_best<int, Lowest>(n_part, part_d, part_i, d, bi);
+  wg_best<int, Lowest>(d, bi);
   if (threadIdx.x == 0) {
     PickResult r;
     r.dist2 = d; r.index = -1; r.pad = 0;
@@ -148,10 +136,6 @@ __global__ __launch_bounds__(kB) void k_pick_final(int n_part, const double* __r
 }
 
 // ---- box ----
-
-__device__ __forceinline__ bool in_box(const double p[3], const double* lo, const double* hi) {
-  return p[0] >= lo[0] && p[0] <= hi[0] && p[1] >= lo[1] && p[1] <= hi[1] && p[2] >= lo[2] && p[2] <= hi[2];
-}
 
 struct Box { double lo[3], hi[3]; };
 
@@ -168,54 +152,25 @@ __global__ __launch_bounds__(kB) void k_box(int n_nodes, const double* __restric
     node_position(i, new_of_old, n_nodes, x0, q, p, &ok);
     hit = ok && in_box(p, box.lo, box.hi);
   }
-  const unsigned long long m = __ballot(hit);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __shared__ int wc[kWaves];
-  if (lane == 0) wc[wave] = __popcll(m);
-  __syncthreads();
+  int total;
+  const int rank = wg_rank(hit, &total);
   if (!WRITE) {
-    if (threadIdx.x == 0) {
-      int c = 0;
-      for (int w = 0; w < kWaves; w++) c += wc[w];
-      cnt[blockIdx.x] = c;
-    }
+    if (threadIdx.x == 0) cnt[blockIdx.x] = total;
     return;
   }
   if (!hit) return;
-  int pos = off[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
-  for (int w = 0; w < wave; w++) pos += wc[w];
+  const int pos = off[blockIdx.x] + rank;
   if (pos < 0 || pos >= capacity) return;
   ids[pos] = i;
   xyz[3 * (size_t)pos] = p[0]; xyz[3 * (size_t)pos + 1] = p[1]; xyz[3 * (size_t)pos + 2] = p[2];
 }
 
 // one workgroup: exclusive scan of the workgroups' counts, the total after the last
-__global__ __launch_bounds__(kB) void k_box_scan(int n, const int* __restrict__ cnt, int* __restrict__ off) {
-  const int per = (n + kB - 1) / kB;
-  const int first = min(threadIdx.x * per, n), last = min(first + per, n);
-  int mine = 0;
-  for (int b = first; b < last; b++) mine += cnt[b];
-  __shared__ int sh[kB];
-  sh[threadIdx.x] = mine;
-  __syncthreads();
-  int base = 0;
-  for (int t = 0; t < (int)threadIdx.x; t++) base += sh[t];
-  for (int b = first; b < last; b++) { off[b] = base; base += cnt[b]; }
-  if (threadIdx.x == kB - 1) off[n] = base;
-}
+__global__ __launch_bounds__(kB) void k_box_scan(int n, const int* __restrict__ cnt, int* __restrict__ off) { wg_scan_partials<1>(n, cnt, off); }
 
 // ---- volume ----
 
-// the sum of the workgroup's 256 values in a fixed tree; valid in thread 0
-__device__ __forceinline__ double sum_reduce(double v) {
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_down(v, o);
-  __shared__ double sh[kWaves];
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
-// A thread per element: |u . (v x w)| / 6 with u, v, w = p0 - p3, p1 - p3, p2 - p3 on x0 + q (Deformable::computeVolume)
+// A thread per element: tet_volume on x0 + q (Deformable::computeVolume)
 __global__ __launch_bounds__(kB) void k_volume(int n_tets, const int4* __restrict__ tets, int n_nodes, const double* __restrict__ x0, const double* __restrict__ q,
                                                double* __restrict__ vol, double* __restrict__ part) {
   const int e = blockIdx.x * kB + threadIdx.x;
@@ -232,20 +187,16 @@ __global__ __launch_bounds__(kB) void k_volume(int n_tets, const int4* __restric
 #pragma unroll
       for (int c = 0; c < 3; c++) p[k][c] = x0[b + c] + q[b + c];
     }
-    const double u[3] = {p[0][0] - p[3][0], p[0][1] - p[3][1], p[0][2] - p[3][2]}, v[3] = {p[1][0] - p[3][0], p[1][1] - p[3][1], p[1][2] - p[3][2]},
-                 w[3] = {p[2][0] - p[3][0], p[2][1] - p[3][1], p[2][2] - p[3][2]};
-    cur = ok ? fabs(u[0] * (v[1] * w[2] - v[2] * w[1]) + u[1] * (v[2] * w[0] - v[0] * w[2]) + u[2] * (v[0] * w[1] - v[1] * w[0])) / 6.0 : 0.0;
+    cur = ok ? tet_volume(p) : 0.0;
     vol[e] = cur;
   }
-  const double s = sum_reduce(cur);
+  const double s = wg_sum(cur);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
 // one workgroup: thread t adds the partials t, t + 256, ... in that order, then the same tree
 __global__ __launch_bounds__(kB) void k_volume_final(int n_part, const double* __restrict__ part, double* __restrict__ total) {
-  double v = 0.0;
-  for (int b = threadIdx.x; b < n_part; b += kB) v += part[b];
-  const double s = sum_reduce(v);
+  const double s = wg_sum(fold_sum(n_part, part));
   if (threadIdx.x == 0) *total = s;
 }
 
@@ -284,10 +235,7 @@ int haptic_spread_rings(hipStream_t s, HapticWork& H, int n_nodes, int n_tets, c
     const int nb = std::min(kHapticBatch, n - base);
     FB_HIP(hipMemsetAsync(H.level.p, 0xFF, (size_t)nb * n_nodes, s));
     FB_TRY(launch_1d(k_hap_seed, nb, s, nb, d_ids + base, new_of_old, n_nodes, H.level.p));
-    for (int j = 1; j < size; j++) {
-      hipLaunchKernelGGL(k_hap_ring, dim3(blocks_for(n_tets), nb), dim3(kB), 0, s, n_tets, tets, n_nodes, j, H.level.p);
-      FB_HIP(hipGetLastError());
-    }
+    for (int j = 1; j < size; j++) FB_TRY(launch_grid(k_hap_ring, dim3(blocks_for(n_tets), nb), s, n_tets, tets, n_nodes, j, H.level.p));
     FB_TRY(launch_1d(k_hap_apply, n_nodes, s, n_nodes, nb, size, H.level.p, d_f3 + 3 * (size_t)base, d_mag, fext));
   }
   return FB_OK;
@@ -296,10 +244,8 @@ int haptic_spread_rings(hipStream_t s, HapticWork& H, int n_nodes, int n_tets, c
 int haptic_pick_vertex(hipStream_t s, HapticWork& H, int n_nodes, const double* x0, const double* q, const int* new_of_old, const double wpos[3], PickResult* out) {
   const int nblk = blocks_for(n_nodes);
   FB_TRY(H.pick_d.reserve((size_t)nblk)); FB_TRY(H.pick_i.reserve((size_t)nblk)); FB_TRY(H.pick_out.reserve(1));
-  hipLaunchKernelGGL(k_pick_part, dim3(nblk), dim3(kB), 0, s, n_nodes, x0, q, new_of_old, wpos[0], wpos[1], wpos[2], H.pick_d.p, H.pick_i.p);
-  FB_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_pick_final, dim3(1), dim3(kB), 0, s, nblk, H.pick_d.p, H.pick_i.p, n_nodes, x0, q, new_of_old, H.pick_out.p);
-  FB_HIP(hipGetLastError());
+  FB_TRY(launch_1d(k_pick_part, n_nodes, s, n_nodes, x0, q, new_of_old, wpos[0], wpos[1], wpos[2], H.pick_d.p, H.pick_i.p));
+  FB_TRY(launch_grid(k_pick_final, dim3(1), s, nblk, H.pick_d.p, H.pick_i.p, n_nodes, x0, q, new_of_old, H.pick_out.p));
   return H.pick_out.download(out, 1, s);
 }
 
@@ -310,15 +256,11 @@ int haptic_pick_box(hipStream_t s, HapticWork& H, int n_nodes, const double* x0,
   FB_TRY(H.box_cnt.reserve((size_t)nblk)); FB_TRY(H.box_off.reserve((size_t)nblk + 1));
   Box box;
   for (int k = 0; k < 3; k++) { box.lo[k] = lo[k]; box.hi[k] = hi[k]; }
-  hipLaunchKernelGGL(k_box<false>, dim3(nblk), dim3(kB), 0, s, n_nodes, x0, q, new_of_old, box, H.box_cnt.p, static_cast<const int*>(nullptr), 0, static_cast<int*>(nullptr),
-                     static_cast<double*>(nullptr));
-  FB_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_box_scan, dim3(1), dim3(kB), 0, s, nblk, H.box_cnt.p, H.box_off.p);
-  FB_HIP(hipGetLastError());
+  FB_TRY(launch_1d(k_box<false>, n_nodes, s, n_nodes, x0, q, new_of_old, box, H.box_cnt.p, nullptr, 0, nullptr, nullptr));
+  FB_TRY(launch_grid(k_box_scan, dim3(1), s, nblk, H.box_cnt.p, H.box_off.p));
   if (cap > 0) {
     FB_TRY(H.box_ids.reserve((size_t)cap)); FB_TRY(H.box_xyz.reserve((size_t)3 * cap));
-    hipLaunchKernelGGL(k_box<true>, dim3(nblk), dim3(kB), 0, s, n_nodes, x0, q, new_of_old, box, static_cast<int*>(nullptr), H.box_off.p, cap, H.box_ids.p, H.box_xyz.p);
-    FB_HIP(hipGetLastError());
+    FB_TRY(launch_1d(k_box<true>, n_nodes, s, n_nodes, x0, q, new_of_old, box, nullptr, H.box_off.p, cap, H.box_ids.p, H.box_xyz.p));
   }
   int total = 0;
   FB_TRY(H.box_off.download(&total, 1, s, (size_t)nblk));
@@ -336,10 +278,8 @@ int haptic_pick_box(hipStream_t s, HapticWork& H, int n_nodes, const double* x0,
 int haptic_volume(hipStream_t s, HapticWork& H, int n_nodes, int n_tets, const int4* tets, const double* x0, const double* q, double* total, double* per_element) {
   const int nblk = blocks_for(n_tets);
   FB_TRY(H.vol.reserve((size_t)std::max(n_tets, 1))); FB_TRY(H.vol_part.reserve((size_t)nblk + 1));
-  hipLaunchKernelGGL(k_volume, dim3(nblk), dim3(kB), 0, s, n_tets, tets, n_nodes, x0, q, H.vol.p, H.vol_part.p);
-  FB_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_volume_final, dim3(1), dim3(kB), 0, s, nblk, H.vol_part.p, H.vol_part.p + nblk);
-  FB_HIP(hipGetLastError());
+  FB_TRY(launch_1d(k_volume, n_tets, s, n_tets, tets, n_nodes, x0, q, H.vol.p, H.vol_part.p));
+  FB_TRY(launch_grid(k_volume_final, dim3(1), s, nblk, H.vol_part.p, H.vol_part.p + nblk));
   if (per_element && n_tets > 0) FB_HIP(hipMemcpyAsync(per_element, H.vol.p, sizeof(double) * (size_t)n_tets, hipMemcpyDeviceToHost, s));
   double t = 0.0;
   FB_TRY(H.vol_part.download(&t, 1, s, (size_t)nblk));

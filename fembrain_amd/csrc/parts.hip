@@ -36,22 +36,15 @@
 #include "device_prims.hip.h"
 #include "fem_handle.h"
 #include "launch.hip.h"
+#include "mesh_device.hip.h"
 #include "parts.h"
+#include "workgroup.hip.h"
 
 namespace fb {
 namespace {
 
 constexpr int kNone = 0x7f7f7f7f;  // a node nobody uses (what a byte fill of 0x7f leaves; above every part index and corner key)
 constexpr int kChunk = 1024;       // sorted elements per volume chunk: 4 per thread of a workgroup
-
-__device__ __forceinline__ int tet_node(const int4& t, int k) { return k == 0 ? t.x : k == 1 ? t.y : k == 2 ? t.z : t.w; }
-
-__device__ __forceinline__ void sort3(unsigned& a, unsigned& b, unsigned& c) {
-  unsigned t;
-  if (a > b) { t = a; a = b; b = t; }
-  if (b > c) { t = b; b = c; c = t; }
-  if (a > b) { t = a; a = b; b = t; }
-}
 
 // local face f of an element: its three nodes other than corner f, ascending
 __device__ __forceinline__ void face_ids(const int4& t, int f, unsigned* x, unsigned* y, unsigned* z) {
@@ -219,16 +212,7 @@ __global__ __launch_bounds__(kB) void k_parts_chunks(int n_parts, const int* __r
   atomicMax(best, (unsigned long long)cnt << 32 | (0xffffffffu - (unsigned)k));
 }
 
-// the sum of the workgroup's 256 values in a fixed tree; valid in thread 0
-__device__ __forceinline__ double sum_reduce(double v) {
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_down(v, o);
-  __shared__ double sh[kB / 64];
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
-// |u . (v x w)| / 6 with u, v, w = p0 - p3, p1 - p3, p2 - p3 on the rest positions (fb_fem_volume's expression)
+// fb_fem_volume's expression on the rest positions
 __device__ __forceinline__ double rest_volume(const int4& t, const double* __restrict__ x0) {
   double p[4][3];
 #pragma unroll
@@ -236,9 +220,7 @@ __device__ __forceinline__ double rest_volume(const int4& t, const double* __res
     const double* s = x0 + 3 * (size_t)tet_node(t, k);
     p[k][0] = s[0]; p[k][1] = s[1]; p[k][2] = s[2];
   }
-  const double u[3] = {p[0][0] - p[3][0], p[0][1] - p[3][1], p[0][2] - p[3][2]}, v[3] = {p[1][0] - p[3][0], p[1][1] - p[3][1], p[1][2] - p[3][2]},
-               w[3] = {p[2][0] - p[3][0], p[2][1] - p[3][1], p[2][2] - p[3][2]};
-  return fabs(u[0] * (v[1] * w[2] - v[2] * w[1]) + u[1] * (v[2] * w[0] - v[0] * w[2]) + u[2] * (v[0] * w[1] - v[1] * w[0])) / 6.0;
+  return tet_volume(p);
 }
 
 // A workgroup per chunk (the grid covers the most chunks there can be): thread t adds the chunk's sorted elements t, t + 256, ... in
@@ -255,7 +237,7 @@ __global__ __launch_bounds__(kB) void k_parts_chunk_volumes(int n_parts, const i
   const int j0 = part_off[lo] + (c - chunk_off[lo]) * kChunk, j1 = min(j0 + kChunk, part_off[lo + 1]);
   double v = 0.0;
   for (int j = j0 + (int)threadIdx.x; j < j1; j += kB) v += rest_volume(tets[sorted[j]], x0);
-  const double s = sum_reduce(v);
+  const double s = wg_sum(v);
   if (threadIdx.x == 0) chunk_vol[c] = s;
 }
 
@@ -265,7 +247,7 @@ __global__ __launch_bounds__(kB) void k_parts_volumes(int n_parts, const int* __
   if (k >= n_parts) return;
   double v = 0.0;
   for (int c = chunk_off[k] + lane; c < chunk_off[k + 1]; c += 64) v += chunk_vol[c];
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_down(v, o);
+  v = wf_sum(v);
   if (lane == 0) part_volume[k] = v;
 }
 

@@ -10,43 +10,22 @@
 #include "device_prims.hip.h"
 #include "launch.hip.h"
 #include "renumber.h"
+#include "workgroup.hip.h"
 
 namespace fb {
 namespace {
 
 constexpr int kBoxBlocks = 64;
 
-__device__ __forceinline__ double wave_min_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ double wave_max_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // per block: min and max of each coordinate (6 doubles); the host folds the kBoxBlocks partials (min / max are exact in any order)
 __global__ __launch_bounds__(kB) void k_bbox(int n, const double* __restrict__ xyz, double* __restrict__ part) {
-  __shared__ double sh[kB / 64][6];
   double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
   for (int i = blockIdx.x * kB + threadIdx.x; i < n; i += gridDim.x * kB)
     for (int k = 0; k < 3; k++) {
       const double v = xyz[3 * (size_t)i + k];
       lo[k] = fmin(lo[k], v); hi[k] = fmax(hi[k], v);   // (fmin / fmax drop a NaN operand: a NaN coordinate is the flat-element check's to report)
     }
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  for (int k = 0; k < 3; k++) {
-    const double a = wave_min_d(lo[k]), b = wave_max_d(hi[k]);
-    if (lane == 0) { sh[w][k] = a; sh[w][3 + k] = b; }
-  }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    double v = sh[0][threadIdx.x];
-    for (int q = 1; q < kB / 64; q++) v = threadIdx.x < 3 ? fmin(v, sh[q][threadIdx.x]) : fmax(v, sh[q][threadIdx.x]);
-    part[6 * blockIdx.x + threadIdx.x] = v;
-  }
+  wg_box(lo, hi, part + 6 * (size_t)blockIdx.x);
 }
 
 __global__ __launch_bounds__(kB) void k_slab_keys(int n, const double* __restrict__ xyz, SlabKeyGeom g, unsigned long long* __restrict__ keys, uint32_t* __restrict__ ids) {

@@ -21,17 +21,13 @@
 #include <vector>
 
 #include "fem_handle.h"
+#include "launch.hip.h"
 #include "stress.h"
 #include "tet_math.hip.h"
+#include "workgroup.hip.h"
 
 namespace fb {
 namespace {
-
-constexpr int kWaves = kBlock / 64;
-inline int blocks_for(int n) { return std::max(1, ceil_div(n, kBlock)); }
-
-__device__ __forceinline__ bool above(double v, int i, double bv, int bi) { return v > bv || (v == bv && i < bi); }
-__device__ __forceinline__ bool below(double v, int i, double bv, int bi) { return v < bv || (v == bv && i < bi); }
 
 // what a thread (element or strided partials) carries into the workgroup's fold
 struct Fold {
@@ -41,16 +37,15 @@ struct Fold {
   double energy;
 };
 
-// over the workgroup; valid in thread 0.  The sum is fb_fem_volume's tree: shuffles down the wavefront, then (w0 + w1) + (w2 + w3).
+// Over the workgroup; valid in thread 0.  The wavefront-level pieces of workgroup.hip.h with ONE exchange through LDS and one barrier for
+// the six values (four wg_* calls would bring eight), so it is called once in a kernel.  The sum is wg_sum's tree.
 __device__ __forceinline__ void fold_reduce(Fold& f) {
-  for (int o = 32; o >= 1; o >>= 1) {
-    const double ov = __shfl_xor(f.vm, o), oj = __shfl_xor(f.J, o);
-    const int ove = __shfl_xor(f.vm_e, o), oje = __shfl_xor(f.J_e, o);
-    if (above(ov, ove, f.vm, f.vm_e)) { f.vm = ov; f.vm_e = ove; }
-    if (below(oj, oje, f.J, f.J_e)) { f.J = oj; f.J_e = oje; }
+  for (int o = 32; o >= 1; o >>= 1) {  // (the three butterflies step by step together: their exchanges overlap)
+    wf_best_step<int, Highest>(f.vm, f.vm_e, o);
+    wf_best_step<int, Lowest>(f.J, f.J_e, o);
     f.inverted += __shfl_xor(f.inverted, o);
   }
-  for (int o = 32; o >= 1; o >>= 1) f.energy += __shfl_down(f.energy, o);
+  f.energy = wf_sum(f.energy);
   __shared__ double s_vm[kWaves], s_J[kWaves], s_en[kWaves];
   __shared__ int s_vme[kWaves], s_Je[kWaves], s_inv[kWaves];
   const int w = threadIdx.x >> 6;
@@ -58,8 +53,8 @@ __device__ __forceinline__ void fold_reduce(Fold& f) {
   __syncthreads();
   if (threadIdx.x == 0) {
     for (int k = 1; k < kWaves; k++) {
-      if (above(s_vm[k], s_vme[k], f.vm, f.vm_e)) { f.vm = s_vm[k]; f.vm_e = s_vme[k]; }
-      if (below(s_J[k], s_Je[k], f.J, f.J_e)) { f.J = s_J[k]; f.J_e = s_Je[k]; }
+      if (Highest()(s_vm[k], s_vme[k], f.vm, f.vm_e)) { f.vm = s_vm[k]; f.vm_e = s_vme[k]; }
+      if (Lowest()(s_J[k], s_Je[k], f.J, f.J_e)) { f.J = s_J[k]; f.J_e = s_Je[k]; }
       f.inverted += s_inv[k];
     }
     static_assert(kWaves == 4, "the sum's tree is written for four wavefronts");
@@ -88,9 +83,9 @@ __device__ __forceinline__ void store6(double* __restrict__ dst, const double* T
 }
 
 template <bool MAT, bool TENSORS>
-__global__ __launch_bounds__(kBlock) void k_tet_stress(StressArgs a, double* __restrict__ vm_out, double* __restrict__ psi_out, double* __restrict__ J_out,
+__global__ __launch_bounds__(kB) void k_tet_stress(StressArgs a, double* __restrict__ vm_out, double* __restrict__ psi_out, double* __restrict__ J_out,
                                                        double* __restrict__ sig_out, double* __restrict__ eps_out, double* __restrict__ part_d, int* __restrict__ part_i) {
-  const int e = blockIdx.x * kBlock + threadIdx.x;
+  const int e = blockIdx.x * kB + threadIdx.x;
   Fold f;
   f.vm = -INFINITY; f.vm_e = INT_MAX; f.J = INFINITY; f.J_e = INT_MAX; f.inverted = 0; f.energy = 0.0;
   if (e < a.n_tets) {
@@ -189,14 +184,14 @@ __global__ __launch_bounds__(kBlock) void k_tet_stress(StressArgs a, double* __r
 }
 
 // one workgroup: thread t folds the partials t, t + 256, ... in that order, then the same fold
-__global__ __launch_bounds__(kBlock) void k_stress_final(int n_part, const double* __restrict__ part_d, const int* __restrict__ part_i, int n_tets, int flags,
+__global__ __launch_bounds__(kB) void k_stress_final(int n_part, const double* __restrict__ part_d, const int* __restrict__ part_i, int n_tets, int flags,
                                                          fb_fem_stress_info* __restrict__ out) {
   Fold f;
   f.vm = -INFINITY; f.vm_e = INT_MAX; f.J = INFINITY; f.J_e = INT_MAX; f.inverted = 0; f.energy = 0.0;
   const size_t nb = (size_t)n_part;
-  for (int k = threadIdx.x; k < n_part; k += kBlock) {
-    if (above(part_d[k], part_i[k], f.vm, f.vm_e)) { f.vm = part_d[k]; f.vm_e = part_i[k]; }
-    if (below(part_d[nb + k], part_i[nb + k], f.J, f.J_e)) { f.J = part_d[nb + k]; f.J_e = part_i[nb + k]; }
+  for (int k = threadIdx.x; k < n_part; k += kB) {  // (one loop for the six arrays, not a fold_* each: their loads go out together)
+    if (Highest()(part_d[k], part_i[k], f.vm, f.vm_e)) { f.vm = part_d[k]; f.vm_e = part_i[k]; }
+    if (Lowest()(part_d[nb + k], part_i[nb + k], f.J, f.J_e)) { f.J = part_d[nb + k]; f.J_e = part_i[nb + k]; }
     f.inverted += part_i[2 * nb + k];
     f.energy += part_d[2 * nb + k];
   }
@@ -213,9 +208,9 @@ __global__ __launch_bounds__(kBlock) void k_stress_final(int n_part, const doubl
 }
 
 // A thread per surface vertex: the fp64 sum of its faces' elements in ascending face order, divided by the face count
-__global__ __launch_bounds__(kBlock) void k_surface_stress(int n_vertices, int n_faces, int n_tets, const int* __restrict__ inc_off, const uint32_t* __restrict__ inc,
+__global__ __launch_bounds__(kB) void k_surface_stress(int n_vertices, int n_faces, int n_tets, const int* __restrict__ inc_off, const uint32_t* __restrict__ inc,
                                                            const int* __restrict__ face_tets, const double* __restrict__ vm, float* __restrict__ out) {
-  const int v = blockIdx.x * kBlock + threadIdx.x;
+  const int v = blockIdx.x * kB + threadIdx.x;
   if (v >= n_vertices) return;
   double sum = 0.0;
   int cnt = 0;
@@ -246,11 +241,9 @@ int stress_elements(hipStream_t s, StressWork& S, const StressArgs& a, bool tens
   if (tensors) { FB_TRY(S.sig.reserve(6 * ne)); FB_TRY(S.eps.reserve(6 * ne)); }
   FB_TRY(S.part_d.reserve((size_t)3 * nblk)); FB_TRY(S.part_i.reserve((size_t)3 * nblk)); FB_TRY(S.out.reserve(1));
   if (nt > 0) {
-    hipLaunchKernelGGL(kStressKernels[a.mat_ids ? 1 : 0][tensors ? 1 : 0], dim3(nblk), dim3(kBlock), 0, s, a, S.vm.p, S.psi.p, S.J.p, tensors ? S.sig.p : nullptr,
-                       tensors ? S.eps.p : nullptr, S.part_d.p, S.part_i.p);
-    FB_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_stress_final, dim3(1), dim3(kBlock), 0, s, nblk, S.part_d.p, S.part_i.p, nt, flags, S.out.p);
-    FB_HIP(hipGetLastError());
+    FB_TRY(launch_1d(kStressKernels[a.mat_ids ? 1 : 0][tensors ? 1 : 0], nt, s, a, S.vm.p, S.psi.p, S.J.p, tensors ? S.sig.p : nullptr, tensors ? S.eps.p : nullptr, S.part_d.p,
+                     S.part_i.p));
+    FB_TRY(launch_grid(k_stress_final, dim3(1), s, nblk, S.part_d.p, S.part_i.p, nt, flags, S.out.p));
     if (out) FB_TRY(S.out.download(out, 1, s));
   } else if (out) {
     out->n_elements = 0; out->flags = flags;
@@ -265,9 +258,7 @@ int stress_elements(hipStream_t s, StressWork& S, const StressArgs& a, bool tens
 int stress_surface(hipStream_t s, StressWork& S, int n_vertices, int n_faces, const int* inc_off, const uint32_t* inc, const int* face_tets) {
   if (n_vertices <= 0) return FB_OK;
   FB_TRY(S.surf_vm.reserve((size_t)n_vertices));
-  hipLaunchKernelGGL(k_surface_stress, dim3(blocks_for(n_vertices)), dim3(kBlock), 0, s, n_vertices, n_faces, S.n_elements, inc_off, inc, face_tets, S.vm.p, S.surf_vm.p);
-  FB_HIP(hipGetLastError());
-  return FB_OK;
+  return launch_1d(k_surface_stress, n_vertices, s, n_vertices, n_faces, S.n_elements, inc_off, inc, face_tets, S.vm.p, S.surf_vm.p);
 }
 
 }  // namespace fb

@@ -16,15 +16,14 @@
 #include <cstring>
 #include <vector>
 
-#include "box_reduce.hip.h"
 #include "device_prims.hip.h"
 #include "launch.hip.h"
+#include "mesh_device.hip.h"
 #include "surface.h"
+#include "workgroup.hip.h"
 
 namespace fb {
 namespace {
-
-__device__ __forceinline__ int tet_node(const int4& t, int k) { return k == 0 ? t.x : k == 1 ? t.y : k == 2 ? t.z : t.w; }
 
 // local faces of SurfaceMesh.cpp:180-190, 2 bits per corner, 6 bits per face: det >= 0 (1,2,3) (2,0,3) (3,0,1) (1,0,2), else
 // (3,2,1) (3,0,2) (1,0,3) (2,0,1)
@@ -33,13 +32,6 @@ __device__ __forceinline__ void face_corners(bool neg, int f, int* c0, int* c1, 
   const unsigned neg_t = (3u | 2u << 2 | 1u << 4) | (3u | 0u << 2 | 2u << 4) << 6 | (1u | 0u << 2 | 3u << 4) << 12 | (2u | 0u << 2 | 1u << 4) << 18;
   const unsigned m = (neg ? neg_t : pos_t) >> (6 * f);
   *c0 = m & 3; *c1 = (m >> 2) & 3; *c2 = (m >> 4) & 3;
-}
-
-__device__ __forceinline__ void sort3(unsigned& a, unsigned& b, unsigned& c) {
-  unsigned t;
-  if (a > b) { t = a; a = b; b = t; }
-  if (b > c) { t = b; b = c; c = t; }
-  if (a > b) { t = a; a = b; b = t; }
 }
 
 // the face of a payload: node ids in the handle's internal order in the payload's winding
@@ -193,7 +185,7 @@ __global__ __launch_bounds__(kB) void k_corner_heads(int n_corners, const uint32
 }
 
 // A thread per surface vertex.  NORMALS = false: positions and box only (the rest box of fb_fem_surface, q == nullptr).
-// The box goes to a per-workgroup partial; k_box_final folds the partials (box_reduce.hip.h).
+// The box goes to a per-workgroup partial; k_box_final folds the partials (workgroup.hip.h).
 template <bool NORMALS>
 __global__ __launch_bounds__(kB) void k_surface_update(int n_max, const int* __restrict__ n_dev, const int* __restrict__ vnode, const int* __restrict__ inc_off, const uint32_t* __restrict__ inc,
                                                        const int* __restrict__ faces_int, const double* __restrict__ x0, const double* __restrict__ q,
@@ -231,7 +223,7 @@ __global__ __launch_bounds__(kB) void k_surface_update(int n_max, const int* __r
       for (int k = 0; k < 3; k++) normals[3 * (size_t)v + k] = len > 0.0 ? (float)(sum[k] / len) : 0.0f;
     }
   }
-  box_workgroup(lo, hi, part + 6 * (size_t)blockIdx.x);
+  wg_box(lo, hi, part + 6 * (size_t)blockIdx.x);
 }
 
 }  // namespace
@@ -280,7 +272,7 @@ int surface_build(hipStream_t s, SurfaceWork& S, int n_nodes, int n_tets, const 
   FB_TRY(S.vertex_ids.alloc((size_t)std::max(nv_max, 1))); FB_TRY(S.vnode.alloc((size_t)std::max(nv_max, 1)));
   FB_TRY(S.inc.alloc((size_t)std::max(nc, 1))); FB_TRY(S.inc_off.alloc((size_t)nv_max + 1));
   FB_TRY(S.out.alloc((size_t)6 * nv_max + 6));  // (the rest box of this build sits in the last six)
-  FB_TRY(S.part.alloc((size_t)6 * std::max(1, ceil_div(nv_max, kB))));
+  FB_TRY(S.part.alloc((size_t)6 * blocks_for(nv_max)));
   FB_TRY(S.bitmap.zero(s));
   if (nf) FB_TRY(launch_1d(k_face_emit, nf, s, nf, tets, caller_of, S.sel.p, S.faces.p, S.faces_int.p, S.face_tets.p, S.bitmap.p));
   FB_TRY(launch_1d(k_word_counts, n_words + 1, s, n_words, S.bitmap.p, S.word_cnt.p));
@@ -300,12 +292,8 @@ int surface_build(hipStream_t s, SurfaceWork& S, int n_nodes, int n_tets, const 
   // the rest box: the grid covers the most vertices there can be and the kernel reads the count on the device, so the count and the box
   // leave together in the second (and last) host wait
   float* rest_box_dev = S.out.p + 6 * (size_t)nv_max;
-  const int nblk = std::max(1, ceil_div(nv_max, kB));
-  hipLaunchKernelGGL(k_surface_update<false>, dim3(nblk), dim3(kB), 0, s, nv_max, S.counts.p + 1, S.vnode.p, S.inc_off.p, S.inc.p, S.faces_int.p, x0,
-                     static_cast<const double*>(nullptr), S.out.p, S.out.p, S.part.p);
-  FB_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_box_final, dim3(1), dim3(kB), 0, s, nblk, S.part.p, rest_box_dev);
-  FB_HIP(hipGetLastError());
+  FB_TRY(launch_1d(k_surface_update<false>, nv_max, s, nv_max, S.counts.p + 1, S.vnode.p, S.inc_off.p, S.inc.p, S.faces_int.p, x0, nullptr, S.out.p, S.out.p, S.part.p));
+  FB_TRY(launch_grid(k_box_final<float>, dim3(1), s, blocks_for(nv_max), S.part.p, rest_box_dev));
   int nv = 0;
   FB_HIP(hipMemcpyAsync(&nv, S.counts.p + 1, sizeof(int), hipMemcpyDeviceToHost, s));
   FB_HIP(hipMemcpyAsync(S.rest_box, rest_box_dev, 6 * sizeof(float), hipMemcpyDeviceToHost, s));
@@ -322,15 +310,11 @@ int surface_build(hipStream_t s, SurfaceWork& S, int n_nodes, int n_tets, const 
 int surface_update(hipStream_t s, SurfaceWork& S, const double* x0, const double* q, bool copy_out) {
   const int nv = S.n_vertices;
   if (!nv) return FB_OK;
-  const int nblk = ceil_div(nv, kB);
   float* xyz = S.out.p;
   float* nrm = S.out.p + 3 * (size_t)nv;
   float* box = S.out.p + 6 * (size_t)nv;
-  hipLaunchKernelGGL(k_surface_update<true>, dim3(nblk), dim3(kB), 0, s, nv, static_cast<const int*>(nullptr), S.vnode.p, S.inc_off.p, S.inc.p, S.faces_int.p, x0, q, xyz, nrm,
-                     S.part.p);
-  FB_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_box_final, dim3(1), dim3(kB), 0, s, nblk, S.part.p, box);
-  FB_HIP(hipGetLastError());
+  FB_TRY(launch_1d(k_surface_update<true>, nv, s, nv, nullptr, S.vnode.p, S.inc_off.p, S.inc.p, S.faces_int.p, x0, q, xyz, nrm, S.part.p));
+  FB_TRY(launch_grid(k_box_final<float>, dim3(1), s, blocks_for(nv), S.part.p, box));
   if (copy_out) {
     S.host.resize((size_t)6 * nv + 6);
     FB_HIP(hipMemcpyAsync(S.host.data(), S.out.p, sizeof(float) * S.host.size(), hipMemcpyDeviceToHost, s));  // 24 n_vertices + 24 bytes

@@ -199,6 +199,7 @@ def lib():
         "fb_fem_read_part": (C.c_int, [vp, C.c_int, _ip, _ip, _dp, _ip]),
         "fb_fem_time_parts": (C.c_int, [vp, C.c_int, _dp, _dp]),
         "fb_fem_parts_wide": (C.c_int, [vp]),
+        "fb_test_workgroup": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.POINTER(C.c_longlong), _bp, _dp, C.POINTER(C.c_longlong)]),
         "fb_fem_detach_part": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(vp), _ip, _ip, C.POINTER(DetachInfo)]),
         "fb_fem_num_constrained_dofs": (C.c_int, [vp]),
         "fb_fem_read_constrained_dofs": (C.c_int, [vp, _ip]),

@@ -1,5 +1,5 @@
 /* fembrain_hip_testing.h -- host-only inspection hooks of libfembrain_hip.so used by the CPU test-suite
- * (no device call is made by any function in this header).  They expose the per-rank plan that
+ * (no device call is made by any function in this header but fb_test_workgroup at its end).  They expose the per-rank plan that
  * fb_fem_create[_sharded] builds -- local numbering, halo/send lists, 3x3-block pattern, SELL-64 layout and the
  * element contribution lists -- so that the partition logic can be checked without a GPU, including with
  * world_size-2 gloo runs.  Not part of the reference-facing surface. */
@@ -58,6 +58,26 @@ int fb_comm_test_allgather(struct fb_comm_s* c, const void* mine, void* all, siz
  * FEMBRAIN_PARTS_WIDE_KEYS=1), 0 when in one, -1 when it has not labelled yet. */
 struct fb_fem_s;
 int fb_fem_parts_wide(struct fb_fem_s* h);
+
+/* The one entry point of this header that DOES run on the device (the default stream of device 0): the in-workgroup primitives of the
+ * mesh-side kernels (fembrain_amd/csrc/workgroup.hip.h) and the run bounds of a sorted key array (mesh_device.hip.h), each through the
+ * two-launch pattern its users have -- a thread per item, per-workgroup partials, a single-workgroup final.  n items, `what`:
+ *   FB_TEST_WG_SUM         values[n] -> out_d[0]: the fp64 sum in the fixed tree
+ *   FB_TEST_WG_BEST_*      values[n], keys[n] -> out_d[0], out_i[0]: the lexicographic best (lowest / highest value, of equal values the
+ *                          lowest key) with int or long long keys (_INT: the keys must fit an int); idle threads carry +-inf and the
+ *                          key type's largest value
+ *   FB_TEST_WG_RANKS       flags[n] -> out_i[n + 4]: per item the set flags in front of it, then the total, the items without a flag
+ *                          (the scan's second counter), the total again as an integer workgroup sum, the most set flags of a workgroup
+ *   FB_TEST_WG_BOX_*       values[3 n] (xyz) -> out_d[6]: lo[3], hi[3] of the points as float or double
+ *   FB_TEST_WG_RUN_BOUNDS  keys[n] ascending in [0, m + FB_TEST_WG_GUARD) -> out_i[2 (m + FB_TEST_WG_GUARD)]: lo then hi of the m keys,
+ *                          each followed by FB_TEST_WG_GUARD entries that start as -1 and that no key may write
+ * FB_EINVAL for n < 1, a case that does not exist or a null array the case reads or writes; nothing is launched then. */
+enum {
+  FB_TEST_WG_SUM = 0, FB_TEST_WG_BEST_LOW_INT = 1, FB_TEST_WG_BEST_HIGH_INT = 2, FB_TEST_WG_BEST_LOW_LL = 3, FB_TEST_WG_BEST_HIGH_LL = 4,
+  FB_TEST_WG_RANKS = 5, FB_TEST_WG_BOX_FLOAT = 6, FB_TEST_WG_BOX_DOUBLE = 7, FB_TEST_WG_RUN_BOUNDS = 8
+};
+#define FB_TEST_WG_GUARD 8
+int fb_test_workgroup(int what, int n, int m, const double* values, const long long* keys, const unsigned char* flags, double* out_d, long long* out_i);
 
 /* Host-only: compiles a BlobTree (operator walk order, slot allocation, expansion of instanced subtrees) exactly as
  * fb_poly_create does and reports the number of evaluation steps and of per-point value slots; needs no device.
