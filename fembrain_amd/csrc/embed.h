@@ -44,6 +44,23 @@ struct EmbedGrid {
   DevBuf<int> cell_elem;            // [n_pairs] elements grouped by cell, ascending inside a cell
 };
 
+// The grid of the element CENTRES over the same box and dim[3] (embed_closest.hip), for the points no element contains.  Nothing of it
+// exists before a search takes the ring path; embed_mesh_changed retires it with the element grid.
+struct EmbedCentreGrid {
+  bool valid = false;
+  int n_builds = 0;
+  DevBuf<int> cell_cnt;     // [cells + 1] centres per cell, 0 in the last
+  DevBuf<int> cell_start;   // [cells + 1] their exclusive prefix sums: a run of cells along x is one range of the arrays below
+  DevBuf<double> centre;    // [3 n_tets] the centres grouped by cell, elements ascending inside a cell: 24 bytes each
+  DevBuf<int> elem;         // [n_tets] ... and their elements
+};
+
+// what the external pass of an embedding's last search did (fb_fem_embed_search_info)
+struct EmbedSearchStats {
+  int path = FB_EMBED_CLOSEST_NONE, n_outside = 0, n_far = 0, max_one = 0;
+  long long tested = 0;
+};
+
 // One embedding.  Nothing is allocated before fb_fem_embed.
 struct Embedding {
   bool live = false;
@@ -52,6 +69,7 @@ struct Embedding {
   int n_orphans = 0;        // points whose element a change in place took away: searched again, from loc, when next read
   int n_points = 0, n_triangles = 0, n_external = 0, n_zeroed = 0, n_locates = 0, n_rebound = 0;
   double zero_threshold = 0.0;
+  EmbedSearchStats search;
   float rest_box[6] = {0, 0, 0, 0, 0, 0};
   DevBuf<double> loc;              // [3 n] the point in the handle's rest shape: what a search looks for
   DevBuf<double> w;                // [4 n]
@@ -94,6 +112,11 @@ struct EmbedWork {
   DevBuf<double> close_d;  // [chunks][such points] the closest centre of every chunk of the element list: its distance
   DevBuf<int> close_e;     // ... and its element
   DevBuf<int> counts;    // [0] such points, [1] external, [2] zeroed, [3] changed element
+  // embed_closest.hip; empty until a search takes the ring path
+  EmbedCentreGrid cgrid;
+  DevBuf<unsigned char> far_flag;  // [such points] the ring search gave the point up at its budget
+  DevBuf<int> far_ids;             // those points, compacted: the full scan's list
+  DevBuf<long long> ring_part;     // [3 workgroups + 4] per-workgroup far points | centres tested | most of one point; the folded three, the list's length
   // embed_touch.hip; empty until one of its entry points is called
   DevBuf<unsigned char> touch_args;  // one upload per add with a list: forces3[3 n] | ids[n]
   DevBuf<int> tr_stats;              // [0] nodes with a run, [1] the longest run of the table being built
@@ -110,7 +133,19 @@ int embed_grid_build(hipStream_t s, EmbedGrid& G, const EmbedMesh& M, PlanWorksp
 int embed_locate(hipStream_t s, EmbedWork& EW, Embedding& E, const EmbedMesh& M, bool count_rebound, PlanWorkspace& W);
 // ... in its two halves: up to the host wait for the number of points without a containing element | the external pass, weights, counts
 int embed_locate_search(hipStream_t s, EmbedWork& EW, Embedding& E, const EmbedMesh& M, bool count_rebound, PlanWorkspace& W, int* n_ext);
-int embed_locate_finish(hipStream_t s, EmbedWork& EW, Embedding& E, const EmbedMesh& M, bool count_rebound, int n_ext);
+int embed_locate_finish(hipStream_t s, EmbedWork& EW, Embedding& E, const EmbedMesh& M, bool count_rebound, PlanWorkspace& W, int n_ext);
+// The external pass alone: E.elem of the n_ext points of EW.ext_ids from the closest centre, E.search filled.  path: FB_EMBED_CLOSEST_SCAN
+// (every centre for every point) or _RING (through the centre grid, built here if this mesh generation has none; the points past
+// `budget` centres go to the scan).  One host wait on the ring path (the far points and the counters), none on the scan's.
+int embed_closest(hipStream_t s, EmbedWork& EW, Embedding& E, const EmbedMesh& M, PlanWorkspace& W, int n_ext, int path, long long budget);
+// the path a search with n_ext outside points takes, and its budget: FEMBRAIN_EMBED_CLOSEST / FEMBRAIN_EMBED_RING_BUDGET, else the rule
+int embed_closest_choice(const EmbedWork& EW, const EmbedMesh& M, int n_ext, long long* budget);
+// embed_closest.hip: the centre grid over EW.grid's box (no host wait) | the ring search (the host wait); n_far points are left in EW.far_ids
+int embed_centre_grid_build(hipStream_t s, EmbedWork& EW, const EmbedMesh& M, PlanWorkspace& W);
+int embed_closest_ring(hipStream_t s, EmbedWork& EW, Embedding& E, const EmbedMesh& M, PlanWorkspace& W, int n_ext, long long budget, int* n_far);
+// false where a coordinate's rounding is not far below a cell of the grid (a box 2^30 of its extents from the origin): the ring's proof
+// does not cover such a mesh and its searches scan
+bool embed_ring_covers(const EmbedGrid& G);
 // the incidence list of E.tris, grouped by point
 int embed_incidence(hipStream_t s, Embedding& E, PlanWorkspace& W);
 // Positions, normals and box into E.out (q null: the rest shape); copy_out: one copy of all three into E.host.

@@ -24,6 +24,7 @@
 
 #include "device_prims.hip.h"
 #include "embed.h"
+#include "embed_grid.hip.h"
 #include "fem_handle.h"
 #include "launch.hip.h"
 #include "mesh_device.hip.h"
@@ -33,20 +34,6 @@ namespace fb {
 namespace {
 
 constexpr int kWideTile = 64;  // overflow elements per LDS tile
-
-// the search grid as the kernels see it
-struct GridDev {
-  double lo[3], hi[3], inv[3], pad;
-  int dim[3];
-  int n_wide;
-  const int *cell_lo, *cell_hi, *cell_elem, *wide;
-};
-
-// the cell of a coordinate that is not below the grid's lower bound; the caller has decided that already
-__device__ __forceinline__ int cell_of(const GridDev& g, int k, double x) {
-  const double c = (x - g.lo[k]) * g.inv[k];
-  return c >= (double)(g.dim[k] - 1) ? g.dim[k] - 1 : (int)c;
-}
 
 // determinant of the rows a, b, c (mat3d.h det: the six products in its order)
 __device__ __forceinline__ double det3(const double* a, const double* b, const double* c) {
@@ -64,15 +51,6 @@ __device__ __forceinline__ bool bary(const double (*v)[3], const double* p, doub
   w[2] = tet_det(v[0], v[1], p, v[3]) / d0;
   w[3] = tet_det(v[0], v[1], v[2], p) / d0;
   return w[0] >= 0 && w[1] >= 0 && w[2] >= 0 && w[3] >= 0;
-}
-
-__device__ __forceinline__ void load_tet(const int4* __restrict__ tets, const double* __restrict__ x0, int e, double (*v)[3]) {
-  const int4 t = tets[e];
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    const double* p = x0 + 3 * (size_t)tet_node(t, k);
-    v[k][0] = p[0]; v[k][1] = p[1]; v[k][2] = p[2];
-  }
 }
 
 // ---- the mesh box (fp64; the partials are folded by k_box_final<double>) ----
@@ -217,14 +195,12 @@ __global__ __launch_bounds__(kB) void k_closest(int n_ext, const int* __restrict
     if ((int)threadIdx.x < m) {
       double v[4][3];
       load_tet(tets, x0, (int)base + threadIdx.x, v);
-#pragma unroll
-      for (int k = 0; k < 3; k++) sc[threadIdx.x][k] = (((v[0][k] + v[1][k]) + v[2][k]) + v[3][k]) * (1.0 / 4);
+      tet_centre(v, sc[threadIdx.x]);
     }
     __syncthreads();
     if (i >= 0)
       for (int j = 0; j < m; j++) {
-        const double dx = p[0] - sc[j][0], dy = p[1] - sc[j][1], dz = p[2] - sc[j][2];
-        const double d = sqrt(dx * dx + dy * dy + dz * dz);
+        const double d = centre_distance(p, sc[j]);
         if (d < best) { best = d; be = (int)base + j; }
       }
   }
@@ -451,15 +427,6 @@ __global__ __launch_bounds__(kB) void k_embed_normals(int n, int n_triangles, co
   for (int k = 0; k < 3; k++) normals[3 * (size_t)i + k] = len > 0.0 ? (float)(sum[k] / len) : 0.0f;
 }
 
-GridDev grid_dev(const EmbedGrid& G) {
-  GridDev g;
-  for (int k = 0; k < 3; k++) { g.lo[k] = G.lo[k]; g.hi[k] = G.hi[k]; g.inv[k] = G.inv[k]; g.dim[k] = G.dim[k]; }
-  g.pad = G.pad;
-  g.n_wide = G.n_wide;
-  g.cell_lo = G.cell_lo.p; g.cell_hi = G.cell_hi.p; g.cell_elem = G.cell_elem.p; g.wide = G.wide.p;
-  return g;
-}
-
 }  // namespace
 
 void Embedding::release_all() {
@@ -470,6 +437,7 @@ void Embedding::release_all() {
   live = orphan_all = lost = tr_valid = false;
   tr_builds = tr_longest = tr_touched = 0;
   n_points = n_triangles = n_external = n_zeroed = n_locates = n_rebound = n_orphans = 0;
+  search = EmbedSearchStats();
 }
 
 int embed_grid_build(hipStream_t s, EmbedGrid& G, const EmbedMesh& M, PlanWorkspace& W) {
@@ -548,7 +516,7 @@ int embed_grid_build(hipStream_t s, EmbedGrid& G, const EmbedMesh& M, PlanWorksp
 int embed_locate(hipStream_t s, EmbedWork& EW, Embedding& E, const EmbedMesh& M, bool count_rebound, PlanWorkspace& W) {
   int n_ext = 0;
   FB_TRY(embed_locate_search(s, EW, E, M, count_rebound, W, &n_ext));
-  return embed_locate_finish(s, EW, E, M, count_rebound, n_ext);
+  return embed_locate_finish(s, EW, E, M, count_rebound, W, n_ext);
 }
 
 int embed_locate_search(hipStream_t s, EmbedWork& EW, Embedding& E, const EmbedMesh& M, bool count_rebound, PlanWorkspace& W, int* n_ext_out) {
@@ -572,19 +540,81 @@ int embed_locate_search(hipStream_t s, EmbedWork& EW, Embedding& E, const EmbedM
   return FB_OK;
 }
 
-int embed_locate_finish(hipStream_t s, EmbedWork& EW, Embedding& E, const EmbedMesh& M, bool count_rebound, int n_ext) {
+namespace {
+// the full scan for the n_list points of `ids`: every centre of the mesh for each
+int closest_scan(hipStream_t s, EmbedWork& EW, Embedding& E, const EmbedMesh& M, int n_list, const int* ids) {
+  // about 2048 workgroups in all: few outside points get many short chunks, many points few long ones (at most 2048 x 256 partial minima)
+  const int bx = ceil_div(n_list, kB), tiles = ceil_div(M.n_tets, kB);
+  const int n_chunks = std::max(1, std::min(tiles, 2048 / bx));
+  const int chunk_len = ceil_div(tiles, n_chunks) * kB;
+  const int used = ceil_div(M.n_tets, chunk_len);  // (chunks that hold an element)
+  FB_TRY(EW.close_d.reserve((size_t)used * n_list)); FB_TRY(EW.close_e.reserve((size_t)used * n_list));
+  FB_TRY(launch_grid(k_closest, dim3((unsigned)bx, (unsigned)used), s, n_list, ids, E.n_points, E.loc.p, M.n_tets, chunk_len, M.tets, M.x0, EW.close_d.p, EW.close_e.p));
+  return launch_1d(k_closest_final, n_list, s, n_list, used, EW.close_d.p, EW.close_e.p, ids, E.n_points, E.elem.p);
+}
+
+// The automatic rule of the external pass, measured on the MI355X with tools/probe_embed.py --outside (profiles/embed_probe_outside.json;
+// medians of HIP-event timings, the ring's figure with its host wait, the centre grid built beforehand):
+// the sphere surface scaled to enclose the cantilever, every vertex outside, the first n_ext of a shuffle of its 38,958 vertices):
+//
+//            |        998,250 tets (grid 100^3)       |        105,456 tets (grid 48^3)
+//    n_ext   |  scan      ring     (ring + build)/scan |  scan      ring     (ring + build)/scan
+//        12  |  0.53 ms   4.00 ms   8.0                |  0.15 ms   1.02 ms   7.5
+//       256  |  0.86 ms   5.60 ms   6.8                |  0.16 ms   1.32 ms   8.7
+//     1,024  |  1.28 ms   4.62 ms   3.8                |  0.24 ms   1.15 ms   5.2
+//     4,096  |  4.14 ms   4.89 ms   1.24               |  0.53 ms   1.21 ms   2.4
+//    16,384  | 15.5  ms   9.11 ms   0.60               |  1.85 ms   2.09 ms   1.17
+//    38,958  | 36.9  ms   8.15 ms   0.23               |  4.07 ms   2.13 ms   0.54
+//    centre grid build: 0.24 ms | 0.076 ms
+//
+// The ring has a floor of a few milliseconds here whatever the count: this surface is up to 40 cells away from the body, the cap of the
+// ball that reaches into the grid covers hundreds of rows, and one wavefront walks them one after another, a few dependent loads each.
+// The two passes cost the same at about 7,000 outside points at 1M tets and about 20,000 at 105k tets.  kRingMinOutside = 8,192: below
+// it a search on a mesh generation without a centre grid scans; between 8,192 and 20,000 points at 105k tets that costs under a
+// millisecond.  With a grid in place the ring is taken at any count.
+// The budget: the ring pass tested 96 M centres in 8.15 ms (85 ps each, 2,473 per point), the scan 38.9 G pairs in 36.9 ms (0.95 ps each),
+// so a wavefront that has tested n_tets / 89 centres has cost what the scan costs for its point.  max(64, n_tets / 32): a point is given up
+// at three times that, and costs under four scans in all.  No point of the probe came near it (the most one tested: 10,200, against 31,195).
+constexpr int kRingMinOutside = 8192;
+constexpr long long kRingBudgetFloor = 64, kRingBudgetDivisor = 32;
+}  // namespace
+
+int embed_closest_choice(const EmbedWork& EW, const EmbedMesh& M, int n_ext, long long* budget) {
+  // (read at every search, like FEMBRAIN_PARTS_WIDE_KEYS: a process may switch between two searches)
+  const char* b = getenv("FEMBRAIN_EMBED_RING_BUDGET");
+  const long long asked = b ? atoll(b) : 0;
+  *budget = asked > 0 ? asked : std::max(kRingBudgetFloor, (long long)M.n_tets / kRingBudgetDivisor);
+  if (!embed_ring_covers(EW.grid)) return FB_EMBED_CLOSEST_SCAN;
+  const char* c = getenv("FEMBRAIN_EMBED_CLOSEST");
+  if (c && !strcmp(c, "scan")) return FB_EMBED_CLOSEST_SCAN;
+  if (c && !strcmp(c, "ring")) return FB_EMBED_CLOSEST_RING;
+  return EW.cgrid.valid || n_ext >= kRingMinOutside ? FB_EMBED_CLOSEST_RING : FB_EMBED_CLOSEST_SCAN;
+}
+
+int embed_closest(hipStream_t s, EmbedWork& EW, Embedding& E, const EmbedMesh& M, PlanWorkspace& W, int n_ext, int path, long long budget) {
+  E.search = EmbedSearchStats();
+  if (!n_ext) return FB_OK;
+  if (path == FB_EMBED_CLOSEST_RING) {
+    int n_far = 0;
+    FB_TRY(embed_closest_ring(s, EW, E, M, W, n_ext, budget, &n_far));
+    if (n_far) FB_TRY(closest_scan(s, EW, E, M, n_far, EW.far_ids.p));
+    E.search.tested += (long long)n_far * M.n_tets;
+    return FB_OK;
+  }
+  FB_TRY(closest_scan(s, EW, E, M, n_ext, EW.ext_ids.p));
+  E.search.path = FB_EMBED_CLOSEST_SCAN;
+  E.search.n_outside = E.search.n_far = n_ext;
+  E.search.max_one = M.n_tets;
+  E.search.tested = (long long)n_ext * M.n_tets;
+  return FB_OK;
+}
+
+int embed_locate_finish(hipStream_t s, EmbedWork& EW, Embedding& E, const EmbedMesh& M, bool count_rebound, PlanWorkspace& W, int n_ext) {
   const int n = E.n_points;
   const unsigned char* only = E.orphan_all || !E.n_orphans ? nullptr : E.orphan.p;
-  if (n_ext) {
-    // about 2048 workgroups in all: few outside points get many short chunks, many points few long ones (at most 2048 x 256 partial minima)
-    const int bx = ceil_div(n_ext, kB), tiles = ceil_div(M.n_tets, kB);
-    const int n_chunks = std::max(1, std::min(tiles, 2048 / bx));
-    const int chunk_len = ceil_div(tiles, n_chunks) * kB;
-    const int used = ceil_div(M.n_tets, chunk_len);  // (chunks that hold an element)
-    FB_TRY(EW.close_d.reserve((size_t)used * n_ext)); FB_TRY(EW.close_e.reserve((size_t)used * n_ext));
-    FB_TRY(launch_grid(k_closest, dim3((unsigned)bx, (unsigned)used), s, n_ext, EW.ext_ids.p, n, E.loc.p, M.n_tets, chunk_len, M.tets, M.x0, EW.close_d.p, EW.close_e.p));
-    FB_TRY(launch_1d(k_closest_final, n_ext, s, n_ext, used, EW.close_d.p, EW.close_e.p, EW.ext_ids.p, n, E.elem.p));
-  }
+  long long budget = 0;
+  const int path = embed_closest_choice(EW, M, n_ext, &budget);
+  FB_TRY(embed_closest(s, EW, E, M, W, n_ext, path, budget));
   FB_TRY(launch_1d(k_bind, n, s, n, only, E.loc.p, E.elem.p, E.need.p, M.n_tets, M.tets, M.x0, M.caller_of, E.zero_threshold, count_rebound ? E.elem_old.p : nullptr, E.w.p, E.vert.p,
                    E.vert_int.p, E.ext.p, E.zeroed.p, count_rebound ? E.changed.p : nullptr));
   FB_TRY(launch_grid(k_flag_sums, dim3(1), s, n, E.ext.p, E.zeroed.p, count_rebound ? E.changed.p : nullptr, EW.counts.p + 1));
@@ -634,6 +664,7 @@ int embed_update(hipStream_t s, Embedding& E, int n_nodes, const double* x0, con
 
 void embed_mesh_changed(EmbedWork& EW, bool in_place) {
   EW.grid.valid = false;
+  EW.cgrid.valid = false;
   for (Embedding& E : EW.slot)
     if (E.live) {
       if (in_place) E.lost = true;
@@ -835,15 +866,21 @@ int time_search(fb_fem_s* h, const Embedding& E, int reps, double* seconds3) {
   for (hipEvent_t& e : ev) FB_HIP(hipEventCreate(&e));
   std::vector<double> t[3];
   int rc = FB_OK;
+  // (as a new mesh: no centre grid yet, so the rule decides on the count alone and a ring search pays for its grid in the third phase;
+  // a grid that was there is this generation's and stands as it was -- a build in here writes the same arrays again)
+  EmbedCentreGrid& CG = h->embed.cgrid;
+  const bool had = CG.valid;
+  const int builds = CG.n_builds;
   for (int r = 0; r < reps && rc == FB_OK; r++) {
     int n_ext = 0;
     T.orphan_all = true;
+    CG.valid = false;
     rc = hipEventRecord(ev[0], s) == hipSuccess ? FB_OK : fail(FB_EDEVICE, "event record failed");
     if (rc == FB_OK) rc = embed_grid_build(s, h->embed.grid, M, h->plan_ws);
     if (rc == FB_OK) (void)hipEventRecord(ev[1], s);
     if (rc == FB_OK) rc = embed_locate_search(s, h->embed, T, M, false, h->plan_ws, &n_ext);
     if (rc == FB_OK) (void)hipEventRecord(ev[2], s);
-    if (rc == FB_OK) rc = embed_locate_finish(s, h->embed, T, M, false, n_ext);
+    if (rc == FB_OK) rc = embed_locate_finish(s, h->embed, T, M, false, h->plan_ws, n_ext);
     if (rc == FB_OK) (void)hipEventRecord(ev[3], s);
     if (rc == FB_OK && hipStreamSynchronize(s) != hipSuccess) rc = fail(FB_EDEVICE, "stream wait failed");
     for (int k = 0; k < 3 && rc == FB_OK; k++) {
@@ -853,6 +890,8 @@ int time_search(fb_fem_s* h, const Embedding& E, int reps, double* seconds3) {
     }
   }
   for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+  CG.valid = rc == FB_OK && had;
+  CG.n_builds = builds;
   FB_TRY(rc);
   for (int k = 0; k < 3; k++) {
     std::sort(t[k].begin(), t[k].end());
@@ -884,4 +923,76 @@ int fb_fem_time_embed_search(fb_fem_t h, int id, int reps, double seconds3[3]) {
   FB_TRY(embedding_current(h, id, &E));
   SlackScope slack(handle_slack_now(h));
   return time_search(h, *E, reps, seconds3);
+}
+
+namespace {
+// The external pass alone, for the outside points of E, on a scratch copy: seconds2[0] the centre grid's build (ring; 0 for the scan),
+// [1] the pass with the given path.  The handle is left as it was: binding, counts, and whether a centre grid exists.
+int time_closest(fb_fem_s* h, const Embedding& E, int reps, int path, double* seconds2) {
+  hipStream_t s = h->stream;
+  const EmbedMesh M = mesh_of(h);
+  if (!h->embed.grid.valid) FB_TRY(embed_grid_build(s, h->embed.grid, M, h->plan_ws));
+  if (path == FB_EMBED_CLOSEST_RING && !embed_ring_covers(h->embed.grid)) return fail(FB_EINVAL, "the ring search does not cover a mesh this far from the origin");
+  Embedding T;
+  T.n_points = E.n_points;
+  T.orphan_all = true;
+  FB_TRY(T.loc.alloc((size_t)3 * E.n_points));
+  FB_HIP(hipMemcpyAsync(T.loc.p, E.loc.p, sizeof(double) * 3 * (size_t)E.n_points, hipMemcpyDeviceToDevice, s));
+  int n_ext = 0;
+  FB_TRY(embed_locate_search(s, h->embed, T, M, false, h->plan_ws, &n_ext));  // (the list of the outside points stays in the handle's workspace)
+  long long budget = 0;
+  (void)embed_closest_choice(h->embed, M, n_ext, &budget);
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  for (hipEvent_t& e : ev) FB_HIP(hipEventCreate(&e));
+  EmbedCentreGrid& CG = h->embed.cgrid;
+  const bool had = CG.valid;
+  const int builds = CG.n_builds;
+  std::vector<double> t[2];
+  int rc = FB_OK;
+  for (int r = 0; r < reps && rc == FB_OK; r++) {
+    rc = hipEventRecord(ev[0], s) == hipSuccess ? FB_OK : fail(FB_EDEVICE, "event record failed");
+    if (rc == FB_OK && path == FB_EMBED_CLOSEST_RING) rc = embed_centre_grid_build(s, h->embed, M, h->plan_ws);
+    if (rc == FB_OK) (void)hipEventRecord(ev[1], s);
+    if (rc == FB_OK) rc = embed_closest(s, h->embed, T, M, h->plan_ws, n_ext, path, budget);
+    if (rc == FB_OK) (void)hipEventRecord(ev[2], s);
+    if (rc == FB_OK && hipStreamSynchronize(s) != hipSuccess) rc = fail(FB_EDEVICE, "stream wait failed");
+    for (int k = 0; k < 2 && rc == FB_OK; k++) {
+      float ms = 0;
+      if (hipEventElapsedTime(&ms, ev[k], ev[k + 1]) != hipSuccess) rc = fail(FB_EDEVICE, "event time failed");
+      t[k].push_back(ms * 1e-3);
+    }
+  }
+  for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+  CG.valid = rc == FB_OK && had;  // (a grid that was there is this generation's: a build in here wrote the same arrays again)
+  CG.n_builds = builds;
+  FB_TRY(rc);
+  for (int k = 0; k < 2; k++) {
+    std::sort(t[k].begin(), t[k].end());
+    seconds2[k] = t[k][t[k].size() / 2];
+  }
+  if (path != FB_EMBED_CLOSEST_RING) seconds2[0] = 0.0;
+  return FB_OK;
+}
+}  // namespace
+
+int fb_fem_embed_search_info_get(fb_fem_t h, int id, fb_fem_embed_search_info* out) {
+  CHECK_HANDLE(h);
+  if (!out) return fail(FB_EINVAL, "out must not be null");
+  Embedding* E = nullptr;
+  FB_TRY(embedding_current(h, id, &E));
+  out->path = E->search.path; out->n_outside = E->search.n_outside; out->n_far = E->search.n_far;
+  out->centre_grid_builds = h->embed.cgrid.n_builds;
+  out->max_centres_one_point = E->search.max_one;
+  out->centres_tested = E->search.tested;
+  return FB_OK;
+}
+
+int fb_fem_time_embed_closest(fb_fem_t h, int id, int reps, int path, double seconds2[2]) {
+  CHECK_HANDLE(h);
+  if (reps < 1 || !seconds2) return fail(FB_EINVAL, "reps must be positive and seconds2 not null");
+  if (path != FB_EMBED_CLOSEST_SCAN && path != FB_EMBED_CLOSEST_RING) return fail(FB_EINVAL, "path must be FB_EMBED_CLOSEST_SCAN or FB_EMBED_CLOSEST_RING");
+  Embedding* E = nullptr;
+  FB_TRY(embedding_current(h, id, &E));
+  SlackScope slack(handle_slack_now(h));
+  return time_closest(h, *E, reps, path, seconds2);
 }

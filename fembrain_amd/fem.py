@@ -364,6 +364,21 @@ class FemIntegrator:
         _l.check(self._L.fb_fem_time_embed_search(self.h, eid, reps, _l.dptr(out)))
         return tuple(float(x) for x in out)
 
+    def embed_search_info(self, eid):
+        """What the pass for the points no element contains did in the last search of embedding ``eid`` (fb_fem_embed_search_info_get):
+        dict of path (lib.FB_EMBED_CLOSEST_NONE / _SCAN / _RING), n_outside, n_far (the points the full scan finished),
+        centre_grid_builds (of the handle), max_centres_one_point and centres_tested"""
+        out = _l.EmbedSearchInfo()
+        _l.check(self._L.fb_fem_embed_search_info_get(self.h, int(eid), C.byref(out)))
+        return {name: int(getattr(out, name)) for name, _ in _l.EmbedSearchInfo._fields_}
+
+    def time_embed_closest(self, eid, path, reps=20):
+        """(centre-grid build, external pass) in seconds for the outside points of embedding ``eid`` with ``path``
+        (lib.FB_EMBED_CLOSEST_SCAN or _RING), medians of ``reps``, on a scratch copy (fb_fem_time_embed_closest)"""
+        out = np.zeros(2)
+        _l.check(self._L.fb_fem_time_embed_closest(self.h, int(eid), int(reps), int(path), _l.dptr(out)))
+        return float(out[0]), float(out[1])
+
     # -- disjoint parts of the (cut) mesh on the device (fb_fem_parts / split_parts / read_part; unsharded handles) --
     def parts(self):
         """The face-connected parts of the mesh the device holds (fb_fem_parts; VolMesh::get_disjoint_parts): dict of n_parts,

@@ -29,6 +29,7 @@ FB_CONTACT_MISS, FB_CONTACT_EMPTY, FB_CONTACT_SET = 0, 1, 2  # fb_fem_contact_in
 FB_CONTACT_SPREAD_RECORDS, FB_CONTACT_SPREAD_LEVELS = 0, 1  # fb_fem_contact_spread_info.path
 FB_MAX_MATERIALS = 256  # entries of a handle's material table (fb_fem_set_materials)
 FB_STRESS_WORLD, FB_STRESS_TENSORS = 1, 2  # fb_fem_stress flags
+FB_EMBED_CLOSEST_NONE, FB_EMBED_CLOSEST_SCAN, FB_EMBED_CLOSEST_RING = 0, 1, 2  # fb_fem_embed_search_info.path
 
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
@@ -74,6 +75,11 @@ class EmbedInfo(C.Structure):
     _fields_ = [("id", C.c_int), ("n_points", C.c_int), ("n_triangles", C.c_int), ("n_external", C.c_int), ("n_zeroed", C.c_int),
                 ("n_locates", C.c_int), ("n_rebound", C.c_int), ("grid", C.c_int * 3), ("n_wide", C.c_int),
                 ("aabb_lo", C.c_float * 3), ("aabb_hi", C.c_float * 3)]
+
+
+class EmbedSearchInfo(C.Structure):
+    _fields_ = [("path", C.c_int), ("n_outside", C.c_int), ("n_far", C.c_int), ("centre_grid_builds", C.c_int),
+                ("max_centres_one_point", C.c_int), ("centres_tested", C.c_longlong)]
 
 
 class PartsInfo(C.Structure):
@@ -188,6 +194,8 @@ def lib():
         "fb_fem_embed_release": (C.c_int, [vp, C.c_int]),
         "fb_fem_time_embed": (C.c_int, [vp, C.c_int, C.c_int, _dp, _dp]),
         "fb_fem_time_embed_search": (C.c_int, [vp, C.c_int, C.c_int, _dp]),
+        "fb_fem_embed_search_info_get": (C.c_int, [vp, C.c_int, C.POINTER(EmbedSearchInfo)]),
+        "fb_fem_time_embed_closest": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, _dp]),
         "fb_fem_embed_add_forces": (C.c_int, [vp, C.c_int, C.c_int, _ip, _dp]),
         "fb_fem_embed_forces_info": (C.c_int, [vp, C.c_int, _ip, _ip, _ip]),
         "fb_fem_embed_pick_ray": (C.c_int, [vp, C.c_int, _dp, _dp, C.c_double, _ip, _dp, _dp, _dp]),

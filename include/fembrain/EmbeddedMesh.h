@@ -46,6 +46,13 @@ class EmbeddedMesh {
   U32 countExternal() const { return (U32)m_info.n_external; }  // points no element contained when they were last searched
   const fb_fem_embed_info& info() const { return m_info; }
   const std::vector<int>& triangles() const { return m_triangles; }
+  // how the points no element contains found their closest centre in the last search (fb_fem_embed_search_info_get): a surface drawn
+  // around the body has most of its points there
+  fb_fem_embed_search_info searchInfo() const {
+    fb_fem_embed_search_info si;
+    HipIntegrator::check(fb_fem_embed_search_info_get(m_lpIntegrator->handle(), m_id, &si));
+    return si;
+  }
 
   // what the deformation callback's receiver did: the current positions, normals and box of the points
   void applyDisplacements() { HipIntegrator::check(fb_fem_embed_update(m_lpIntegrator->handle(), m_id, m_xyz.data(), m_normals.data(), &m_info)); }

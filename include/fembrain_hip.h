@@ -338,7 +338,27 @@ int fb_fem_time_surface(fb_fem_t h, int reps, double* seconds_build, double* sec
  *  - An orphan has no binding to refresh rest_xyz through: if a FB_CUT_BAKE cut or fb_fem_split_parts moves the rest shape before the
  *    orphan has been searched (no read or update in between), it is searched where it stood in the OLD rest shape.  Read or update the
  *    embedding between such changes.
- * fb_fem_detach_part does not copy embeddings to the new handle. */
+ * fb_fem_detach_part does not copy embeddings to the new handle.
+ *
+ * Points outside.  A surface drawn AROUND the body (a skin over coarser tets, a cage) has half or all of its points external.  Their
+ * closest centre is found by one of two passes that give the same binding bit for bit: SCAN tests every centre of the mesh for every
+ * such point; RING looks, one wavefront per point, only at the cells of a grid of the centres that could hold a closer one (built once
+ * per mesh generation, on the first search that takes this path), and hands a point that has tested more than a budget of centres -- one
+ * that sees much of the mesh at about its closest distance -- to the scan.  A search chooses by itself: RING when the centre grid of this
+ * mesh generation exists already or the search has at least 8,192 external points, else SCAN.  FEMBRAIN_EMBED_CLOSEST=scan|ring forces a
+ * path and FEMBRAIN_EMBED_RING_BUDGET=n sets the budget (default max(64, n_tets / 32)); both are read at every search. */
+#define FB_EMBED_CLOSEST_NONE 0 /* the last search had no external point */
+#define FB_EMBED_CLOSEST_SCAN 1
+#define FB_EMBED_CLOSEST_RING 2
+typedef struct fb_fem_embed_search_info {
+  int path;                  /* FB_EMBED_CLOSEST_*: the external pass of the last search of this embedding */
+  int n_outside;             /* points that search sent to the external pass */
+  int n_far;                 /* ... of them, those the scan finished (SCAN: all of them) */
+  int centre_grid_builds;    /* centre grids built since the handle was made */
+  int max_centres_one_point; /* the most centres one point tested in that search (SCAN: n_tets; RING: in the ring pass, where a far
+                                point's count ends past the budget) */
+  long long centres_tested;  /* all centres tested in that search: SCAN n_outside * n_tets; RING the ring pass plus n_far * n_tets */
+} fb_fem_embed_search_info;
 typedef struct fb_fem_embed_params { double zero_threshold; /* <= 0: off */ } fb_fem_embed_params;
 typedef struct fb_fem_embed_info {
   int id, n_points, n_triangles;
@@ -367,6 +387,14 @@ int fb_fem_time_embed(fb_fem_t h, int id, int reps, double* seconds_locate, doub
  * overflow list with the compaction of the points without an element (and the host wait for their number), [2] the external pass
  * (closest centre), the weights and the counts.  Each the median of `reps`; fb_fem_time_embed's seconds_locate is their sum. */
 int fb_fem_time_embed_search(fb_fem_t h, int id, int reps, double seconds3[3]);
+/* What the external pass of embedding id's last search did (points that wait for a search are searched first).  FB_EINVAL for an id
+ * without an embedding. */
+int fb_fem_embed_search_info_get(fb_fem_t h, int id, fb_fem_embed_search_info* out);
+/* Medians of `reps` HIP-event timings of the external pass alone, for this embedding's external points, with path FB_EMBED_CLOSEST_SCAN or
+ * _RING: seconds2[0] the centre grid's build (0 for SCAN), seconds2[1] the pass (RING: with its host wait and the scan of its far points).
+ * On a scratch copy, like fb_fem_time_embed_search: the binding, its counts, n_locates, the search info and whether the handle has a
+ * centre grid are left as they are.  In fb_fem_time_embed_search a centre grid's build, when the search makes one, belongs to [2]. */
+int fb_fem_time_embed_closest(fb_fem_t h, int id, int reps, int path, double seconds2[2]);
 
 /* ---- The way back: touching, picking and colouring what an embedding draws ----
  * fb_fem_embed sends data outward, from the tets to the drawn points.  These calls go the other way, on the device, so that a host which

@@ -14,7 +14,13 @@ The way back (fb_fem_embed_add_forces / pick_ray / pick_point / embed_stress), b
 timings of the call followed by a device synchronise, every shape warmed first: the first add of a fresh embedding (table build +
 dense add; one sample per spare slot), a dense add, a 3-point add, a ray pick, a point pick, embed_stress -- and, in the same run, the
 host route they replace: fb_fem_read_embedding + np.add.at + fb_fem_set_external_forces, and a numpy Moeller-Trumbore pass over the
-positions fb_fem_embed_update reads back."""
+positions fb_fem_embed_update reads back.
+
+    python tools/probe_embed.py --outside [--out profiles/embed_probe_outside.json] [--reps 10] [--n 56]
+
+The enclosing case alone: the same surface scaled to ENCLOSE the cantilever, every vertex outside the tets.  The closest-centre pass by
+path (fb_fem_time_embed_closest: the scan, the ring through the centre grid, the grid's build) for the first 1 .. 16,384 vertices of a
+shuffle and for all of them, at n^3 and at the 27^3 cube (105,456 tets), with what the automatic rule chose and the search info."""
 import argparse
 import json
 import os
@@ -126,13 +132,63 @@ def touch_row(g, eid, pts, tri, reps):
     return out
 
 
+def outside_rows(n, sx, tri, reps):
+    """--outside: the sphere scaled to ENCLOSE the n^3 cantilever, every vertex outside the tets.  The external pass alone, by path
+    (fb_fem_time_embed_closest: HIP events, medians, on a scratch copy), for all vertices and for the first k of a shuffle of them (the
+    crossover of the two paths); what the automatic rule chose for the embedding; the search info under either path."""
+    v, t = truth_cube(n, n, n, 0.1)
+    v = np.asarray(v, np.float64).reshape(-1, 3)
+    fixed = fixed_vertices_to_dofs(cube_fixed_plane_i0(n, n))
+    lo, hi = v.min(0), v.max(0)
+    radius = np.linalg.norm(sx.astype(np.float64), axis=1)
+    pts = 0.5 * (lo + hi) + sx.astype(np.float64) * (1.05 * 0.5 * np.linalg.norm(hi - lo) / radius.min())
+    order = np.random.default_rng(0).permutation(len(pts))
+    g = FemIntegrator(v, t, fixed)
+    rows = []
+    counts = [k for k in (1, 4, 12, 16, 64, 256, 1024, 4096, 16384) if k < len(pts)] + [len(pts)]
+    for name in ("FEMBRAIN_EMBED_CLOSEST", "FEMBRAIN_EMBED_RING_BUDGET"):
+        os.environ.pop(name, None)
+    # what the rule chooses on a mesh generation without a centre grid: ascending counts, so that the first grid is one the rule asked for
+    auto_path = {}
+    for k in counts:
+        e = g.embed(pts[order[:k]])
+        auto_path[k] = g.embed_search_info(e)["path"]
+        g.embed_release(e)
+    for k in counts:
+        whole = k == len(pts)
+        eid, info = g.embed(pts if whole else pts[order[:k]], tri if whole else None, info=True)
+        auto = dict(path=auto_path[k])
+        assert info["n_external"] == k, info
+        r_scan = max(1, min(reps, 3)) if k * len(t) > 1 << 33 else reps  # (seconds per repetition up there)
+        scan = g.time_embed_closest(eid, fl.FB_EMBED_CLOSEST_SCAN, r_scan)
+        ring = g.time_embed_closest(eid, fl.FB_EMBED_CLOSEST_RING, reps)
+        g.embed_release(eid)
+        by_path = {}
+        for path in ("scan", "ring"):  # the same points bound under either path: the counters, and the same binding
+            os.environ["FEMBRAIN_EMBED_CLOSEST"] = path
+            e = g.embed(pts if whole else pts[order[:k]])
+            by_path[path] = (g.embed_search_info(e), g.embedding(e))
+            g.embed_release(e)
+        os.environ.pop("FEMBRAIN_EMBED_CLOSEST")
+        same = all(by_path["scan"][1][key].tobytes() == by_path["ring"][1][key].tobytes() for key in ("elements", "vertices", "weights"))
+        out = dict(case="outside%d" % n, n_tets=len(t), n_outside=k, grid=list(info["grid"]), auto_path=auto["path"], seconds_scan=scan[1], reps_scan=r_scan,
+                   seconds_ring=ring[1], seconds_centre_grid_build=ring[0], ring_plus_build_over_scan=(ring[0] + ring[1]) / scan[1],
+                   same_binding=same, info_ring=by_path["ring"][0], info_scan=by_path["scan"][0])
+        print(json.dumps(out), flush=True)
+        rows.append(out)
+    g.close()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "embed_probe.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--n", type=int, default=56)
     ap.add_argument("--cell", type=float, default=0.01)
+    ap.add_argument("--outside", action="store_true", help="the enclosing-surface case only: every vertex outside the tets (profiles/embed_probe_outside.json)")
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "embed_probe_outside.json" if a.outside else "embed_probe.json")
     v, t = truth_cube(a.n, a.n, a.n, 0.1)
     v = np.asarray(v, np.float64).reshape(-1, 3)
     fixed = fixed_vertices_to_dofs(cube_fixed_plane_i0(a.n, a.n))
@@ -147,6 +203,12 @@ def main():
     pts = 0.5 * (lo + hi) + sx.astype(np.float64) * (0.45 * (hi - lo).min() / r)
     tri = st.astype(np.int32)
     poly.close()
+    if a.outside:
+        rows = outside_rows(a.n, sx, tri, a.reps) + outside_rows(27, sx, tri, a.reps)  # 998,250 tets at the default n | the 105,456-tet cube
+        with open(a.out, "w") as fh:
+            json.dump(dict(tool="tools/probe_embed.py --outside", reps=a.reps, timer="HIP events inside fb_fem_time_embed_closest (medians; the ring's figure includes its host wait)", rows=rows), fh, indent=1)
+            fh.write("\n")
+        return
     rows = []
 
     def row(name, g, eid, **extra):
