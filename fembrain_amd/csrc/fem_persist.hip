@@ -21,6 +21,7 @@ struct PipeKernel {
   bool timing, shard, bj, help, xyz;
   bool ahead;           // the run-ahead form: for launches with a service wavefront (pcg_pipe.hip.h)
   int regs;             // register slots per slice it holds (pcg_pipe_regs.hip.h), 0: none
+  int prio;             // wavefront priority through the product (pcg_pipe.hip.h): 0 none, 1 progress, 2 static, 3 progress + service wavefront
   const void* fn;
 };
 
@@ -33,14 +34,19 @@ namespace {
 // unsharded one-row kernel without the task table comes in two forms, one per launch form: with its barriers (as many slices as
 // wavefronts) and run-ahead (a service wavefront); the others keep their barriers with or without a service wavefront.  The run-ahead LDS-window
 // kernels of the plain Jacobi solver -- (12, 6) and (12, 7), the headline's -- come a second time with register slots (k_pcg_pipe_regs, REGS = 3);
-// FEMBRAIN_PIPE_REGS=0 launches the one without.
+// FEMBRAIN_PIPE_REGS=0 launches the one without.  Those four, and the TIMING (12, 6) run-ahead pair for the phase tables, come once more per priority
+// form (PRIO = 1, 2, 3; FEMBRAIN_PIPE_PRIO picks, 0 launches the one without).
 #define FB_PIPE1F(C16, WMAX, KLT, TIMING, SHARD, BJ, HELP, XYZ, AHEAD, REGS) \
-  {1, C16, WMAX, KLT, TIMING, SHARD, BJ, HELP, XYZ, AHEAD, REGS, (const void*)k_pcg_pipe<float, C16, WMAX, KLT, TIMING, SHARD, BJ, HELP, XYZ, AHEAD, REGS>}
+  {1, C16, WMAX, KLT, TIMING, SHARD, BJ, HELP, XYZ, AHEAD, REGS, 0, (const void*)k_pcg_pipe<float, C16, WMAX, KLT, TIMING, SHARD, BJ, HELP, XYZ, AHEAD, REGS>}
 #define FB_PIPE1(C16, WMAX, KLT, TIMING, SHARD, BJ, HELP, XYZ) FB_PIPE1F(C16, WMAX, KLT, TIMING, SHARD, BJ, HELP, XYZ, false, 0)
 #define FB_PIPE1A(C16, WMAX, KLT, TIMING, BJ) FB_PIPE1F(C16, WMAX, KLT, TIMING, false, BJ, false, false, true, 0)
 #define FB_PIPE1R(C16, KLT) \
-  {1, C16, 12, KLT, false, false, false, false, false, true, kPipeRegsMax, (const void*)k_pcg_pipe_regs<float, C16, 12, KLT, false, false, false, false, false, true, kPipeRegsMax>}
-#define FB_PIPE2(C16, SHARD, XYZ) {2, C16, 12, kPipe2Klt, false, SHARD, false, false, XYZ, false, 0, (const void*)k_pcg_pipe2<C16, SHARD, XYZ>}
+  {1, C16, 12, KLT, false, false, false, false, false, true, kPipeRegsMax, 0, (const void*)k_pcg_pipe_regs<float, C16, 12, KLT, false, false, false, false, false, true, kPipeRegsMax>}
+#define FB_PIPE1RP(C16, KLT, PRIO) \
+  {1, C16, 12, KLT, false, false, false, false, false, true, kPipeRegsMax, PRIO, (const void*)k_pcg_pipe_regs<float, C16, 12, KLT, false, false, false, false, false, true, kPipeRegsMax, PRIO>}
+#define FB_PIPE1TP(C16, PRIO) \
+  {1, C16, 12, 6, true, false, false, false, false, true, 0, PRIO, (const void*)k_pcg_pipe<float, C16, 12, 6, true, false, false, false, false, true, 0, PRIO>}
+#define FB_PIPE2(C16, SHARD, XYZ) {2, C16, 12, kPipe2Klt, false, SHARD, false, false, XYZ, false, 0, 0, (const void*)k_pcg_pipe2<C16, SHARD, XYZ>}
 const PipeKernel kPipeKernels[] = {
     FB_PIPE1(true, 5, 16, false, false, false, false, false),  FB_PIPE1(false, 5, 16, false, false, false, false, false),
     FB_PIPE1(true, 8, 8, false, false, false, false, false),   FB_PIPE1(false, 8, 8, false, false, false, false, false),
@@ -62,10 +68,15 @@ const PipeKernel kPipeKernels[] = {
     FB_PIPE1A(true, 12, 6, true, false),   FB_PIPE1A(false, 12, 6, true, false),
     FB_PIPE1A(true, 8, 8, false, true),    FB_PIPE1A(false, 8, 8, false, true),    FB_PIPE1A(true, 12, 6, false, true),   FB_PIPE1A(false, 12, 6, false, true),
     FB_PIPE1R(true, 6),  FB_PIPE1R(false, 6),  FB_PIPE1R(true, 7),  FB_PIPE1R(false, 7),
+    FB_PIPE1RP(true, 6, 1),  FB_PIPE1RP(false, 6, 1),  FB_PIPE1RP(true, 7, 1),  FB_PIPE1RP(false, 7, 1),  FB_PIPE1TP(true, 1),  FB_PIPE1TP(false, 1),
+    FB_PIPE1RP(true, 6, 2),  FB_PIPE1RP(false, 6, 2),  FB_PIPE1RP(true, 7, 2),  FB_PIPE1RP(false, 7, 2),  FB_PIPE1TP(true, 2),  FB_PIPE1TP(false, 2),
+    FB_PIPE1RP(true, 6, 3),  FB_PIPE1RP(false, 6, 3),  FB_PIPE1RP(true, 7, 3),  FB_PIPE1RP(false, 7, 3),  FB_PIPE1TP(true, 3),  FB_PIPE1TP(false, 3),
     FB_PIPE2(true, false, false),  FB_PIPE2(false, false, false),  FB_PIPE2(true, false, true),  FB_PIPE2(false, false, true),
     FB_PIPE2(false, true, false),
 };
 #undef FB_PIPE2
+#undef FB_PIPE1TP
+#undef FB_PIPE1RP
 #undef FB_PIPE1R
 #undef FB_PIPE1A
 #undef FB_PIPE1
@@ -104,6 +115,7 @@ PersistKnobs read_persist_knobs() {
   k.plain_stores = env_int("FEMBRAIN_PIPE_PLAIN_STORES", -1);
   k.mirror = env_int("FEMBRAIN_PIPE_MIRROR", 1) != 0;
   k.regs = env_int("FEMBRAIN_PIPE_REGS", -1);
+  k.prio = env_int("FEMBRAIN_PIPE_PRIO", -1);
   k.verbose = getenv("FEMBRAIN_TIMING") != nullptr;
   return k;
 }
@@ -130,10 +142,13 @@ int resolve_pipe_kernel(fb_fem_s* h, const PersistKnobs& kn) {
   const bool regs_form = want.rows == 1 && want.wmax == 12 && want.ahead && !want.timing && !want.bj && !want.xyz && ps.pipe_mir_knob != 0 && kn.regs != 0;
   want.regs = regs_form ? kPipeRegsMax : 0;
   ps.pipe_regs = kn.regs < 0 ? want.regs : std::min(kn.regs, want.regs);
+  // wavefront priority: the kernels with register slots, and the TIMING (12, 6) run-ahead kernel; FEMBRAIN_PIPE_PRIO picks the form (0: the kernel without)
+  const bool prio_form = regs_form || (want.rows == 1 && want.wmax == 12 && want.klt == 6 && want.ahead && want.timing && !want.bj && !want.xyz);
+  want.prio = prio_form ? (kn.prio < 0 ? kPipePrioDefault : std::min(kn.prio, 3)) : 0;
   ps.kernel = nullptr;
   for (const PipeKernel& k : kPipeKernels)
     if (k.rows == want.rows && k.c16 == want.c16 && k.wmax == want.wmax && k.klt == want.klt && k.timing == want.timing && k.shard == want.shard && k.bj == want.bj &&
-        k.help == want.help && k.xyz == want.xyz && k.ahead == want.ahead && k.regs == want.regs)
+        k.help == want.help && k.xyz == want.xyz && k.ahead == want.ahead && k.regs == want.regs && k.prio == want.prio)
       ps.kernel = &k;
   if (!ps.kernel) return fail(FB_EINVAL, "FEMBRAIN_PERSIST_TIMING is built for one row per lane: (12, 6) and (5, 16) with 16-bit column words, (8, 8)");
   return FB_OK;
@@ -722,6 +737,8 @@ int fb_fem_persist_regs(fb_fem_t h, int* slots_per_slice) {
   if (slots_per_slice) *slots_per_slice = on ? std::min(h->ps.pipe_regs, h->ps.kernel->regs) : 0;
   return on ? h->ps.pipe_mir_got[3] : 0;
 }
+
+int fb_fem_persist_prio(fb_fem_t h) { return h && h->ps.persist && h->ps.kernel ? h->ps.kernel->prio : 0; }
 
 int fb_fem_persist_gather(fb_fem_t h, double* lines_planes, double* lines_records) {
   if (lines_planes) *lines_planes = h && h->ps.persist ? h->ps.pipe_gather_lines[0] : 0.0;

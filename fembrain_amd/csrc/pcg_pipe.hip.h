@@ -52,6 +52,17 @@
 // totals or of failure, and the service wavefront meets no wait between the barrier behind the poll and its collection.  A wavefront that
 // leaves the loop executes no barrier any more, and no sibling waits at one for it: between the second barrier of a product and the exits
 // that follow it (the hand-over, the iteration count at the head of the loop) there is none, and every sibling takes the same exit.
+// Priority 0 before every wait (round 10; the PRIO instantiations: the (12, 6) and (12, 7) register-slot kernels and the TIMING (12, 6) run-ahead one,
+// FEMBRAIN_PIPE_PRIO).  VALU issue on a SIMD goes by priority, then age, so the youngest of a SIMD's three slice wavefronts finishes its product 1.7-2 us
+// behind the oldest, and the product's barrier waits for it.  PRIO = 1 (progress): a slice wavefront raises itself to 3 behind the second barrier of
+// product() and steps down as it gets on -- 2 into the on-chip run, 1 into the plain layers, 0 into the register layers behind the window or the streamed
+// rest -- so the sibling furthest behind wins the arbitration; PRIO = 2 (static): wavefronts 8-10 run their product at 1; PRIO = 3: progress, and the
+// service wavefront collects the sums at 1.  The rule that keeps this from starving anyone: a wavefront is above priority 0 ONLY between the second barrier
+// of a product and that product's last slot (the service wavefront: between that barrier and its hand-over, and not while it polls a record that is
+// missing).  It is at 0 at both barriers, during wavefront 0's poll, in every spin and s_sleep, through the wait for the totals, the recurrences, the
+// publish stores and their drain, and at every exit: the raised region contains no wait, no branch that leaves the loop and no return -- a failed wait
+// for the neighbours returns in front of it, a failed collection is handed over behind it, the iteration cap is tested at 0.  The steps are taken from
+// the wave-uniform values the regions are entered by; no control flow depends on them.
 #pragma once
 #include "fem_kernels.h"
 #include "pcg_pipe_stream.hip.h"
@@ -140,6 +151,14 @@ __device__ __forceinline__ uint4 ld_sc1_u128(const void* p) {
   uint4 v;
   asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(p) : "memory");
   return v;
+}
+
+// The wavefront's issue priority (0..3; header, "Priority 0 before every wait").  The instruction is scalar and ignores EXEC; as a volatile statement it
+// keeps its place among the volatile assembly regions and every memory operation, and a branch around it is kept even where no lane is active.
+template <int P>
+__device__ __forceinline__ void pipe_setprio() {
+  static_assert(P >= 0 && P <= 3, "s_setprio takes 0..3");
+  asm volatile("s_setprio %0" : : "n"(P) : "memory");
 }
 
 // a value every lane holds alike, moved to scalar registers (a uniform double in vector registers costs two per lane for nothing)
@@ -347,6 +366,8 @@ __global__ __launch_bounds__(64 * kMirWaves) void k_pipe_mirror_plan(int n_slice
 
 // One wavefront's share of the collection of all workgroups' posted sums of sequence number `sums`: lane `l0` of `stride` takes workgroups
 // l0, l0 + stride, ...; adds their two values to t0s / t1s in that order (the callers fix the order of the rest).  Bounded by the wall clock.
+// SERVE_PRIO (the service wavefront of a PRIO = 3 kernel, which enters at priority 1): a record that is not there yet is polled at priority 0.
+template <bool SERVE_PRIO = false>
 __device__ __forceinline__ void pipe_collect_posts(const PipeArgs& pa, unsigned int sums, int nb, int lane, int stride, int l0, long long t0, long long t_limit, bool& failed,
                                                    double& t0s, double& t1s) {
   const unsigned long long* post = pa.post + (size_t)(sums & 1u) * nb * 4;
@@ -361,9 +382,11 @@ __device__ __forceinline__ void pipe_collect_posts(const PipeArgs& pa, unsigned 
         ok = q4[0].y == sums && q4[0].w == sums && q4[1].y == sums && q4[1].w == sums;
       }
       if (__ballot(!ok) == 0ULL) break;
+      if constexpr (SERVE_PRIO) pipe_setprio<0>();  // from here on a spin
       if (ld_sc1_u32(pa.error) != 0u || wall_clock64() - t0 > t_limit) { failed = true; break; }
       __builtin_amdgcn_s_sleep(1);
     }
+    if constexpr (SERVE_PRIO) pipe_setprio<1>();
     if (mine && !failed) {
       t0s += __longlong_as_double((long long)(((unsigned long long)q4[0].x << 32) | (unsigned long long)q4[0].z));
       t1s += __longlong_as_double((long long)(((unsigned long long)q4[1].x << 32) | (unsigned long long)q4[1].z));

@@ -33,7 +33,10 @@ namespace fb {
 // REGS (2 or 3; 0: none): up to that many streamed slots of every slice, those next to the LDS window, keep their values in registers above the compiler's cap for the launch and
 // run with the on-chip run (pcg_pipe_regs.hip.h; how many a slice has is the plan's word, PipeArgs::mirror).  Only for the run-ahead LDS-window
 // instantiations; the temporaries of the hand-written loops are then v64..v99, which is what leaves the registers.
-template <typename MT, bool C16, int WMAX, int KLT, bool TIMING, bool SHARD, bool BJ = false, bool HELP = false, bool XYZ = false, bool AHEAD = false, int REGS = 0>
+// PRIO (0: none, and nothing of it in the kernel; 1 progress, 2 static, 3 progress + service wavefront): wavefront priority through the product
+// (header of pcg_pipe.hip.h, "Priority 0 before every wait").  The register-slot kernels and the TIMING (12, 6) run-ahead kernel only.
+template <typename MT, bool C16, int WMAX, int KLT, bool TIMING, bool SHARD, bool BJ = false, bool HELP = false, bool XYZ = false, bool AHEAD = false, int REGS = 0,
+          int PRIO = 0>
 __global__ __launch_bounds__(64 * WMAX) FB_PIPE_KERNEL_ATTR void FB_PIPE_KERNEL(SellView sv, const MT* __restrict__ vals, const MT* __restrict__ dlo,
                                                         const double* __restrict__ invdiag, const double* __restrict__ bvec, double* __restrict__ xg,
                                                         double* __restrict__ rg, double* __restrict__ wg, double* __restrict__ zg,
@@ -46,6 +49,9 @@ __global__ __launch_bounds__(64 * WMAX) FB_PIPE_KERNEL_ATTR void FB_PIPE_KERNEL(
   static_assert((REGS > 0) == FB_PIPE_KERNEL_HOLDS, "register slots: k_pcg_pipe_regs, and only there");
   static_assert(REGS == 0 || (AHEAD && !TIMING && !BJ && !XYZ && WMAX == 12 && (KLT == 6 || KLT == 7) && REGS <= kPipeRegsMax),
                 "register slots: the run-ahead LDS-window instantiations");
+  static_assert(PRIO >= 0 && PRIO <= 3 && (PRIO == 0 || (AHEAD && !BJ && !XYZ && WMAX == 12 && (REGS > 0 || (TIMING && KLT == 6)))),
+                "wavefront priority: the register-slot kernels and the TIMING (12, 6) run-ahead kernel");
+  constexpr bool kProgress = PRIO == 1 || PRIO == 3;
   static_assert(sizeof(MT) == 4, "k_pcg_pipe keeps part of the matrix in LDS as fp32 words and streams the rest as fp32");
   extern __shared__ double lds[];  // the request is padded so that one workgroup fills a CU
   double* wsum = lds;                          // [2][16] wave sums
@@ -328,6 +334,9 @@ __global__ __launch_bounds__(64 * WMAX) FB_PIPE_KERNEL_ATTR void FB_PIPE_KERNEL(
     lap(1);  // flag + wait for the producers + acquire
     if (uniform_flag(bc[3] != 0.0 || (SHARD && bc[4] != 0.0))) { failed = true; return; }
     if (plain_cand && !xcc_known) { through = !uniform_flag(bc[5] != 0.0); xcc_known = true; }
+    // (PRIO) behind the second barrier: a slice wavefront starts its product at 3 (progress), the youngest of every SIMD runs it at 1 (static)
+    if constexpr (kProgress) { if (uniform_flag(live)) pipe_setprio<3>(); }
+    if constexpr (PRIO == 2) { if (uniform_flag(live && wv >= 8)) pipe_setprio<1>(); }
     // the low part of the diagonal block times the own entry first: vin is not needed beyond this point
     double y0 = 0, y1 = 0, y2 = 0;
     if (rvalid) {
@@ -359,15 +368,17 @@ __global__ __launch_bounds__(64 * WMAX) FB_PIPE_KERNEL_ATTR void FB_PIPE_KERNEL(
                                        C16 ? (const void*)sv.coldelta : (const void*)sv.colidx, pl, pl + xs, pl + 2 * xs, row, y0, y1, y2);
           }
         }
+        if constexpr (kProgress) pipe_setprio<2>();  // the seam into the on-chip run
         seam(5, tseam);
         // the on-chip run, m mirror layers and then KL plain ones: hand-scheduled, the gathers four slots ahead (pcg_pipe_onchip.hip.h)
         const char* lbase = (const char*)(lds + kPipeSyncDoubles);
         if constexpr (REGS > 0) {  // ... with the register layers at both ends of it (pcg_pipe_regs.hip.h)
-          pipe_onchip_slots_regs<C16>(reg_f, mir_m, max(KL, 0), reg_b, (const unsigned int*)(lbase + mir_tab) + lane, (const unsigned short*)(lbase + mir_tab) + lane, lres, lcd,
+          pipe_onchip_slots_regs<C16, kProgress>(reg_f, mir_m, max(KL, 0), reg_b, (const unsigned int*)(lbase + mir_tab) + lane, (const unsigned short*)(lbase + mir_tab) + lane, lres, lcd,
                                       lbase, pl, pl + xs, pl + 2 * xs, row, y0, y1, y2);
         } else
-        pipe_onchip_slots<C16>(mir_m, max(KL, 0), (const unsigned int*)(lbase + mir_tab) + lane, (const unsigned short*)(lbase + mir_tab) + lane, lres, lcd, lbase, pl, pl + xs,
+        pipe_onchip_slots<C16, kProgress>(mir_m, max(KL, 0), (const unsigned int*)(lbase + mir_tab) + lane, (const unsigned short*)(lbase + mir_tab) + lane, lres, lcd, lbase, pl, pl + xs,
                                pl + 2 * xs, row, y0, y1, y2);
+        if constexpr (kProgress) pipe_setprio<0>();  // the seam into the streamed rest (a run that ended in register layers is there already)
       }
       if (sizeof(MT) == 4 && KLT >= 16) {
         // whole slices in LDS, five wavefronts per CU: registers to spare, so ALL gathers of the product are in flight before the first
@@ -452,6 +463,7 @@ __global__ __launch_bounds__(64 * WMAX) FB_PIPE_KERNEL_ATTR void FB_PIPE_KERNEL(
       double* hp = ypart + (size_t)help_idx * 3 * 64 + lane;
       hp[0] = h0; hp[64] = h1; hp[128] = h2;
     }
+    if constexpr (PRIO != 0) pipe_setprio<0>();  // every wavefront, whatever it held: what follows are waits, recurrences and exits
     y[0] = y0; y[1] = y1; y[2] = y2;
     lap(2);  // product
   };
@@ -567,9 +579,10 @@ __global__ __launch_bounds__(64 * WMAX) FB_PIPE_KERNEL_ATTR void FB_PIPE_KERNEL(
       // slice, it idles through the product -- collect the sums meanwhile: same order of additions as below, so the same bits;
       // the others find the totals behind ONE barrier, or (AHEAD, the header's run-ahead form) each behind its own wait for their number.
       if (wv == n_waves - 1) {
+        if constexpr (PRIO == 3) pipe_setprio<1>();  // the youngest wavefront of its SIMD: its collection at 1, a poll of a missing record at 0, 0 behind the hand-over
         const long long t0 = wall_clock64();
         double t0s = 0, t1s = 0;
-        pipe_collect_posts(pa, sums, nb, lane, 64, lane, t0, t_limit, failed, t0s, t1s);
+        pipe_collect_posts<PRIO == 3>(pa, sums, nb, lane, 64, lane, t0, t_limit, failed, t0s, t1s);
         failed = uniform_flag(failed);
         if (failed && lane == 0) st_sc1_u32(pa.error, 1u);
         t0s = wave_sum(t0s); t1s = wave_sum(t1s);
@@ -577,6 +590,7 @@ __global__ __launch_bounds__(64 * WMAX) FB_PIPE_KERNEL_ATTR void FB_PIPE_KERNEL(
           bc[0] = t0s; bc[1] = t1s; bc[2] = (failed || ld_sc1_u32(pa.error) != 0u) ? 1.0 : 0.0;
           if constexpr (AHEAD) __hip_atomic_store(tot_seq, sums, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);  // totals or failure: always handed over
         }
+        if constexpr (PRIO == 3) pipe_setprio<0>();
       }
       if constexpr (AHEAD) {
         while ((unsigned int)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(tot_seq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) != sums) __builtin_amdgcn_s_sleep(1);

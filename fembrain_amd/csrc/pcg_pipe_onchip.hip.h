@@ -130,7 +130,8 @@ namespace fb {
   "s_waitcnt vmcnt(0)\n"                                                   \
   ".Lfbo_wd" J "_%=:\n\t"
 // one slot from set J (nc slots left to compute, the first mc of them mirror layers), then the slot four behind it into the same set
-#define FBO_SLOT(J, ISSUE_MIR, ISSUE_PLAIN, x0, x1, x2, A)                 \
+// (PP: text at the head of a plain layer's path -- nothing, or the priority step of the seam into the plain layers, FBO_PRIO_PLAIN)
+#define FBO_SLOTP(J, PP, ISSUE_MIR, ISSUE_PLAIN, x0, x1, x2, A)            \
   "s_cmp_lt_i32 %[nc], 1\n\t"                                              \
   "s_cbranch_scc1 .Lfbo_end_%=\n\t"                                        \
   "s_sub_i32 %[nc], %[nc], 1\n\t"                                          \
@@ -143,6 +144,7 @@ namespace fb {
   FBO_COMPUTE_MIR(x0, x1, x2, A)                                           \
   "s_branch .Lfbo_ci" J "_%=\n"                                            \
   ".Lfbo_cp" J "_%=:\n\t"                                                  \
+  PP                                                                       \
   FBO_FIRST_PLAIN(A)                                                       \
   FBO_WAITVM("p" J)                                                        \
   FBO_COMPUTE_PLAIN(x0, x1, x2, A)                                         \
@@ -153,8 +155,13 @@ namespace fb {
 #define FBO_SET2 FBV_136_137, FBV_138_139, FBV_140_141, FBV_150
 #define FBO_SET3 FBV_142_143, FBV_144_145, FBV_146_147, FBV_151
 #define FBO_ISSUE_(J, ISSUE_MIR, ISSUE_PLAIN, SET) FBO_ISSUE(J, ISSUE_MIR, ISSUE_PLAIN, SET)
-#define FBO_SLOT_(J, ISSUE_MIR, ISSUE_PLAIN, SET) FBO_SLOT(J, ISSUE_MIR, ISSUE_PLAIN, SET)
-#define FBO_BODY(ISSUE_MIR, ISSUE_PLAIN)                                                                        \
+#define FBO_SLOT_(J, PP, ISSUE_MIR, ISSUE_PLAIN, SET) FBO_SLOTP(J, PP, ISSUE_MIR, ISSUE_PLAIN, SET)
+// Priority by progress (round 10, the PRIO instantiations of pcg_pipe_kernel.h): the wavefront steps its priority down to 1 where its on-chip run
+// passes from the mirror layers to the plain ones.  The run is ONE rotating loop over both kinds, so the step stands at the head of the plain
+// layers' path and is executed again by every plain layer: one scalar instruction without an operand, the same priority again.
+#define FBO_PRIO_PLAIN "s_setprio 1\n\t"
+#define FBO_BODY(ISSUE_MIR, ISSUE_PLAIN) FBO_BODYP(ISSUE_MIR, ISSUE_PLAIN, "")
+#define FBO_BODYP(ISSUE_MIR, ISSUE_PLAIN, PP)                                                                   \
   /* scalar operands fresh from v_readfirstlane, read by vector memory instructions: 5 wait states (see FBP_BODYG) */ \
   "s_nop 4\n\t"                                                                                                 \
   "s_mov_b32 %[fl], 0\n\t"                                                                                      \
@@ -164,10 +171,10 @@ namespace fb {
   FBO_ISSUE_("c", ISSUE_MIR, ISSUE_PLAIN, FBO_SET2)                                                             \
   FBO_ISSUE_("d", ISSUE_MIR, ISSUE_PLAIN, FBO_SET3)                                                             \
   ".Lfbo_loop_%=:\n\t"                                                                                          \
-  FBO_SLOT_("0", ISSUE_MIR, ISSUE_PLAIN, FBO_SET0)                                                              \
-  FBO_SLOT_("1", ISSUE_MIR, ISSUE_PLAIN, FBO_SET1)                                                              \
-  FBO_SLOT_("2", ISSUE_MIR, ISSUE_PLAIN, FBO_SET2)                                                              \
-  FBO_SLOT_("3", ISSUE_MIR, ISSUE_PLAIN, FBO_SET3)                                                              \
+  FBO_SLOT_("0", PP, ISSUE_MIR, ISSUE_PLAIN, FBO_SET0)                                                          \
+  FBO_SLOT_("1", PP, ISSUE_MIR, ISSUE_PLAIN, FBO_SET1)                                                          \
+  FBO_SLOT_("2", PP, ISSUE_MIR, ISSUE_PLAIN, FBO_SET2)                                                          \
+  FBO_SLOT_("3", PP, ISSUE_MIR, ISSUE_PLAIN, FBO_SET3)                                                          \
   "s_branch .Lfbo_loop_%=\n"                                                                                    \
   ".Lfbo_end_%=:\n\t"
 // clang-format on
@@ -182,7 +189,7 @@ __device__ __forceinline__ unsigned int lds_byte_address(const void* p) {
 // 384 bytes per layer, and lmt2 + 256 the lane's halfword of the block's LDS word); lres: the lane's first word of the first plain layer
 // (9 x 256 bytes per layer and, C16, lcd: the lane's halfword of its column - row; else 10 x 256 bytes, the tenth word the column);
 // lmat: the LDS byte address the mirror tables' block words count from; pl0..2: the planes of the gathered vector.  All 64 lanes active.
-template <bool C16>
+template <bool C16, bool PRIO = false>
 __device__ __forceinline__ void pipe_onchip_slots(int m, int kl, const void* lmt, const void* lmt2, const void* lres, const void* lcd, const void* lmat,
                                                   const double* pl0, const double* pl1, const double* pl2, int row, double& y0, double& y1, double& y2) {
   pl0 = scalar_ptr(pl0); pl1 = scalar_ptr(pl1); pl2 = scalar_ptr(pl2);
@@ -191,6 +198,13 @@ __device__ __forceinline__ void pipe_onchip_slots(int m, int kl, const void* lmt
   unsigned int almt = lds_byte_address(lmt), ares = lds_byte_address(lres);
   if constexpr (C16) {
     unsigned int acd = lds_byte_address(lcd);
+    if constexpr (PRIO)
+      asm volatile(FBO_BODYP(FBO_ISSUE_MIR16, FBO_ISSUE_PLAIN16, FBO_PRIO_PLAIN)
+                   : [y0] "+v"(y0), [y1] "+v"(y1), [y2] "+v"(y2), [lmt] "+v"(almt), [lres] "+v"(ares), [lcd] "+v"(acd), [mi] "+s"(mi), [pi] "+s"(pi),
+                     [mc] "+s"(mc), [nc] "+s"(nc), [fl] "=&s"(fl)
+                   : [lmat] "s"(almat), [spl0] "s"(pl0), [spl1] "s"(pl1), [spl2] "s"(pl2), [row] "v"(row)
+                   : FBP_CLOBBERS);
+    else
     asm volatile(FBO_BODY(FBO_ISSUE_MIR16, FBO_ISSUE_PLAIN16)
                  : [y0] "+v"(y0), [y1] "+v"(y1), [y2] "+v"(y2), [lmt] "+v"(almt), [lres] "+v"(ares), [lcd] "+v"(acd), [mi] "+s"(mi), [pi] "+s"(pi),
                    [mc] "+s"(mc), [nc] "+s"(nc), [fl] "=&s"(fl)
@@ -198,6 +212,13 @@ __device__ __forceinline__ void pipe_onchip_slots(int m, int kl, const void* lmt
                  : FBP_CLOBBERS);
   } else {
     unsigned int almt2 = lds_byte_address(lmt2);
+    if constexpr (PRIO)
+      asm volatile(FBO_BODYP(FBO_ISSUE_MIR32, FBO_ISSUE_PLAIN32, FBO_PRIO_PLAIN)
+                   : [y0] "+v"(y0), [y1] "+v"(y1), [y2] "+v"(y2), [lmt] "+v"(almt), [lmt2] "+v"(almt2), [lres] "+v"(ares), [mi] "+s"(mi), [pi] "+s"(pi),
+                     [mc] "+s"(mc), [nc] "+s"(nc), [fl] "=&s"(fl)
+                   : [lmat] "s"(almat), [spl0] "s"(pl0), [spl1] "s"(pl1), [spl2] "s"(pl2)
+                   : FBP_CLOBBERS);
+    else
     asm volatile(FBO_BODY(FBO_ISSUE_MIR32, FBO_ISSUE_PLAIN32)
                  : [y0] "+v"(y0), [y1] "+v"(y1), [y2] "+v"(y2), [lmt] "+v"(almt), [lmt2] "+v"(almt2), [lres] "+v"(ares), [mi] "+s"(mi), [pi] "+s"(pi),
                    [mc] "+s"(mc), [nc] "+s"(nc), [fl] "=&s"(fl)

@@ -17,6 +17,7 @@ namespace fb {
 // build (handle creation and every re-sync) unless a field says otherwise.  -1 = not set: the rule next to the field decides.
 // Read elsewhere, at another moment: FEMBRAIN_PERSIST_TIMEOUT_MS (read_persist_timeout: per plan build and per re-arm) and
 // FEMBRAIN_PERSIST_MAX_RUN / _STRICT / _CAP_CHECK (fem.hip pcg_solve_pipe: per solve, on a live handle).
+constexpr int kPipePrioDefault = 1;  // FEMBRAIN_PIPE_PRIO not set (PersistKnobs::prio)
 struct PersistKnobs {
   // FEMBRAIN_PCG_PERSIST=0/1: off / on for FB_PCG_MERGED, FB_PCG_PERSISTENT and FB_PCG_BLOCK_JACOBI handles.  Not set: asked for
   // explicitly (FB_PCG_PERSISTENT), or by default where it was measured faster than the two-launch iteration (min_waves)
@@ -79,6 +80,10 @@ struct PersistKnobs {
   // FEMBRAIN_PIPE_REGS=0|2|3: streamed slots per slice whose values the run-ahead LDS-window kernels keep in registers for a launch
   // (pcg_pipe_regs.hip.h).  Not set: as many as the instantiation holds, 3; 0: the kernel without
   int regs = -1;
+  // FEMBRAIN_PIPE_PRIO=0|1|2|3: wavefront priority through the product of the register-slot kernels (and of the TIMING (12, 6) run-ahead kernel):
+  // off, by progress, static (wavefronts 8-10 at 1), by progress + the service wavefront's collection at 1 (pcg_pipe.hip.h, "Priority 0 before
+  // every wait").  Not set: kPipePrioDefault, what profiles/r10_prio_ab_cube56.txt decided; 0: the kernel without
+  int prio = -1;
   // FEMBRAIN_TIMING (the library's): one line per decision on stderr
   bool verbose = false;
 };

@@ -113,7 +113,11 @@ static_assert(2 * FB_PIPE_REGS_VGPR_PAIRS == kPipeRegsFirst && kPipeRegsFirst + 
   "s_add_i32 %[fl], %[fl], 1\n"                                            \
   ".Lfbr_id" J "_%=:\n\t"
 // one slot from set J (nc left to compute: fc register layers, mc mirror layers, pc plain layers, then register layers), then the slot four behind it
-#define FBR_SLOT(J, ISSUE_MIR, ISSUE_PLAIN, x0, x1, x2, A)                 \
+// (priority by progress, FBR_BODYP: PP = the step at the head of a plain layer's path, as FBO_SLOTP's; BL / BACK = where a register layer BEHIND the
+// window goes and the step in front of it -- "cr" and nothing without the form: the text of the parent's loop)
+#define FBR_BACK_NONE(J)
+#define FBR_BACK_PRIO(J) ".Lfbr_cb" J "_%=:\n\t" "s_setprio 0\n\t"
+#define FBR_SLOTP(J, PP, BL, BACK, ISSUE_MIR, ISSUE_PLAIN, x0, x1, x2, A)  \
   "s_cmp_lt_i32 %[nc], 1\n\t"                                              \
   "s_cbranch_scc1 .Lfbr_end_%=\n\t"                                        \
   "s_sub_i32 %[nc], %[nc], 1\n\t"                                          \
@@ -132,20 +136,27 @@ static_assert(2 * FB_PIPE_REGS_VGPR_PAIRS == kPipeRegsFirst && kPipeRegsFirst + 
   "s_branch .Lfbr_ci" J "_%=\n"                                            \
   ".Lfbr_cp" J "_%=:\n\t"                                                  \
   "s_cmp_lt_i32 %[pc], 1\n\t"                                              \
-  "s_cbranch_scc1 .Lfbr_cr" J "_%=\n\t"                                    \
+  "s_cbranch_scc1 .Lfbr_" BL J "_%=\n\t"                                   \
   "s_sub_i32 %[pc], %[pc], 1\n\t"                                          \
+  PP                                                                       \
   FBO_FIRST_PLAIN(A)                                                       \
   FBO_WAITVM("p" J)                                                        \
   FBO_COMPUTE_PLAIN(x0, x1, x2, A)                                         \
   "s_branch .Lfbr_ci" J "_%=\n"                                            \
+  BACK(J)                                                                  \
   ".Lfbr_cr" J "_%=:\n\t"                                                  \
   FBO_WAITVM("r" J)                                                        \
   FBR_COMPUTE_REG(J, x0, x1, x2)                                           \
   ".Lfbr_ci" J "_%=:\n\t"                                                  \
   FBR_ISSUE(J, ISSUE_MIR, ISSUE_PLAIN, x0, x1, x2, A)
 #define FBR_ISSUE_(J, ISSUE_MIR, ISSUE_PLAIN, SET) FBR_ISSUE(J, ISSUE_MIR, ISSUE_PLAIN, SET)
-#define FBR_SLOT_(J, ISSUE_MIR, ISSUE_PLAIN, SET) FBR_SLOT(J, ISSUE_MIR, ISSUE_PLAIN, SET)
-#define FBR_BODY(ISSUE_MIR, ISSUE_PLAIN)                                                                        \
+#define FBR_SLOT_(J, PP, BL, BACK, ISSUE_MIR, ISSUE_PLAIN, SET) FBR_SLOTP(J, PP, BL, BACK, ISSUE_MIR, ISSUE_PLAIN, SET)
+// Priority by progress (round 10): the run is entered at priority 2 (register layers in front, mirror layers), steps to 1 at the head of the plain
+// layers' path and to 0 in front of the register layers behind the window -- the same scalar instruction again for every layer of the kind, the
+// run being one rotating loop (FBO_PRIO_PLAIN).  A kind without layers is stepped over with its path.
+#define FBR_BODY(ISSUE_MIR, ISSUE_PLAIN) FBR_BODYP(ISSUE_MIR, ISSUE_PLAIN, "", "cr", FBR_BACK_NONE)
+#define FBR_BODY_PRIO(ISSUE_MIR, ISSUE_PLAIN) FBR_BODYP(ISSUE_MIR, ISSUE_PLAIN, FBO_PRIO_PLAIN, "cb", FBR_BACK_PRIO)
+#define FBR_BODYP(ISSUE_MIR, ISSUE_PLAIN, PP, BL, BACK)                                                         \
   /* scalar operands fresh from v_readfirstlane, read by vector memory instructions: 5 wait states (see FBP_BODYG) */ \
   "s_nop 4\n\t"                                                                                                 \
   "s_mov_b32 %[fl], 0\n\t"                                                                                      \
@@ -157,10 +168,10 @@ static_assert(2 * FB_PIPE_REGS_VGPR_PAIRS == kPipeRegsFirst && kPipeRegsFirst + 
   FBR_ISSUE_("c", ISSUE_MIR, ISSUE_PLAIN, FBO_SET2)                                                             \
   FBR_ISSUE_("d", ISSUE_MIR, ISSUE_PLAIN, FBO_SET3)                                                             \
   ".Lfbr_loop_%=:\n\t"                                                                                          \
-  FBR_SLOT_("0", ISSUE_MIR, ISSUE_PLAIN, FBO_SET0)                                                              \
-  FBR_SLOT_("1", ISSUE_MIR, ISSUE_PLAIN, FBO_SET1)                                                              \
-  FBR_SLOT_("2", ISSUE_MIR, ISSUE_PLAIN, FBO_SET2)                                                              \
-  FBR_SLOT_("3", ISSUE_MIR, ISSUE_PLAIN, FBO_SET3)                                                              \
+  FBR_SLOT_("0", PP, BL, BACK, ISSUE_MIR, ISSUE_PLAIN, FBO_SET0)                                                \
+  FBR_SLOT_("1", PP, BL, BACK, ISSUE_MIR, ISSUE_PLAIN, FBO_SET1)                                                \
+  FBR_SLOT_("2", PP, BL, BACK, ISSUE_MIR, ISSUE_PLAIN, FBO_SET2)                                                \
+  FBR_SLOT_("3", PP, BL, BACK, ISSUE_MIR, ISSUE_PLAIN, FBO_SET3)                                                \
   "s_branch .Lfbr_loop_%=\n"                                                                                    \
   ".Lfbr_end_%=:\n\t"
 // clang-format on
@@ -224,7 +235,8 @@ __device__ __forceinline__ void pipe_stream_slots_low(int n, unsigned int voff, 
 // The on-chip run with register layers: nf register layers, m mirror layers, kl plain layers, nb register layers (all wave-uniform, any may be 0;
 // nf + nb <= 3), accumulated into y0, y1, y2 in that order.  The register layers are numbered in that order, as pipe_regs_fill filled them.
 // The rest as pipe_onchip_slots.
-template <bool C16>
+// PRIO: with the priority steps of FBR_BODY_PRIO (the caller enters at priority 2 and sets 0 behind the run whatever it held).
+template <bool C16, bool PRIO = false>
 __device__ __forceinline__ void pipe_onchip_slots_regs(int nf, int m, int kl, int nb, const void* lmt, const void* lmt2, const void* lres, const void* lcd,
                                                        const void* lmat, const double* pl0, const double* pl1, const double* pl2, int row, double& y0, double& y1,
                                                        double& y2) {
@@ -235,6 +247,13 @@ __device__ __forceinline__ void pipe_onchip_slots_regs(int nf, int m, int kl, in
   unsigned int almt = lds_byte_address(lmt), ares = lds_byte_address(lres);
   if constexpr (C16) {
     unsigned int acd = lds_byte_address(lcd);
+    if constexpr (PRIO)
+      asm volatile(FBR_BODY_PRIO(FBO_ISSUE_MIR16, FBO_ISSUE_PLAIN16)
+                   : [y0] "+v"(y0), [y1] "+v"(y1), [y2] "+v"(y2), [lmt] "+v"(almt), [lres] "+v"(ares), [lcd] "+v"(acd), [fi] "+s"(fi), [mi] "+s"(mi), [pi] "+s"(pi),
+                     [ni] "+s"(ni), [fc] "+s"(fc), [mc] "+s"(mc), [pc] "+s"(pc), [nc] "+s"(nc), [fl] "=&s"(fl), [qc] "=&s"(qc), [qi] "=&s"(qi)
+                   : [lmat] "s"(almat), [spl0] "s"(pl0), [spl1] "s"(pl1), [spl2] "s"(pl2), [row] "v"(row)
+                   : FBP_CLOBBERS);
+    else
     asm volatile(FBR_BODY(FBO_ISSUE_MIR16, FBO_ISSUE_PLAIN16)
                  : [y0] "+v"(y0), [y1] "+v"(y1), [y2] "+v"(y2), [lmt] "+v"(almt), [lres] "+v"(ares), [lcd] "+v"(acd), [fi] "+s"(fi), [mi] "+s"(mi), [pi] "+s"(pi),
                    [ni] "+s"(ni), [fc] "+s"(fc), [mc] "+s"(mc), [pc] "+s"(pc), [nc] "+s"(nc), [fl] "=&s"(fl), [qc] "=&s"(qc), [qi] "=&s"(qi)
@@ -242,6 +261,13 @@ __device__ __forceinline__ void pipe_onchip_slots_regs(int nf, int m, int kl, in
                  : FBP_CLOBBERS);
   } else {
     unsigned int almt2 = lds_byte_address(lmt2);
+    if constexpr (PRIO)
+      asm volatile(FBR_BODY_PRIO(FBO_ISSUE_MIR32, FBO_ISSUE_PLAIN32)
+                   : [y0] "+v"(y0), [y1] "+v"(y1), [y2] "+v"(y2), [lmt] "+v"(almt), [lmt2] "+v"(almt2), [lres] "+v"(ares), [fi] "+s"(fi), [mi] "+s"(mi), [pi] "+s"(pi),
+                     [ni] "+s"(ni), [fc] "+s"(fc), [mc] "+s"(mc), [pc] "+s"(pc), [nc] "+s"(nc), [fl] "=&s"(fl), [qc] "=&s"(qc), [qi] "=&s"(qi)
+                   : [lmat] "s"(almat), [spl0] "s"(pl0), [spl1] "s"(pl1), [spl2] "s"(pl2)
+                   : FBP_CLOBBERS);
+    else
     asm volatile(FBR_BODY(FBO_ISSUE_MIR32, FBO_ISSUE_PLAIN32)
                  : [y0] "+v"(y0), [y1] "+v"(y1), [y2] "+v"(y2), [lmt] "+v"(almt), [lmt2] "+v"(almt2), [lres] "+v"(ares), [fi] "+s"(fi), [mi] "+s"(mi), [pi] "+s"(pi),
                    [ni] "+s"(ni), [fc] "+s"(fc), [mc] "+s"(mc), [pc] "+s"(pc), [nc] "+s"(nc), [fl] "=&s"(fl), [qc] "=&s"(qc), [qi] "=&s"(qi)

@@ -801,6 +801,11 @@ class FemIntegrator:
             _l.check(total)
         return r.value, total
 
+    def persist_prio(self):
+        """The wavefront-priority form of this handle's persistent launches (FEMBRAIN_PIPE_PRIO: 1 progress, 2 static, 3 progress + service
+        wavefront), 0 where the kernel has none -- fb_fem_persist_prio"""
+        return int(self._L.fb_fem_persist_prio(self.h))
+
     def pcg_path(self):
         """What ran: dict(path = FB_PCG_PATH_* of the last solve, kernel = the persistent instantiation this handle launches or '',
         launches, fallbacks, max_producers)"""

@@ -849,6 +849,10 @@ int fb_fem_persist_mirror(fb_fem_t h, int* mirror_layers, int* pool_entries, int
  * every launch; the iterates do not change by a bit).  slots_per_slice (may be NULL) = what this handle's launches hold per slice at most: 3,
  * or what FEMBRAIN_PIPE_REGS=0|2|3 said when the plan was built; a slice holds that many or as many as it streams.  Returns the register slots over all slices (0 / 0: another instantiation, no window, FEMBRAIN_PIPE_REGS=0), < 0: an error. */
 int fb_fem_persist_regs(fb_fem_t h, int* slots_per_slice);
+/* Wavefront priority through the product of the persistent kernels that have a priority form (the register-slot kernels; the development build
+ * with the phase clocks at (12, 6)): the form this handle's launches use -- 1 by progress, 2 static, 3 by progress with the service wavefront's
+ * collection raised (FEMBRAIN_PIPE_PRIO when the plan was built; the iterates do not change by a bit) -- and 0 where the kernel has none. */
+int fb_fem_persist_prio(fb_fem_t h);
 /* average device seconds of ONE persistent launch that starts a solve of the current system and is cut after n_iters
  * iterations (tolerance out of reach), HIP events on the handle's stream around the launch; the difference of two lengths
  * prices an iteration without the launch's fixed cost */
