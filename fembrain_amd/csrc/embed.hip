@@ -35,23 +35,7 @@ namespace {
 
 constexpr int kWideTile = 64;  // overflow elements per LDS tile
 
-// determinant of the rows a, b, c (mat3d.h det: the six products in its order)
-__device__ __forceinline__ double det3(const double* a, const double* b, const double* c) {
-  return (-a[2] * b[1] * c[0] + a[1] * b[2] * c[0] + a[2] * b[0] * c[1] - a[0] * b[2] * c[1] - a[1] * b[0] * c[2] + a[0] * b[1] * c[2]);
-}
-// determinant of [a 1; b 1; c 1; d 1] (TetMesh::getTetDeterminant)
-__device__ __forceinline__ double tet_det(const double* a, const double* b, const double* c, const double* d) {
-  return (-det3(b, c, d) + det3(a, c, d) - det3(a, b, d) + det3(a, b, c));
-}
-// the four weights of p in the element v; true when all are >= 0 (a flat element has none: NaN or infinite weights compare false)
-__device__ __forceinline__ bool bary(const double (*v)[3], const double* p, double* w) {
-  const double d0 = tet_det(v[0], v[1], v[2], v[3]);
-  w[0] = tet_det(p, v[1], v[2], v[3]) / d0;
-  w[1] = tet_det(v[0], p, v[2], v[3]) / d0;
-  w[2] = tet_det(v[0], v[1], p, v[3]) / d0;
-  w[3] = tet_det(v[0], v[1], v[2], p) / d0;
-  return w[0] >= 0 && w[1] >= 0 && w[2] >= 0 && w[3] >= 0;
-}
+// (det3, tet_det and bary, the weights of a point in an element: embed_grid.hip.h)
 
 // ---- the mesh box (fp64; the partials are folded by k_box_final<double>) ----
 __global__ __launch_bounds__(kB) void k_node_box(int n_nodes, const double* __restrict__ x0, double* __restrict__ part) {

@@ -89,14 +89,7 @@ __global__ __launch_bounds__(kB) void k_centre_store(int n_tets, const int* __re
   centre[3 * (size_t)j] = c[0]; centre[3 * (size_t)j + 1] = c[1]; centre[3 * (size_t)j + 2] = c[2];
 }
 
-constexpr double kRingGrow = 1.0 + 0x1p-40;  // what a distance, its square and a root are widened by: far above their roundings
-
-// the gap between x and the slab of cell j on axis k, widened by 2^-10 of a cell and open outward at both ends of the axis
-__device__ __forceinline__ double slab_gap(const GridDev& g, int k, int j, double h, double x) {
-  const double s = h * 0x1p-10;
-  const double below = j > 0 ? (g.lo[k] + j * h - s) - x : 0.0, above = j < g.dim[k] - 1 ? x - (g.lo[k] + (j + 1) * h + s) : 0.0;
-  return fmax(0.0, fmax(below, above));
-}
+// (kRingGrow and slab_gap: embed_grid.hip.h)
 
 // One wavefront per point without a containing element (ext_ids[t]).  Everything that decides a branch is the same in every lane: the
 // ranges come from cell_start, the best pair is folded over the wavefront whenever a lane has improved it.

@@ -1,5 +1,6 @@
-// What the two units of the embedding search (embed.hip, embed_closest.hip) both evaluate, each written once: the search grid as a kernel
-// sees it with its cell function, an element's vertices, its centre and the distance of a point from a centre.  The units are built with
+// What the units that search through a grid (embed.hip, embed_closest.hip, body_contact.hip) all evaluate, each written once: the search grid
+// as a kernel sees it with its cell function, an element's vertices, its centre, the distance of a point from a centre, the weights of a point
+// in an element, and the slab of a cell as the ring searches widen it.  The units are built with
 // -ffp-contract=off, so one function is one sequence of roundings wherever it is called: the closest centre of the full scan and of the
 // search through the centre grid are compared on the same bits.
 #pragma once
@@ -54,6 +55,35 @@ __device__ __forceinline__ void tet_centre(const double (*v)[3], double* c) {
 __device__ __forceinline__ double centre_distance(const double* p, const double* c) {
   const double dx = p[0] - c[0], dy = p[1] - c[1], dz = p[2] - c[2];
   return sqrt(dx * dx + dy * dy + dz * dz);
+}
+
+
+// determinant of the rows a, b, c (mat3d.h det: the six products in its order)
+__device__ __forceinline__ double det3(const double* a, const double* b, const double* c) {
+  return (-a[2] * b[1] * c[0] + a[1] * b[2] * c[0] + a[2] * b[0] * c[1] - a[0] * b[2] * c[1] - a[1] * b[0] * c[2] + a[0] * b[1] * c[2]);
+}
+// determinant of [a 1; b 1; c 1; d 1] (TetMesh::getTetDeterminant)
+__device__ __forceinline__ double tet_det(const double* a, const double* b, const double* c, const double* d) {
+  return (-det3(b, c, d) + det3(a, c, d) - det3(a, b, d) + det3(a, b, c));
+}
+// the four weights of p in the element v; true when all are >= 0 (a flat element has none: NaN or infinite weights compare false)
+__device__ __forceinline__ bool bary(const double (*v)[3], const double* p, double* w) {
+  const double d0 = tet_det(v[0], v[1], v[2], v[3]);
+  w[0] = tet_det(p, v[1], v[2], v[3]) / d0;
+  w[1] = tet_det(v[0], p, v[2], v[3]) / d0;
+  w[2] = tet_det(v[0], v[1], p, v[3]) / d0;
+  w[3] = tet_det(v[0], v[1], v[2], p) / d0;
+  return w[0] >= 0 && w[1] >= 0 && w[2] >= 0 && w[3] >= 0;
+}
+
+// ---- the search through a grid of points (embed_closest.hip, body_contact.hip) ----
+constexpr double kRingGrow = 1.0 + 0x1p-40;  // what a distance, its square and a root are widened by: far above their roundings
+
+// the gap between x and the slab of cell j on axis k, widened by 2^-10 of a cell and open outward at both ends of the axis
+__device__ __forceinline__ double slab_gap(const GridDev& g, int k, int j, double h, double x) {
+  const double s = h * 0x1p-10;
+  const double below = j > 0 ? (g.lo[k] + j * h - s) - x : 0.0, above = j < g.dim[k] - 1 ? x - (g.lo[k] + (j + 1) * h + s) : 0.0;
+  return fmax(0.0, fmax(below, above));
 }
 
 }  // namespace fb

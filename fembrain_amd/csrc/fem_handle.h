@@ -1,7 +1,7 @@
 // The FEM handle (fb_fem_t of include/fembrain_hip.h) and what the units that work on it share: fem.hip (assembly, the two-launch
 // solver, the steps and the rest of the C ABI), fem_build.hip (life cycle: plan build, creation, re-sync, cut), fem_persist.hip (the
 // persistent solver's host side), haptic.hip (the probe's entry points), stress.hip (element stress and strain), parts.hip (disjoint parts),
-// detach.hip (a part into a handle of its own), embed.hip (point sets bound to the elements), embed_touch.hip (forces, picks and stress on them) and contact.hip (the probe's box contact).
+// detach.hip (a part into a handle of its own), embed.hip (point sets bound to the elements), embed_touch.hip (forces, picks and stress on them), contact.hip (the probe's box contact) and body_contact.hip (contact between two handles).
 // Internal: not installed, included by these units only.
 #pragma once
 #include "comm.h"
@@ -19,6 +19,7 @@
 #include "detach.h"
 #include "embed.h"
 #include "contact.h"
+#include "body_contact.h"
 
 namespace fb {
 
@@ -194,6 +195,7 @@ struct fb_fem_s {
   DetachWork detach;      // fb_fem_detach_part: the constrained DOFs of the part being detached (detach.h); empty until somebody asks
   EmbedWork embed;        // fb_fem_embed: point sets bound to the elements, and their search grid (embed.h); empty until somebody asks
   ContactWork contact;    // fb_fem_contact_move / apply: the probe's touched set, force list and spread records (contact.h); empty until somebody asks
+  BodyContactWork bodyc;  // fb_fem_body_contact: contact with another handle, kept in the handle the call names first (body_contact.h); empty until somebody asks
   HapticWork hap;         // fb_fem_add_haptic_forces / pick / volume: level array and scratch (haptic.h); empty until somebody asks
   std::vector<int> fixed_caller;  // the constrained DOFs in the caller's numbering (unsharded): what fb_fem_cut keeps
   DevBuf<int4> tets_next, tets_caller;   // (the element list being built; swapped with `tets`)

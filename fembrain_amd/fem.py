@@ -673,6 +673,49 @@ class FemIntegrator:
         _l.check(self._L.fb_fem_contact_apply(self.h, int(neighborhood_size), C.byref(c)))
         return dict(n_sources=c.n_sources, n_pushing=c.n_pushing, path=c.path, n_targets=c.n_targets, n_records=c.n_records)
 
+    # -- contact between two bodies on the device (fb_fem_body_contact; unsharded handles on one device) --
+    _BODY_DIRECTIONS = {"both": _l.FB_BODY_A_INTO_B | _l.FB_BODY_B_INTO_A, "a_into_b": _l.FB_BODY_A_INTO_B, "b_into_a": _l.FB_BODY_B_INTO_A}
+
+    def _body_params(self, stiffness, depth_cap, directions):
+        p = _l.BodyContactParams()
+        p.stiffness, p.depth_cap = float(stiffness), float(depth_cap)
+        p.directions = self._BODY_DIRECTIONS[directions] if isinstance(directions, str) else int(directions)
+        return p
+
+    def body_contact(self, other, stiffness, depth_cap=0.0, directions="both"):
+        """Penalty contact between this body (a) and ``other`` (b) at their current states, ADDED into both external force vectors (set
+        gravity or zero first): every surface vertex of one body that lies inside an element of the other is pushed to the closest point
+        of the other's boundary with F = stiffness * min(depth, depth_cap) * n (no cap where depth_cap is 0), and the face that holds that
+        point is pushed back by -F, spread by its weights.  directions: "both", "a_into_b" (this body's vertices in ``other``), "b_into_a",
+        or the FB_BODY_* bits.  Returns the dict of the fb_fem_body_contact_info fields; counts are (a into b, b into a)."""
+        p, info = self._body_params(stiffness, depth_cap, directions), _l.BodyContactInfo()
+        _l.check(self._L.fb_fem_body_contact(self.h, other.h, C.byref(p), C.byref(info)))
+        out = dict(n_candidates=tuple(info.n_candidates), n_contacts=tuple(info.n_contacts), n_degenerate=tuple(info.n_degenerate), path=int(info.path),
+                   n_tet_grid_builds=int(info.n_tet_grid_builds), n_face_grid_builds=int(info.n_face_grid_builds), faces_tested=int(info.faces_tested),
+                   max_depth=float(info.max_depth), force_on_a=np.array(info.force_on_a[:]), force_on_b=np.array(info.force_on_b[:]))
+        self._body_contacts = out["n_contacts"]
+        return out
+
+    def read_body_contact(self, direction):
+        """The contacts of one direction ("a_into_b" / "b_into_a" or the FB_BODY_* bit) of the last ``body_contact`` of this handle: dict of
+        node (the vertex, in its body's ids), element and face (of the other body: ``read_mesh`` / ``surface`` order), closest (k, 3), bary
+        (k, 3) the weights of the closest point on the face's corners, and depth (k,) before the cap; ascending node."""
+        d = self._BODY_DIRECTIONS[direction] if isinstance(direction, str) else int(direction)
+        if d not in (_l.FB_BODY_A_INTO_B, _l.FB_BODY_B_INTO_A):
+            raise ValueError("one direction, not %r" % (direction,))
+        k = getattr(self, "_body_contacts", (0, 0))[0 if d == _l.FB_BODY_A_INTO_B else 1]
+        node, elem, face = np.zeros(k, np.int32), np.zeros(k, np.int32), np.zeros(k, np.int32)
+        closest, bary, depth = np.zeros((k, 3)), np.zeros((k, 3)), np.zeros(k)
+        _l.check(self._L.fb_fem_read_body_contact(self.h, d, _l.iptr(node), _l.iptr(elem), _l.iptr(face), _l.dptr(closest), _l.dptr(bary), _l.dptr(depth)))
+        return dict(node=node, element=elem, face=face, closest=closest, bary=bary, depth=depth)
+
+    def time_body_contact(self, other, stiffness, depth_cap=0.0, directions="both", reps=5):
+        """Seconds of the five stages of ``body_contact`` (boxes, element grid and containment, face grid, closest faces, scatter), means of
+        ``reps`` runs with their host waits (fb_fem_time_body_contact).  Adds no force."""
+        p, sec = self._body_params(stiffness, depth_cap, directions), np.zeros(5)
+        _l.check(self._L.fb_fem_time_body_contact(self.h, other.h, C.byref(p), int(reps), _l.dptr(sec)))
+        return sec
+
     # -- element stress and strain on the device (fb_fem_stress / read_stress / surface_stress; unsharded handles) --
     def stress(self, world=False, tensors=False):
         """Stress and strain of every element at the current state, kept on the device (fb_fem_stress): the bracket of the corotational
@@ -982,6 +1025,17 @@ class Deformable:
         self._contact_list = False   # the list set last is the device session's (probe_move on the device route), not haptic_indices
         self.on_deform = None  # FOnApplyDeformations(dof, q), Deformable.h:46
         self._embed_tris = {}  # triangles of the embeddings made through embed()
+        self.collision_body, self.collision_stiffness = None, 0.0  # set_collision_body
+
+    def collide_with(self, other, stiffness, depth_cap=0.0):
+        """Penalty contact with another ``Deformable`` on the same device at the current states of both, ADDED to the external forces of
+        both (``FemIntegrator.body_contact``).  ``timestep`` sets the forces anew before it steps: its callers use ``set_collision_body``."""
+        return self.integrator.body_contact(other.integrator, stiffness, depth_cap)
+
+    def set_collision_body(self, other, stiffness=0.0):
+        """Opt-in: every ``timestep`` adds the contact forces with ``other`` behind gravity and the probe, just before it steps (None: off).
+        The call adds to both bodies and ``other`` sets its forces anew in its own ``timestep``, so two bodies that both step set each other."""
+        self.collision_body, self.collision_stiffness = other, float(stiffness)
 
     def set_deform_callback(self, fn):
         self.on_deform = fn
@@ -1060,6 +1114,8 @@ class Deformable:
             it.set_uniform_force(1, self.GRAVITY_FORCE)
         else:
             it.set_external_forces_to_zero()
+        if self.collision_body is not None:
+            self.collide_with(self.collision_body, self.collision_stiffness)
         iters = it.do_timestep()
         if self.floor_y is not None:
             self.ct_collided = it.floor_collision(self.floor_y, 0.4)

@@ -27,6 +27,8 @@ FB_CUT_UNHANDLED_IDS = 64  # unhandled element ids fb_fem_read_cut returns at mo
 FB_HAPTIC_MAX_SOURCES = 256  # sources fb_fem_add_haptic_forces takes in one call
 FB_CONTACT_MISS, FB_CONTACT_EMPTY, FB_CONTACT_SET = 0, 1, 2  # fb_fem_contact_info.status
 FB_CONTACT_SPREAD_RECORDS, FB_CONTACT_SPREAD_LEVELS = 0, 1  # fb_fem_contact_spread_info.path
+FB_BODY_A_INTO_B, FB_BODY_B_INTO_A = 1, 2  # fb_fem_body_contact_params.directions
+FB_BODY_CONTACT_NONE, FB_BODY_CONTACT_SCAN, FB_BODY_CONTACT_RING = 0, 1, 2  # fb_fem_body_contact_info.path
 FB_MAX_MATERIALS = 256  # entries of a handle's material table (fb_fem_set_materials)
 FB_STRESS_WORLD, FB_STRESS_TENSORS = 1, 2  # fb_fem_stress flags
 FB_EMBED_CLOSEST_NONE, FB_EMBED_CLOSEST_SCAN, FB_EMBED_CLOSEST_RING = 0, 1, 2  # fb_fem_embed_search_info.path
@@ -107,6 +109,16 @@ class ContactInfo(C.Structure):
 
 class ContactSpreadInfo(C.Structure):
     _fields_ = [("n_sources", C.c_int), ("n_pushing", C.c_int), ("path", C.c_int), ("n_targets", C.c_int), ("n_records", C.c_longlong)]
+
+
+class BodyContactParams(C.Structure):
+    _fields_ = [("stiffness", C.c_double), ("depth_cap", C.c_double), ("directions", C.c_int), ("reserved", C.c_int)]
+
+
+class BodyContactInfo(C.Structure):
+    _fields_ = [("n_candidates", C.c_int * 2), ("n_contacts", C.c_int * 2), ("n_degenerate", C.c_int * 2), ("path", C.c_int),
+                ("n_tet_grid_builds", C.c_int), ("n_face_grid_builds", C.c_int), ("faces_tested", C.c_longlong), ("max_depth", C.c_double),
+                ("force_on_a", C.c_double * 3), ("force_on_b", C.c_double * 3)]
 
 
 class PolyCounts(C.Structure):
@@ -242,6 +254,9 @@ def lib():
         "fb_fem_contact_reset": (C.c_int, [vp, C.c_int]),
         "fb_fem_read_contact": (C.c_int, [vp, _ip, _dp, _dp]),
         "fb_fem_contact_apply": (C.c_int, [vp, C.c_int, C.POINTER(ContactSpreadInfo)]),
+        "fb_fem_body_contact": (C.c_int, [vp, vp, C.POINTER(BodyContactParams), C.POINTER(BodyContactInfo)]),
+        "fb_fem_read_body_contact": (C.c_int, [vp, C.c_int, _ip, _ip, _ip, _dp, _dp, _dp]),
+        "fb_fem_time_body_contact": (C.c_int, [vp, vp, C.POINTER(BodyContactParams), C.c_int, _dp]),
         "fb_fem_stress": (C.c_int, [vp, C.c_int, C.POINTER(StressInfo)]),
         "fb_fem_read_stress": (C.c_int, [vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]),
         "fb_fem_surface_stress": (C.c_int, [vp, _fp]),

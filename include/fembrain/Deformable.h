@@ -199,6 +199,21 @@ class HipIntegrator {
     check(fb_fem_contact_apply(h_, neighbourhoodSize, &info));
     return info;
   }
+  // Contact with another body on the same device (fembrain_hip.h, "Contact between two bodies"): the surface vertices of each that lie
+  // inside the other are pushed to the closest point of its boundary, the face there is pushed back; ADDED to both external force vectors.
+  fb_fem_body_contact_info BodyContact(HipIntegrator& other, double stiffness, double depthCap = 0.0, int directions = FB_BODY_A_INTO_B | FB_BODY_B_INTO_A) {
+    const fb_fem_body_contact_params p = {stiffness, depthCap, directions, 0};
+    fb_fem_body_contact_info info;
+    check(fb_fem_body_contact(h_, other.h_, &p, &info));
+    return info;
+  }
+  // the contacts of one direction of the last BodyContact of this integrator, info.n_contacts[direction == FB_BODY_A_INTO_B ? 0 : 1] entries
+  void ReadBodyContact(int direction, int n, std::vector<int>& node, std::vector<int>& element, std::vector<int>& face, std::vector<double>& closestXyz,
+                       std::vector<double>& bary3, std::vector<double>& depth) {
+    node.assign((size_t)n, 0); element.assign((size_t)n, 0); face.assign((size_t)n, 0);
+    closestXyz.assign(3 * (size_t)n, 0.0); bary3.assign(3 * (size_t)n, 0.0); depth.assign((size_t)n, 0.0);
+    check(fb_fem_read_body_contact(h_, direction, node.data(), element.data(), face.data(), closestXyz.data(), bary3.data(), depth.data()));
+  }
   // Element stress and strain on the device (fembrain_hip.h): von Mises stress, energy density and J of every element at the current
   // state stay on the device, `out` brings the summary.  flags: FB_STRESS_WORLD | FB_STRESS_TENSORS.
   void ComputeStress(int flags, fb_fem_stress_info* out) { check(fb_fem_stress(h_, flags, out)); }
@@ -411,6 +426,7 @@ class Deformable {
     } else {
       m_lpIntegrator->SetExternalForcesToZero();
     }
+    if (m_lpCollisionBody != nullptr) collideWith(*m_lpCollisionBody, m_collisionStiffness);  // (behind gravity and the probe)
     m_lpIntegrator->DoTimestep();
     if (m_hasFloor) m_ctCollided = (U32)m_lpIntegrator->FloorCollision(m_floorY, 0.4);
     if (m_fOnDeform) {
@@ -698,6 +714,19 @@ class Deformable {
   void setGravity(bool g) { m_bApplyGravity = g; }
   bool getGravity() const { return m_bApplyGravity; }
   void setFloor(double y) { m_hasFloor = true; m_floorY = y; }  // stands in for setCollisionObject(SGNode*): the floor plane height
+  // What setCollisionObject / collisionDetect do through CollisionDetection (Bullet) in the reference, for another Deformable on the same
+  // device: penalty contact at the current states of both, ADDED to the external forces of both on the device (fb_fem_body_contact).  The
+  // forces act in the next DoTimestep of each integrator; timestep() itself sets the external forces anew before it steps, so a caller of
+  // timestep() uses setCollisionBody instead.
+  fb_fem_body_contact_info collideWith(Deformable& other, double stiffness, double depthCap = 0) {
+    return m_lpIntegrator->BodyContact(*other.m_lpIntegrator, stiffness, depthCap);
+  }
+  // Opt-in: every timestep() of this body adds the contact forces with `other` behind gravity and the probe, just before it steps
+  // (nullptr: off again).  The call adds to BOTH bodies, and `other` sets its forces anew in its own timestep(): two bodies that both
+  // step set each other, and each then steps with exactly one set of contact forces.  Never set: timestep() does what it always did.
+  // Not owned; the caller keeps `other` alive or clears the pointer.
+  void setCollisionBody(Deformable* other, double stiffness) { m_lpCollisionBody = other; m_collisionStiffness = stiffness; }
+  Deformable* getCollisionBody() const { return m_lpCollisionBody; }
   // Deformable::collisionDetect (Deformable.cpp:541-600) against the floor plane set with setFloor: vertices at or below it are
   // put back on it and their velocity reflected (the device pass timestep() also runs); true if any vertex was touched
   bool collisionDetect() {
@@ -846,6 +875,7 @@ class Deformable {
     m_hapticForceNeighorhoodSize = 5;  // DEFAULT_FORCE_NEIGHBORHOOD_SIZE, Deformable.h:41
     m_bApplyGravity = true;  // left uninitialised by the reference's init(); true is what its .sim files set
     m_boxCapacity = 64; m_lpIntegrator = nullptr; m_lpSurface = nullptr; m_hasFloor = false; m_floorY = 0.0; m_dof = 0; m_restVolume = -1.0;
+    m_lpCollisionBody = nullptr; m_collisionStiffness = 0.0;
   }
   std::vector<double> m_rest;
   std::vector<int> m_elements;
@@ -854,13 +884,14 @@ class Deformable {
   std::vector<double> m_q, m_qVel, m_arrExtForces, m_hapticStage, m_boxStage;
   HipIntegrator* m_lpIntegrator;
   SurfaceMesh* m_lpSurface;
+  Deformable* m_lpCollisionBody;  // setCollisionBody: not owned
   std::vector<EmbeddedMesh*> m_vEmbedded;
   FOnApplyDeformations m_fOnDeform;
   U32 m_dof, m_ctCollided, m_ctTimeStep;
   int m_idxPulledVertex, m_device, m_hapticForceNeighorhoodSize, m_boxCapacity;
   bool m_bHapticInProgress, m_bApplyGravity, m_hasFloor;
   bool m_bContactList;  // the list set last is the device session's (probeMove), not m_vHapticIndices
-  double m_dampingMassCoeff, m_dampingStiffnessCoeff, m_timeStep, m_floorY, m_restVolume;
+  double m_dampingMassCoeff, m_dampingStiffnessCoeff, m_timeStep, m_floorY, m_restVolume, m_collisionStiffness;
   std::string m_strModelName;
 };
 

@@ -704,6 +704,56 @@ int fb_fem_read_contact(fb_fem_t h, int* ids, double* first_xyz, double* forces3
 typedef struct fb_fem_contact_spread_info { int n_sources, n_pushing, path, n_targets; long long n_records; } fb_fem_contact_spread_info;
 int fb_fem_contact_apply(fb_fem_t h, int neighbourhood_size, fb_fem_contact_spread_info* out);
 
+/* ---- Contact between two bodies, on the device ----
+ * What Deformable::setCollisionObject / collisionDetect ask of CollisionDetection (Bullet) in the reference: two handles in one process
+ * -- a parent and the piece fb_fem_detach_part made of it, or any two -- push each other apart.  Both unsharded and on the same device
+ * (FB_EINVAL otherwise); node, element and face ids are the CALLER's (fb_fem_read_mesh, fb_fem_read_surface), also on renumbered handles.
+ * The call uses the current states of both and ADDS penalty forces into both external force vectors, as fb_fem_add_haptic_forces and
+ * fb_fem_contact_apply do (set gravity or zero first).  It is ordered by events after what both handles have queued, and what either
+ * queues afterwards runs after it.  A handle that never calls it allocates and launches nothing extra.
+ *
+ * Direction "a into b" (FB_BODY_A_INTO_B; FB_BODY_B_INTO_A is the same with the roles swapped), every operation fp64, no contraction:
+ *  1. Points: the surface vertices of a (fb_fem_surface's vertex_ids, ascending) at p = x0 + q.
+ *  2. Candidates: the points in the closed box of b's current node positions.  Where the box of a's surface vertices and the box of b's
+ *     nodes do not meet the direction ends: no grid is built, no force vector written.
+ *  3. Containment: p is in contact if an element of b at b's current positions has four weights >= 0 (fb_fem_embed's weights D_i / D_0,
+ *     no threshold); the lowest-numbered such element is recorded.
+ *  4. Closest boundary point: over ALL boundary faces of b (fb_fem_read_surface's, at current positions) the closest point c of a face to
+ *     p by the region-based closest point on a triangle (Ericson, Real-Time Collision Detection 5.1.5: vertex A, vertex B, edge AB,
+ *     vertex C, edge AC, edge BC, interior, in that order, dot(u, v) = (u0 v0 + u1 v1) + u2 v2), d = sqrt(dx dx + dy dy + dz dz).  The
+ *     least d wins, of bitwise equal d the lowest face.
+ *  5. Force: d == 0 is counted as degenerate and pushes nothing.  Else n = (c - p) / d, depth = depth_cap > 0 ? min(d, depth_cap) : d,
+ *     F = (stiffness * depth) * n.  +F goes to the node of p in a, (-F) * b_k to corner k of the face in b, with b1, b2 from the
+ *     closest-point routine and b0 = (1 - b1) - b2.
+ *  6. A node receives its contributions onto the value the force vector had, a into b before b into a, inside a direction by ascending
+ *     surface vertex, inside a contact corners 0, 1, 2.  No floating-point atomics: two calls from one state give the same bits.
+ *
+ * path says how the closest faces of the last direction that had contacts were found: FB_BODY_CONTACT_RING -- through a grid of the
+ * face centroids, a wavefront per contact, only the cells that can hold a closer face -- or FB_BODY_CONTACT_SCAN, every face for every
+ * contact; the same bits.  FEMBRAIN_BODY_CONTACT=scan|ring chooses (read at every call; default: ring wherever its coverage proof holds,
+ * see body_contact.hip), FEMBRAIN_BODY_CONTACT_BUDGET the faces one point may test on the ring path before it goes to the scan (default:
+ * the face count).  n_tet_grid_builds / n_face_grid_builds: grids built by this call; faces_tested: closest-point evaluations of the
+ * searches; max_depth: the largest depth that entered a force (after the cap); force_on_a / force_on_b: the fp64 sums of all
+ * contributions to each body, in the order of 6.  Indices [0] / [1] of the counts: a into b / b into a.
+ *
+ * fb_fem_read_body_contact(a, direction): the last call's contacts of ONE direction (n_contacts[..] entries each, any pointer may be NULL):
+ * node of the point, containing element, closest face, closest point [3], weights b0 b1 b2 [3], and depth = d before the cap.
+ * fb_fem_time_body_contact: seconds of the five stages (boxes | element grid and containment | face grid | closest faces | scatter),
+ * means of `reps` runs, host waits included; it adds no force. */
+#define FB_BODY_A_INTO_B 1
+#define FB_BODY_B_INTO_A 2
+#define FB_BODY_CONTACT_NONE 0
+#define FB_BODY_CONTACT_SCAN 1
+#define FB_BODY_CONTACT_RING 2
+typedef struct fb_fem_body_contact_params { double stiffness, depth_cap; int directions /* FB_BODY_A_INTO_B | FB_BODY_B_INTO_A */; int reserved; } fb_fem_body_contact_params;
+typedef struct fb_fem_body_contact_info {
+  int n_candidates[2], n_contacts[2], n_degenerate[2]; int path; int n_tet_grid_builds, n_face_grid_builds;
+  long long faces_tested; double max_depth; double force_on_a[3], force_on_b[3];
+} fb_fem_body_contact_info;
+int fb_fem_body_contact(fb_fem_t a, fb_fem_t b, const fb_fem_body_contact_params* p, fb_fem_body_contact_info* out);
+int fb_fem_read_body_contact(fb_fem_t a, int direction, int* node, int* element, int* face, double* closest_xyz, double* bary3, double* depth);
+int fb_fem_time_body_contact(fb_fem_t a, fb_fem_t b, const fb_fem_body_contact_params* p, int reps, double seconds[5]);
+
 /* ---- Element stress and strain, on the device ----
  * The bracket of the corotational element force f_e,i = V R [lambda tr(H) I + mu (H + H^T)] b_i, which the assembly forms every step
  * (E B (R^T x - x0) of corotationalLinearFEM.cpp:107-137, 270-286) and does not keep.  Unsharded handles only (FB_EINVAL otherwise, as
