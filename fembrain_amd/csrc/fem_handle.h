@@ -20,6 +20,7 @@
 #include "embed.h"
 #include "contact.h"
 #include "body_contact.h"
+#include "self_contact.h"
 
 namespace fb {
 
@@ -196,6 +197,7 @@ struct fb_fem_s {
   EmbedWork embed;        // fb_fem_embed: point sets bound to the elements, and their search grid (embed.h); empty until somebody asks
   ContactWork contact;    // fb_fem_contact_move / apply: the probe's touched set, force list and spread records (contact.h); empty until somebody asks
   BodyContactWork bodyc;  // fb_fem_body_contact: contact with another handle, kept in the handle the call names first (body_contact.h); empty until somebody asks
+  SelfContactWork selfc;  // fb_fem_self_contact: contact of this handle with itself (self_contact.h); empty until somebody asks
   HapticWork hap;         // fb_fem_add_haptic_forces / pick / volume: level array and scratch (haptic.h); empty until somebody asks
   std::vector<int> fixed_caller;  // the constrained DOFs in the caller's numbering (unsharded): what fb_fem_cut keeps
   DevBuf<int4> tets_next, tets_caller;   // (the element list being built; swapped with `tets`)
@@ -339,6 +341,7 @@ int embedding_current(fb_fem_s* h, int id, Embedding** out);
 
 // parts.hip
 PartsMesh parts_mesh(fb_fem_s* h);         // the handle's arrays the calls of parts.h work on
+int parts_current(fb_fem_s* h, bool force = false);  // builds the labels where they are stale (what fb_fem_parts does first); force: in any case
 
 // fem_persist.hip
 bool auto_matrix_f64(const fb_fem_s* h, int n_nodes, int n_ranks);

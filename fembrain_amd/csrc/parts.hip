@@ -615,16 +615,19 @@ PartsMesh parts_mesh(fb_fem_s* h) {
   M.caller_of = h->ren.active ? h->ren.d_old_of_new.p : nullptr;
   return M;
 }
+int parts_current(fb_fem_s* h, bool force) {
+  if (h->parts.valid && !force) return FB_OK;
+  SlackScope slack(handle_slack_now(h));
+  const char* wk = getenv("FEMBRAIN_PARTS_WIDE_KEYS");  // read at every build, like FEMBRAIN_SURFACE_WIDE_KEYS
+  return parts_build(h->stream, h->parts, parts_mesh(h), wk && atoi(wk) != 0, h->plan_ws);
+}
 }  // namespace fb
 
 namespace {
 
 int parts_ready(fb_fem_s* h, const char* who, bool force) {
   if (h->plan.n_ranks > 1) return fail(FB_EINVAL, "%s is for unsharded handles", who);
-  if (h->parts.valid && !force) return FB_OK;
-  SlackScope slack(handle_slack_now(h));
-  const char* wk = getenv("FEMBRAIN_PARTS_WIDE_KEYS");  // read at every build, like FEMBRAIN_SURFACE_WIDE_KEYS
-  return parts_build(h->stream, h->parts, parts_mesh(h), wk && atoi(wk) != 0, h->plan_ws);
+  return fb::parts_current(h, force);
 }
 
 // the plane of a swept quad (CuttableMesh.cpp:555-564) and the shift; FB_EINVAL for a quad without a normal or a number that is none

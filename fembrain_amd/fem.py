@@ -716,6 +716,46 @@ class FemIntegrator:
         _l.check(self._L.fb_fem_time_body_contact(self.h, other.h, C.byref(p), int(reps), _l.dptr(sec)))
         return sec
 
+    # -- contact of the body with itself on the device (fb_fem_self_contact; unsharded handles) --
+    _SELF_MODES = {"any": _l.FB_SELF_CONTACT_ANY, "other_parts": _l.FB_SELF_CONTACT_OTHER_PARTS}
+
+    def _self_params(self, stiffness, depth_cap, mode):
+        p = _l.SelfContactParams()
+        p.stiffness, p.depth_cap = float(stiffness), float(depth_cap)
+        p.mode = self._SELF_MODES[mode] if isinstance(mode, str) else int(mode)
+        return p
+
+    def self_contact(self, stiffness, depth_cap=0.0, mode="any"):
+        """Penalty contact of this body with itself at its current state, ADDED into the external force vector (set gravity or zero first):
+        every surface vertex that lies inside an element it may meet is pushed to the closest point of the boundary it may meet with
+        F = stiffness * min(depth, depth_cap) * n (no cap where depth_cap is 0), and the face there is pushed back by -F, spread by its
+        weights.  mode "any": a vertex may not meet the elements and faces that use its own node (a fold of one part); "other_parts": it may
+        not meet its own part (the halves of a cut; the labels of ``parts`` are built first where they are stale); or the FB_SELF_CONTACT_*
+        values.  Returns the dict of the fb_fem_self_contact_info fields."""
+        p, info = self._self_params(stiffness, depth_cap, mode), _l.SelfContactInfo()
+        _l.check(self._L.fb_fem_self_contact(self.h, C.byref(p), C.byref(info)))
+        out = {name: int(getattr(info, name)) for name in ("n_points", "n_contacts", "n_degenerate", "path", "n_point_grid_builds", "n_face_grid_builds",
+                                                            "n_parts_builds", "faces_tested")}
+        out.update(max_depth=float(info.max_depth), force_on_points=np.array(info.force_on_points[:]), force_on_faces=np.array(info.force_on_faces[:]))
+        self._self_contacts = out["n_contacts"]
+        return out
+
+    def read_self_contact(self):
+        """The contacts of the last ``self_contact``: dict of node (the vertex), element and face (``read_mesh`` / ``surface`` order), closest
+        (k, 3), bary (k, 3) the weights of the closest point on the face's corners, and depth (k,) before the cap; ascending node."""
+        k = getattr(self, "_self_contacts", 0)
+        node, elem, face = np.zeros(k, np.int32), np.zeros(k, np.int32), np.zeros(k, np.int32)
+        closest, bary, depth = np.zeros((k, 3)), np.zeros((k, 3)), np.zeros(k)
+        _l.check(self._L.fb_fem_read_self_contact(self.h, _l.iptr(node), _l.iptr(elem), _l.iptr(face), _l.dptr(closest), _l.dptr(bary), _l.dptr(depth)))
+        return dict(node=node, element=elem, face=face, closest=closest, bary=bary, depth=depth)
+
+    def time_self_contact(self, stiffness, depth_cap=0.0, mode="any", reps=5):
+        """Seconds of the five stages of ``self_contact`` (positions and box, point grid and containment, face grid, closest faces,
+        scatter), means of ``reps`` runs with their host waits (fb_fem_time_self_contact).  Adds no force."""
+        p, sec = self._self_params(stiffness, depth_cap, mode), np.zeros(5)
+        _l.check(self._L.fb_fem_time_self_contact(self.h, C.byref(p), int(reps), _l.dptr(sec)))
+        return sec
+
     # -- element stress and strain on the device (fb_fem_stress / read_stress / surface_stress; unsharded handles) --
     def stress(self, world=False, tensors=False):
         """Stress and strain of every element at the current state, kept on the device (fb_fem_stress): the bracket of the corotational
@@ -1026,6 +1066,7 @@ class Deformable:
         self.on_deform = None  # FOnApplyDeformations(dof, q), Deformable.h:46
         self._embed_tris = {}  # triangles of the embeddings made through embed()
         self.collision_body, self.collision_stiffness = None, 0.0  # set_collision_body
+        self.self_collision = None  # set_self_collision: (stiffness, depth_cap, mode)
 
     def collide_with(self, other, stiffness, depth_cap=0.0):
         """Penalty contact with another ``Deformable`` on the same device at the current states of both, ADDED to the external forces of
@@ -1036,6 +1077,15 @@ class Deformable:
         """Opt-in: every ``timestep`` adds the contact forces with ``other`` behind gravity and the probe, just before it steps (None: off).
         The call adds to both bodies and ``other`` sets its forces anew in its own ``timestep``, so two bodies that both step set each other."""
         self.collision_body, self.collision_stiffness = other, float(stiffness)
+
+    def self_collide(self, stiffness, depth_cap=0.0, mode="any"):
+        """Penalty contact of this body with itself at its current state, ADDED to its external forces (``FemIntegrator.self_contact``)."""
+        return self.integrator.self_contact(stiffness, depth_cap, mode)
+
+    def set_self_collision(self, stiffness=None, depth_cap=0.0, mode="other_parts"):
+        """Opt-in: every ``timestep`` adds the body's contact forces with itself behind gravity and the probe, just before it steps
+        (stiffness None: off).  mode "other_parts" for the halves of a cut, "any" for a fold of one part."""
+        self.self_collision = None if stiffness is None else (float(stiffness), float(depth_cap), mode)
 
     def set_deform_callback(self, fn):
         self.on_deform = fn
@@ -1116,6 +1166,8 @@ class Deformable:
             it.set_external_forces_to_zero()
         if self.collision_body is not None:
             self.collide_with(self.collision_body, self.collision_stiffness)
+        if self.self_collision is not None:
+            self.self_collide(*self.self_collision)
         iters = it.do_timestep()
         if self.floor_y is not None:
             self.ct_collided = it.floor_collision(self.floor_y, 0.4)

@@ -29,6 +29,7 @@ FB_CONTACT_MISS, FB_CONTACT_EMPTY, FB_CONTACT_SET = 0, 1, 2  # fb_fem_contact_in
 FB_CONTACT_SPREAD_RECORDS, FB_CONTACT_SPREAD_LEVELS = 0, 1  # fb_fem_contact_spread_info.path
 FB_BODY_A_INTO_B, FB_BODY_B_INTO_A = 1, 2  # fb_fem_body_contact_params.directions
 FB_BODY_CONTACT_NONE, FB_BODY_CONTACT_SCAN, FB_BODY_CONTACT_RING = 0, 1, 2  # fb_fem_body_contact_info.path
+FB_SELF_CONTACT_ANY, FB_SELF_CONTACT_OTHER_PARTS = 0, 1  # fb_fem_self_contact_params.mode
 FB_MAX_MATERIALS = 256  # entries of a handle's material table (fb_fem_set_materials)
 FB_STRESS_WORLD, FB_STRESS_TENSORS = 1, 2  # fb_fem_stress flags
 FB_EMBED_CLOSEST_NONE, FB_EMBED_CLOSEST_SCAN, FB_EMBED_CLOSEST_RING = 0, 1, 2  # fb_fem_embed_search_info.path
@@ -119,6 +120,16 @@ class BodyContactInfo(C.Structure):
     _fields_ = [("n_candidates", C.c_int * 2), ("n_contacts", C.c_int * 2), ("n_degenerate", C.c_int * 2), ("path", C.c_int),
                 ("n_tet_grid_builds", C.c_int), ("n_face_grid_builds", C.c_int), ("faces_tested", C.c_longlong), ("max_depth", C.c_double),
                 ("force_on_a", C.c_double * 3), ("force_on_b", C.c_double * 3)]
+
+
+class SelfContactParams(C.Structure):
+    _fields_ = [("stiffness", C.c_double), ("depth_cap", C.c_double), ("mode", C.c_int), ("reserved", C.c_int)]
+
+
+class SelfContactInfo(C.Structure):
+    _fields_ = [("n_points", C.c_int), ("n_contacts", C.c_int), ("n_degenerate", C.c_int), ("path", C.c_int), ("n_point_grid_builds", C.c_int),
+                ("n_face_grid_builds", C.c_int), ("n_parts_builds", C.c_int), ("faces_tested", C.c_longlong), ("max_depth", C.c_double),
+                ("force_on_points", C.c_double * 3), ("force_on_faces", C.c_double * 3)]
 
 
 class PolyCounts(C.Structure):
@@ -257,6 +268,9 @@ def lib():
         "fb_fem_body_contact": (C.c_int, [vp, vp, C.POINTER(BodyContactParams), C.POINTER(BodyContactInfo)]),
         "fb_fem_read_body_contact": (C.c_int, [vp, C.c_int, _ip, _ip, _ip, _dp, _dp, _dp]),
         "fb_fem_time_body_contact": (C.c_int, [vp, vp, C.POINTER(BodyContactParams), C.c_int, _dp]),
+        "fb_fem_self_contact": (C.c_int, [vp, C.POINTER(SelfContactParams), C.POINTER(SelfContactInfo)]),
+        "fb_fem_read_self_contact": (C.c_int, [vp, _ip, _ip, _ip, _dp, _dp, _dp]),
+        "fb_fem_time_self_contact": (C.c_int, [vp, C.POINTER(SelfContactParams), C.c_int, _dp]),
         "fb_fem_stress": (C.c_int, [vp, C.c_int, C.POINTER(StressInfo)]),
         "fb_fem_read_stress": (C.c_int, [vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]),
         "fb_fem_surface_stress": (C.c_int, [vp, _fp]),

@@ -214,6 +214,22 @@ class HipIntegrator {
     closestXyz.assign(3 * (size_t)n, 0.0); bary3.assign(3 * (size_t)n, 0.0); depth.assign((size_t)n, 0.0);
     check(fb_fem_read_body_contact(h_, direction, node.data(), element.data(), face.data(), closestXyz.data(), bary3.data(), depth.data()));
   }
+  // Contact of the body with itself (fembrain_hip.h, "Contact of a body with itself"): every surface vertex inside an element it may meet
+  // is pushed to the closest point of the boundary it may meet, the face there is pushed back; ADDED to the external force vector.
+  // mode: FB_SELF_CONTACT_ANY (a fold of one part) or FB_SELF_CONTACT_OTHER_PARTS (the halves of a cut).
+  fb_fem_self_contact_info SelfContact(double stiffness, double depthCap = 0.0, int mode = FB_SELF_CONTACT_ANY) {
+    const fb_fem_self_contact_params p = {stiffness, depthCap, mode, 0};
+    fb_fem_self_contact_info info;
+    check(fb_fem_self_contact(h_, &p, &info));
+    return info;
+  }
+  // the contacts of the last SelfContact of this integrator, info.n_contacts entries
+  void ReadSelfContact(int n, std::vector<int>& node, std::vector<int>& element, std::vector<int>& face, std::vector<double>& closestXyz,
+                       std::vector<double>& bary3, std::vector<double>& depth) {
+    node.assign((size_t)n, 0); element.assign((size_t)n, 0); face.assign((size_t)n, 0);
+    closestXyz.assign(3 * (size_t)n, 0.0); bary3.assign(3 * (size_t)n, 0.0); depth.assign((size_t)n, 0.0);
+    check(fb_fem_read_self_contact(h_, node.data(), element.data(), face.data(), closestXyz.data(), bary3.data(), depth.data()));
+  }
   // Element stress and strain on the device (fembrain_hip.h): von Mises stress, energy density and J of every element at the current
   // state stay on the device, `out` brings the summary.  flags: FB_STRESS_WORLD | FB_STRESS_TENSORS.
   void ComputeStress(int flags, fb_fem_stress_info* out) { check(fb_fem_stress(h_, flags, out)); }
@@ -427,6 +443,7 @@ class Deformable {
       m_lpIntegrator->SetExternalForcesToZero();
     }
     if (m_lpCollisionBody != nullptr) collideWith(*m_lpCollisionBody, m_collisionStiffness);  // (behind gravity and the probe)
+    if (m_selfCollision) selfCollide(m_selfStiffness, m_selfDepthCap, m_selfMode);
     m_lpIntegrator->DoTimestep();
     if (m_hasFloor) m_ctCollided = (U32)m_lpIntegrator->FloorCollision(m_floorY, 0.4);
     if (m_fOnDeform) {
@@ -727,6 +744,16 @@ class Deformable {
   // Not owned; the caller keeps `other` alive or clears the pointer.
   void setCollisionBody(Deformable* other, double stiffness) { m_lpCollisionBody = other; m_collisionStiffness = stiffness; }
   Deformable* getCollisionBody() const { return m_lpCollisionBody; }
+  // The body against itself -- the lips of a cut in one handle, a fold: penalty contact at the current state, ADDED to the external forces
+  // on the device (fb_fem_self_contact; the reference has no counterpart).  As with collideWith, a caller of timestep() opts in instead:
+  fb_fem_self_contact_info selfCollide(double stiffness, double depthCap = 0, int mode = FB_SELF_CONTACT_ANY) {
+    return m_lpIntegrator->SelfContact(stiffness, depthCap, mode);
+  }
+  // every timestep() adds the self-contact forces behind gravity, the probe and the collision body, just before it steps (on = false: off)
+  void setSelfCollision(bool on, double stiffness = 0.0, double depthCap = 0.0, int mode = FB_SELF_CONTACT_OTHER_PARTS) {
+    m_selfCollision = on; m_selfStiffness = stiffness; m_selfDepthCap = depthCap; m_selfMode = mode;
+  }
+  bool getSelfCollision() const { return m_selfCollision; }
   // Deformable::collisionDetect (Deformable.cpp:541-600) against the floor plane set with setFloor: vertices at or below it are
   // put back on it and their velocity reflected (the device pass timestep() also runs); true if any vertex was touched
   bool collisionDetect() {
@@ -876,6 +903,7 @@ class Deformable {
     m_bApplyGravity = true;  // left uninitialised by the reference's init(); true is what its .sim files set
     m_boxCapacity = 64; m_lpIntegrator = nullptr; m_lpSurface = nullptr; m_hasFloor = false; m_floorY = 0.0; m_dof = 0; m_restVolume = -1.0;
     m_lpCollisionBody = nullptr; m_collisionStiffness = 0.0;
+    m_selfCollision = false; m_selfStiffness = m_selfDepthCap = 0.0; m_selfMode = FB_SELF_CONTACT_OTHER_PARTS;
   }
   std::vector<double> m_rest;
   std::vector<int> m_elements;
@@ -885,6 +913,9 @@ class Deformable {
   HipIntegrator* m_lpIntegrator;
   SurfaceMesh* m_lpSurface;
   Deformable* m_lpCollisionBody;  // setCollisionBody: not owned
+  bool m_selfCollision;           // setSelfCollision
+  double m_selfStiffness, m_selfDepthCap;
+  int m_selfMode;
   std::vector<EmbeddedMesh*> m_vEmbedded;
   FOnApplyDeformations m_fOnDeform;
   U32 m_dof, m_ctCollided, m_ctTimeStep;

@@ -754,6 +754,59 @@ int fb_fem_body_contact(fb_fem_t a, fb_fem_t b, const fb_fem_body_contact_params
 int fb_fem_read_body_contact(fb_fem_t a, int direction, int* node, int* element, int* face, double* closest_xyz, double* bary3, double* depth);
 int fb_fem_time_body_contact(fb_fem_t a, fb_fem_t b, const fb_fem_body_contact_params* p, int reps, double seconds[5]);
 
+/* ---- Contact of a body with itself, on the device ----
+ * fb_fem_cut leaves both halves of a cut in one handle and fb_fem_split_parts opens it: one mesh that can pass through itself.  So can a
+ * body that was never cut, a beam folded onto itself.  fb_fem_body_contact needs two handles (and refuses a == b); this call is the
+ * contact of ONE handle with itself.  The reference has no counterpart (its Deformable collides with one Bullet object and its floor):
+ * the rule is this project's.  Unsharded handles only (FB_EINVAL otherwise); node, element and face ids are the CALLER's
+ * (fb_fem_read_mesh, fb_fem_read_surface), also on renumbered handles.  The call uses the current state and ADDS penalty forces into
+ * the external force vector (set gravity or zero first), on the handle's stream.  A handle that never calls it allocates and launches
+ * nothing extra.  Every operation fp64, in the order written, no contraction:
+ *  1. Points: the surface vertices of h (fb_fem_surface's vertex_ids, ascending) at p = x0 + q.  A position of the body that is not
+ *     finite gives FB_EINVAL before anything is written.
+ *  2. Exclusion, for the point on node n.  FB_SELF_CONTACT_ANY: every element that has n among its four nodes and every boundary face
+ *     that has n among its three.  FB_SELF_CONTACT_OTHER_PARTS: every element whose part equals part(n) and every boundary face whose
+ *     element (fb_fem_read_surface's face_tets) is in that part; part(n) is fb_fem_read_parts' node_part, the lowest part using the node
+ *     (the labels are built first where they are stale: n_parts_builds).  A mesh of one part has no contacts under OTHER_PARTS: no grid is
+ *     built, the force vector is not written.
+ *  3. Containment: p is in contact if some element that is not excluded has, at the current positions, four weights >= 0 (fb_fem_embed's
+ *     weights D_i / D_0, no threshold: the function fb_fem_body_contact evaluates); the lowest-numbered such element is recorded.
+ *  4. Closest boundary point: over all boundary faces that are not excluded, at current positions, the closest point c of a face to p
+ *     and d = |c - p| exactly as step 4 of "Contact between two bodies" forms them.  The least d wins, of bitwise equal d the lowest
+ *     face.  A contact for which no face is left is dropped and not counted.
+ *  5. Force: d == 0 is counted in n_degenerate and pushes nothing.  Else n = (c - p) / d, depth = depth_cap > 0 ? min(d, depth_cap) : d,
+ *     F = (stiffness * depth) * n, b0 = (1 - b1) - b2.
+ *  6. Scatter into the one external force vector.  Contact i, by ascending surface vertex, makes four records: 4i is +F on the point's
+ *     node, 4i + 1..3 are (-F) * b_k on corner k of the face.  A node -- it may be a point of one contact and a corner of others --
+ *     receives its records in ascending record index onto the value the vector had.  No floating-point atomics: two calls from one
+ *     state give the same bits.  force_on_points / force_on_faces are the fp64 sums of the +F and of the corner records in record order.
+ *
+ * Right after a cut the twin nodes of the lips coincide bit for bit (FB_CUT_BAKE and FB_CUT_CARRY alike).  Whatever rounding decides
+ * about their containment, their closest face is at d == 0: a body that has just been cut receives NO force from this call; only a lip
+ * pressed into the other does.
+ * FB_SELF_CONTACT_ANY is correct while the penetration is shallower than the distance from the vertex to the nearest face of its own
+ * side that does not touch it -- about half a cell.  Beyond that a face of its own side can win.  (The cut beam of the tests, pressed in
+ * by 0.31 of a cell: the largest depth is 0.0275 under ANY and 0.0309 under OTHER_PARTS, by the numpy restatement of the rule.)
+ * OTHER_PARTS is the mode for the halves of a cut, ANY the mode for a fold of one part.
+ *
+ * path, faces_tested, max_depth as in fb_fem_body_contact_info (FB_BODY_CONTACT_NONE | _SCAN | _RING); FEMBRAIN_SELF_CONTACT=scan|ring
+ * and FEMBRAIN_SELF_CONTACT_BUDGET=n are this call's knobs, read at every call (default: the ring wherever its coverage proof holds,
+ * self_contact.hip).  n_points: the surface vertices; n_point_grid_builds / n_face_grid_builds / n_parts_builds: built by this call.
+ * fb_fem_read_self_contact: the last adding call's contacts (n_contacts entries each, any pointer may be NULL) in the layout of
+ * fb_fem_read_body_contact; depth = d before the cap.  fb_fem_time_self_contact: seconds of the five stages (positions and box | point
+ * grid and containment | face grid | closest faces | scatter), means of `reps` runs, host waits included; it adds no force. */
+#define FB_SELF_CONTACT_ANY         0  /* exclusion by incidence */
+#define FB_SELF_CONTACT_OTHER_PARTS 1  /* exclusion by part (fb_fem_parts' labels, built first if stale) */
+typedef struct fb_fem_self_contact_params { double stiffness, depth_cap; int mode, reserved; } fb_fem_self_contact_params;
+typedef struct fb_fem_self_contact_info {
+  int n_points, n_contacts, n_degenerate, path /* FB_BODY_CONTACT_NONE | _SCAN | _RING */;
+  int n_point_grid_builds, n_face_grid_builds, n_parts_builds;
+  long long faces_tested; double max_depth; double force_on_points[3], force_on_faces[3];
+} fb_fem_self_contact_info;
+int fb_fem_self_contact(fb_fem_t h, const fb_fem_self_contact_params* p, fb_fem_self_contact_info* out);
+int fb_fem_read_self_contact(fb_fem_t h, int* node, int* element, int* face, double* closest_xyz, double* bary3, double* depth);
+int fb_fem_time_self_contact(fb_fem_t h, const fb_fem_self_contact_params* p, int reps, double seconds[5]);
+
 /* ---- Element stress and strain, on the device ----
  * The bracket of the corotational element force f_e,i = V R [lambda tr(H) I + mu (H + H^T)] b_i, which the assembly forms every step
  * (E B (R^T x - x0) of corotationalLinearFEM.cpp:107-137, 270-286) and does not keep.  Unsharded handles only (FB_EINVAL otherwise, as
