@@ -1359,6 +1359,8 @@ int fb_fem_step(fb_fem_t h, fb_step_info* info) {
   hipStream_t s = h->stream;
   FB_HIP(hipEventRecord(h->ev[0], s));
   FB_TRY(assemble_system(h));
+  const bool moved = motion_active(h);  // constrained DOFs that follow targets (motion.hip): a right-hand side correction, reactions, their own state
+  if (moved) FB_TRY(motion_correct_rhs(h));
   FB_HIP(hipEventRecord(h->ev[1], s));
   int iters = 0;
   CGState fin;
@@ -1366,10 +1368,12 @@ int fb_fem_step(fb_fem_t h, fb_step_info* info) {
   FB_HIP(hipEventRecord(h->ev[2], s));
   const bool ok = iters >= 0;
   if (ok) {
+    if (moved) FB_TRY(motion_reactions(h));
     const int n = 3 * h->plan.n_owned;
     hipLaunchKernelGGL(k_state_update, dim3(ceil_div(n, kBlock)), dim3(kBlock), 0, s, n, h->x.p, h->dofmask.p, h->prm.timestep, h->q.p,
                        h->qvel.p);
     FB_HIP(hipGetLastError());
+    if (moved) FB_TRY(motion_apply(h));
   }
   FB_HIP(hipStreamSynchronize(s));
   float ms_a = 0, ms_s = 0;
@@ -1412,6 +1416,7 @@ int fb_fem_reset(fb_fem_t h) {
     FB_TRY(h->x.zero(h->stream));  // the solver's start vector (IntegratorBase::ResetToRest clears its buffers)
   }
   h->system_valid = false;
+  motion_clear(h->motion);
   return FB_OK;
 }
 
@@ -1692,6 +1697,7 @@ int fb_fem_assemble(fb_fem_t h, const double* u, double* f, double* K_blocks) {
 int fb_fem_system(fb_fem_t h, double* Keff_blocks, double* rhs) {
   CHECK_HANDLE(h);
   FB_TRY(assemble_system(h));
+  if (motion_active(h)) FB_TRY(motion_correct_rhs(h));  // (the right-hand side the step would solve)
   if (rhs) FB_TRY(download_owned(h, h->rhs, rhs));
   if (Keff_blocks) FB_TRY(download_blocks(h, Keff_blocks));
   return FB_OK;

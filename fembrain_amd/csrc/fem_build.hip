@@ -50,6 +50,7 @@ enum { kKeepOrder = 1, kKeepCsr = 2 };
 void begin_mesh_generation(fb_fem_s* h, int keep = 0) {
   drop_graph(h);
   h->surf.valid = h->stress.valid = h->parts.valid = false;  // (fb_fem_surface; fb_fem_read_stress / fb_fem_surface_stress; fb_fem_parts)
+  motion_mesh_changed(h->motion);  // (fb_fem_set_constrained_motion: the element table is built again, the set filtered by the new constrained list)
   embed_mesh_changed(h->embed, keep != 0 || h->map_from_delta);  // (fb_fem_embed: a change in place, or its full rebuild, is followed by resync_delta)
   contact_mesh_changed(h->contact, keep != 0 || h->map_from_delta);  // (fb_fem_contact_move: the same two keep the session, a full re-sync clears it)
   if (!(keep & kKeepCsr)) h->csr_ready = false;
@@ -636,6 +637,7 @@ int fb_fem_resync(fb_fem_t h, int n_nodes, const double* xyz, int n_tets, const 
   FB_HIP(hipStreamSynchronize(h->stream));
   if (h->plan.n_ranks > 1) return resync_sharded(h, n_nodes, xyz, n_tets, tets, n_fixed_dofs, fixed_dofs, nullptr);
   ResyncScope scope(h);
+  motion_clear(h->motion);  // (a state reset: the moved DOFs and the grasp go with the state)
   FB_TRY(build(h, n_nodes, xyz, n_tets, tets, n_fixed_dofs, fixed_dofs, 1, 0, nullptr));
   scope.commit();
   return FB_OK;
@@ -934,7 +936,7 @@ int fb_fem_set_constrained_dofs(fb_fem_t h, int n_fixed_dofs, const int* fixed_d
     if (h->plan.n_ranks == 1) h->fixed_caller.assign(fixed_dofs, fixed_dofs + n_fixed_dofs);  // (fb_fem_read_constrained_dofs)
   }
   h->system_valid = false;
-  return FB_OK;
+  return motion_constraints_changed(h);  // (moved DOFs that are no longer constrained leave the set; q and qvel stay)
 }
 
 int fb_fem_resync_path(fb_fem_t h) { return h ? h->last_resync_path : FB_RESYNC_FULL; }

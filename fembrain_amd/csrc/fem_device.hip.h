@@ -67,41 +67,14 @@ __global__ __launch_bounds__(kBlock) void k_tet_rest(int nt, const int4* __restr
 //   K0[ij] = V [lambda b_i b_j^T + mu b_j b_i^T + mu (b_i.b_j) I]).
 // rec[16*e + 4*k + d] = c_k[d] (MT), rec[16*e + 4*k + 3] = V; fe[12*e + 3*k + d] fp64.
 // ------------------------------------------------------------------------------------------------------
-// y_i = sum_j K0[ij] v_j with the undeformed element stiffness in closed form, K0[ij] = V [lambda b_i b_j^T + mu b_j b_i^T + mu (b_i.b_j) I]
-__device__ inline void k0_apply(const double b[4][3], double V, double lambda, double mu, const double* v, double* y) {
-  double sl = 0.0, sm[3] = {0, 0, 0}, sg[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    const double bv = b[j][0] * v[3 * j] + b[j][1] * v[3 * j + 1] + b[j][2] * v[3 * j + 2];
-    sl += bv;                                   // sum_j b_j . v_j
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-      sm[a] += b[j][a] * bv;                    // unused below (kept symmetric form): sum_j b_j (b_j . v_j)
-#pragma unroll
-      for (int c = 0; c < 3; c++) sg[a][c] += b[j][a] * v[3 * j + c];  // sum_j b_j v_j^T
-    }
-  }
-  (void)sm;
-#pragma unroll
-  for (int i = 0; i < 4; i++)
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-      // lambda b_i (sum_j b_j.v_j) + mu sum_j b_j (b_i.v_j) + mu sum_j (b_i.b_j) v_j
-      double t1 = 0.0, t2 = 0.0;
-#pragma unroll
-      for (int c = 0; c < 3; c++) { t1 += sg[a][c] * b[i][c]; t2 += b[i][c] * sg[c][a]; }
-      y[3 * i + a] = V * (lambda * b[i][a] * sl + mu * t1 + mu * t2);
-    }
-}
+// (k0_apply, the element stiffness in closed form, lives in tet_math.hip.h: motion.hip applies it too)
 
 // Per-element materials (fb_fem_set_materials / fb_fem_set_element_materials).  The table is three planes of kMaxMaterials doubles --
 // lambda | mu | rho/20 -- always allocated in full and padded with entry 0, so that ANY byte indexes inside it; the ids themselves are
 // checked on the host before they reach the device.  MAT is a template parameter of every kernel that reads a material: a handle
 // without an element map launches the instantiations without it, whose code is what it was.
 // k_tet_warp<.., MAT> writes the id into the V lane of quarter 1 of the step record ((float)id is exact up to 255; quarter 0 keeps V):
-// the assembly kernels that hold the whole record anyway get the id without another gather.
-template <typename MT>
-__device__ __forceinline__ int rec_mat_id(MT w) { return (int)w & (kMaxMaterials - 1); }
+// the assembly kernels that hold the whole record anyway get the id without another gather (rec_mat_id, tet_math.hip.h).
 
 // kcorr (may be null): warp = 2 of CorotationalLinearFEMForceModel (corotationalLinearFEM.cpp:296-428) -- the two terms the
 // derivative of the element rotation adds to the element stiffness, as a row-major 12 x 12 matrix per element (MT):

@@ -1,7 +1,7 @@
 // The FEM handle (fb_fem_t of include/fembrain_hip.h) and what the units that work on it share: fem.hip (assembly, the two-launch
 // solver, the steps and the rest of the C ABI), fem_build.hip (life cycle: plan build, creation, re-sync, cut), fem_persist.hip (the
 // persistent solver's host side), haptic.hip (the probe's entry points), stress.hip (element stress and strain), parts.hip (disjoint parts),
-// detach.hip (a part into a handle of its own), embed.hip (point sets bound to the elements), embed_touch.hip (forces, picks and stress on them), contact.hip (the probe's box contact) and body_contact.hip (contact between two handles).
+// detach.hip (a part into a handle of its own), embed.hip (point sets bound to the elements), embed_touch.hip (forces, picks and stress on them), contact.hip (the probe's box contact), body_contact.hip (contact between two handles), self_contact.hip (a handle with itself) and motion.hip (constrained DOFs that follow a tool).
 // Internal: not installed, included by these units only.
 #pragma once
 #include "comm.h"
@@ -21,6 +21,7 @@
 #include "contact.h"
 #include "body_contact.h"
 #include "self_contact.h"
+#include "motion.h"
 
 namespace fb {
 
@@ -198,6 +199,7 @@ struct fb_fem_s {
   ContactWork contact;    // fb_fem_contact_move / apply: the probe's touched set, force list and spread records (contact.h); empty until somebody asks
   BodyContactWork bodyc;  // fb_fem_body_contact: contact with another handle, kept in the handle the call names first (body_contact.h); empty until somebody asks
   SelfContactWork selfc;  // fb_fem_self_contact: contact of this handle with itself (self_contact.h); empty until somebody asks
+  MotionWork motion;      // fb_fem_set_constrained_motion / fb_fem_grasp: the moved constrained DOFs, their element table and reactions (motion.h); empty until somebody asks
   HapticWork hap;         // fb_fem_add_haptic_forces / pick / volume: level array and scratch (haptic.h); empty until somebody asks
   std::vector<int> fixed_caller;  // the constrained DOFs in the caller's numbering (unsharded): what fb_fem_cut keeps
   DevBuf<int4> tets_next, tets_caller;   // (the element list being built; swapped with `tets`)
@@ -222,7 +224,7 @@ struct fb_fem_s {
   fb::AsmKernels asm_k;              // the assembly kernels of this plan
   // Per mesh generation -- begin_mesh_generation (fem_build.hip) is the one place that resets them, for build(), its host-builder fallback
   // and fb_fem_resync_delta: ren, l2c, order_sum, x0_ready, masks_ready, caller_pattern, csr_ready, span_stale (all below), the embeddings' grid and bindings (embed_mesh_changed), the contact session (contact_mesh_changed), surf.valid,
-  // stress.valid and parts.valid (above); batch_graph is dropped with them.  (fb_fem_resync_delta keeps ren, and csr_ready while it decides, and says so.)
+  // stress.valid, parts.valid and motion.table_valid (above); batch_graph is dropped with them.  (fb_fem_resync_delta keeps ren, and csr_ready while it decides, and says so.)
   // locality renumbering behind the ABI (renumber.h): the handle works in its own node order, ids are mapped on the way in and out
   Renumbering ren;
   DevBuf<double> xyz_in;               // the caller-order rest positions the order was derived from
@@ -281,6 +283,7 @@ struct fb_fem_s {
 
 namespace fb {
 
+inline bool motion_active(const fb_fem_s* h) { return !h->motion.dofs.empty(); }  // (no set: the step launches nothing of motion.hip)
 inline bool has_material_map(const fb_fem_s* h) { return h->mat_ids.p != nullptr; }  // (none: nothing allocated, the kernels' uniform instantiations)
 
 inline SellView sell_view(const fb_fem_s* h) {

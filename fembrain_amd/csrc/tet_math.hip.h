@@ -61,4 +61,36 @@ __device__ inline double polar_rotation(const double* F, double* R, double tol) 
   return det;
 }
 
+// y_i = sum_j K0[ij] v_j with the undeformed element stiffness in closed form, K0[ij] = V [lambda b_i b_j^T + mu b_j b_i^T + mu (b_i.b_j) I]
+// (fem_device.hip.h: k_tet_warp's exact tangent; motion.hip: with the rotated gradients c_k for b_k it is the element's K_e)
+__device__ inline void k0_apply(const double b[4][3], double V, double lambda, double mu, const double* v, double* y) {
+  double sl = 0.0, sm[3] = {0, 0, 0}, sg[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const double bv = b[j][0] * v[3 * j] + b[j][1] * v[3 * j + 1] + b[j][2] * v[3 * j + 2];
+    sl += bv;                                   // sum_j b_j . v_j
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      sm[a] += b[j][a] * bv;                    // unused below (kept symmetric form): sum_j b_j (b_j . v_j)
+#pragma unroll
+      for (int c = 0; c < 3; c++) sg[a][c] += b[j][a] * v[3 * j + c];  // sum_j b_j v_j^T
+    }
+  }
+  (void)sm;
+#pragma unroll
+  for (int i = 0; i < 4; i++)
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      // lambda b_i (sum_j b_j.v_j) + mu sum_j b_j (b_i.v_j) + mu sum_j (b_i.b_j) v_j
+      double t1 = 0.0, t2 = 0.0;
+#pragma unroll
+      for (int c = 0; c < 3; c++) { t1 += sg[a][c] * b[i][c]; t2 += b[i][c] * sg[c][a]; }
+      y[3 * i + a] = V * (lambda * b[i][a] * sl + mu * t1 + mu * t2);
+    }
+}
+
+// the material id k_tet_warp<.., MAT> leaves in the V lane of quarter 1 of an element's step record (fem_device.hip.h, "Per-element materials")
+template <typename MT>
+__device__ __forceinline__ int rec_mat_id(MT w) { return (int)w & (kMaxMaterials - 1); }
+
 }  // namespace fb

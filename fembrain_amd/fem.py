@@ -756,6 +756,63 @@ class FemIntegrator:
         _l.check(self._L.fb_fem_time_self_contact(self.h, C.byref(p), int(reps), _l.dptr(sec)))
         return sec
 
+    # -- constrained DOFs that follow a tool, and the force they return (fb_fem_set_constrained_motion / fb_fem_grasp; unsharded handles) --
+    def set_constrained_motion(self, dofs, displacements):
+        """Replaces the motion set: ``dofs`` (caller ids, ascending, each a constrained DOF of the handle) end the next ``do_timestep``
+        at ``displacements`` bit for bit, with qvel = (u - q) / h; the free DOFs feel them through the matrix columns the stored matrix
+        does not hold, as a right-hand-side correction.  The targets stay until they are changed; an empty list clears the set.  A target
+        far from q is a large velocity in one step: move it a little per step."""
+        d = np.ascontiguousarray(dofs, np.int32).reshape(-1)
+        u = np.ascontiguousarray(displacements, np.float64).reshape(-1)
+        if len(d) != len(u):
+            raise ValueError("one displacement per DOF")
+        _l.check(self._L.fb_fem_set_constrained_motion(self.h, len(d), _l.iptr(d), _l.dptr(u)))
+
+    def constrained_motion(self):
+        """(dofs, displacements) of the motion set (fb_fem_read_constrained_motion)"""
+        n = max(int(self._L.fb_fem_num_constrained_motion(self.h)), 0)
+        d, u = np.zeros(n, np.int32), np.zeros(n)
+        _l.check(self._L.fb_fem_read_constrained_motion(self.h, _l.iptr(d), _l.dptr(u)))
+        return d, u
+
+    def reactions(self):
+        """(forces, sum3): the force the constraint put on the body at every DOF of the motion set during the last step, in the set's
+        order, and its sum by axis (fb_fem_read_reactions); zeros before a step with the set.  A haptic device is fed ``-sum3``."""
+        n = max(int(self._L.fb_fem_num_constrained_motion(self.h)), 0)
+        f, s = np.zeros(n), np.zeros(3)
+        _l.check(self._L.fb_fem_read_reactions(self.h, _l.dptr(f), _l.dptr(s)))
+        return f, s
+
+    def motion_info(self):
+        """dict of the fb_fem_motion_info fields: n_dofs, n_listed_elements, n_touched_nodes, longest_run, table_builds, table_valid, n_grasp_nodes"""
+        info = _l.MotionInfo()
+        _l.check(self._L.fb_fem_motion_info_get(self.h, C.byref(info)))
+        return {name: int(getattr(info, name)) for name, _ in _l.MotionInfo._fields_ if name != "reserved"}
+
+    def time_motion(self, reps=5):
+        """Seconds of the table build, the right-hand-side correction, the reactions and the write of the moved DOFs, means of ``reps``
+        runs (fb_fem_time_motion); state and reactions stay what they are."""
+        sec = np.zeros(4)
+        _l.check(self._L.fb_fem_time_motion(self.h, int(reps), _l.dptr(sec)))
+        return sec
+
+    def grasp(self, nodes):
+        """Holds ``nodes`` (caller ids, ascending): their DOFs join the constrained list and the motion set with their current q as the
+        target, their world positions are remembered (fb_fem_grasp).  Returns ``motion_info()``."""
+        ids = np.ascontiguousarray(nodes, np.int32).reshape(-1)
+        info = _l.MotionInfo()
+        _l.check(self._L.fb_fem_grasp(self.h, len(ids), _l.iptr(ids), C.byref(info)))
+        return {name: int(getattr(info, name)) for name, _ in _l.MotionInfo._fields_ if name != "reserved"}
+
+    def grasp_move(self, R=None, t=(0.0, 0.0, 0.0), pivot=(0.0, 0.0, 0.0)):
+        """Targets of the grasped nodes = R (p_grab - pivot) + pivot + t - x0, set on the device (fb_fem_grasp_move); R 3x3, row-major"""
+        R = np.eye(3) if R is None else R
+        _l.check(self._L.fb_fem_grasp_move(self.h, _l.dptr(_l.as_f64(R, 9)), _l.dptr(_l.as_f64(t, 3)), _l.dptr(_l.as_f64(pivot, 3))))
+
+    def release(self):
+        """Lets go: what ``grasp`` added leaves the constrained list and the motion set, q and qvel stay (fb_fem_release)"""
+        _l.check(self._L.fb_fem_release(self.h))
+
     # -- element stress and strain on the device (fb_fem_stress / read_stress / surface_stress; unsharded handles) --
     def stress(self, world=False, tensors=False):
         """Stress and strain of every element at the current state, kept on the device (fb_fem_stress): the bracket of the corotational
@@ -1081,6 +1138,24 @@ class Deformable:
     def self_collide(self, stiffness, depth_cap=0.0, mode="any"):
         """Penalty contact of this body with itself at its current state, ADDED to its external forces (``FemIntegrator.self_contact``)."""
         return self.integrator.self_contact(stiffness, depth_cap, mode)
+
+    # -- held and moved: what IAvatar::grip() only flags (IScalpel.cpp:42-44) --
+    def grip(self, nodes):
+        """A tool closes on ``nodes`` (ids as ``pick_box`` returns them): they are held where they are (``FemIntegrator.grasp``)."""
+        return self.integrator.grasp(np.unique(np.asarray(nodes, np.int32)))
+
+    def move_grip(self, R=None, t=(0.0, 0.0, 0.0), pivot=(0.0, 0.0, 0.0)):
+        """The held nodes follow the tool: rotated by R about pivot and shifted by t from where they were gripped (``grasp_move``).  The
+        next ``timestep`` takes them there in one step: move a little per step."""
+        self.integrator.grasp_move(R, t, pivot)
+
+    def release_grip(self):
+        """The tool opens: the held nodes are free again with the state they have (``FemIntegrator.release``)."""
+        self.integrator.release()
+
+    def grip_force(self):
+        """The force the tissue returned to the tool during the last step: minus the sum of the reactions (3,)"""
+        return -self.integrator.reactions()[1]
 
     def set_self_collision(self, stiffness=None, depth_cap=0.0, mode="other_parts"):
         """Opt-in: every ``timestep`` adds the body's contact forces with itself behind gravity and the probe, just before it steps

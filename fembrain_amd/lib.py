@@ -132,6 +132,11 @@ class SelfContactInfo(C.Structure):
                 ("force_on_points", C.c_double * 3), ("force_on_faces", C.c_double * 3)]
 
 
+class MotionInfo(C.Structure):
+    _fields_ = [("n_dofs", C.c_int), ("n_listed_elements", C.c_int), ("n_touched_nodes", C.c_int), ("longest_run", C.c_int),
+                ("table_builds", C.c_int), ("table_valid", C.c_int), ("n_grasp_nodes", C.c_int), ("reserved", C.c_int)]
+
+
 class PolyCounts(C.Structure):
     _fields_ = [("grid", C.c_int * 3), ("n_points", C.c_int), ("n_cells", C.c_int), ("n_crossed_edges", C.c_int),
                 ("n_surface_cells", C.c_int), ("n_included_cells", C.c_int),
@@ -271,6 +276,15 @@ def lib():
         "fb_fem_self_contact": (C.c_int, [vp, C.POINTER(SelfContactParams), C.POINTER(SelfContactInfo)]),
         "fb_fem_read_self_contact": (C.c_int, [vp, _ip, _ip, _ip, _dp, _dp, _dp]),
         "fb_fem_time_self_contact": (C.c_int, [vp, C.POINTER(SelfContactParams), C.c_int, _dp]),
+        "fb_fem_set_constrained_motion": (C.c_int, [vp, C.c_int, _ip, _dp]),
+        "fb_fem_num_constrained_motion": (C.c_int, [vp]),
+        "fb_fem_read_constrained_motion": (C.c_int, [vp, _ip, _dp]),
+        "fb_fem_read_reactions": (C.c_int, [vp, _dp, _dp]),
+        "fb_fem_motion_info_get": (C.c_int, [vp, C.POINTER(MotionInfo)]),
+        "fb_fem_time_motion": (C.c_int, [vp, C.c_int, _dp]),
+        "fb_fem_grasp": (C.c_int, [vp, C.c_int, _ip, C.POINTER(MotionInfo)]),
+        "fb_fem_grasp_move": (C.c_int, [vp, _dp, _dp, _dp]),
+        "fb_fem_release": (C.c_int, [vp]),
         "fb_fem_stress": (C.c_int, [vp, C.c_int, C.POINTER(StressInfo)]),
         "fb_fem_read_stress": (C.c_int, [vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]),
         "fb_fem_surface_stress": (C.c_int, [vp, _fp]),

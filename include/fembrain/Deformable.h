@@ -230,6 +230,33 @@ class HipIntegrator {
     closestXyz.assign(3 * (size_t)n, 0.0); bary3.assign(3 * (size_t)n, 0.0); depth.assign((size_t)n, 0.0);
     check(fb_fem_read_self_contact(h_, node.data(), element.data(), face.data(), closestXyz.data(), bary3.data(), depth.data()));
   }
+  // Constrained DOFs that follow targets, and the force they return (fembrain_hip.h, "Constrained motion"): dofs ascending, each a
+  // constrained DOF of the handle; the next DoTimestep ends with q = displacements there, bit for bit.  n = 0 clears the set.
+  void SetConstrainedMotion(int n, const int* dofs, const double* displacements) { check(fb_fem_set_constrained_motion(h_, n, dofs, displacements)); }
+  void ReadConstrainedMotion(std::vector<int>& dofs, std::vector<double>& displacements) {
+    const size_t n = (size_t)std::max(0, fb_fem_num_constrained_motion(h_));
+    dofs.assign(n, 0); displacements.assign(n, 0.0);
+    check(fb_fem_read_constrained_motion(h_, dofs.data(), displacements.data()));
+  }
+  // the reactions of the last DoTimestep in the set's order (null: not wanted) and their sum by axis
+  void ReadReactions(std::vector<double>* forces, double sum3[3]) {
+    if (forces) forces->assign((size_t)std::max(0, fb_fem_num_constrained_motion(h_)), 0.0);
+    check(fb_fem_read_reactions(h_, forces ? forces->data() : nullptr, sum3));
+  }
+  fb_fem_motion_info MotionInfo() {
+    fb_fem_motion_info info;
+    check(fb_fem_motion_info_get(h_, &info));
+    return info;
+  }
+  void TimeMotion(int reps, double seconds[4]) { check(fb_fem_time_motion(h_, reps, seconds)); }
+  // the grasp on top: nodes ascending; targets = R (p_grab - pivot) + pivot + t - x0 set on the device; Release frees what Grasp constrained
+  fb_fem_motion_info Grasp(int n, const int* nodes) {
+    fb_fem_motion_info info;
+    check(fb_fem_grasp(h_, n, nodes, &info));
+    return info;
+  }
+  void GraspMove(const double R[9], const double t[3], const double pivot[3]) { check(fb_fem_grasp_move(h_, R, t, pivot)); }
+  void Release() { check(fb_fem_release(h_)); }
   // Element stress and strain on the device (fembrain_hip.h): von Mises stress, energy density and J of every element at the current
   // state stay on the device, `out` brings the summary.  flags: FB_STRESS_WORLD | FB_STRESS_TENSORS.
   void ComputeStress(int flags, fb_fem_stress_info* out) { check(fb_fem_stress(h_, flags, out)); }
@@ -754,6 +781,20 @@ class Deformable {
     m_selfCollision = on; m_selfStiffness = stiffness; m_selfDepthCap = depthCap; m_selfMode = mode;
   }
   bool getSelfCollision() const { return m_selfCollision; }
+  // Held and moved -- what the reference only flags (IAvatar::grip() sets m_isGripped, src/deformable/IScalpel.cpp:42-44, read at
+  // AvatarRing.cpp:177; its integrator nails constrained DOFs to rest).  grip: the tool closes on `nodes` (ascending ids, e.g. pickVertices'),
+  // which are held where they are.  moveGrip: they follow the tool, rotated by R (row-major) about pivot and shifted by t from where they
+  // were gripped; the next timestep() takes them there in ONE step, so move a little per step.  releaseGrip: the tool opens, the nodes
+  // are free again with the state they have.  gripForce: what the tissue returned to the tool during the last step, minus the sum of
+  // the reactions -- what a displacement-driven haptic device is fed (fembrain_hip.h, "Constrained motion").  The held DOFs are constrained
+  // in the handle, not in the fixed-vertex list of this class: setFixedVertices / syncForceModel while gripping let the tool go.
+  fb_fem_motion_info grip(int n, const int* nodes) { return m_lpIntegrator->Grasp(n, nodes); }
+  void moveGrip(const double R[9], const double t[3], const double pivot[3]) { m_lpIntegrator->GraspMove(R, t, pivot); }
+  void releaseGrip() { m_lpIntegrator->Release(); }
+  void gripForce(double force[3]) {
+    m_lpIntegrator->ReadReactions(nullptr, force);
+    for (int k = 0; k < 3; k++) force[k] = -force[k];
+  }
   // Deformable::collisionDetect (Deformable.cpp:541-600) against the floor plane set with setFloor: vertices at or below it are
   // put back on it and their velocity reflected (the device pass timestep() also runs); true if any vertex was touched
   bool collisionDetect() {

@@ -807,6 +807,76 @@ int fb_fem_self_contact(fb_fem_t h, const fb_fem_self_contact_params* p, fb_fem_
 int fb_fem_read_self_contact(fb_fem_t h, int* node, int* element, int* face, double* closest_xyz, double* bary3, double* depth);
 int fb_fem_time_self_contact(fb_fem_t h, const fb_fem_self_contact_params* p, int reps, double seconds[5]);
 
+/* ---- Constrained motion: held nodes follow a tool, reaction forces on the device ----
+ * A constrained DOF is otherwise nailed to q = 0 for life.  A MOTION SET is a subset of the handle's constrained DOFs, each with a
+ * target displacement u_c: a grasper that drags tissue, a clamp that moves, a displacement-driven haptic device that is told what force
+ * the tissue returns.  The reference has only the stub (IAvatar::grip() sets a flag, IScalpel.cpp:42-44, AvatarRing.cpp:177; its
+ * integrator zeroes constrained DOFs as fb_fem_step does), so the rule is this library's (tests/motionref.py restates it
+ * in NumPy on the oracle's matrices).  Unsharded handles with the default integrator only: a sharded handle and FB_INTEGRATOR_NEWMARK
+ * return FB_EINVAL.  A handle with an empty set launches nothing new and steps bit for bit as before.
+ *
+ * The rule.  A constrained DOF outside the set behaves as ever (q = 0, qvel = 0 after a step).  For a DOF c of the set, the next
+ * fb_fem_step ends with
+ *     q_c = u_c  (the target's bits)      qvel_c = v*_c = (u_c - q_c_before) / h
+ * and the target stays until it is changed, so the step after that has v* = 0.  dv_c = v*_c - qvel_c_before is known before the
+ * solve, and the free rows solve the reference's system with the known part moved to the right:
+ *     Keff_ff dv_f = rhs_f - Keff_fc dv_c,     Keff = s_k K + s_m M  (the UNMASKED matrix; s_k = h (h + cK), s_m = 1 + h cM)
+ * Keff_fc couples free DOF f to moved DOF c -- the two other DOFs of the SAME node included where only one or two DOFs of a node are
+ * in the set.  The stored matrix, its identity rows, the right-hand side on constrained rows (0) and the solution there (0) are
+ * untouched: the solvers see only a different right-hand side.  fb_fem_system's rhs INCLUDES the correction while the handle has a set
+ * (it is the right-hand side the step would solve; its matrix is bitwise that of a handle without a set).
+ * The correction is formed from the elements, not from the matrix (whose columns are zeroed): every element with a node that has a DOF
+ * in the set contributes (s_k K_e + s_m M_e) times the 12-vector that holds dv_c, K_e in the closed form the assembly sums (rotated
+ * gradients of the step; under warp = 2 the symmetric part of the rotation-derivative terms), M_e = rho/20 V (1 + delta_ij), materials
+ * per element where the handle has a map.  The 4 x 3 results are records 4p + k (corner k of the p-th such element, ascending), sorted
+ * stably by node; a node's records are subtracted from its FREE DOFs in record order.  No floating-point atomics: two calls from one
+ * state give the same bits.
+ *
+ * The REACTION on a DOF of the set is the force the constraint puts on the body during the step, from the unmasked row c and the full
+ * dv (the moved DOFs included):
+ *     lambda_c = (1/h) [Keff dv]_c + [(g_k K + g_m M) qvel + fint - fext]_c        (g_k = h + cK, g_m = cM; qvel before the step)
+ * summed in the same record order.  What a haptic device is fed is -lambda, summed over the grasp: sum3 is the sum of lambda by axis
+ * in one fixed tree.
+ *
+ * The targets are explicit: a target far from q means a large v* in ONE step ((u - q) / h), which is the caller's to bound (move the
+ * target a little every step).  There are no velocity or acceleration limits, no sub-stepping, no friction at the jaws and no soft
+ * grasp.  A target that is not finite is refused with FB_EINVAL where it is set; the step checks again on the device (a state that is
+ * not finite at a moved DOF): it then returns FB_EINVAL and the moved DOFs hold what a step without the set writes (0).
+ *
+ * fb_fem_set_constrained_motion replaces the set: n caller DOF ids, ascending, each a constrained DOF of the handle, and their targets;
+ * anything else is FB_EINVAL and nothing changes.  n = 0 clears.  fb_fem_num_constrained_motion / fb_fem_read_constrained_motion read it
+ * back (either pointer may be NULL).  fb_fem_read_reactions: lambda of the last fb_fem_step in the set's order and its sum (either
+ * may be NULL); zeros before a step with the set.  fb_fem_motion_info_get: the set's size, and of the element table the listed
+ * elements, the touched nodes, the longest run of records of one node and how many times it was built (once per set and mesh
+ * generation, at the first step that needs it; a change of targets alone builds nothing).  fb_fem_time_motion: seconds of the table
+ * build | the correction | the reactions | the write of the moved DOFs, means of `reps` runs with a host wait each, written to
+ * scratch (state, right-hand side, reactions and table_builds stay what they are); FB_EINVAL without a set.
+ *
+ * The grasp, on top: fb_fem_grasp adds the three DOFs of each node (caller ids, ascending) to the constrained list -- merged with what
+ * the list held, masks rebuilt as fb_fem_set_constrained_dofs rebuilds them -- and to the set with target = their current q (bit for
+ * bit, taken on the device), and remembers their current world positions p_grab = x0 + q.  One grasp per handle.  fb_fem_grasp_move
+ * sets the targets of the grasped DOFs to R (p_grab - pivot) + pivot + t - x0 by a kernel (R row-major; no whole-mesh vector crosses
+ * the bus).  fb_fem_release takes what fb_fem_grasp added out of the constrained list and out of the set; q and qvel stay, so the
+ * tissue springs back as free DOFs.
+ *
+ * With the rest of the interface: fb_fem_set_constrained_dofs, fb_fem_resync_delta and fb_fem_cut keep the entries whose DOF is still
+ * constrained, with their targets, and drop the others (a dropped DOF keeps its q and qvel where the call carries state; the table
+ * is built again at the next step).  fb_fem_resync and fb_fem_reset clear the set and the grasp.  A piece made by
+ * fb_fem_detach_part starts with an empty set.  Renumbered handles map the ids at the boundary, as every entry point does. */
+typedef struct fb_fem_motion_info {
+  int n_dofs, n_listed_elements, n_touched_nodes, longest_run;
+  int table_builds, table_valid, n_grasp_nodes, reserved;
+} fb_fem_motion_info;
+int fb_fem_set_constrained_motion(fb_fem_t h, int n, const int* dofs, const double* displacements);
+int fb_fem_num_constrained_motion(fb_fem_t h);  /* -1: null or unusable handle */
+int fb_fem_read_constrained_motion(fb_fem_t h, int* dofs, double* displacements);
+int fb_fem_read_reactions(fb_fem_t h, double* forces, double* sum3);
+int fb_fem_motion_info_get(fb_fem_t h, fb_fem_motion_info* out);
+int fb_fem_time_motion(fb_fem_t h, int reps, double seconds[4]);
+int fb_fem_grasp(fb_fem_t h, int n_nodes, const int* node_ids, fb_fem_motion_info* info);
+int fb_fem_grasp_move(fb_fem_t h, const double R[9], const double t[3], const double pivot[3]);
+int fb_fem_release(fb_fem_t h);
+
 /* ---- Element stress and strain, on the device ----
  * The bracket of the corotational element force f_e,i = V R [lambda tr(H) I + mu (H + H^T)] b_i, which the assembly forms every step
  * (E B (R^T x - x0) of corotationalLinearFEM.cpp:107-137, 270-286) and does not keep.  Unsharded handles only (FB_EINVAL otherwise, as
