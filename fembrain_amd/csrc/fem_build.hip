@@ -1016,6 +1016,7 @@ int fb_fem_cut(fb_fem_t h, int n_strip_points, const double* strip_xyz, int mode
       FB_TRY(cut_interpolate(s, C, n_old, dst));
     }
   } else {
+    if (motion_active(h)) FB_TRY(motion_rest_absorbs_q(h));  // (the targets are displacements from the rest shape that is about to move)
     FB_TRY(cut_bake(s, 3LL * n_old, h->x0.p, h->q.p));  // the deformed shape is the new rest shape (Deformable.cpp:144-147)
   }
   const std::vector<int> fixed = h->fixed_caller;

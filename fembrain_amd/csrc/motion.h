@@ -60,6 +60,7 @@ int motion_apply(fb_fem_s* h);         // after the state update: q_c = u_c, qve
 // fem_build.hip
 void motion_mesh_changed(MotionWork& W);   // begin_mesh_generation: the table goes stale (the set is filtered when it is built again)
 void motion_clear(MotionWork& W);          // a state reset: the set and the grasp go
+int motion_rest_absorbs_q(fb_fem_s* h);    // FB_CUT_BAKE, before x0 += q and q = 0: u_c -= q_c, a held node's world-space target stays (asked only where motion_active())
 int motion_constraints_changed(fb_fem_s* h);  // the constrained list was replaced: entries whose DOF is no longer in it are dropped
 
 }  // namespace fb

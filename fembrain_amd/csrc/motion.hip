@@ -251,6 +251,15 @@ __global__ __launch_bounds__(kB) void k_motion_gather(int n_touched, const int* 
   }
 }
 
+// Before the gather: an entry on a node that no element uses (what FB_DETACH_REMOVE leaves) has an empty row in the rule, lambda = -fext;
+// every other entry is written by the gather
+__global__ __launch_bounds__(kB) void k_motion_react_init(int n, const int* __restrict__ dof, const double* __restrict__ fext, double* __restrict__ react) {
+  const int i = blockIdx.x * kB + threadIdx.x;
+  if (i >= n + 3) return;
+  const int d = i < n ? dof[i] : -1;
+  react[i] = d >= 0 ? -fext[d] : 0.0;
+}
+
 // one workgroup: the reactions summed by axis in one fixed tree (thread t takes the entries t, t + 256, ... in that order)
 __global__ __launch_bounds__(kB) void k_motion_sum3(int n, const int* __restrict__ dof, const double* __restrict__ react, double* __restrict__ sum3) {
   for (int a = 0; a < 3; a++) {
@@ -271,6 +280,19 @@ __global__ __launch_bounds__(kB) void k_motion_apply(int n, const int* __restric
   if (d < 0) return;
   q[d] = target[i];
   qvel[d] = vstar[i];
+}
+
+// FB_CUT_BAKE is about to add q to the rest positions and zero it: a target is a displacement from the rest shape, so u_c -= q_c keeps
+// the world-space target x0_c + u_c where it is.  From the caller's ids, as k_motion_map: the table may be stale here.
+__global__ __launch_bounds__(kB) void k_motion_rebase(int n, const int* __restrict__ dofs_caller, const int* __restrict__ new_of_old, int n_nodes,
+                                                      const double* __restrict__ q, double* __restrict__ target) {
+  const int i = blockIdx.x * kB + threadIdx.x;
+  if (i >= n) return;
+  const int c = dofs_caller[i], node = c / 3;
+  if ((unsigned)node >= (unsigned)n_nodes) return;
+  const int in = new_of_old ? new_of_old[node] : node;
+  if ((unsigned)in >= (unsigned)n_nodes) return;
+  target[i] -= q[3 * (size_t)in + (c - 3 * node)];
 }
 
 // ---- the grasp ----
@@ -461,7 +483,7 @@ int reactions(fb_fem_s* h, double* react) {
   hipStream_t s = h->stream;
   const int n = (int)W.dofs.size();
   const double hh = h->prm.timestep, cM = h->prm.damping_mass, cK = h->prm.damping_stiffness;
-  FB_HIP(hipMemsetAsync(react, 0, sizeof(double) * ((size_t)n + 3), s));
+  FB_TRY(launch_1d(k_motion_react_init, n + 3, s, n, W.dof.p, h->fext.p, react));
   if (W.n_listed > 0) {
     MotionParams P = element_params(h);
     P.a_k = hh * (hh + cK) / hh; P.a_m = (1.0 + hh * cM) / hh;  // (1/h) Keff
@@ -524,6 +546,17 @@ int motion_apply(fb_fem_s* h) {
 }
 
 void motion_mesh_changed(MotionWork& W) { W.table_valid = false; W.grasp_slots_valid = false; }
+
+int motion_rest_absorbs_q(fb_fem_s* h) {
+  MotionWork& W = h->motion;
+  FB_TRY(filter_set(h));
+  const int n = (int)W.dofs.size();
+  if (n == 0) return FB_OK;
+  hipStream_t s = h->stream;
+  FB_TRY(reserve_set(W, (size_t)n));
+  FB_HIP(hipMemcpyAsync(W.dofs_dev.p, W.dofs.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, s));
+  return launch_1d(k_motion_rebase, n, s, n, W.dofs_dev.p, h->ren.active ? h->ren.d_new_of_old.p : nullptr, h->plan.n_global, h->q.p, W.target.p);
+}
 
 void motion_clear(MotionWork& W) {
   W.dofs.clear();
@@ -675,6 +708,7 @@ int fb_fem_grasp(fb_fem_t h, int n_nodes, const int* node_ids, fb_fem_motion_inf
   std::set_union(W.dofs.begin(), W.dofs.end(), mine.begin(), mine.end(), std::back_inserter(set2));
   std::vector<double> u2(set2.size(), 0.0);
   for (size_t i = 0; i < W.dofs.size(); i++) u2[(size_t)(std::lower_bound(set2.begin(), set2.end(), W.dofs[i]) - set2.begin())] = u_old[i];
+  const std::vector<int> set_old = W.dofs;
   FB_TRY(fb_fem_set_constrained_dofs(h, (int)merged.size(), merged.data()));
   FB_TRY(install_set(h, set2, u2));
   W.grasp_nodes.assign(node_ids, node_ids + n_nodes);
@@ -687,6 +721,12 @@ int fb_fem_grasp(fb_fem_t h, int n_nodes, const int* node_ids, fb_fem_motion_inf
   FB_TRY(grasp_slots(h));
   FB_TRY(launch_1d(k_grasp_take, n_nodes, s, n_nodes, W.grasp_nodes_dev.p, h->ren.active ? h->ren.d_new_of_old.p : nullptr, h->plan.n_global, h->x0.p, h->q.p,
                    W.grasp_slot.p, W.grasp_pos.p, W.target.p));
+  // an entry the set held before the grasp keeps its target: k_grasp_take wrote the current q over it (rare, and a few doubles)
+  for (size_t i = 0; i < set_old.size(); i++)
+    if (std::binary_search(mine.begin(), mine.end(), set_old[i])) {
+      const size_t at = (size_t)(std::lower_bound(set2.begin(), set2.end(), set_old[i]) - set2.begin());
+      FB_HIP(hipMemcpyAsync(W.target.p + at, &u_old[i], sizeof(double), hipMemcpyHostToDevice, s));
+    }
   FB_HIP(hipStreamSynchronize(s));
   if (info) return fb_fem_motion_info_get(h, info);
   return FB_OK;

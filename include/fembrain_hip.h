@@ -854,14 +854,18 @@ int fb_fem_time_self_contact(fb_fem_t h, const fb_fem_self_contact_params* p, in
  *
  * The grasp, on top: fb_fem_grasp adds the three DOFs of each node (caller ids, ascending) to the constrained list -- merged with what
  * the list held, masks rebuilt as fb_fem_set_constrained_dofs rebuilds them -- and to the set with target = their current q (bit for
- * bit, taken on the device), and remembers their current world positions p_grab = x0 + q.  One grasp per handle.  fb_fem_grasp_move
+ * bit, taken on the device; an entry the set already held keeps its target, and fb_fem_release gives it back as it was), and
+ * remembers their current world positions p_grab = x0 + q.  One grasp per handle.  fb_fem_grasp_move
  * sets the targets of the grasped DOFs to R (p_grab - pivot) + pivot + t - x0 by a kernel (R row-major; no whole-mesh vector crosses
  * the bus).  fb_fem_release takes what fb_fem_grasp added out of the constrained list and out of the set; q and qvel stay, so the
  * tissue springs back as free DOFs.
  *
  * With the rest of the interface: fb_fem_set_constrained_dofs, fb_fem_resync_delta and fb_fem_cut keep the entries whose DOF is still
  * constrained, with their targets, and drop the others (a dropped DOF keeps its q and qvel where the call carries state; the table
- * is built again at the next step).  fb_fem_resync and fb_fem_reset clear the set and the grasp.  A piece made by
+ * is built again at the next step).  A cut does not move a held node's world-space target: fb_fem_cut(FB_CUT_BAKE), which adds q to the
+ * rest positions and zeroes it, subtracts q_c from the targets first (u_c - q_c; a node held at its target keeps target 0).  An entry
+ * on a node that no element uses any more (FB_DETACH_REMOVE) ends at its target with lambda_c = -fext_c, the rule's empty row.
+ * fb_fem_resync and fb_fem_reset clear the set and the grasp.  A piece made by
  * fb_fem_detach_part starts with an empty set.  Renumbered handles map the ids at the boundary, as every entry point does. */
 typedef struct fb_fem_motion_info {
   int n_dofs, n_listed_elements, n_touched_nodes, longest_run;

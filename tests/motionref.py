@@ -14,6 +14,10 @@ A motion set is a subset of the constrained DOFs with target displacements u_c. 
 
 Per-element materials go through tests/matref.py (sums of uniform oracles per element), whose f, K and M have the same layout.
 tests/test_motion_ref.py pins this file against OrcFem.step() (targets 0 on the clamp) and by the momentum identity.
+
+Orphan nodes (no element: what FB_DETACH_REMOVE leaves behind) have empty rows here and identity rows on the device; with
+``orphans_constrained`` step() treats their DOFs as constrained (the free block would be singular otherwise), ``orphan_dofs`` lists them
+and comparisons skip those that are neither in the caller's constrained list nor in the set.
 """
 import numpy as np
 import scipy.sparse as sp
@@ -27,6 +31,10 @@ class MotionRef:
         """materials / ids: [(E, nu, rho)] and one id per element (MatRef); else the uniform oracle of (E, nu, rho)"""
         self.h, self.cM, self.cK = float(timestep), float(cM), float(cK)
         self.mat = None
+        used = np.zeros(len(np.asarray(verts).reshape(-1, 3)), bool)
+        used[np.asarray(tets, np.int64).reshape(-1)] = True
+        lone = np.flatnonzero(~used)
+        self.orphan_dofs = (3 * lone[:, None] + np.arange(3)[None]).reshape(-1)   # DOFs of nodes that no element uses, ascending
         if materials is not None:
             from matref import MatRef
             self.mat = MatRef(verts, tets, materials, ids, warp=warp)
@@ -61,10 +69,11 @@ class MotionRef:
         g = ((h + cK) * K + cM * self.M) @ np.asarray(qvel, np.float64) + f - np.asarray(fext, np.float64)
         return keff.tocsr(), -h * g, g
 
-    def step(self, q, qvel, fext, fixed, dofs=(), targets=()):
+    def step(self, q, qvel, fext, fixed, dofs=(), targets=(), orphans_constrained=False):
         """One step.  fixed: every constrained DOF; dofs / targets: the motion set (a subset of fixed).  Returns a dict: q, qvel (after),
         dv (all DOFs), rhs (the corrected right-hand side, 0 on constrained rows), lam (reactions in the set's order), lam_sum (3,),
-        residual (r = Keff_ff dv_f - rhs_f on all DOFs, 0 on constrained ones), keff"""
+        residual (r = Keff_ff dv_f - rhs_f on all DOFs, 0 on constrained ones), keff.  orphans_constrained: the DOFs of nodes without an
+        element count as constrained too (q = qvel = 0 after the step unless they are in the set)"""
         h = self.h
         q = np.array(q, np.float64)
         qvel = np.array(qvel, np.float64)
@@ -74,6 +83,8 @@ class MotionRef:
         assert len(dofs) == len(u) and np.isin(dofs, fixed).all()
         free = np.ones(self.r, bool)
         free[fixed] = False
+        if orphans_constrained:
+            free[self.orphan_dofs] = False
         keff, rhs0, g = self.system(q, qvel, fext)
         vstar = (u - q[dofs]) / h
         dv = np.zeros(self.r)
@@ -102,22 +113,24 @@ def reactions_at(ref, q, qvel, fext, dofs, dv):
 
 
 def momentum_terms(ref, q, qvel, fext, fixed, dv, residual, lam=None):
-    """The four terms of the momentum identity by axis, (3, 4): sum(lambda over ALL constrained DOFs; ``lam``, in the order of
+    """The five terms of the momentum identity by axis, (3, 5): sum(lambda over ALL constrained DOFs; ``lam``, in the order of
     ``fixed``, where the caller has its own -- the device's -- else formed here from dv), sum(fext),
-    -(1/h) sum_b m_b dv_b, (1/h) sum_f r_f.  With cM = 0 they add up to zero for ANY dv whose free rows leave the residual r:
-    the rows of K sum to zero over the nodes and so does f, so summing (1/h) Keff dv + (hK + D) qvel + f - fext over all rows of an
-    axis leaves (1/h) sum_b m_b dv_b - sum fext; the free rows contribute (1/h) r (r = Keff_ff dv_f - rhs_f: they solve the system up
-    to r), the constrained rows lambda.  That is  sum(lambda) + sum(fext) - (1/h) sum_b m_b dv_b = -(1/h) sum_f r_f."""
-    h = ref.h
-    assert ref.cM == 0.0
+    -((1 + h cM) / h) sum_b m_b dv_b, -cM sum_b m_b qvel_b, (1/h) sum_f r_f.  They add up to zero for ANY dv whose free rows leave the
+    residual r: the rows of K sum to zero over the nodes and so does f, so summing (1/h) Keff dv + (hK + D) qvel + f - fext over all
+    rows of an axis leaves ((1 + h cM) / h) sum_b m_b dv_b + cM sum_b m_b qvel_b - sum fext (m_b: the column sums of M; D = cK K + cM M);
+    the free rows contribute (1/h) r (r = Keff_ff dv_f - rhs_f: they solve the system up to r), the constrained rows lambda.  That is
+    sum(lambda) + sum(fext) - ((1 + h cM) / h) sum_b m_b dv_b - cM sum_b m_b qvel_b = -(1/h) sum_f r_f."""
+    h, cM = ref.h, ref.cM
     keff, _, g = ref.system(q, qvel, fext)
     fixed = np.asarray(fixed, np.int64)
     lam_all = (keff @ dv)[fixed] / h + g[fixed] if lam is None else np.asarray(lam, np.float64)
     mcol = np.asarray(ref.M.sum(axis=0)).reshape(-1)
-    out = np.zeros((3, 4))
+    qvel = np.asarray(qvel, np.float64)
+    out = np.zeros((3, 5))
     for a in range(3):
         out[a, 0] = lam_all[fixed % 3 == a].sum()
         out[a, 1] = np.asarray(fext, np.float64)[a::3].sum()
-        out[a, 2] = -(mcol[a::3] * dv[a::3]).sum() / h
-        out[a, 3] = residual[a::3].sum() / h
+        out[a, 2] = -(1.0 + h * cM) * (mcol[a::3] * dv[a::3]).sum() / h
+        out[a, 3] = -cM * (mcol[a::3] * qvel[a::3]).sum()
+        out[a, 4] = residual[a::3].sum() / h
     return out

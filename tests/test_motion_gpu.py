@@ -79,7 +79,7 @@ def _steps(g, ref, fixed, dofs, u, q, qv, fext, steps, tol):
         _close(qg, out["q"], tol, "q after step %d" % k)
         _close(vg, out["qvel"], 10 * tol, "qvel after step %d" % k)
         assert np.array_equal(qg[dofs], u), k                              # the target's bits
-        vs = (np.asarray(u, np.float64) - qb[dofs]) / H
+        vs = (np.asarray(u, np.float64) - qb[dofs]) / ref.h
         assert np.all(np.abs(vg[dofs] - vs) <= 4 * np.spacing(np.abs(vs))), k   # (u - q_before) / h to 4 ulp
         assert not qg[held].any() and not vg[held].any(), k                # every other constrained DOF is nailed as ever
         q, qv = out["q"], out["qvel"]
@@ -345,7 +345,7 @@ def _check_reactions(g, ref, fixed, dofs, u, qb, vb, fext, rtol, momentum=False)
     free[fixed] = False
     dv = np.zeros(ref.r)
     dv[free] = (va - vb)[free]
-    dv[dofs] = (np.asarray(u, np.float64) - qb[dofs]) / H - vb[dofs]
+    dv[dofs] = (np.asarray(u, np.float64) - qb[dofs]) / ref.h - vb[dofs]
     lam_ref = reactions_at(ref, qb, vb, fext, dofs, dv)
     lam, s3 = g.reactions()
     _close(lam, lam_ref, rtol, "reactions")
