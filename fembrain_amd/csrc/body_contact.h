@@ -22,6 +22,14 @@ struct BodyContactRec {
   int far;            // the search through the grid gave the point up at its budget
 };
 
+// What the friction calls keep per contact beside its BodyContactRec (contact_friction.hip.h): only their force kernels write it
+struct ContactFrictionRec {
+  double N;      // the normal force after damping, never negative
+  double s;      // |t|
+  double t[3];   // the tangential velocity of the point relative to the face
+  double mf[3];  // -f, the friction on the point's node
+};
+
 // The working state of the calls, kept in handle `a`.  Nothing is allocated before the first call; everything grows only.
 struct BodyContactWork {
   hipEvent_t ev_in = nullptr, ev_out = nullptr;  // the other handle's stream -> this one's, and back
@@ -41,9 +49,11 @@ struct BodyContactWork {
   DevBuf<BodyContactRec> rec;        // [contacts]
   DevBuf<uint32_t> r_key, r_key_s, r_val, r_val_s;  // the other side's records (node | 3 contact + corner), before and after the sort
   DevBuf<double> scratch[2];         // fb_fem_time_body_contact: what the scatter adds into instead of the force vectors
+  DevBuf<ContactFrictionRec> fric;   // [contacts] fb_fem_body_contact_friction only
   // the last call, per direction
   std::vector<BodyContactRec> host[2];
   fb_fem_body_contact_info info = {};
+  std::vector<ContactFrictionRec> fric_host[2];  // the last friction call, per direction
   ~BodyContactWork() {
     if (ev_in) (void)hipEventDestroy(ev_in);
     if (ev_out) (void)hipEventDestroy(ev_out);

@@ -60,6 +60,7 @@
 #include <cstring>
 #include <vector>
 
+#include "contact_friction.hip.h"
 #include "device_prims.hip.h"
 #include "embed_grid.hip.h"
 #include "face_search.hip.h"
@@ -405,6 +406,44 @@ __global__ __launch_bounds__(kB) void k_bc_force(SearchDev S, double stiffness, 
   }
 }
 
+// k_bc_force under the friction law (contact_friction.hip.h): the same push test, own-node addition and records, F the law's total --
+// normal force with damping, minus the friction -- from the velocities of the point's node in P and of the face's corners in T, read
+// from the handles' own qvel arrays (internal order, as the positions).  side[t]: N, |t|, t, -f; zero for a contact that pushes nothing.
+__global__ __launch_bounds__(kB) void k_bc_force_friction(SearchDev S, double stiffness, double depth_cap, FrictionLaw law, const double* __restrict__ qvel_p,
+                                                          const double* __restrict__ qvel_t, BodyContactRec* __restrict__ rec, ContactFrictionRec* __restrict__ side,
+                                                          double* __restrict__ fext_p, uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+  const int t = blockIdx.x * kB + threadIdx.x;
+  if (t >= S.n_contacts) return;
+  double p[3] = {0.0, 0.0, 0.0};
+  const int vr = contact_point(S, t, p);
+  const BodyContactRec r = rec[t];
+  const bool push = vr >= 0 && (unsigned)r.face < (unsigned)S.nf && r.d > 0.0;
+  ContactFrictionRec o = {0.0, 0.0, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+  if (push) {
+    const int nd = S.vnode[vr];
+    double vp[3], vt[3][3], F[3];
+    node_velocity(qvel_p, S.n_nodes_p, nd, vp);
+#pragma unroll
+    for (int k = 0; k < 3; k++) node_velocity(qvel_t, S.n_nodes_t, S.faces_int[3 * (size_t)r.face + k], vt[k]);
+    contact_friction_law(p, r.c, r.b, r.d, stiffness, depth_cap, law, vp, vt, F, o);
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      fext_p[3 * (size_t)nd + k] += F[k];
+      rec[t].f[k] = F[k];
+    }
+  } else {
+    rec[t].d = 0.0;  // (nothing is pushed: degenerate)
+  }
+  side[t] = o;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    int nd = push ? S.faces_int[3 * (size_t)r.face + k] : S.n_nodes_t;
+    if ((unsigned)nd >= (unsigned)S.n_nodes_t) nd = S.n_nodes_t;  // (no node: sorted behind every node, and skipped)
+    keys[3 * (size_t)t + k] = (uint32_t)nd;
+    vals[3 * (size_t)t + k] = (uint32_t)(3 * t + k);
+  }
+}
+
 // A thread per sorted record: the first of a node's segment does that node's additions in record order
 __global__ __launch_bounds__(kB) void k_bc_segments(int n_rec, const uint32_t* __restrict__ keys_s, const uint32_t* __restrict__ vals_s, int n_contacts, int n_nodes_t,
                                                     const BodyContactRec* __restrict__ rec, double* __restrict__ fext_t) {
@@ -491,9 +530,11 @@ struct DirResult {
 };
 
 // One direction: the surface vertices of P against T.  s: the calling handle's stream; fext_p / fext_t: where the forces are added.
+// law: null for the frictionless rule; else the friction call's, its side records into side_out.
 int run_direction(hipStream_t s, BodyContactWork& W, PlanWorkspace& ws, const Body& P, const Body& T, const fb_fem_body_contact_params& prm, double* fext_p, double* fext_t,
-                  Stages& tm, std::vector<BodyContactRec>& out, DirResult& res) {
+                  Stages& tm, std::vector<BodyContactRec>& out, DirResult& res, const FrictionLaw* law = nullptr, std::vector<ContactFrictionRec>* side_out = nullptr) {
   out.clear();
+  if (side_out) side_out->clear();
   const SurfaceWork& SP = P.h->surf;
   const SurfaceWork& ST = T.h->surf;
   const int nv = SP.n_vertices, nf = ST.n_faces;
@@ -619,10 +660,19 @@ int run_direction(hipStream_t s, BodyContactWork& W, PlanWorkspace& ws, const Bo
   FB_TRY(tm.begin());
   const size_t n_rec = (size_t)3 * n_contacts;
   FB_TRY(W.r_key.reserve(n_rec)); FB_TRY(W.r_key_s.reserve(n_rec)); FB_TRY(W.r_val.reserve(n_rec)); FB_TRY(W.r_val_s.reserve(n_rec));
-  FB_TRY(launch_1d(k_bc_force, n_contacts, s, S, prm.stiffness, prm.depth_cap, W.rec.p, fext_p, W.r_key.p, W.r_val.p));
+  if (law) {
+    FB_TRY(W.fric.reserve((size_t)n_contacts));
+    FB_TRY(launch_1d(k_bc_force_friction, n_contacts, s, S, prm.stiffness, prm.depth_cap, *law, P.h->qvel.p, T.h->qvel.p, W.rec.p, W.fric.p, fext_p, W.r_key.p, W.r_val.p));
+  } else {
+    FB_TRY(launch_1d(k_bc_force, n_contacts, s, S, prm.stiffness, prm.depth_cap, W.rec.p, fext_p, W.r_key.p, W.r_val.p));
+  }
   FB_TRY(sort_pairs(ws.temp, s, W.r_key.p, W.r_key_s.p, W.r_val.p, W.r_val_s.p, n_rec, (unsigned)bits_of((long long)T.n_nodes + 1)));
   FB_TRY(launch_1d(k_bc_segments, (long long)n_rec, s, (int)n_rec, W.r_key_s.p, W.r_val_s.p, n_contacts, T.n_nodes, W.rec.p, fext_t));
   out.resize((size_t)n_contacts);
+  if (law && side_out) {
+    side_out->resize((size_t)n_contacts);
+    FB_HIP(hipMemcpyAsync(side_out->data(), W.fric.p, sizeof(ContactFrictionRec) * (size_t)n_contacts, hipMemcpyDeviceToHost, s));  // (the wait below covers it)
+  }
   FB_TRY(W.rec.download(out.data(), (size_t)n_contacts, s));  // a host wait
   FB_TRY(tm.end(4));
   return FB_OK;
@@ -642,8 +692,10 @@ int check_pair(fb_fem_s* a, fb_fem_s* b, const fb_fem_body_contact_params* p) {
   return FB_OK;
 }
 
-// add: into the two external force vectors, the result kept for fb_fem_read_body_contact; else into scratch, nothing kept (seconds: the stages)
-int body_contact(fb_fem_s* a, fb_fem_s* b, const fb_fem_body_contact_params& prm, bool add, double* seconds, fb_fem_body_contact_info* out) {
+// add: into the two external force vectors, the result kept for fb_fem_read_body_contact; else into scratch, nothing kept (seconds: the stages).
+// fr: null for the frictionless call; else the friction call's parameters, fout its info.
+int body_contact(fb_fem_s* a, fb_fem_s* b, const fb_fem_body_contact_params& prm, bool add, double* seconds, fb_fem_body_contact_info* out,
+                 const fb_fem_contact_friction_params* fr = nullptr, fb_fem_contact_friction_info* fout = nullptr) {
   BodyContactWork& W = a->bodyc;
   hipStream_t s = a->stream;
   // both surfaces belong to the current meshes (each is built on its own handle's stream, with its host waits)
@@ -656,17 +708,25 @@ int body_contact(fb_fem_s* a, fb_fem_s* b, const fb_fem_body_contact_params& prm
   Stages tm;
   tm.W = &W; tm.s = s; tm.seconds = seconds;
   FB_TRY(tm.begin());
-  FB_TRY(W.boxes.reserve(24));
+  const size_t n_boxes = fr ? 25 : 24;  // (the friction call: behind the boxes the flag of a velocity that is not finite, read in the same wait)
+  FB_TRY(W.boxes.reserve(n_boxes));
   FB_TRY(body_boxes(s, W, a, 0));
   FB_TRY(body_boxes(s, W, b, 1));
-  double boxes[24];
-  FB_TRY(W.boxes.download(boxes, 24, s));  // a host wait
+  if (fr) {
+    FB_HIP(hipMemsetAsync(W.boxes.p + 24, 0, sizeof(double), s));
+    FB_TRY(launch_1d(k_cf_finite, 3LL * a->plan.n_global, s, 3LL * a->plan.n_global, a->qvel.p, W.boxes.p + 24));
+    FB_TRY(launch_1d(k_cf_finite, 3LL * b->plan.n_global, s, 3LL * b->plan.n_global, b->qvel.p, W.boxes.p + 24));
+  }
+  double boxes[25];
+  boxes[24] = 0.0;
+  FB_TRY(W.boxes.download(boxes, n_boxes, s));  // a host wait
   FB_TRY(tm.end(0));
   Body A = {a, a->plan.n_global, a->plan.n_tets, W.cur[0].p, {}, {}, a->fext.p}, B = {b, b->plan.n_global, b->plan.n_tets, W.cur[1].p, {}, {}, b->fext.p};
   memcpy(A.node_box, boxes, sizeof(double) * 6); memcpy(A.surf_box, boxes + 6, sizeof(double) * 6);
   memcpy(B.node_box, boxes + 12, sizeof(double) * 6); memcpy(B.surf_box, boxes + 18, sizeof(double) * 6);
   for (int k = 0; k < 6; k++)
     if (!std::isfinite(A.node_box[k]) || !std::isfinite(B.node_box[k])) return fail(FB_EINVAL, "fb_fem_body_contact: a position of a body is not finite");
+  if (boxes[24] != 0.0) return fail(FB_EINVAL, "fb_fem_body_contact_friction: a velocity of a body is not finite");
   if (!add) {
     FB_TRY(W.scratch[0].reserve((size_t)3 * A.n_nodes)); FB_TRY(W.scratch[1].reserve((size_t)3 * B.n_nodes));
     FB_TRY(W.scratch[0].zero(s)); FB_TRY(W.scratch[1].zero(s));
@@ -675,14 +735,19 @@ int body_contact(fb_fem_s* a, fb_fem_s* b, const fb_fem_body_contact_params& prm
   fb_fem_body_contact_info I;
   memset(&I, 0, sizeof(I));
   std::vector<BodyContactRec> recs[2];
+  std::vector<ContactFrictionRec> side[2];
+  fb_fem_contact_friction_info FI;
+  memset(&FI, 0, sizeof(FI));
+  const FrictionLaw law = {fr ? fr->mu : 0.0, fr ? fr->slip_speed : 0.0, fr ? fr->damping : 0.0};
   int rc = FB_OK;
   for (int dir = 0; dir < 2 && rc == FB_OK; dir++) {
     if (!(prm.directions & (dir == 0 ? FB_BODY_A_INTO_B : FB_BODY_B_INTO_A))) continue;
     const Body& P = dir == 0 ? A : B;
     const Body& T = dir == 0 ? B : A;
     DirResult R;
-    rc = run_direction(s, W, a->plan_ws, P, T, prm, P.fext, T.fext, tm, recs[dir], R);
+    rc = run_direction(s, W, a->plan_ws, P, T, prm, P.fext, T.fext, tm, recs[dir], R, fr ? &law : nullptr, fr ? &side[dir] : nullptr);
     if (rc != FB_OK) break;
+    if (fr) friction_sums(recs[dir], side[dir], *fr, dir, FI);
     I.n_candidates[dir] = R.n_candidates; I.n_contacts[dir] = R.n_contacts;
     I.n_tet_grid_builds += R.tet_grids; I.n_face_grid_builds += R.face_grids;
     if (R.n_contacts > 0) I.path = R.path;
@@ -707,8 +772,10 @@ int body_contact(fb_fem_s* a, fb_fem_s* b, const fb_fem_body_contact_params& prm
   if (add) {
     W.host[0].swap(recs[0]); W.host[1].swap(recs[1]);
     W.info = I;
+    if (fr) { W.fric_host[0].swap(side[0]); W.fric_host[1].swap(side[1]); }
   }
   if (out) *out = I;
+  if (fr && fout) *fout = FI;
   return FB_OK;
 }
 
@@ -722,6 +789,22 @@ int fb_fem_body_contact(fb_fem_t a, fb_fem_t b, const fb_fem_body_contact_params
   CHECK_HANDLE(b);
   FB_TRY(check_pair(a, b, p));
   return body_contact(a, b, *p, true, nullptr, out);
+}
+
+int fb_fem_body_contact_friction(fb_fem_t a, fb_fem_t b, const fb_fem_body_contact_params* p, const fb_fem_contact_friction_params* fr, fb_fem_body_contact_info* out,
+                                 fb_fem_contact_friction_info* fout) {
+  CHECK_HANDLE(a);
+  CHECK_HANDLE(b);
+  FB_TRY(check_pair(a, b, p));
+  FB_TRY(check_friction(fr, "fb_fem_body_contact_friction"));
+  return body_contact(a, b, *p, true, nullptr, out, fr, fout);
+}
+
+int fb_fem_read_body_contact_friction(fb_fem_t a, int direction, double* normal_force, double* slip3, double* friction3) {
+  CHECK_HANDLE(a);
+  if (direction != FB_BODY_A_INTO_B && direction != FB_BODY_B_INTO_A) return fail(FB_EINVAL, "fb_fem_read_body_contact_friction: direction %d", direction);
+  read_friction(a->bodyc.fric_host[direction == FB_BODY_A_INTO_B ? 0 : 1], normal_force, slip3, friction3);
+  return FB_OK;
 }
 
 int fb_fem_read_body_contact(fb_fem_t a, int direction, int* node, int* element, int* face, double* closest_xyz, double* bary3, double* depth) {

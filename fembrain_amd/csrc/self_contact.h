@@ -40,9 +40,11 @@ struct SelfContactWork {
   DevBuf<BodyContactRec> rec;  // [contacts]
   DevBuf<uint32_t> r_key, r_key_s, r_val, r_val_s;  // the records (node | 4 contact + record), before and after the sort
   DevBuf<double> scratch;     // fb_fem_time_self_contact: what the scatter adds into instead of the force vector
+  DevBuf<ContactFrictionRec> fric;  // [contacts] fb_fem_self_contact_friction only
   // the last adding call
   std::vector<BodyContactRec> host;
   fb_fem_self_contact_info info = {};
+  std::vector<ContactFrictionRec> fric_host;  // the last friction call
   ~SelfContactWork() {
     for (auto& e : ev_t) if (e) (void)hipEventDestroy(e);
   }

@@ -36,6 +36,7 @@
 #include <cstring>
 #include <vector>
 
+#include "contact_friction.hip.h"
 #include "device_prims.hip.h"
 #include "embed_grid.hip.h"
 #include "face_search.hip.h"
@@ -404,6 +405,40 @@ __global__ __launch_bounds__(kB) void k_sc_force(SearchDev S, double stiffness, 
   }
 }
 
+// k_sc_force under the friction law (contact_friction.hip.h): the same push test and records, F the law's total from the velocities of
+// the point's node and of the face's corners -- one body, one qvel array, internal order.  side[t]: N, |t|, t, -f; zero for a contact
+// that pushes nothing.
+__global__ __launch_bounds__(kB) void k_sc_force_friction(SearchDev S, double stiffness, double depth_cap, FrictionLaw law, const double* __restrict__ qvel,
+                                                          BodyContactRec* __restrict__ rec, ContactFrictionRec* __restrict__ side, uint32_t* __restrict__ keys,
+                                                          uint32_t* __restrict__ vals) {
+  const int t = blockIdx.x * kB + threadIdx.x;
+  if (t >= S.n_contacts) return;
+  double p[3] = {0.0, 0.0, 0.0};
+  const int vr = contact_point(S, t, p);
+  const BodyContactRec r = rec[t];
+  const bool push = vr >= 0 && (unsigned)r.face < (unsigned)S.nf && r.d > 0.0;
+  ContactFrictionRec o = {0.0, 0.0, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+  if (push) {
+    double vp[3], vt[3][3], F[3];
+    node_velocity(qvel, S.n_nodes_p, S.vnode[vr], vp);
+#pragma unroll
+    for (int k = 0; k < 3; k++) node_velocity(qvel, S.n_nodes_t, S.faces_int[3 * (size_t)r.face + k], vt[k]);
+    contact_friction_law(p, r.c, r.b, r.d, stiffness, depth_cap, law, vp, vt, F, o);
+#pragma unroll
+    for (int k = 0; k < 3; k++) rec[t].f[k] = F[k];
+  } else {
+    rec[t].d = 0.0;  // (nothing is pushed: degenerate, or no face left)
+  }
+  side[t] = o;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    int nd = !push ? S.n_nodes_t : k == 0 ? S.vnode[vr] : S.faces_int[3 * (size_t)r.face + (k - 1)];
+    if ((unsigned)nd >= (unsigned)S.n_nodes_t) nd = S.n_nodes_t;  // (no node: sorted behind every node, and skipped)
+    keys[4 * (size_t)t + k] = (uint32_t)nd;
+    vals[4 * (size_t)t + k] = (uint32_t)(4 * t + k);
+  }
+}
+
 // A thread per sorted record: the first of a node's segment does that node's additions in record order, however many they are
 __global__ __launch_bounds__(kB) void k_sc_segments(int n_rec, const uint32_t* __restrict__ keys_s, const uint32_t* __restrict__ vals_s, int n_contacts, int n_nodes,
                                                     const BodyContactRec* __restrict__ rec, double* __restrict__ fext) {
@@ -471,8 +506,10 @@ int check_self(fb_fem_s* h, const fb_fem_self_contact_params* p) {
 
 constexpr int kWideWorkgroups = 64;  // of k_sc_contain_wide: 256 wavefronts share the overflow list
 
-// add: into the external force vector, the result kept for fb_fem_read_self_contact; else into scratch, nothing kept (seconds: the stages)
-int self_contact(fb_fem_s* h, const fb_fem_self_contact_params& prm, bool add, double* seconds, fb_fem_self_contact_info* out) {
+// add: into the external force vector, the result kept for fb_fem_read_self_contact; else into scratch, nothing kept (seconds: the stages).
+// fr: null for the frictionless call; else the friction call's parameters, fout its info.
+int self_contact(fb_fem_s* h, const fb_fem_self_contact_params& prm, bool add, double* seconds, fb_fem_self_contact_info* out,
+                 const fb_fem_contact_friction_params* fr = nullptr, fb_fem_contact_friction_info* fout = nullptr) {
   SelfContactWork& W = h->selfc;
   PlanWorkspace& ws = h->plan_ws;
   hipStream_t s = h->stream;
@@ -497,16 +534,24 @@ int self_contact(fb_fem_s* h, const fb_fem_self_contact_params& prm, bool add, d
   // ---- positions and box ----
   FB_TRY(tm.begin());
   const int nb = blocks_for(n_nodes);
-  FB_TRY(W.cur.reserve((size_t)3 * n_nodes)); FB_TRY(W.box_part.reserve((size_t)6 * nb)); FB_TRY(W.boxes.reserve(6));
+  const size_t n_box = fr ? 7 : 6;  // (the friction call: behind the box the flag of a velocity that is not finite, read in the same wait)
+  FB_TRY(W.cur.reserve((size_t)3 * n_nodes)); FB_TRY(W.box_part.reserve((size_t)6 * nb)); FB_TRY(W.boxes.reserve(n_box));
   FB_TRY(launch_1d(k_sc_positions, n_nodes, s, n_nodes, h->x0.p, h->q.p, W.cur.p, W.box_part.p));
   FB_TRY(launch_grid(k_box_final<double>, dim3(1), s, nb, W.box_part.p, W.boxes.p));
-  double box[6];
-  FB_TRY(W.boxes.download(box, 6, s));  // a host wait
+  if (fr) {
+    FB_HIP(hipMemsetAsync(W.boxes.p + 6, 0, sizeof(double), s));
+    FB_TRY(launch_1d(k_cf_finite, 3LL * n_nodes, s, 3LL * n_nodes, h->qvel.p, W.boxes.p + 6));
+  }
+  double box[7];
+  box[6] = 0.0;
+  FB_TRY(W.boxes.download(box, n_box, s));  // a host wait
   FB_TRY(tm.end(0));
   for (int k = 0; k < 6; k++)
     if (!std::isfinite(box[k])) return fail(FB_EINVAL, "fb_fem_self_contact: a position of the body is not finite");
+  if (box[6] != 0.0) return fail(FB_EINVAL, "fb_fem_self_contact_friction: a velocity of the body is not finite");
   const bool nothing = nv <= 0 || nf <= 0 || n_tets <= 0 || (by_part && h->parts.n_parts < 2);  // (one part has nothing to meet: no grid, no write)
   std::vector<BodyContactRec> recs;
+  std::vector<ContactFrictionRec> side;
   int n_found = 0;
   double* fext = h->fext.p;
   if (!add) {
@@ -606,21 +651,34 @@ int self_contact(fb_fem_s* h, const fb_fem_self_contact_params& prm, bool add, d
     FB_TRY(tm.begin());
     const size_t n_rec = (size_t)4 * n_found;
     FB_TRY(W.r_key.reserve(n_rec)); FB_TRY(W.r_key_s.reserve(n_rec)); FB_TRY(W.r_val.reserve(n_rec)); FB_TRY(W.r_val_s.reserve(n_rec));
-    FB_TRY(launch_1d(k_sc_force, n_found, s, S, prm.stiffness, prm.depth_cap, W.rec.p, W.r_key.p, W.r_val.p));
+    if (fr) {
+      const FrictionLaw law = {fr->mu, fr->slip_speed, fr->damping};
+      FB_TRY(W.fric.reserve((size_t)n_found));
+      FB_TRY(launch_1d(k_sc_force_friction, n_found, s, S, prm.stiffness, prm.depth_cap, law, h->qvel.p, W.rec.p, W.fric.p, W.r_key.p, W.r_val.p));
+    } else {
+      FB_TRY(launch_1d(k_sc_force, n_found, s, S, prm.stiffness, prm.depth_cap, W.rec.p, W.r_key.p, W.r_val.p));
+    }
     FB_TRY(sort_pairs(ws.temp, s, W.r_key.p, W.r_key_s.p, W.r_val.p, W.r_val_s.p, n_rec, (unsigned)bits_of((long long)n_nodes + 1)));
     FB_TRY(launch_1d(k_sc_segments, (long long)n_rec, s, (int)n_rec, W.r_key_s.p, W.r_val_s.p, n_found, n_nodes, W.rec.p, fext));
     recs.resize((size_t)n_found);
+    if (fr) {
+      side.resize((size_t)n_found);
+      FB_HIP(hipMemcpyAsync(side.data(), W.fric.p, sizeof(ContactFrictionRec) * (size_t)n_found, hipMemcpyDeviceToHost, s));  // (the wait below covers it)
+    }
     FB_TRY(W.rec.download(recs.data(), (size_t)n_found, s));  // a host wait
     FB_TRY(tm.end(4));
   }
 
   // the sums, in record order; a contact without a face is dropped here (it made no record that counts)
   std::vector<BodyContactRec> kept;
+  std::vector<ContactFrictionRec> kept_side;
   kept.reserve(recs.size());
-  for (const BodyContactRec& r : recs) {
+  for (size_t i = 0; i < recs.size(); i++) {
+    const BodyContactRec& r = recs[i];
     I.faces_tested += r.tested;
     if (r.face < 0) continue;
     kept.push_back(r);
+    if (fr) kept_side.push_back(side[i]);
     if (!(r.d > 0.0)) { I.n_degenerate++; continue; }
     const double depth = prm.depth_cap > 0.0 ? std::min(r.d, prm.depth_cap) : r.d;
     I.max_depth = std::max(I.max_depth, depth);
@@ -629,9 +687,16 @@ int self_contact(fb_fem_s* h, const fb_fem_self_contact_params& prm, bool add, d
       for (int k = 0; k < 3; k++) I.force_on_faces[k] += (-r.f[k]) * r.b[c];
   }
   I.n_contacts = (int)kept.size();
+  if (fr) {
+    fb_fem_contact_friction_info FI;
+    memset(&FI, 0, sizeof(FI));
+    friction_sums(kept, kept_side, *fr, 0, FI);
+    if (fout) *fout = FI;
+  }
   if (add) {
     W.host.swap(kept);
     W.info = I;
+    if (fr) W.fric_host.swap(kept_side);
   }
   if (out) *out = I;
   return FB_OK;
@@ -646,6 +711,20 @@ int fb_fem_self_contact(fb_fem_t h, const fb_fem_self_contact_params* p, fb_fem_
   CHECK_HANDLE(h);
   FB_TRY(check_self(h, p));
   return self_contact(h, *p, true, nullptr, out);
+}
+
+int fb_fem_self_contact_friction(fb_fem_t h, const fb_fem_self_contact_params* p, const fb_fem_contact_friction_params* fr, fb_fem_self_contact_info* out,
+                                 fb_fem_contact_friction_info* fout) {
+  CHECK_HANDLE(h);
+  FB_TRY(check_self(h, p));
+  FB_TRY(check_friction(fr, "fb_fem_self_contact_friction"));
+  return self_contact(h, *p, true, nullptr, out, fr, fout);
+}
+
+int fb_fem_read_self_contact_friction(fb_fem_t h, double* normal_force, double* slip3, double* friction3) {
+  CHECK_HANDLE(h);
+  read_friction(h->selfc.fric_host, normal_force, slip3, friction3);
+  return FB_OK;
 }
 
 int fb_fem_read_self_contact(fb_fem_t h, int* node, int* element, int* face, double* closest_xyz, double* bary3, double* depth) {

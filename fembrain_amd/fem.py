@@ -682,19 +682,56 @@ class FemIntegrator:
         p.directions = self._BODY_DIRECTIONS[directions] if isinstance(directions, str) else int(directions)
         return p
 
-    def body_contact(self, other, stiffness, depth_cap=0.0, directions="both"):
+    @staticmethod
+    def _friction_params(mu, slip_speed, damping):
+        fr = _l.ContactFrictionParams()
+        fr.mu, fr.slip_speed, fr.damping, fr.reserved = float(mu), float(slip_speed), float(damping), 0.0
+        return fr
+
+    @staticmethod
+    def _friction_info(fi):
+        return dict(n_sticking=tuple(fi.n_sticking), n_sliding=tuple(fi.n_sliding), n_separating=tuple(fi.n_separating), max_slip_speed=float(fi.max_slip_speed),
+                    max_normal_force=float(fi.max_normal_force), max_stick_rate=float(fi.max_stick_rate),
+                    friction_on_points=np.array([fi.friction_on_points[0][:], fi.friction_on_points[1][:]]))
+
+    def body_contact(self, other, stiffness, depth_cap=0.0, directions="both", mu=0.0, slip_speed=0.0, damping=0.0):
         """Penalty contact between this body (a) and ``other`` (b) at their current states, ADDED into both external force vectors (set
         gravity or zero first): every surface vertex of one body that lies inside an element of the other is pushed to the closest point
         of the other's boundary with F = stiffness * min(depth, depth_cap) * n (no cap where depth_cap is 0), and the face that holds that
         point is pushed back by -F, spread by its weights.  directions: "both", "a_into_b" (this body's vertices in ``other``), "b_into_a",
-        or the FB_BODY_* bits.  Returns the dict of the fb_fem_body_contact_info fields; counts are (a into b, b into a)."""
+        or the FB_BODY_* bits.  Returns the dict of the fb_fem_body_contact_info fields; counts are (a into b, b into a).
+        mu, slip_speed, damping: with any of them non-zero the force law is fb_fem_body_contact_friction's -- regularised Coulomb friction
+        (linear below slip_speed, mu N at and above it) and a damper along the normal, from the two bodies' velocities; explicit, so keep
+        mu N / slip_speed * dt and damping * dt below the mass a contact pushes (``max_stick_rate`` comes back for that).  The dict then
+        also holds the fb_fem_contact_friction_info fields."""
         p, info = self._body_params(stiffness, depth_cap, directions), _l.BodyContactInfo()
-        _l.check(self._L.fb_fem_body_contact(self.h, other.h, C.byref(p), C.byref(info)))
+        friction = None
+        if mu == 0.0 and slip_speed == 0.0 and damping == 0.0:
+            _l.check(self._L.fb_fem_body_contact(self.h, other.h, C.byref(p), C.byref(info)))
+        else:
+            fr, fi = self._friction_params(mu, slip_speed, damping), _l.ContactFrictionInfo()
+            _l.check(self._L.fb_fem_body_contact_friction(self.h, other.h, C.byref(p), C.byref(fr), C.byref(info), C.byref(fi)))
+            friction = self._friction_info(fi)
         out = dict(n_candidates=tuple(info.n_candidates), n_contacts=tuple(info.n_contacts), n_degenerate=tuple(info.n_degenerate), path=int(info.path),
                    n_tet_grid_builds=int(info.n_tet_grid_builds), n_face_grid_builds=int(info.n_face_grid_builds), faces_tested=int(info.faces_tested),
                    max_depth=float(info.max_depth), force_on_a=np.array(info.force_on_a[:]), force_on_b=np.array(info.force_on_b[:]))
         self._body_contacts = out["n_contacts"]
+        if friction is not None:
+            out.update(friction)
+            self._body_friction_contacts = out["n_contacts"]
         return out
+
+    def read_body_contact_friction(self, direction):
+        """Per contact of one direction of the last ``body_contact`` that ran with friction or damping, in ``read_body_contact``'s order:
+        dict of normal_force (k,) N, slip (k, 3) the tangential velocity of the point relative to the face, and friction (k, 3) the
+        friction on the point's node, -f."""
+        d = self._BODY_DIRECTIONS[direction] if isinstance(direction, str) else int(direction)
+        if d not in (_l.FB_BODY_A_INTO_B, _l.FB_BODY_B_INTO_A):
+            raise ValueError("one direction, not %r" % (direction,))
+        k = getattr(self, "_body_friction_contacts", (0, 0))[0 if d == _l.FB_BODY_A_INTO_B else 1]
+        N, slip, friction = np.zeros(k), np.zeros((k, 3)), np.zeros((k, 3))
+        _l.check(self._L.fb_fem_read_body_contact_friction(self.h, d, _l.dptr(N), _l.dptr(slip), _l.dptr(friction)))
+        return dict(normal_force=N, slip=slip, friction=friction)
 
     def read_body_contact(self, direction):
         """The contacts of one direction ("a_into_b" / "b_into_a" or the FB_BODY_* bit) of the last ``body_contact`` of this handle: dict of
@@ -725,20 +762,38 @@ class FemIntegrator:
         p.mode = self._SELF_MODES[mode] if isinstance(mode, str) else int(mode)
         return p
 
-    def self_contact(self, stiffness, depth_cap=0.0, mode="any"):
+    def self_contact(self, stiffness, depth_cap=0.0, mode="any", mu=0.0, slip_speed=0.0, damping=0.0):
         """Penalty contact of this body with itself at its current state, ADDED into the external force vector (set gravity or zero first):
         every surface vertex that lies inside an element it may meet is pushed to the closest point of the boundary it may meet with
         F = stiffness * min(depth, depth_cap) * n (no cap where depth_cap is 0), and the face there is pushed back by -F, spread by its
         weights.  mode "any": a vertex may not meet the elements and faces that use its own node (a fold of one part); "other_parts": it may
         not meet its own part (the halves of a cut; the labels of ``parts`` are built first where they are stale); or the FB_SELF_CONTACT_*
-        values.  Returns the dict of the fb_fem_self_contact_info fields."""
+        values.  Returns the dict of the fb_fem_self_contact_info fields.  mu, slip_speed, damping: as in ``body_contact``, through
+        fb_fem_self_contact_friction; the dict then also holds the fb_fem_contact_friction_info fields (index 0 of the pairs)."""
         p, info = self._self_params(stiffness, depth_cap, mode), _l.SelfContactInfo()
-        _l.check(self._L.fb_fem_self_contact(self.h, C.byref(p), C.byref(info)))
+        friction = None
+        if mu == 0.0 and slip_speed == 0.0 and damping == 0.0:
+            _l.check(self._L.fb_fem_self_contact(self.h, C.byref(p), C.byref(info)))
+        else:
+            fr, fi = self._friction_params(mu, slip_speed, damping), _l.ContactFrictionInfo()
+            _l.check(self._L.fb_fem_self_contact_friction(self.h, C.byref(p), C.byref(fr), C.byref(info), C.byref(fi)))
+            friction = self._friction_info(fi)
         out = {name: int(getattr(info, name)) for name in ("n_points", "n_contacts", "n_degenerate", "path", "n_point_grid_builds", "n_face_grid_builds",
                                                             "n_parts_builds", "faces_tested")}
         out.update(max_depth=float(info.max_depth), force_on_points=np.array(info.force_on_points[:]), force_on_faces=np.array(info.force_on_faces[:]))
         self._self_contacts = out["n_contacts"]
+        if friction is not None:
+            out.update(friction)
+            self._self_friction_contacts = out["n_contacts"]
         return out
+
+    def read_self_contact_friction(self):
+        """Per contact of the last ``self_contact`` that ran with friction or damping, in ``read_self_contact``'s order: dict of
+        normal_force (k,), slip (k, 3) and friction (k, 3) = -f."""
+        k = getattr(self, "_self_friction_contacts", 0)
+        N, slip, friction = np.zeros(k), np.zeros((k, 3)), np.zeros((k, 3))
+        _l.check(self._L.fb_fem_read_self_contact_friction(self.h, _l.dptr(N), _l.dptr(slip), _l.dptr(friction)))
+        return dict(normal_force=N, slip=slip, friction=friction)
 
     def read_self_contact(self):
         """The contacts of the last ``self_contact``: dict of node (the vertex), element and face (``read_mesh`` / ``surface`` order), closest
@@ -1123,21 +1178,25 @@ class Deformable:
         self.on_deform = None  # FOnApplyDeformations(dof, q), Deformable.h:46
         self._embed_tris = {}  # triangles of the embeddings made through embed()
         self.collision_body, self.collision_stiffness = None, 0.0  # set_collision_body
-        self.self_collision = None  # set_self_collision: (stiffness, depth_cap, mode)
+        self.collision_friction = (0.0, 0.0, 0.0)  # set_collision_body: (mu, slip_speed, damping)
+        self.self_collision = None  # set_self_collision: (stiffness, depth_cap, mode, mu, slip_speed, damping)
 
-    def collide_with(self, other, stiffness, depth_cap=0.0):
+    def collide_with(self, other, stiffness, depth_cap=0.0, mu=0.0, slip_speed=0.0, damping=0.0):
         """Penalty contact with another ``Deformable`` on the same device at the current states of both, ADDED to the external forces of
-        both (``FemIntegrator.body_contact``).  ``timestep`` sets the forces anew before it steps: its callers use ``set_collision_body``."""
-        return self.integrator.body_contact(other.integrator, stiffness, depth_cap)
+        both (``FemIntegrator.body_contact``).  ``timestep`` sets the forces anew before it steps: its callers use ``set_collision_body``.
+        mu, slip_speed, damping: friction and contact damping, as in ``FemIntegrator.body_contact`` (all zero: the frictionless call)."""
+        return self.integrator.body_contact(other.integrator, stiffness, depth_cap, mu=mu, slip_speed=slip_speed, damping=damping)
 
-    def set_collision_body(self, other, stiffness=0.0):
+    def set_collision_body(self, other, stiffness=0.0, mu=0.0, slip_speed=0.0, damping=0.0):
         """Opt-in: every ``timestep`` adds the contact forces with ``other`` behind gravity and the probe, just before it steps (None: off).
         The call adds to both bodies and ``other`` sets its forces anew in its own ``timestep``, so two bodies that both step set each other."""
         self.collision_body, self.collision_stiffness = other, float(stiffness)
+        self.collision_friction = (float(mu), float(slip_speed), float(damping))
 
-    def self_collide(self, stiffness, depth_cap=0.0, mode="any"):
-        """Penalty contact of this body with itself at its current state, ADDED to its external forces (``FemIntegrator.self_contact``)."""
-        return self.integrator.self_contact(stiffness, depth_cap, mode)
+    def self_collide(self, stiffness, depth_cap=0.0, mode="any", mu=0.0, slip_speed=0.0, damping=0.0):
+        """Penalty contact of this body with itself at its current state, ADDED to its external forces (``FemIntegrator.self_contact``,
+        with its friction and contact damping)."""
+        return self.integrator.self_contact(stiffness, depth_cap, mode, mu=mu, slip_speed=slip_speed, damping=damping)
 
     # -- held and moved: what IAvatar::grip() only flags (IScalpel.cpp:42-44) --
     def grip(self, nodes):
@@ -1157,10 +1216,10 @@ class Deformable:
         """The force the tissue returned to the tool during the last step: minus the sum of the reactions (3,)"""
         return -self.integrator.reactions()[1]
 
-    def set_self_collision(self, stiffness=None, depth_cap=0.0, mode="other_parts"):
+    def set_self_collision(self, stiffness=None, depth_cap=0.0, mode="other_parts", mu=0.0, slip_speed=0.0, damping=0.0):
         """Opt-in: every ``timestep`` adds the body's contact forces with itself behind gravity and the probe, just before it steps
         (stiffness None: off).  mode "other_parts" for the halves of a cut, "any" for a fold of one part."""
-        self.self_collision = None if stiffness is None else (float(stiffness), float(depth_cap), mode)
+        self.self_collision = None if stiffness is None else (float(stiffness), float(depth_cap), mode, float(mu), float(slip_speed), float(damping))
 
     def set_deform_callback(self, fn):
         self.on_deform = fn
@@ -1240,7 +1299,7 @@ class Deformable:
         else:
             it.set_external_forces_to_zero()
         if self.collision_body is not None:
-            self.collide_with(self.collision_body, self.collision_stiffness)
+            self.collide_with(self.collision_body, self.collision_stiffness, 0.0, *self.collision_friction)
         if self.self_collision is not None:
             self.self_collide(*self.self_collision)
         iters = it.do_timestep()

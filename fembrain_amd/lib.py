@@ -132,6 +132,15 @@ class SelfContactInfo(C.Structure):
                 ("force_on_points", C.c_double * 3), ("force_on_faces", C.c_double * 3)]
 
 
+class ContactFrictionParams(C.Structure):
+    _fields_ = [("mu", C.c_double), ("slip_speed", C.c_double), ("damping", C.c_double), ("reserved", C.c_double)]
+
+
+class ContactFrictionInfo(C.Structure):
+    _fields_ = [("n_sticking", C.c_int * 2), ("n_sliding", C.c_int * 2), ("n_separating", C.c_int * 2), ("max_slip_speed", C.c_double),
+                ("max_normal_force", C.c_double), ("max_stick_rate", C.c_double), ("friction_on_points", (C.c_double * 3) * 2)]
+
+
 class MotionInfo(C.Structure):
     _fields_ = [("n_dofs", C.c_int), ("n_listed_elements", C.c_int), ("n_touched_nodes", C.c_int), ("longest_run", C.c_int),
                 ("table_builds", C.c_int), ("table_valid", C.c_int), ("n_grasp_nodes", C.c_int), ("reserved", C.c_int)]
@@ -273,6 +282,12 @@ def lib():
         "fb_fem_body_contact": (C.c_int, [vp, vp, C.POINTER(BodyContactParams), C.POINTER(BodyContactInfo)]),
         "fb_fem_read_body_contact": (C.c_int, [vp, C.c_int, _ip, _ip, _ip, _dp, _dp, _dp]),
         "fb_fem_time_body_contact": (C.c_int, [vp, vp, C.POINTER(BodyContactParams), C.c_int, _dp]),
+        "fb_fem_body_contact_friction": (C.c_int, [vp, vp, C.POINTER(BodyContactParams), C.POINTER(ContactFrictionParams), C.POINTER(BodyContactInfo),
+                                                   C.POINTER(ContactFrictionInfo)]),
+        "fb_fem_read_body_contact_friction": (C.c_int, [vp, C.c_int, _dp, _dp, _dp]),
+        "fb_fem_self_contact_friction": (C.c_int, [vp, C.POINTER(SelfContactParams), C.POINTER(ContactFrictionParams), C.POINTER(SelfContactInfo),
+                                                   C.POINTER(ContactFrictionInfo)]),
+        "fb_fem_read_self_contact_friction": (C.c_int, [vp, _dp, _dp, _dp]),
         "fb_fem_self_contact": (C.c_int, [vp, C.POINTER(SelfContactParams), C.POINTER(SelfContactInfo)]),
         "fb_fem_read_self_contact": (C.c_int, [vp, _ip, _ip, _ip, _dp, _dp, _dp]),
         "fb_fem_time_self_contact": (C.c_int, [vp, C.POINTER(SelfContactParams), C.c_int, _dp]),

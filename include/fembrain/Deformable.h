@@ -204,8 +204,27 @@ class HipIntegrator {
   fb_fem_body_contact_info BodyContact(HipIntegrator& other, double stiffness, double depthCap = 0.0, int directions = FB_BODY_A_INTO_B | FB_BODY_B_INTO_A) {
     const fb_fem_body_contact_params p = {stiffness, depthCap, directions, 0};
     fb_fem_body_contact_info info;
-    check(fb_fem_body_contact(h_, other.h_, &p, &info));
+    if (frictionless()) check(fb_fem_body_contact(h_, other.h_, &p, &info));
+    else check(fb_fem_body_contact_friction(h_, other.h_, &p, &friction_, &info, &frictionInfo_));
     return info;
+  }
+  // Friction and damping of the contacts BodyContact and SelfContact of THIS integrator make from here on (fembrain_hip.h, "Friction and
+  // damping of a contact"): regularised Coulomb friction, linear below slipSpeed and mu N at and above it, and a damper along the normal,
+  // from the velocities of both sides.  Explicit: keep mu N / slipSpeed * dt and damping * dt below the mass a contact pushes
+  // (LastContactFriction().max_stick_rate tells the first).  All zero, the default: the frictionless calls, as ever.
+  void SetContactFriction(double mu, double slipSpeed, double damping) {
+    friction_.mu = mu; friction_.slip_speed = slipSpeed; friction_.damping = damping; friction_.reserved = 0.0;
+  }
+  // classes, maxima and friction sums of the last BodyContact / SelfContact that ran with friction or damping
+  const fb_fem_contact_friction_info& LastContactFriction() const { return frictionInfo_; }
+  // per contact of that call, in ReadBodyContact's / ReadSelfContact's order: N, the tangential velocity t[3], the friction on the point -f[3]
+  void ReadBodyContactFriction(int direction, int n, std::vector<double>& normalForce, std::vector<double>& slip3, std::vector<double>& friction3) {
+    normalForce.assign((size_t)n, 0.0); slip3.assign(3 * (size_t)n, 0.0); friction3.assign(3 * (size_t)n, 0.0);
+    check(fb_fem_read_body_contact_friction(h_, direction, normalForce.data(), slip3.data(), friction3.data()));
+  }
+  void ReadSelfContactFriction(int n, std::vector<double>& normalForce, std::vector<double>& slip3, std::vector<double>& friction3) {
+    normalForce.assign((size_t)n, 0.0); slip3.assign(3 * (size_t)n, 0.0); friction3.assign(3 * (size_t)n, 0.0);
+    check(fb_fem_read_self_contact_friction(h_, normalForce.data(), slip3.data(), friction3.data()));
   }
   // the contacts of one direction of the last BodyContact of this integrator, info.n_contacts[direction == FB_BODY_A_INTO_B ? 0 : 1] entries
   void ReadBodyContact(int direction, int n, std::vector<int>& node, std::vector<int>& element, std::vector<int>& face, std::vector<double>& closestXyz,
@@ -220,7 +239,8 @@ class HipIntegrator {
   fb_fem_self_contact_info SelfContact(double stiffness, double depthCap = 0.0, int mode = FB_SELF_CONTACT_ANY) {
     const fb_fem_self_contact_params p = {stiffness, depthCap, mode, 0};
     fb_fem_self_contact_info info;
-    check(fb_fem_self_contact(h_, &p, &info));
+    if (frictionless()) check(fb_fem_self_contact(h_, &p, &info));
+    else check(fb_fem_self_contact_friction(h_, &p, &friction_, &info, &frictionInfo_));
     return info;
   }
   // the contacts of the last SelfContact of this integrator, info.n_contacts entries
@@ -356,6 +376,9 @@ class HipIntegrator {
   fb_fem_t h_;
   fb_fem_params prm_;
   fb_step_info info_;
+  bool frictionless() const { return friction_.mu == 0.0 && friction_.slip_speed == 0.0 && friction_.damping == 0.0; }
+  fb_fem_contact_friction_params friction_ = {0.0, 0.0, 0.0, 0.0};  // SetContactFriction
+  fb_fem_contact_friction_info frictionInfo_ = {};
 };
 
 // ---- the narrower VegaFEM seams, for hosts that keep their own integrator -------------------------
@@ -770,6 +793,10 @@ class Deformable {
   // step set each other, and each then steps with exactly one set of contact forces.  Never set: timestep() does what it always did.
   // Not owned; the caller keeps `other` alive or clears the pointer.
   void setCollisionBody(Deformable* other, double stiffness) { m_lpCollisionBody = other; m_collisionStiffness = stiffness; }
+  // Friction and damping for collideWith, selfCollide and the two timestep() opt-ins of THIS body (HipIntegrator::SetContactFriction):
+  // a piece rests on a stump whose cut is not level, and lands without ringing.  All zero, the default: the frictionless contact.
+  void setContactFriction(double mu, double slipSpeed, double damping) { m_lpIntegrator->SetContactFriction(mu, slipSpeed, damping); }
+  const fb_fem_contact_friction_info& lastContactFriction() const { return m_lpIntegrator->LastContactFriction(); }
   Deformable* getCollisionBody() const { return m_lpCollisionBody; }
   // The body against itself -- the lips of a cut in one handle, a fold: penalty contact at the current state, ADDED to the external forces
   // on the device (fb_fem_self_contact; the reference has no counterpart).  As with collideWith, a caller of timestep() opts in instead:

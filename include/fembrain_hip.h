@@ -807,6 +807,69 @@ int fb_fem_self_contact(fb_fem_t h, const fb_fem_self_contact_params* p, fb_fem_
 int fb_fem_read_self_contact(fb_fem_t h, int* node, int* element, int* face, double* closest_xyz, double* bary3, double* depth);
 int fb_fem_time_self_contact(fb_fem_t h, const fb_fem_self_contact_params* p, int reps, double seconds[5]);
 
+/* ---- Friction and damping of a contact, on the device ----
+ * fb_fem_body_contact and fb_fem_self_contact push along the normal with stiffness * depth and nothing else: a piece glides off a stump
+ * whose cut is not level and rings on the penalty spring.  The two calls below are those calls with a force law that also uses the
+ * velocity of the point relative to the face: regularised Coulomb friction and a damper along the normal.  The reference has no
+ * counterpart; the rule is this project's (tests/frictionref.py restates it in numpy).  The frictionless calls, their
+ * kernels and their bits are untouched, and a handle that never calls the new entry points allocates and launches nothing for them.
+ *
+ * Steps 1-4 of "Contact between two bodies" -- for the self call, steps 1-4 of "Contact of a body with itself", exclusions and dropped
+ * contacts included -- are unchanged.  Step 5 is replaced.  The contact has the point on node i of body P at p and the closest point c
+ * on face (j0, j1, j2) of body T with weights b0 = (1 - b1) - b2, b1, b2, and d = |c - p|.  d == 0 is degenerate as before: counted in
+ * n_degenerate, nothing pushed.  Otherwise, with vP and vT the velocities (qvel) of the two handles as fb_fem_get_state would return them
+ * at the moment of the call (one array for the self call), every operation fp64, in the order written, no contraction:
+ *     n_k   = (c_k - p_k) / d
+ *     depth = depth_cap > 0 ? min(d, depth_cap) : d
+ *     sd    = stiffness * depth
+ *     vf_k  = (b0 * vT[j0][k] + b1 * vT[j1][k]) + b2 * vT[j2][k]
+ *     w_k   = vP[i][k] - vf_k
+ *     vn    = (w_0 n_0 + w_1 n_1) + w_2 n_2
+ *     N     = sd - damping * vn;   if !(N > 0) N = 0              (no adhesion)
+ *     t_k   = w_k - vn * n_k
+ *     s     = sqrt((t_0 t_0 + t_1 t_1) + t_2 t_2)
+ *     g     = (mu * N) / max(s, slip_speed)                        (0 where max(s, slip_speed) == 0, which needs mu == 0)
+ *     f_k   = g * t_k
+ *     F_k   = N * n_k - f_k
+ * Regularised Coulomb: the friction grows linearly with the slip below slip_speed and has |f| = mu N at and above it.  +F goes to node
+ * i and (-F) * b_k to corner k through the scatter of the frictionless call (step 6 there: own-node addition and sorted corner records,
+ * a into b before b into a; the four records 4i .. 4i + 3 of the self call).  With mu == 0 and damping == 0 the rule gives the bits of
+ * the frictionless step 5.  A contact is classed by the first of these that holds: SEPARATING, N == 0 (it has d > 0, is still a contact,
+ * still comes back from the read calls, and receives a zero force); STICKING, s < slip_speed; SLIDING, anything else.
+ *
+ * The law is EXPLICIT, like the penalty force: the step that follows sees forces formed from the velocities before it.  Below slip_speed
+ * the friction is a damper of rate mu N / slip_speed on the tangential velocity, and `damping` is one on the normal velocity; an explicit
+ * damper of rate r on a mass m reverses the velocity it acts on when r dt > m.  The caller keeps
+ *     mu * N / slip_speed * dt   below the mass a contact pushes, and
+ *     damping * dt               below the same mass.
+ * (A 27 kg block resting under 384 N on its contacts with mu = 0.5 and dt = 0.01: slip_speed >= 0.5 * 384 * 0.01 / 27 = 0.071.)
+ * max_stick_rate is the largest mu * N / slip_speed of the call (0 where slip_speed == 0), so the first bound can be checked without
+ * reading anything back.
+ *
+ * `out` is filled exactly as the frictionless call fills it: force_on_* are the sums of the contributions actually added, so they hold
+ * F with friction; max_depth as before.  fout: the classes per direction ([0] / [1]: a into b / b into a; the self call uses [0]); the
+ * largest s, N and mu N / slip_speed over the contacts that are not degenerate; friction_on_points, per direction the fp64 sum of (-f)
+ * over its contacts by ascending surface vertex.  They are formed on the host, in record order.
+ * fb_fem_read_body_contact_friction / fb_fem_read_self_contact_friction: per contact of the last friction call, in the order of
+ * fb_fem_read_body_contact / fb_fem_read_self_contact, N, t[3] and -f[3] (zero for a degenerate contact); any pointer may be NULL.
+ * fb_fem_read_body_contact / fb_fem_read_self_contact serve the geometry of whichever call ran last, with or without friction.
+ * FB_EINVAL before anything is launched or written: a null fr; mu, slip_speed or damping negative or not finite; mu > 0 with
+ * slip_speed == 0; a non-zero reserved; everything the frictionless call refuses.  A velocity of either body that is not finite gives
+ * FB_EINVAL before any force vector is written (a pass over qvel raises a flag that is read in the host wait for the boxes).
+ * Stream and event ordering is the frictionless calls': b's qvel is read under the event that covers b's q. */
+typedef struct fb_fem_contact_friction_params { double mu, slip_speed, damping, reserved; } fb_fem_contact_friction_params;
+typedef struct fb_fem_contact_friction_info {
+  int n_sticking[2], n_sliding[2], n_separating[2];     /* [0] / [1]: a into b / b into a; self contact uses [0] */
+  double max_slip_speed, max_normal_force, max_stick_rate;
+  double friction_on_points[2][3];                      /* per direction: the fp64 sum of (-f) over its contacts, ascending surface vertex */
+} fb_fem_contact_friction_info;
+int fb_fem_body_contact_friction(fb_fem_t a, fb_fem_t b, const fb_fem_body_contact_params* p, const fb_fem_contact_friction_params* fr,
+                                 fb_fem_body_contact_info* out, fb_fem_contact_friction_info* fout);
+int fb_fem_read_body_contact_friction(fb_fem_t a, int direction, double* normal_force, double* slip3, double* friction3);
+int fb_fem_self_contact_friction(fb_fem_t h, const fb_fem_self_contact_params* p, const fb_fem_contact_friction_params* fr,
+                                 fb_fem_self_contact_info* out, fb_fem_contact_friction_info* fout);
+int fb_fem_read_self_contact_friction(fb_fem_t h, double* normal_force, double* slip3, double* friction3);
+
 /* ---- Constrained motion: held nodes follow a tool, reaction forces on the device ----
  * A constrained DOF is otherwise nailed to q = 0 for life.  A MOTION SET is a subset of the handle's constrained DOFs, each with a
  * target displacement u_c: a grasper that drags tissue, a clamp that moves, a displacement-driven haptic device that is told what force

@@ -14,7 +14,13 @@ and once per case:
            host by the same rule) against the elements of the mesh
   host     the route the call replaces: both states and surfaces read back, tests/bodycontactref.py's brute force on the elements the
            filter keeps and ALL faces, two force vectors uploaded.  The brute force runs on --host-points candidates per direction, evenly
-           spaced, and `scaled_seconds` scales its time to all of them: it is an estimate and labelled so."""
+           spaced, and `scaled_seconds` scales its time to all of them: it is an estimate and labelled so.
+
+    python tools/probe_body_contact.py --friction [--out profiles/body_contact_friction_probe.json]
+
+--friction: the resting case only, the piece moving at (0.2, -0.1, 0.05); one call by wall clock, the median of --reps, WITHOUT and WITH
+friction and damping (fb_fem_body_contact against fb_fem_body_contact_friction, mu 0.5, slip speed 0.15, damping 40) in the same run,
+default path.  The pair goes into a JSON of its own."""
 import argparse
 import json
 import os
@@ -123,13 +129,42 @@ def measure(ga, gb, reps, points):
     return out
 
 
+MU, SLIP, DAMPING = 0.5, 0.15, 40.0
+
+
+def measure_friction(ga, gb, reps):
+    """one call by wall clock without and with friction, from the same state"""
+    out = {}
+    for name, kw in (("frictionless", {}), ("friction", dict(mu=MU, slip_speed=SLIP, damping=DAMPING))):
+        for g in (ga, gb):
+            g.set_external_forces_to_zero()
+        info = ga.body_contact(gb, K, **kw)   # (warm)
+        walls = []
+        for _ in range(reps):
+            for g in (ga, gb):
+                g.set_external_forces_to_zero()
+            t0 = time.perf_counter()
+            info = ga.body_contact(gb, K, **kw)
+            walls.append(time.perf_counter() - t0)
+        out[name] = dict(call_seconds=median(walls), call_all=walls, path=int(info["path"]), n_contacts=list(info["n_contacts"]), faces_tested=info["faces_tested"])
+        for key in ("n_sticking", "n_sliding", "n_separating", "max_slip_speed", "max_normal_force", "max_stick_rate"):
+            if key in info:
+                out[name][key] = list(info[key]) if isinstance(info[key], tuple) else info[key]
+        print("  %-12s call %.3f ms (%s); %d contacts" % (name, 1e3 * out[name]["call_seconds"], " ".join("%.3f" % (1e3 * w) for w in walls), sum(info["n_contacts"])), flush=True)
+    out["friction_over_frictionless"] = out["friction"]["call_seconds"] / out["frictionless"]["call_seconds"]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "body_contact_probe.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--friction", action="store_true")
     ap.add_argument("--n", type=int, default=56)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--host-points", type=int, default=128)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "body_contact_friction_probe.json" if a.friction else "body_contact_probe.json")
     n, h = a.n, 0.1
     v, t = truth_cube(n, n, n, h)
     v = np.asarray(v, np.float64).reshape(-1, 3)
@@ -150,6 +185,19 @@ def main():
     x = piece.read_mesh()[0]
     lift = np.array([v[:, 0].min() + 0.37 * h - x[:, 0].min(), v[:, 1].max() - 0.3 * h - x[:, 1].min(), 0.41 * h])
     piece.set_q_state(np.tile(lift, len(x)))
+    if a.friction:
+        piece.set_q_state(np.tile(lift, len(x)), np.tile([0.2, -0.1, 0.05], len(x)))
+        print("resting, without and with friction:", flush=True)
+        pair = measure_friction(piece, stump, a.reps)
+        piece.close()
+        stump.close()
+        out = dict(tool="tools/probe_body_contact.py --friction", mesh="cube %d^3 after a mid-span cut, the free half detached and laid onto the stump" % n, reps=a.reps,
+                   stiffness=K, mu=MU, slip_speed=SLIP, damping=DAMPING, sizes=sizes, resting=pair, kernel_sources_sha256=fl.source_sha256("fem"))
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1, sort_keys=True)
+            f.write("\n")
+        print("wrote", a.out)
+        return
     print("resting:", flush=True)
     cases["resting"] = measure(piece, stump, a.reps, a.host_points)
     piece.close()

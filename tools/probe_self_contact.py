@@ -13,7 +13,13 @@ Yardsticks, measured in the same run:
   detach   fb_fem_body_contact on the same two halves at the same positions after detach_part(remove=True): two handles, the call and
            its stages (default path)
 Also written: the point grid's cell count by the library's grid rule and the elements per cell, the first thing to tune where the
-containment stage is what costs."""
+containment stage is what costs.
+
+    python tools/probe_self_contact.py --friction [--out profiles/self_contact_friction_probe.json]
+
+--friction: the same pressed handle with the free half moving at (0.2, -0.1, 0.05); one call by wall clock, the median of --reps, WITHOUT
+and WITH friction and damping (fb_fem_self_contact against fb_fem_self_contact_friction, mu 0.5, slip speed 0.15, damping 40) in the same
+run, default path.  The pair goes into a JSON of its own."""
 import argparse
 import json
 import os
@@ -42,10 +48,13 @@ def median(xs):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "self_contact_probe.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--friction", action="store_true")
     ap.add_argument("--n", type=int, default=56)
     ap.add_argument("--reps", type=int, default=5)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "self_contact_friction_probe.json" if a.friction else "self_contact_probe.json")
     n, h = a.n, 0.1
     v, t = truth_cube(n, n, n, h)
     v = np.asarray(v, np.float64).reshape(-1, 3)
@@ -67,6 +76,33 @@ def main():
     nv, nf = len(surf["vertex_ids"]), len(surf["faces"])
     print("one handle: %d tets on %d nodes, %d surface vertices (%d before the cut), %d boundary faces" % (n_tets, n_nodes, nv, surface_before, nf), flush=True)
     out = {}
+    if a.friction:
+        mu, slip, damping = 0.5, 0.15, 40.0
+        g.set_q_state(q.reshape(-1), np.where(in_free[:, None], np.array([0.2, -0.1, 0.05])[None, :], 0.0).reshape(-1))
+        for name, kw in (("frictionless", {}), ("friction", dict(mu=mu, slip_speed=slip, damping=damping))):
+            g.set_external_forces_to_zero()
+            c = g.self_contact(K, mode="other_parts", **kw)   # (warm)
+            walls = []
+            for _ in range(a.reps):
+                g.set_external_forces_to_zero()
+                t0 = time.perf_counter()
+                c = g.self_contact(K, mode="other_parts", **kw)
+                walls.append(time.perf_counter() - t0)
+            out[name] = dict(call_seconds=median(walls), call_all=walls, path=c["path"], n_contacts=c["n_contacts"], faces_tested=c["faces_tested"])
+            for key in ("n_sticking", "n_sliding", "n_separating", "max_slip_speed", "max_normal_force", "max_stick_rate"):
+                if key in c:
+                    out[name][key] = list(c[key]) if isinstance(c[key], tuple) else c[key]
+            print("  %-12s call %.3f ms (%s); %d contacts" % (name, 1e3 * out[name]["call_seconds"], " ".join("%.3f" % (1e3 * w) for w in walls), c["n_contacts"]), flush=True)
+        out["friction_over_frictionless"] = out["friction"]["call_seconds"] / out["frictionless"]["call_seconds"]
+        g.close()
+        res = dict(tool="tools/probe_self_contact.py --friction", mesh="cube %d^3 after a mid-span cut, one handle, the free half pressed 0.3 of a cell into the clamped one" % n,
+                   mode="other_parts", reps=a.reps, stiffness=K, mu=mu, slip_speed=slip, damping=damping,
+                   sizes=dict(n_tets=n_tets, n_nodes=n_nodes, surface_vertices=nv, faces=nf), results=out, kernel_sources_sha256=fl.source_sha256("fem"))
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1, sort_keys=True)
+            f.write("\n")
+        print("wrote", a.out)
+        return
     for path in ("ring", "scan"):
         os.environ["FEMBRAIN_SELF_CONTACT"] = path
         g.set_external_forces_to_zero()
