@@ -30,10 +30,23 @@ struct ContactFrictionRec {
   double mf[3];  // -f, the friction on the point's node
 };
 
+// What both contact units keep for the closest-face search and the force stage (face_search.hip.h, contact_force.hip.h)
+struct FaceSearchWork {
+  hipEvent_t ev_t[2] = {nullptr, nullptr};  // fb_fem_time_*_contact's stages
+  DevBuf<int> f_cnt, f_start, f_face;  // the face grid: faces per cell, prefix sums, faces by cell
+  DevBuf<double> f_tri;              // [9][faces] their current coordinates in that order, a plane per coordinate
+  DevBuf<double> f_R;                // per-workgroup partials of the largest centroid-to-vertex distance; the padded maximum in the last
+  DevBuf<BodyContactRec> rec;        // [contacts]
+  DevBuf<uint32_t> r_key, r_key_s, r_val, r_val_s;  // the records (node | records-per-contact contact + record), before and after the sort
+  DevBuf<ContactFrictionRec> fric;   // [contacts] the friction calls only
+  ~FaceSearchWork() {
+    for (auto& e : ev_t) if (e) (void)hipEventDestroy(e);
+  }
+};
+
 // The working state of the calls, kept in handle `a`.  Nothing is allocated before the first call; everything grows only.
 struct BodyContactWork {
   hipEvent_t ev_in = nullptr, ev_out = nullptr;  // the other handle's stream -> this one's, and back
-  hipEvent_t ev_t[2] = {nullptr, nullptr};       // fb_fem_time_body_contact's stages
   // current positions and boxes: [0] of this handle, [1] of the other
   DevBuf<double> cur[2];
   DevBuf<double> box_part;   // per-workgroup boxes of the running fold
@@ -43,13 +56,8 @@ struct BodyContactWork {
   DevBuf<int> cand, hit, sel, counts;  // candidates (surface-vertex ranks) | contacts (candidate ranks) | binned elements | the selections' lengths
   DevBuf<int> t_cnt, t_off, cell_lo, cell_hi, cell_elem;  // the element grid: cells per binned element, prefix sums, runs per cell, elements by cell
   DevBuf<int> c_elem;                // [candidates] the containing element or -1
-  DevBuf<int> f_cnt, f_start, f_face;  // the face grid: faces per cell, prefix sums, faces by cell
-  DevBuf<double> f_tri;              // [9][faces] their current coordinates in that order, a plane per coordinate
-  DevBuf<double> f_R;                // per-workgroup partials of the largest centroid-to-vertex distance; the padded maximum in the last
-  DevBuf<BodyContactRec> rec;        // [contacts]
-  DevBuf<uint32_t> r_key, r_key_s, r_val, r_val_s;  // the other side's records (node | 3 contact + corner), before and after the sort
+  FaceSearchWork fs;                 // the face grid, the contacts and the other side's records (node | 3 contact + corner)
   DevBuf<double> scratch[2];         // fb_fem_time_body_contact: what the scatter adds into instead of the force vectors
-  DevBuf<ContactFrictionRec> fric;   // [contacts] fb_fem_body_contact_friction only
   // the last call, per direction
   std::vector<BodyContactRec> host[2];
   fb_fem_body_contact_info info = {};
@@ -57,7 +65,6 @@ struct BodyContactWork {
   ~BodyContactWork() {
     if (ev_in) (void)hipEventDestroy(ev_in);
     if (ev_out) (void)hipEventDestroy(ev_out);
-    for (auto& e : ev_t) if (e) (void)hipEventDestroy(e);
   }
 };
 

@@ -7,50 +7,13 @@
 //    and a large body does not pay a whole-mesh grid per step -- are binned into a grid over that overlap with the cell functions of
 //    embed_grid.hip.h (an element over more than kEmbedWideCells cells goes to an overflow list, as in embed.hip); a thread per candidate
 //    walks its cell, elements ascending, with embed's weight function: the first that contains it is the lowest;
-//  - closest face: below;
-//  - forces: a thread per contact forms F and adds it to its own node of P (the contacts of a direction are different nodes); the three
-//    corners of the face in T become records (node, 3 contact + corner), sorted stably by node, and a thread per node's segment adds them
-//    in record order -- ascending contact, corners 0 1 2 -- onto the value the vector had.  No floating-point atomics.
+//  - closest face: k_face_scan / k_face_ring of face_search.hip.h, nothing excluded (the argument why the ring misses no face is there);
+//  - forces: contact_force.hip.h with three records per contact -- a thread per contact forms F and adds it to its own node of P (the
+//    contacts of a direction are different nodes); the three corners of the face in T become records (node, 3 contact + corner), sorted
+//    stably by node, and a thread per node's segment adds them in record order -- ascending contact, corners 0 1 2 -- onto the value
+//    the vector had.  No floating-point atomics.
 // Node ids cross from the caller's numbering to the handles' internal orders here: the surface's vnode / faces_int index the internal
 // arrays, its vertex_ids / face order are what the caller reads.
-//
-// The closest face, one wavefront per contact (k_bc_ring).  The faces of T are binned by CENTROID into a grid over T's current box; their
-// nine current coordinates are stored grouped by cell, faces ascending inside a cell, a plane per coordinate, so a run of cells along x
-// is one contiguous range that the lanes stride over with coalesced loads.  Each lane keeps its minimum under the key (d, face) and
-// wf_best folds them whenever a lane has improved.  R is the largest centroid-to-vertex distance over all faces, folded once per build
-// and widened by 2^-40.
-//  1. Shells of cells around the point's cell until one holds a face, then one more: a candidate (best_d, best_f).  At most kShells
-//     shells: a point deeper inside takes the bound of the box instead, best_d = m (1 + 2^-40) with m its least distance to a side of the
-//     grid's box along an axis and no face attached.  (A point inside the body leaves the body no later than the box on its way along an
-//     axis, and where it leaves lies a boundary face: a face within m exists.  Nothing rests on that: see the last point below.)
-//  2. Every cell the box [p - D, p + D] overlaps, D = (best_d + R) (1 + 2^-40), widened by one cell on every side, layer by layer and in a
-//     layer 64 rows at a time -- a lane per row forms the x-range that is left of D after the row's distance in y and z, the wavefront
-//     walks the rows that hold a face.  best_d tightens as it goes; a row's range formed under an earlier, larger best_d is a superset.
-// Why no face outside the visited cells can have a distance <= best_d:
-//  - Let f be a face whose COMPUTED distance d(p, f) is <= best_d.  Its computed closest point c lies, up to a few roundings of a
-//    coordinate, in the triangle, and a triangle lies within the largest centroid-to-vertex distance of its centroid (the distance from a
-//    point is convex, so its maximum over the triangle is at a vertex): |c - g| <= R for the centroid g as the grid binned it, the
-//    roundings covered by R's widening.  The exact |c - p| is at most d (1 + 2^-50).  So |g - p| <= best_d + R < D, and so is each of
-//    |g_x - p_x|, |g_y - p_y|, |g_z - p_z|.
-//  - From here on the argument is embed_closest.hip's with g in the place of the centre: cell_clamped is monotone, so from g_k >= p_k - D
-//    follows cell(g_k) >= cell(p_k - D) wherever p_k - D is formed exactly; its one rounding, relative to a coordinate of the box, is
-//    below 2^-13 of a cell (embed_ring_covers has checked it: a body it does not cover scans), and a whole cell on either side covers
-//    that.  A centroid whose computed cell on the axis y is j lies in the slab of j widened by 2^-10 of a cell (slab_gap), the first and
-//    the last cell of an axis are taken as unbounded outward, so the clamps need no argument; a row with g_y^2 + g_z^2 > D^2 (1 + 2^-40)
-//    holds no such centroid, and in any other row g lies in the x-range of the root of the difference.
-//  - Tightening best_d only removes faces that could no longer win under (d, face): a face with d == best_d and a lower index is still
-//    inside, because every comparison above is <=.
-//  - The argument needs best_d to be an upper bound of the answer's distance at every moment.  A best_d with a face attached is one.  The
-//    bound of the box is one whenever some face has a computed distance <= it; the search then ends with that face or a better one, found
-//    in cells the argument covers.  If no face has -- a boundary that is not closed, a rounding at the box's side -- the search ends
-//    without a face, and such a point is flagged and scanned like one past its budget.
-// Every loop is bounded by numbers the host knows: the shells by the largest dim, the rows by dim[1] dim[2], a row by the face count; a
-// point that has tested more than `budget` faces stops, is flagged, and k_bc_scan -- every face for the flagged points, the whole path
-// for a body the proof does not cover, and the test twin -- finds the same (d, face): closest_on_triangle and centre_distance are one
-// sequence of roundings on the same operands, and (d, face) is a total order.  The winner's closest point and weights are formed again
-// from the face itself by bc_finish, for both paths alike.  Nothing spins.
-// (closest_on_triangle, the grid rule, the face grid's kernels, SearchDev and bc_finish live in face_search.hip.h: self_contact.hip's
-// twins of the two searches use them too.)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -60,7 +23,7 @@
 #include <cstring>
 #include <vector>
 
-#include "contact_friction.hip.h"
+#include "contact_force.hip.h"
 #include "device_prims.hip.h"
 #include "embed_grid.hip.h"
 #include "face_search.hip.h"
@@ -76,23 +39,7 @@ struct Box3 {
   double lo[3], hi[3];
 };
 
-// ---- positions and boxes ----
-
-// A thread per node (internal order): x0 + q, and the workgroup's box of them
-__global__ __launch_bounds__(kB) void k_bc_positions(int n_nodes, const double* __restrict__ x0, const double* __restrict__ q, double* __restrict__ cur, double* __restrict__ part) {
-  const int i = blockIdx.x * kB + threadIdx.x;
-  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-  if (i < n_nodes) {
-    const size_t b = 3 * (size_t)i;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      const double v = x0[b + k] + q[b + k];
-      cur[b + k] = v;
-      lo[k] = hi[k] = v;
-    }
-  }
-  wg_box(lo, hi, part + 6 * (size_t)blockIdx.x);
-}
+// ---- boxes ----
 
 // A thread per surface vertex: the workgroup's box of their current positions
 __global__ __launch_bounds__(kB) void k_bc_surface_box(int nv, const int* __restrict__ vnode, int n_nodes, const double* __restrict__ cur, double* __restrict__ part) {
@@ -228,242 +175,6 @@ __global__ __launch_bounds__(kB) void k_bc_contain(int n_cand, const int* __rest
   flag[t] = best == INT_MAX ? 0 : 1;
 }
 
-// ---- the closest face ----
-
-// One wavefront per contact, every face of T in its own order, lanes striding.  only_far: the points the ring search flagged, the others
-// keep their records.
-__global__ __launch_bounds__(kB) void k_bc_scan(SearchDev S, int only_far, BodyContactRec* __restrict__ rec) {
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int t = blockIdx.x * kWaves + wave;
-  if (t >= S.n_contacts) return;
-  if (only_far && rec[t].far == 0) return;  // (the same in every lane)
-  double p[3] = {0.0, 0.0, 0.0};
-  const int vr = contact_point(S, t, p);
-  double bd = DBL_MAX;
-  int bf = INT_MAX;
-  if (vr >= 0)
-    for (int f = lane; f < S.nf; f += 64) {
-      double v[3][3];
-      load_face(S.faces_int, S.n_nodes_t, S.cur_t, f, v);
-      const double d = triangle_distance(p, v[0], v[1], v[2]);
-      if (d < DBL_MAX && Lowest()(d, f, bd, bf)) { bd = d; bf = f; }
-    }
-  wf_best<int, Lowest>(bd, bf);
-  if (lane == 0) bc_finish(S, t, vr, p, bf, (long long)S.nf, only_far != 0, rec);
-}
-
-// One wavefront per contact through the face grid.  Everything that decides a branch is the same in every lane: the ranges come from
-// cell_start, the best pair is folded over the wavefront whenever a lane has improved it.
-__global__ __launch_bounds__(kB) void k_bc_ring(SearchDev S, GridDev g, FaceDev fg, long long budget, BodyContactRec* __restrict__ rec) {
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int t = blockIdx.x * kWaves + wave;
-  if (t >= S.n_contacts) return;
-  double p[3] = {0.0, 0.0, 0.0};
-  const int vr = contact_point(S, t, p);
-  long long tested = 0;
-  bool far = false;
-  double bd = DBL_MAX;
-  int bf = INT_MAX;
-  if (vr >= 0) {
-    const double R = *fg.R;
-    const size_t nf = (size_t)S.nf;
-    // the range [j0, j1) of the sorted faces (a run of cells along x): every lane its share, the best pair folded
-    auto scan_range = [&](int j0, int j1) {
-      bool improved = false;
-      for (int j = j0 + lane; j < j1; j += 64) {
-        const double a[3] = {fg.tri[j], fg.tri[nf + j], fg.tri[2 * nf + j]}, b[3] = {fg.tri[3 * nf + j], fg.tri[4 * nf + j], fg.tri[5 * nf + j]},
-                     c[3] = {fg.tri[6 * nf + j], fg.tri[7 * nf + j], fg.tri[8 * nf + j]};
-        const int f = fg.face[j];
-        const double d = triangle_distance(p, a, b, c);
-        if (d < DBL_MAX && Lowest()(d, f, bd, bf)) { bd = d; bf = f; improved = true; }
-      }
-      if (__any(improved)) wf_best<int, Lowest>(bd, bf);
-      if (j1 > j0) tested += j1 - j0;
-      if (tested > budget) far = true;
-      return j1 > j0;
-    };
-    // ... of the cells x0c .. x1c of the row that begins at cell `row`
-    auto scan_cells = [&](int row, int x0c, int x1c) { return scan_range(max(fg.cell_start[row + x0c], 0), min(fg.cell_start[row + x1c + 1], S.nf)); };
-    int pc[3], rmax = 0;
-    double to_box = DBL_MAX;  // the least distance from p to a side of the grid's box along an axis
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      pc[k] = cell_clamped(g, k, p[k]);
-      rmax = max(rmax, max(pc[k], g.dim[k] - 1 - pc[k]));
-      to_box = fmin(to_box, fmin(p[k] - g.lo[k], g.hi[k] - p[k]));
-    }
-    // 1. shells until one holds a face, and the one after it; no further than kShells, behind which the bound of the box stands in
-    int stop = -1;
-    for (int r = 0; r <= min(rmax, kShells) && !far; r++) {
-      bool got = false;
-      const int z1 = min(pc[2] + r, g.dim[2] - 1), y1 = min(pc[1] + r, g.dim[1] - 1), xa = pc[0] - r, xb = pc[0] + r;
-      for (int z = max(pc[2] - r, 0); z <= z1 && !far; z++)
-        for (int y = max(pc[1] - r, 0); y <= y1 && !far; y++) {
-          const int row = (z * g.dim[1] + y) * g.dim[0];
-          if (z == pc[2] - r || z == pc[2] + r || y == pc[1] - r || y == pc[1] + r) {  // a row of the shell's faces: all of it
-            got |= scan_cells(row, max(xa, 0), min(xb, g.dim[0] - 1));
-          } else {  // its two ends
-            if (xa >= 0) got |= scan_cells(row, xa, xa);
-            if (xb < g.dim[0] && !far) got |= scan_cells(row, xb, xb);
-          }
-        }
-      if (got && stop < 0) stop = r + 1;
-      if (r == stop) break;
-    }
-    if (bf == INT_MAX && to_box >= 0.0 && to_box < DBL_MAX) bd = to_box * kRingGrow;  // (no face attached: any face at a distance <= bd takes its place)
-    // 2. every cell that could hold the centroid of a face at a distance <= best_d
-    if (!far) {
-      const double D0 = (bd + R) * kRingGrow;
-      const bool none = !(D0 < DBL_MAX);  // (no bound below DBL_MAX, or an R that is not finite: the whole grid)
-      const double h[3] = {1.0 / g.inv[0], 1.0 / g.inv[1], 1.0 / g.inv[2]};
-      const int z0 = none ? 0 : max(cell_clamped(g, 2, p[2] - D0) - 1, 0), z1 = none ? g.dim[2] - 1 : min(cell_clamped(g, 2, p[2] + D0) + 1, g.dim[2] - 1);
-      const int y0 = none ? 0 : max(cell_clamped(g, 1, p[1] - D0) - 1, 0), y1 = none ? g.dim[1] - 1 : min(cell_clamped(g, 1, p[1] + D0) + 1, g.dim[1] - 1);
-      for (int z = z0; z <= z1 && !far; z++) {
-        const double gz = slab_gap(g, 2, z, h[2], p[2]);
-        int ya = y0, yb = y1;  // the rows of this layer that are left of D after its distance in z: the x-range's argument with g_y = 0
-        {
-          const double D = (bd + R) * kRingGrow, D2 = D * D * kRingGrow;
-          if (D2 < DBL_MAX) {
-            if (gz * gz > D2) continue;
-            const double rem = sqrt(D2 - gz * gz) * kRingGrow;
-            ya = max(y0, cell_clamped(g, 1, p[1] - rem) - 1);
-            yb = min(y1, cell_clamped(g, 1, p[1] + rem) + 1);
-          }
-        }
-        // 64 rows at a time: a lane per row forms the row's range under the best_d of this moment (a tighter one later in the batch would
-        // only have shortened it), and the wavefront walks the rows that hold a face -- deep inside a body most rows hold none
-        for (int yc = ya; yc <= yb && !far; yc += 64) {
-          const int y = yc + lane;
-          int j0 = 0, j1 = 0;
-          if (y <= yb) {
-            int xa = 0, xb = g.dim[0] - 1;
-            bool skip = false;
-            const double D = (bd + R) * kRingGrow, D2 = D * D * kRingGrow;
-            if (D2 < DBL_MAX) {  // (else the square is out of range: the whole row)
-              const double gy = slab_gap(g, 1, y, h[1], p[1]);
-              const double g2 = gy * gy + gz * gz;
-              if (g2 > D2) {
-                skip = true;
-              } else {
-                const double rem = sqrt(D2 - g2) * kRingGrow;
-                xa = max(cell_clamped(g, 0, p[0] - rem) - 1, 0);
-                xb = min(cell_clamped(g, 0, p[0] + rem) + 1, g.dim[0] - 1);
-              }
-            }
-            if (!skip) {
-              const int row = (z * g.dim[1] + y) * g.dim[0];
-              j0 = max(fg.cell_start[row + xa], 0);
-              j1 = min(fg.cell_start[row + xb + 1], S.nf);
-            }
-          }
-          unsigned long long rows = __ballot(j1 > j0);
-          while (rows != 0ull && !far) {
-            const int l = __ffsll((long long)rows) - 1;
-            rows &= rows - 1ull;
-            scan_range(__shfl(j0, l), __shfl(j1, l));
-          }
-        }
-      }
-    }
-    if (bf == INT_MAX) far = true;  // (no face within the bound -- a boundary that is not closed, a rounding at the box's side: the scan decides)
-  }
-  if (lane == 0) {
-    bc_finish(S, t, vr, p, far ? INT_MAX : bf, tested, false, rec);
-    if (far) rec[t].far = 1;
-  }
-}
-
-// ---- forces ----
-
-// A thread per contact: F, its addition to the point's own node of P, and the three records of the face's corners in T
-__global__ __launch_bounds__(kB) void k_bc_force(SearchDev S, double stiffness, double depth_cap, BodyContactRec* __restrict__ rec, double* __restrict__ fext_p,
-                                                 uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
-  const int t = blockIdx.x * kB + threadIdx.x;
-  if (t >= S.n_contacts) return;
-  double p[3] = {0.0, 0.0, 0.0};
-  const int vr = contact_point(S, t, p);
-  BodyContactRec r = rec[t];
-  const bool push = vr >= 0 && (unsigned)r.face < (unsigned)S.nf && r.d > 0.0;
-  if (push) {
-    const double depth = depth_cap > 0.0 ? fmin(r.d, depth_cap) : r.d;
-    const double sd = stiffness * depth;
-    const int nd = S.vnode[vr];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      r.f[k] = sd * ((r.c[k] - p[k]) / r.d);
-      fext_p[3 * (size_t)nd + k] += r.f[k];
-    }
-    rec[t].f[0] = r.f[0]; rec[t].f[1] = r.f[1]; rec[t].f[2] = r.f[2];
-  } else {
-    rec[t].d = 0.0;  // (nothing is pushed: degenerate)
-  }
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    int nd = push ? S.faces_int[3 * (size_t)r.face + k] : S.n_nodes_t;
-    if ((unsigned)nd >= (unsigned)S.n_nodes_t) nd = S.n_nodes_t;  // (no node: sorted behind every node, and skipped)
-    keys[3 * (size_t)t + k] = (uint32_t)nd;
-    vals[3 * (size_t)t + k] = (uint32_t)(3 * t + k);
-  }
-}
-
-// k_bc_force under the friction law (contact_friction.hip.h): the same push test, own-node addition and records, F the law's total --
-// normal force with damping, minus the friction -- from the velocities of the point's node in P and of the face's corners in T, read
-// from the handles' own qvel arrays (internal order, as the positions).  side[t]: N, |t|, t, -f; zero for a contact that pushes nothing.
-__global__ __launch_bounds__(kB) void k_bc_force_friction(SearchDev S, double stiffness, double depth_cap, FrictionLaw law, const double* __restrict__ qvel_p,
-                                                          const double* __restrict__ qvel_t, BodyContactRec* __restrict__ rec, ContactFrictionRec* __restrict__ side,
-                                                          double* __restrict__ fext_p, uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
-  const int t = blockIdx.x * kB + threadIdx.x;
-  if (t >= S.n_contacts) return;
-  double p[3] = {0.0, 0.0, 0.0};
-  const int vr = contact_point(S, t, p);
-  const BodyContactRec r = rec[t];
-  const bool push = vr >= 0 && (unsigned)r.face < (unsigned)S.nf && r.d > 0.0;
-  ContactFrictionRec o = {0.0, 0.0, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
-  if (push) {
-    const int nd = S.vnode[vr];
-    double vp[3], vt[3][3], F[3];
-    node_velocity(qvel_p, S.n_nodes_p, nd, vp);
-#pragma unroll
-    for (int k = 0; k < 3; k++) node_velocity(qvel_t, S.n_nodes_t, S.faces_int[3 * (size_t)r.face + k], vt[k]);
-    contact_friction_law(p, r.c, r.b, r.d, stiffness, depth_cap, law, vp, vt, F, o);
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      fext_p[3 * (size_t)nd + k] += F[k];
-      rec[t].f[k] = F[k];
-    }
-  } else {
-    rec[t].d = 0.0;  // (nothing is pushed: degenerate)
-  }
-  side[t] = o;
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    int nd = push ? S.faces_int[3 * (size_t)r.face + k] : S.n_nodes_t;
-    if ((unsigned)nd >= (unsigned)S.n_nodes_t) nd = S.n_nodes_t;  // (no node: sorted behind every node, and skipped)
-    keys[3 * (size_t)t + k] = (uint32_t)nd;
-    vals[3 * (size_t)t + k] = (uint32_t)(3 * t + k);
-  }
-}
-
-// A thread per sorted record: the first of a node's segment does that node's additions in record order
-__global__ __launch_bounds__(kB) void k_bc_segments(int n_rec, const uint32_t* __restrict__ keys_s, const uint32_t* __restrict__ vals_s, int n_contacts, int n_nodes_t,
-                                                    const BodyContactRec* __restrict__ rec, double* __restrict__ fext_t) {
-  const int i = blockIdx.x * kB + threadIdx.x;
-  if (i >= n_rec) return;
-  const uint32_t node = keys_s[i];
-  if (node >= (uint32_t)n_nodes_t || (i > 0 && keys_s[i - 1] == node)) return;
-  double a[3] = {fext_t[3 * (size_t)node], fext_t[3 * (size_t)node + 1], fext_t[3 * (size_t)node + 2]};
-  for (int k = i; k < n_rec && keys_s[k] == node; k++) {
-    const uint32_t v = vals_s[k];
-    const uint32_t t = v / 3u, corner = v % 3u;
-    if (t >= (uint32_t)n_contacts) continue;
-    const BodyContactRec& r = rec[t];
-    if (!(r.d > 0.0)) continue;
-    const double w = r.b[corner];
-    a[0] += (-r.f[0]) * w; a[1] += (-r.f[1]) * w; a[2] += (-r.f[2]) * w;
-  }
-  fext_t[3 * (size_t)node] = a[0]; fext_t[3 * (size_t)node + 1] = a[1]; fext_t[3 * (size_t)node + 2] = a[2];
-}
-
 // ---- host ----
 
 // one body as a direction sees it
@@ -475,41 +186,10 @@ struct Body {
   double* fext;
 };
 
-// the stages of fb_fem_time_body_contact: events around each, on the calling handle's stream
-struct Stages {
-  BodyContactWork* W = nullptr;
-  hipStream_t s = nullptr;
-  double* seconds = nullptr;  // null: not timing
-  int begin() {
-    if (seconds) FB_HIP(hipEventRecord(W->ev_t[0], s));
-    return FB_OK;
-  }
-  int end(int stage) {
-    if (!seconds) return FB_OK;
-    FB_HIP(hipEventRecord(W->ev_t[1], s));
-    FB_HIP(hipEventSynchronize(W->ev_t[1]));
-    float ms = 0;
-    FB_HIP(hipEventElapsedTime(&ms, W->ev_t[0], W->ev_t[1]));
-    seconds[stage] += ms * 1e-3;
-    return FB_OK;
-  }
-};
-
-// FEMBRAIN_BODY_CONTACT, read at every call: FB_BODY_CONTACT_SCAN / _RING, 0 where it is not set
-int path_knob() {
-  const char* env = getenv("FEMBRAIN_BODY_CONTACT");
-  if (!env || !*env) return FB_BODY_CONTACT_NONE;
-  if (!strcmp(env, "scan")) return FB_BODY_CONTACT_SCAN;
-  if (!strcmp(env, "ring")) return FB_BODY_CONTACT_RING;
-  return FB_BODY_CONTACT_NONE;
-}
-
 int ensure_events(BodyContactWork& W) {
   if (!W.ev_in) FB_HIP(hipEventCreateWithFlags(&W.ev_in, hipEventDisableTiming));
   if (!W.ev_out) FB_HIP(hipEventCreateWithFlags(&W.ev_out, hipEventDisableTiming));
-  for (auto& e : W.ev_t)
-    if (!e) FB_HIP(hipEventCreate(&e));
-  return FB_OK;
+  return stage_events(W.fs);
 }
 
 // current positions of a body and the boxes of its nodes and of its surface vertices, into boxes[12 which ..]
@@ -518,7 +198,7 @@ int body_boxes(hipStream_t s, BodyContactWork& W, fb_fem_s* h, int which) {
   const int nb = blocks_for(n), nbv = blocks_for(nv);
   FB_TRY(W.cur[which].reserve((size_t)3 * n));
   FB_TRY(W.box_part.reserve((size_t)6 * std::max(nb, nbv)));
-  FB_TRY(launch_1d(k_bc_positions, n, s, n, h->x0.p, h->q.p, W.cur[which].p, W.box_part.p));
+  FB_TRY(launch_1d(k_contact_positions, n, s, n, h->x0.p, h->q.p, W.cur[which].p, W.box_part.p));
   FB_TRY(launch_grid(k_box_final<double>, dim3(1), s, nb, W.box_part.p, W.boxes.p + 12 * which));
   FB_TRY(launch_1d(k_bc_surface_box, nv, s, nv, h->surf.vnode.p, n, W.cur[which].p, W.box_part.p));
   FB_TRY(launch_grid(k_box_final<double>, dim3(1), s, nbv, W.box_part.p, W.boxes.p + 12 * which + 6));
@@ -616,64 +296,27 @@ int run_direction(hipStream_t s, BodyContactWork& W, PlanWorkspace& ws, const Bo
 
   // ---- the path, and the face grid where it is the ring's ----
   GridDev fgrid = make_grid(TB.lo, TB.hi, pad, nf);
-  const int knob = path_knob();
-  const bool ring = knob != FB_BODY_CONTACT_SCAN && grid_covered(fgrid);  // (default: the ring wherever its proof holds; DESIGN.md 3k has the table)
+  const bool ring = path_knob("FEMBRAIN_BODY_CONTACT") != FB_BODY_CONTACT_SCAN && grid_covered(fgrid);  // (default: the ring wherever its proof holds; DESIGN.md 3k has the table)
   res.path = ring ? FB_BODY_CONTACT_RING : FB_BODY_CONTACT_SCAN;
-  long long budget = nf;  // (a point that has tested as many faces as a scan tests gains nothing from going on)
-  if (const char* env = getenv("FEMBRAIN_BODY_CONTACT_BUDGET"))
-    if (*env) budget = std::max(0LL, atoll(env));
   FB_TRY(tm.begin());
   if (ring) {
-    const int n_cells = fgrid.dim[0] * fgrid.dim[1] * fgrid.dim[2], nbf = blocks_for(nf);
-    FB_TRY(W.f_cnt.reserve((size_t)n_cells + 1)); FB_TRY(W.f_start.reserve((size_t)n_cells + 1)); FB_TRY(W.f_face.reserve((size_t)nf));
-    FB_TRY(W.f_tri.reserve((size_t)9 * nf)); FB_TRY(W.f_R.reserve((size_t)nbf + 1));
-    FB_HIP(hipMemsetAsync(W.f_cnt.p, 0, sizeof(int) * ((size_t)n_cells + 1), s));
-    FB_TRY(ws.keys.reserve(((size_t)nf + 1) / 2)); FB_TRY(ws.keys_s.reserve(((size_t)nf + 1) / 2)); FB_TRY(ws.vals.reserve((size_t)nf));
-    uint32_t* ck = reinterpret_cast<uint32_t*>(ws.keys.p);
-    uint32_t* ck_s = reinterpret_cast<uint32_t*>(ws.keys_s.p);
-    FB_TRY(launch_1d(k_bc_face_keys, nf, s, nf, ST.faces_int.p, T.n_nodes, T.cur, fgrid, ck, ws.vals.p, W.f_cnt.p, W.f_R.p));
-    FB_TRY(launch_grid(k_bc_R_final, dim3(1), s, nbf, W.f_R.p, W.f_R.p + nbf));
-    FB_TRY(sort_pairs(ws.temp, s, ck, ck_s, ws.vals.p, reinterpret_cast<uint32_t*>(W.f_face.p), (size_t)nf, (unsigned)bits_of(n_cells)));
-    FB_TRY(exclusive_scan(ws.temp, s, W.f_cnt.p, W.f_start.p, 0, (size_t)n_cells + 1));
-    FB_TRY(launch_1d(k_bc_face_store, nf, s, nf, W.f_face.p, ST.faces_int.p, T.n_nodes, T.cur, W.f_tri.p));
+    FB_TRY(build_face_grid(s, ws, W.fs, ST.faces_int.p, nf, T.n_nodes, T.cur, fgrid));
     res.face_grids = 1;
   }
   FB_TRY(tm.end(2));
 
   // ---- the closest faces ----
   FB_TRY(tm.begin());
-  FB_TRY(W.rec.reserve((size_t)n_contacts));
   SearchDev S;
   S.n_contacts = n_contacts; S.hit = W.hit.p; S.cand = W.cand.p; S.vnode = SP.vnode.p; S.vertex_ids = SP.vertex_ids.p; S.c_elem = W.c_elem.p;
   S.n_cand = n_cand; S.nv = nv; S.n_nodes_p = P.n_nodes; S.cur_p = P.cur;
   S.nf = nf; S.n_nodes_t = T.n_nodes; S.faces_int = ST.faces_int.p; S.cur_t = T.cur;
-  if (ring) {
-    const FaceDev fg = {W.f_start.p, W.f_face.p, W.f_tri.p, W.f_R.p + blocks_for(nf)};
-    FB_TRY(launch_waves(k_bc_ring, n_contacts, s, S, fgrid, fg, budget, W.rec.p));
-    FB_TRY(launch_waves(k_bc_scan, n_contacts, s, S, 1, W.rec.p));  // (the points past their budget; a wavefront of any other returns at once)
-  } else {
-    FB_TRY(launch_waves(k_bc_scan, n_contacts, s, S, 0, W.rec.p));
-  }
+  FB_TRY(search_faces(s, W.fs, S, NoExclusion(), ring, fgrid, budget_knob("FEMBRAIN_BODY_CONTACT_BUDGET", nf)));
   FB_TRY(tm.end(3));
 
   // ---- forces ----
   FB_TRY(tm.begin());
-  const size_t n_rec = (size_t)3 * n_contacts;
-  FB_TRY(W.r_key.reserve(n_rec)); FB_TRY(W.r_key_s.reserve(n_rec)); FB_TRY(W.r_val.reserve(n_rec)); FB_TRY(W.r_val_s.reserve(n_rec));
-  if (law) {
-    FB_TRY(W.fric.reserve((size_t)n_contacts));
-    FB_TRY(launch_1d(k_bc_force_friction, n_contacts, s, S, prm.stiffness, prm.depth_cap, *law, P.h->qvel.p, T.h->qvel.p, W.rec.p, W.fric.p, fext_p, W.r_key.p, W.r_val.p));
-  } else {
-    FB_TRY(launch_1d(k_bc_force, n_contacts, s, S, prm.stiffness, prm.depth_cap, W.rec.p, fext_p, W.r_key.p, W.r_val.p));
-  }
-  FB_TRY(sort_pairs(ws.temp, s, W.r_key.p, W.r_key_s.p, W.r_val.p, W.r_val_s.p, n_rec, (unsigned)bits_of((long long)T.n_nodes + 1)));
-  FB_TRY(launch_1d(k_bc_segments, (long long)n_rec, s, (int)n_rec, W.r_key_s.p, W.r_val_s.p, n_contacts, T.n_nodes, W.rec.p, fext_t));
-  out.resize((size_t)n_contacts);
-  if (law && side_out) {
-    side_out->resize((size_t)n_contacts);
-    FB_HIP(hipMemcpyAsync(side_out->data(), W.fric.p, sizeof(ContactFrictionRec) * (size_t)n_contacts, hipMemcpyDeviceToHost, s));  // (the wait below covers it)
-  }
-  FB_TRY(W.rec.download(out.data(), (size_t)n_contacts, s));  // a host wait
+  FB_TRY(contact_forces<3>(s, ws, W.fs, S, prm.stiffness, prm.depth_cap, law, P.h->qvel.p, T.h->qvel.p, fext_p, fext_t, out, side_out));
   FB_TRY(tm.end(4));
   return FB_OK;
 }
@@ -683,8 +326,7 @@ int check_pair(fb_fem_s* a, fb_fem_s* b, const fb_fem_body_contact_params* p) {
   if (a->plan.n_ranks > 1 || b->plan.n_ranks > 1) return fail(FB_EINVAL, "fb_fem_body_contact is for unsharded handles");
   if (a->prm.device != b->prm.device) return fail(FB_EINVAL, "fb_fem_body_contact: the handles are on devices %d and %d", a->prm.device, b->prm.device);
   if (!p) return fail(FB_EINVAL, "null body contact parameters");
-  if (!std::isfinite(p->stiffness) || p->stiffness < 0.0) return fail(FB_EINVAL, "body contact stiffness %g", p->stiffness);
-  if (!std::isfinite(p->depth_cap) || p->depth_cap < 0.0) return fail(FB_EINVAL, "body contact depth cap %g", p->depth_cap);
+  FB_TRY(check_penalty("body contact", p->stiffness, p->depth_cap));
   if ((p->directions & (FB_BODY_A_INTO_B | FB_BODY_B_INTO_A)) == 0 || (p->directions & ~(FB_BODY_A_INTO_B | FB_BODY_B_INTO_A)) != 0)
     return fail(FB_EINVAL, "body contact directions %d", p->directions);
   if (a->plan.n_global <= 0 || b->plan.n_global <= 0 || a->plan.n_global >= (1 << 28) || b->plan.n_global >= (1 << 28))
@@ -706,7 +348,7 @@ int body_contact(fb_fem_s* a, fb_fem_s* b, const fb_fem_body_contact_params& prm
   FB_HIP(hipEventRecord(W.ev_in, b->stream));
   FB_HIP(hipStreamWaitEvent(s, W.ev_in, 0));
   Stages tm;
-  tm.W = &W; tm.s = s; tm.seconds = seconds;
+  tm.ev = W.fs.ev_t; tm.s = s; tm.seconds = seconds;
   FB_TRY(tm.begin());
   const size_t n_boxes = fr ? 25 : 24;  // (the friction call: behind the boxes the flag of a velocity that is not finite, read in the same wait)
   FB_TRY(W.boxes.reserve(n_boxes));
@@ -753,15 +395,12 @@ int body_contact(fb_fem_s* a, fb_fem_s* b, const fb_fem_body_contact_params& prm
     if (R.n_contacts > 0) I.path = R.path;
     double* on_p = dir == 0 ? I.force_on_a : I.force_on_b;
     double* on_t = dir == 0 ? I.force_on_b : I.force_on_a;
-    for (const BodyContactRec& r : recs[dir]) {
-      I.faces_tested += r.tested;
-      if (!(r.d > 0.0)) { I.n_degenerate[dir]++; continue; }
-      const double depth = prm.depth_cap > 0.0 ? std::min(r.d, prm.depth_cap) : r.d;
-      I.max_depth = std::max(I.max_depth, depth);
-      for (int k = 0; k < 3; k++) on_p[k] += r.f[k];
-      for (int c = 0; c < 3; c++)
-        for (int k = 0; k < 3; k++) on_t[k] += (-r.f[k]) * r.b[c];
-    }
+    ContactSums sums;
+    sums.faces_tested = I.faces_tested; sums.max_depth = I.max_depth;
+    for (int k = 0; k < 3; k++) { sums.on_points[k] = on_p[k]; sums.on_faces[k] = on_t[k]; }
+    sums = contact_sums(recs[dir], prm.depth_cap, sums, [](size_t, const BodyContactRec&) { return true; });
+    I.faces_tested = sums.faces_tested; I.n_degenerate[dir] = sums.n_degenerate; I.max_depth = sums.max_depth;
+    for (int k = 0; k < 3; k++) { on_p[k] = sums.on_points[k]; on_t[k] = sums.on_faces[k]; }
   }
   // what b queues from here on runs after this call (also after a failure: the kernels launched so far read b's arrays)
   const hipError_t e1 = hipEventRecord(W.ev_out, s);
@@ -810,16 +449,7 @@ int fb_fem_read_body_contact_friction(fb_fem_t a, int direction, double* normal_
 int fb_fem_read_body_contact(fb_fem_t a, int direction, int* node, int* element, int* face, double* closest_xyz, double* bary3, double* depth) {
   CHECK_HANDLE(a);
   if (direction != FB_BODY_A_INTO_B && direction != FB_BODY_B_INTO_A) return fail(FB_EINVAL, "fb_fem_read_body_contact: direction %d", direction);
-  const std::vector<BodyContactRec>& v = a->bodyc.host[direction == FB_BODY_A_INTO_B ? 0 : 1];
-  for (size_t i = 0; i < v.size(); i++) {
-    const BodyContactRec& r = v[i];
-    if (node) node[i] = r.node;
-    if (element) element[i] = r.elem;
-    if (face) face[i] = r.face;
-    if (closest_xyz) memcpy(closest_xyz + 3 * i, r.c, sizeof(double) * 3);
-    if (bary3) memcpy(bary3 + 3 * i, r.b, sizeof(double) * 3);
-    if (depth) depth[i] = r.d;
-  }
+  read_contacts(a->bodyc.host[direction == FB_BODY_A_INTO_B ? 0 : 1], node, element, face, closest_xyz, bary3, depth);
   return FB_OK;
 }
 

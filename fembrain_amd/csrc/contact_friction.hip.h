@@ -1,7 +1,7 @@
 // Coulomb friction and damping of a contact, for body_contact.hip and self_contact.hip: the law of include/fembrain_hip.h ("Friction and
 // damping of a contact"), written once, the side record it leaves per contact, the pass that looks for a velocity that is not finite,
-// and what the host makes of the side records.  The searches, BodyContactRec and the scatter are untouched: the force kernels of the
-// friction calls write the TOTAL force into rec[t].f, where k_bc_segments / k_sc_segments and the host sums find it.
+// and what the host makes of the side records.  The searches, BodyContactRec and the scatter know nothing of it: the friction instances
+// of k_contact_force (contact_force.hip.h) write the TOTAL force into rec[t].f, where k_contact_segments and the host sums find it.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,4 +1,4 @@
-// What the units that search through a grid (embed.hip, embed_closest.hip, body_contact.hip) all evaluate, each written once: the search grid
+// What the units that search through a grid (embed.hip, embed_closest.hip, face_search.hip.h) all evaluate, each written once: the search grid
 // as a kernel sees it with its cell function, an element's vertices, its centre, the distance of a point from a centre, the weights of a point
 // in an element, and the slab of a cell as the ring searches widen it.  The units are built with
 // -ffp-contract=off, so one function is one sequence of roundings wherever it is called: the closest centre of the full scan and of the
@@ -76,7 +76,7 @@ __device__ __forceinline__ bool bary(const double (*v)[3], const double* p, doub
   return w[0] >= 0 && w[1] >= 0 && w[2] >= 0 && w[3] >= 0;
 }
 
-// ---- the search through a grid of points (embed_closest.hip, body_contact.hip) ----
+// ---- the search through a grid of points (embed_closest.hip, face_search.hip.h) ----
 constexpr double kRingGrow = 1.0 + 0x1p-40;  // what a distance, its square and a root are widened by: far above their roundings
 
 // the gap between x and the slab of cell j on axis k, widened by 2^-10 of a cell and open outward at both ends of the axis

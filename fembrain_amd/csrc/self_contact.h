@@ -16,7 +16,6 @@ namespace fb {
 // from the surface of that call (a cut, a delta or a re-sync changes the surface; no count is carried from one mesh generation to the
 // next except `ident_n`, which says how much of `ident` is filled and does not depend on the mesh).
 struct SelfContactWork {
-  hipEvent_t ev_t[2] = {nullptr, nullptr};  // fb_fem_time_self_contact's stages
   DevBuf<double> cur;         // [3 nodes] x0 + q, internal order
   DevBuf<double> box_part;    // per-workgroup boxes of the running fold
   DevBuf<double> boxes;       // [6] the nodes' box (infinite where a position is not finite)
@@ -35,19 +34,12 @@ struct SelfContactWork {
   DevBuf<int> hit;            // [contacts] surface vertices in contact, ascending
   // the closest faces
   DevBuf<int> face_part;      // [faces] OTHER_PARTS: the part of the face's element
-  DevBuf<int> f_cnt, f_start, f_face;
-  DevBuf<double> f_tri, f_R;
-  DevBuf<BodyContactRec> rec;  // [contacts]
-  DevBuf<uint32_t> r_key, r_key_s, r_val, r_val_s;  // the records (node | 4 contact + record), before and after the sort
+  FaceSearchWork fs;          // the face grid, the contacts and their records (node | 4 contact + record)
   DevBuf<double> scratch;     // fb_fem_time_self_contact: what the scatter adds into instead of the force vector
-  DevBuf<ContactFrictionRec> fric;  // [contacts] fb_fem_self_contact_friction only
   // the last adding call
   std::vector<BodyContactRec> host;
   fb_fem_self_contact_info info = {};
   std::vector<ContactFrictionRec> fric_host;  // the last friction call
-  ~SelfContactWork() {
-    for (auto& e : ev_t) if (e) (void)hipEventDestroy(e);
-  }
 };
 
 }  // namespace fb

@@ -713,7 +713,8 @@ int fb_fem_contact_apply(fb_fem_t h, int neighbourhood_size, fb_fem_contact_spre
  * queues afterwards runs after it.  A handle that never calls it allocates and launches nothing extra.
  *
  * Direction "a into b" (FB_BODY_A_INTO_B; FB_BODY_B_INTO_A is the same with the roles swapped), every operation fp64, no contraction:
- *  1. Points: the surface vertices of a (fb_fem_surface's vertex_ids, ascending) at p = x0 + q.
+ *  1. Points: the surface vertices of a (fb_fem_surface's vertex_ids, ascending) at p = x0 + q.  A position of either body that is not
+ *     finite, a NaN included, gives FB_EINVAL before anything is written.
  *  2. Candidates: the points in the closed box of b's current node positions.  Where the box of a's surface vertices and the box of b's
  *     nodes do not meet the direction ends: no grid is built, no force vector written.
  *  3. Containment: p is in contact if an element of b at b's current positions has four weights >= 0 (fb_fem_embed's weights D_i / D_0,
@@ -731,7 +732,7 @@ int fb_fem_contact_apply(fb_fem_t h, int neighbourhood_size, fb_fem_contact_spre
  * path says how the closest faces of the last direction that had contacts were found: FB_BODY_CONTACT_RING -- through a grid of the
  * face centroids, a wavefront per contact, only the cells that can hold a closer face -- or FB_BODY_CONTACT_SCAN, every face for every
  * contact; the same bits.  FEMBRAIN_BODY_CONTACT=scan|ring chooses (read at every call; default: ring wherever its coverage proof holds,
- * see body_contact.hip), FEMBRAIN_BODY_CONTACT_BUDGET the faces one point may test on the ring path before it goes to the scan (default:
+ * see face_search.hip.h), FEMBRAIN_BODY_CONTACT_BUDGET the faces one point may test on the ring path before it goes to the scan (default:
  * the face count).  n_tet_grid_builds / n_face_grid_builds: grids built by this call; faces_tested: closest-point evaluations of the
  * searches; max_depth: the largest depth that entered a force (after the cap); force_on_a / force_on_b: the fp64 sums of all
  * contributions to each body, in the order of 6.  Indices [0] / [1] of the counts: a into b / b into a.
@@ -791,7 +792,7 @@ int fb_fem_time_body_contact(fb_fem_t a, fb_fem_t b, const fb_fem_body_contact_p
  *
  * path, faces_tested, max_depth as in fb_fem_body_contact_info (FB_BODY_CONTACT_NONE | _SCAN | _RING); FEMBRAIN_SELF_CONTACT=scan|ring
  * and FEMBRAIN_SELF_CONTACT_BUDGET=n are this call's knobs, read at every call (default: the ring wherever its coverage proof holds,
- * self_contact.hip).  n_points: the surface vertices; n_point_grid_builds / n_face_grid_builds / n_parts_builds: built by this call.
+ * face_search.hip.h).  n_points: the surface vertices; n_point_grid_builds / n_face_grid_builds / n_parts_builds: built by this call.
  * fb_fem_read_self_contact: the last adding call's contacts (n_contacts entries each, any pointer may be NULL) in the layout of
  * fb_fem_read_body_contact; depth = d before the cap.  fb_fem_time_self_contact: seconds of the five stages (positions and box | point
  * grid and containment | face grid | closest faces | scatter), means of `reps` runs, host waits included; it adds no force. */

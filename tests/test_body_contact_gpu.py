@@ -317,6 +317,25 @@ def test_invalid_arguments():
     ga.close(); gb.close()
 
 
+def test_a_position_that_is_not_a_number_is_refused():
+    """one NaN in q of either body: FB_EINVAL after the boxes, and neither force vector is written"""
+    for which in (1, 0):  # the NaN in body b, then in body a
+        ga, gb = _pair("two_way")
+        rng = np.random.default_rng(11)
+        fa0, fb0 = rng.normal(size=3 * ga.n_nodes), rng.normal(size=3 * gb.n_nodes)
+        ga.set_external_forces(fa0)
+        gb.set_external_forces(fb0)
+        g = (ga, gb)[which]
+        q = np.zeros(3 * g.n_nodes)
+        q[3 * 17 + 1] = np.nan
+        g.set_q_state(q)
+        with pytest.raises(fl.FbError) as e:
+            ga.body_contact(gb, K)
+        assert e.value.code == fl.FB_EINVAL and "not finite" in str(e.value)
+        assert np.array_equal(ga.external_forces(), fa0) and np.array_equal(gb.external_forces(), fb0)   # nothing was written
+        ga.close(); gb.close()
+
+
 def _sharded_worker(rank, world, shm_name, q):
     try:
         import ctypes as C
