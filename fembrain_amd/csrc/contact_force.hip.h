@@ -120,13 +120,6 @@ int contact_forces(hipStream_t s, PlanWorkspace& ws, FaceSearchWork& F, const Se
   return F.rec.download(out.data(), (size_t)n, s);  // a host wait
 }
 
-// the penalty's two numbers as the calls accept them; who: "body contact" / "self contact"
-int check_penalty(const char* who, double stiffness, double depth_cap) {
-  if (!std::isfinite(stiffness) || stiffness < 0.0) return fail(FB_EINVAL, "%s stiffness %g", who, stiffness);
-  if (!std::isfinite(depth_cap) || depth_cap < 0.0) return fail(FB_EINVAL, "%s depth cap %g", who, depth_cap);
-  return FB_OK;
-}
-
 // What the info structs sum over the records of one direction, in record order, onto the values S came with (the second direction of
 // two bodies goes on where the first ended: the order of the additions is the rule's).  keep(i, r): false for a record the caller drops
 // (its tested faces still count).  The sums are formed in a local and handed back by value: accumulated through pointers into the

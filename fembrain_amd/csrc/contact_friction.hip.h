@@ -70,6 +70,13 @@ __global__ __launch_bounds__(kB) void k_cf_finite(long long n, const double* __r
 
 // ---- host ----
 
+// the penalty's two numbers as the calls accept them (here, where tool_contact.hip finds it too); who: "body contact" / "self contact" / "tool contact"
+int check_penalty(const char* who, double stiffness, double depth_cap) {
+  if (!std::isfinite(stiffness) || stiffness < 0.0) return fail(FB_EINVAL, "%s stiffness %g", who, stiffness);
+  if (!std::isfinite(depth_cap) || depth_cap < 0.0) return fail(FB_EINVAL, "%s depth cap %g", who, depth_cap);
+  return FB_OK;
+}
+
 // fb_fem_contact_friction_params as the calls accept them
 int check_friction(const fb_fem_contact_friction_params* fr, const char* who) {
   if (!fr) return fail(FB_EINVAL, "%s: null friction parameters", who);

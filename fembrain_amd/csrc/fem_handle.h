@@ -1,7 +1,7 @@
 // The FEM handle (fb_fem_t of include/fembrain_hip.h) and what the units that work on it share: fem.hip (assembly, the two-launch
 // solver, the steps and the rest of the C ABI), fem_build.hip (life cycle: plan build, creation, re-sync, cut), fem_persist.hip (the
 // persistent solver's host side), haptic.hip (the probe's entry points), stress.hip (element stress and strain), parts.hip (disjoint parts),
-// detach.hip (a part into a handle of its own), embed.hip (point sets bound to the elements), embed_touch.hip (forces, picks and stress on them), contact.hip (the probe's box contact), body_contact.hip (contact between two handles), self_contact.hip (a handle with itself) and motion.hip (constrained DOFs that follow a tool).
+// detach.hip (a part into a handle of its own), embed.hip (point sets bound to the elements), embed_touch.hip (forces, picks and stress on them), contact.hip (the probe's box contact), body_contact.hip (contact between two handles), self_contact.hip (a handle with itself), tool_contact.hip (a rigid tool's shapes against the tissue) and motion.hip (constrained DOFs that follow a tool).
 // Internal: not installed, included by these units only.
 #pragma once
 #include "comm.h"
@@ -22,6 +22,7 @@
 #include "body_contact.h"
 #include "self_contact.h"
 #include "motion.h"
+#include "tool_contact.h"
 
 namespace fb {
 
@@ -199,6 +200,7 @@ struct fb_fem_s {
   ContactWork contact;    // fb_fem_contact_move / apply: the probe's touched set, force list and spread records (contact.h); empty until somebody asks
   BodyContactWork bodyc;  // fb_fem_body_contact: contact with another handle, kept in the handle the call names first (body_contact.h); empty until somebody asks
   SelfContactWork selfc;  // fb_fem_self_contact: contact of this handle with itself (self_contact.h); empty until somebody asks
+  ToolContactWork toolc;  // fb_fem_tool_contact: a rigid tool's spheres, capsules and boxes against the points (tool_contact.h); empty until somebody asks
   MotionWork motion;      // fb_fem_set_constrained_motion / fb_fem_grasp: the moved constrained DOFs, their element table and reactions (motion.h); empty until somebody asks
   HapticWork hap;         // fb_fem_add_haptic_forces / pick / volume: level array and scratch (haptic.h); empty until somebody asks
   std::vector<int> fixed_caller;  // the constrained DOFs in the caller's numbering (unsharded): what fb_fem_cut keeps

@@ -811,6 +811,80 @@ class FemIntegrator:
         _l.check(self._L.fb_fem_time_self_contact(self.h, C.byref(p), int(reps), _l.dptr(sec)))
         return sec
 
+    # -- contact with a rigid tool on the device (fb_fem_tool_contact; unsharded handles) --
+    _TOOL_POINTS = {"surface": _l.FB_TOOL_SURFACE_VERTICES, "all_nodes": _l.FB_TOOL_ALL_NODES}
+
+    @staticmethod
+    def _tool(shapes, origin, velocity, omega):
+        """fb_tool from erosion.py's shape tuples, checked by ``erosion.check_shapes``"""
+        from . import erosion
+        shapes = list(shapes)
+        erosion.check_shapes(shapes)
+        if not 1 <= len(shapes) <= _l.FB_TOOL_MAX_SHAPES:
+            raise ValueError("a tool has 1 .. %d shapes, not %d" % (_l.FB_TOOL_MAX_SHAPES, len(shapes)))
+        T = _l.Tool()
+        T.n_shapes = len(shapes)
+        for S, s in zip(T.shapes, shapes):
+            S.a[:] = _l.as_f64(s[1], 3)
+            if s[0] == "sphere":
+                S.kind, S.size[0] = _l.FB_TOOL_SPHERE, float(s[2])
+            elif s[0] == "capsule":
+                S.kind, S.size[0] = _l.FB_TOOL_CAPSULE, float(s[3])
+                S.b[:] = _l.as_f64(s[2], 3)
+            else:
+                S.kind = _l.FB_TOOL_BOX
+                S.size[:] = _l.as_f64(s[2], 3)
+                S.R[:] = _l.as_f64(np.eye(3) if len(s) < 4 or s[3] is None else s[3], 9)
+        T.origin[:], T.velocity[:], T.omega[:] = _l.as_f64(origin, 3), _l.as_f64(velocity, 3), _l.as_f64(omega, 3)
+        return T
+
+    def _tool_params(self, stiffness, depth_cap, points):
+        p = _l.ToolContactParams()
+        p.stiffness, p.depth_cap = float(stiffness), float(depth_cap)
+        p.points = self._TOOL_POINTS[points] if isinstance(points, str) else int(points)
+        return p
+
+    def tool_contact(self, shapes, stiffness, depth_cap=0.0, points="surface", origin=(0, 0, 0), velocity=(0, 0, 0), omega=(0, 0, 0), mu=0.0, slip_speed=0.0,
+                     damping=0.0):
+        """Penalty contact of a rigid tool with this body at its current state, ADDED into the external force vector (set gravity or zero
+        first).  shapes: erosion.py's tuples -- ("sphere", centre, radius), ("capsule", a, b, radius), ("box", centre, half, R) -- in the
+        world frame, 1 .. 16 of them; every point (points "surface": the surface vertices; "all_nodes": every node) that a shape holds is
+        pushed out along that shape's normal with F = stiffness * min(depth, depth_cap) * n (no cap where depth_cap is 0), of several
+        shapes the deepest.  origin, velocity, omega: the tool's reference point, its velocity and its angular velocity;
+        mu, slip_speed, damping: with any of them non-zero the force law is the friction calls' (``body_contact``), with the tool's
+        velocity at the point in place of a face's.  Returns the dict of the fb_fem_tool_contact_info fields: force_on_tool and
+        torque_on_tool (about origin) are what the tissue returns to the tool."""
+        T, p, info = self._tool(shapes, origin, velocity, omega), self._tool_params(stiffness, depth_cap, points), _l.ToolContactInfo()
+        fr = None if mu == 0.0 and slip_speed == 0.0 and damping == 0.0 else C.byref(self._friction_params(mu, slip_speed, damping))
+        _l.check(self._L.fb_fem_tool_contact(self.h, C.byref(T), C.byref(p), fr, C.byref(info)))
+        out = {name: int(getattr(info, name)) for name in ("n_points", "n_contacts", "n_degenerate", "n_sticking", "n_sliding", "n_separating")}
+        out.update({name: float(getattr(info, name)) for name in ("max_depth", "max_slip_speed", "max_normal_force", "max_stick_rate")})
+        out.update(contacts_by_shape=np.array(info.contacts_by_shape[:T.n_shapes]), force_on_body=np.array(info.force_on_body[:]),
+                   force_on_tool=np.array(info.force_on_tool[:]), torque_on_tool=np.array(info.torque_on_tool[:]))
+        return out
+
+    def read_tool_contact(self):
+        """The contacts of the last ``tool_contact``, ascending point: dict of node, shape (the winning one), depth (k,) before the cap,
+        normal (k, 3), force (k, 3) the force added to the node, and normal_force (k,), slip (k, 3), friction (k, 3) = -f of the friction
+        law (zero after a frictionless call)."""
+        k = int(self._L.fb_fem_num_tool_contacts(self.h))
+        if k < 0:
+            _l.check(k)
+        node, shape, depth, normal, force = np.zeros(k, np.int32), np.zeros(k, np.int32), np.zeros(k), np.zeros((k, 3)), np.zeros((k, 3))
+        N, slip, friction = np.zeros(k), np.zeros((k, 3)), np.zeros((k, 3))
+        _l.check(self._L.fb_fem_read_tool_contact(self.h, _l.iptr(node), _l.iptr(shape), _l.dptr(depth), _l.dptr(normal), _l.dptr(force), _l.dptr(N), _l.dptr(slip),
+                                                  _l.dptr(friction)))
+        return dict(node=node, shape=shape, depth=depth, normal=normal, force=force, normal_force=N, slip=slip, friction=friction)
+
+    def time_tool_contact(self, shapes, stiffness, depth_cap=0.0, points="surface", origin=(0, 0, 0), velocity=(0, 0, 0), omega=(0, 0, 0), mu=0.0, slip_speed=0.0,
+                          damping=0.0, reps=5):
+        """Seconds of the three stages of ``tool_contact`` (points against shapes, compaction and the host wait, forces and the records'
+        way back), means of ``reps`` runs (fb_fem_time_tool_contact).  Adds no force and leaves the records of the last call alone."""
+        T, p, sec = self._tool(shapes, origin, velocity, omega), self._tool_params(stiffness, depth_cap, points), np.zeros(3)
+        fr = None if mu == 0.0 and slip_speed == 0.0 and damping == 0.0 else C.byref(self._friction_params(mu, slip_speed, damping))
+        _l.check(self._L.fb_fem_time_tool_contact(self.h, C.byref(T), C.byref(p), fr, int(reps), _l.dptr(sec)))
+        return sec
+
     # -- constrained DOFs that follow a tool, and the force they return (fb_fem_set_constrained_motion / fb_fem_grasp; unsharded handles) --
     def set_constrained_motion(self, dofs, displacements):
         """Replaces the motion set: ``dofs`` (caller ids, ascending, each a constrained DOF of the handle) end the next ``do_timestep``
@@ -1180,6 +1254,8 @@ class Deformable:
         self.collision_body, self.collision_stiffness = None, 0.0  # set_collision_body
         self.collision_friction = (0.0, 0.0, 0.0)  # set_collision_body: (mu, slip_speed, damping)
         self.self_collision = None  # set_self_collision: (stiffness, depth_cap, mode, mu, slip_speed, damping)
+        self.tool = None            # set_tool: (shapes, stiffness, keywords of FemIntegrator.tool_contact)
+        self.last_tool_contact = None  # the info of the last collide_tool
 
     def collide_with(self, other, stiffness, depth_cap=0.0, mu=0.0, slip_speed=0.0, damping=0.0):
         """Penalty contact with another ``Deformable`` on the same device at the current states of both, ADDED to the external forces of
@@ -1197,6 +1273,29 @@ class Deformable:
         """Penalty contact of this body with itself at its current state, ADDED to its external forces (``FemIntegrator.self_contact``,
         with its friction and contact damping)."""
         return self.integrator.self_contact(stiffness, depth_cap, mode, mu=mu, slip_speed=slip_speed, damping=damping)
+
+    def collide_tool(self, shapes, stiffness, **kw):
+        """Penalty contact of a rigid tool -- erosion.py's shape tuples in the world frame -- with this body at its current state, ADDED
+        to its external forces (``FemIntegrator.tool_contact``, with its keywords: depth_cap, points, origin, velocity, omega, mu,
+        slip_speed, damping).  ``timestep`` sets the forces anew before it steps: its callers use ``set_tool``."""
+        self.last_tool_contact = self.integrator.tool_contact(shapes, stiffness, **kw)
+        return self.last_tool_contact
+
+    def set_tool(self, shapes, stiffness=0.0, **kw):
+        """Opt-in: every ``timestep`` applies the tool behind gravity, the probe, the collision body and the self contact, just before it
+        steps (shapes None: off).  The caller sets the tool again whenever it has moved."""
+        self.tool = None if shapes is None else (list(shapes), float(stiffness), dict(kw))
+
+    def clear_tool(self):
+        self.tool = None
+
+    def tool_force(self):
+        """The force the tissue returned to the tool in the last ``collide_tool`` (3,); zero before any"""
+        return np.zeros(3) if self.last_tool_contact is None else self.last_tool_contact["force_on_tool"]
+
+    def tool_torque(self):
+        """... and the torque about the tool's origin (3,)"""
+        return np.zeros(3) if self.last_tool_contact is None else self.last_tool_contact["torque_on_tool"]
 
     # -- held and moved: what IAvatar::grip() only flags (IScalpel.cpp:42-44) --
     def grip(self, nodes):
@@ -1302,6 +1401,8 @@ class Deformable:
             self.collide_with(self.collision_body, self.collision_stiffness, 0.0, *self.collision_friction)
         if self.self_collision is not None:
             self.self_collide(*self.self_collision)
+        if self.tool is not None:
+            self.collide_tool(self.tool[0], self.tool[1], **self.tool[2])
         iters = it.do_timestep()
         if self.floor_y is not None:
             self.ct_collided = it.floor_collision(self.floor_y, 0.4)

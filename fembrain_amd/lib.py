@@ -30,6 +30,9 @@ FB_CONTACT_SPREAD_RECORDS, FB_CONTACT_SPREAD_LEVELS = 0, 1  # fb_fem_contact_spr
 FB_BODY_A_INTO_B, FB_BODY_B_INTO_A = 1, 2  # fb_fem_body_contact_params.directions
 FB_BODY_CONTACT_NONE, FB_BODY_CONTACT_SCAN, FB_BODY_CONTACT_RING = 0, 1, 2  # fb_fem_body_contact_info.path
 FB_SELF_CONTACT_ANY, FB_SELF_CONTACT_OTHER_PARTS = 0, 1  # fb_fem_self_contact_params.mode
+FB_TOOL_SPHERE, FB_TOOL_CAPSULE, FB_TOOL_BOX = 0, 1, 2  # fb_tool_shape.kind
+FB_TOOL_MAX_SHAPES = 16  # shapes of one fb_tool
+FB_TOOL_SURFACE_VERTICES, FB_TOOL_ALL_NODES = 0, 1  # fb_fem_tool_contact_params.points
 FB_MAX_MATERIALS = 256  # entries of a handle's material table (fb_fem_set_materials)
 FB_STRESS_WORLD, FB_STRESS_TENSORS = 1, 2  # fb_fem_stress flags
 FB_EMBED_CLOSEST_NONE, FB_EMBED_CLOSEST_SCAN, FB_EMBED_CLOSEST_RING = 0, 1, 2  # fb_fem_embed_search_info.path
@@ -139,6 +142,26 @@ class ContactFrictionParams(C.Structure):
 class ContactFrictionInfo(C.Structure):
     _fields_ = [("n_sticking", C.c_int * 2), ("n_sliding", C.c_int * 2), ("n_separating", C.c_int * 2), ("max_slip_speed", C.c_double),
                 ("max_normal_force", C.c_double), ("max_stick_rate", C.c_double), ("friction_on_points", (C.c_double * 3) * 2)]
+
+
+class ToolShape(C.Structure):
+    _fields_ = [("kind", C.c_int), ("reserved", C.c_int), ("a", C.c_double * 3), ("b", C.c_double * 3), ("size", C.c_double * 3), ("R", C.c_double * 9)]
+
+
+class Tool(C.Structure):
+    _fields_ = [("n_shapes", C.c_int), ("reserved", C.c_int), ("shapes", ToolShape * FB_TOOL_MAX_SHAPES), ("origin", C.c_double * 3),
+                ("velocity", C.c_double * 3), ("omega", C.c_double * 3)]
+
+
+class ToolContactParams(C.Structure):
+    _fields_ = [("stiffness", C.c_double), ("depth_cap", C.c_double), ("points", C.c_int), ("reserved", C.c_int)]
+
+
+class ToolContactInfo(C.Structure):
+    _fields_ = [("n_points", C.c_int), ("n_contacts", C.c_int), ("n_degenerate", C.c_int), ("contacts_by_shape", C.c_int * FB_TOOL_MAX_SHAPES),
+                ("n_sticking", C.c_int), ("n_sliding", C.c_int), ("n_separating", C.c_int), ("max_depth", C.c_double), ("max_slip_speed", C.c_double),
+                ("max_normal_force", C.c_double), ("max_stick_rate", C.c_double), ("force_on_body", C.c_double * 3), ("force_on_tool", C.c_double * 3),
+                ("torque_on_tool", C.c_double * 3)]
 
 
 class MotionInfo(C.Structure):
@@ -291,6 +314,10 @@ def lib():
         "fb_fem_self_contact": (C.c_int, [vp, C.POINTER(SelfContactParams), C.POINTER(SelfContactInfo)]),
         "fb_fem_read_self_contact": (C.c_int, [vp, _ip, _ip, _ip, _dp, _dp, _dp]),
         "fb_fem_time_self_contact": (C.c_int, [vp, C.POINTER(SelfContactParams), C.c_int, _dp]),
+        "fb_fem_tool_contact": (C.c_int, [vp, C.POINTER(Tool), C.POINTER(ToolContactParams), C.POINTER(ContactFrictionParams), C.POINTER(ToolContactInfo)]),
+        "fb_fem_num_tool_contacts": (C.c_int, [vp]),
+        "fb_fem_read_tool_contact": (C.c_int, [vp, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp]),
+        "fb_fem_time_tool_contact": (C.c_int, [vp, C.POINTER(Tool), C.POINTER(ToolContactParams), C.POINTER(ContactFrictionParams), C.c_int, _dp]),
         "fb_fem_set_constrained_motion": (C.c_int, [vp, C.c_int, _ip, _dp]),
         "fb_fem_num_constrained_motion": (C.c_int, [vp]),
         "fb_fem_read_constrained_motion": (C.c_int, [vp, _ip, _dp]),

@@ -250,6 +250,29 @@ class HipIntegrator {
     closestXyz.assign(3 * (size_t)n, 0.0); bary3.assign(3 * (size_t)n, 0.0); depth.assign((size_t)n, 0.0);
     check(fb_fem_read_self_contact(h_, node.data(), element.data(), face.data(), closestXyz.data(), bary3.data(), depth.data()));
   }
+  // Contact with a rigid tool (fembrain_hip.h, "Contact with a rigid tool"): every point -- surface vertex, or node -- that a sphere,
+  // capsule or oriented box of the tool holds is pushed out along that shape's normal; ADDED to the external force vector.  The info
+  // holds what the tissue returns to the tool: force_on_tool, torque_on_tool about tool.origin.  SetContactFriction applies: the law
+  // then takes the tool's velocity at the point from tool.velocity and tool.omega.
+  fb_fem_tool_contact_info ToolContact(const fb_tool& tool, double stiffness, double depthCap = 0.0, int points = FB_TOOL_SURFACE_VERTICES) {
+    const fb_fem_tool_contact_params p = {stiffness, depthCap, points, 0};
+    fb_fem_tool_contact_info info;
+    check(fb_fem_tool_contact(h_, &tool, &p, frictionless() ? nullptr : &friction_, &info));
+    return info;
+  }
+  // the contacts of the last ToolContact of this integrator, n = info.n_contacts entries (a smaller or negative n reads them all): node,
+  // winning shape, depth before the cap, normal, force
+  void ReadToolContact(int n, std::vector<int>& node, std::vector<int>& shape, std::vector<double>& depth, std::vector<double>& normal3, std::vector<double>& force3) {
+    n = std::max(n, fb_fem_num_tool_contacts(h_));
+    node.assign((size_t)n, 0); shape.assign((size_t)n, 0); depth.assign((size_t)n, 0.0); normal3.assign(3 * (size_t)n, 0.0); force3.assign(3 * (size_t)n, 0.0);
+    check(fb_fem_read_tool_contact(h_, node.data(), shape.data(), depth.data(), normal3.data(), force3.data(), nullptr, nullptr, nullptr));
+  }
+  // ... and what the friction law left per contact: N, the tangential velocity t[3], the friction on the node -f[3] (zero after a frictionless call)
+  void ReadToolContactFriction(int n, std::vector<double>& normalForce, std::vector<double>& slip3, std::vector<double>& friction3) {
+    n = std::max(n, fb_fem_num_tool_contacts(h_));
+    normalForce.assign((size_t)n, 0.0); slip3.assign(3 * (size_t)n, 0.0); friction3.assign(3 * (size_t)n, 0.0);
+    check(fb_fem_read_tool_contact(h_, nullptr, nullptr, nullptr, nullptr, nullptr, normalForce.data(), slip3.data(), friction3.data()));
+  }
   // Constrained DOFs that follow targets, and the force they return (fembrain_hip.h, "Constrained motion"): dofs ascending, each a
   // constrained DOF of the handle; the next DoTimestep ends with q = displacements there, bit for bit.  n = 0 clears the set.
   void SetConstrainedMotion(int n, const int* dofs, const double* displacements) { check(fb_fem_set_constrained_motion(h_, n, dofs, displacements)); }
@@ -494,6 +517,7 @@ class Deformable {
     }
     if (m_lpCollisionBody != nullptr) collideWith(*m_lpCollisionBody, m_collisionStiffness);  // (behind gravity and the probe)
     if (m_selfCollision) selfCollide(m_selfStiffness, m_selfDepthCap, m_selfMode);
+    if (m_hasTool) collideTool(m_tool, m_toolStiffness, m_toolDepthCap, m_toolPoints);
     m_lpIntegrator->DoTimestep();
     if (m_hasFloor) m_ctCollided = (U32)m_lpIntegrator->FloorCollision(m_floorY, 0.4);
     if (m_fOnDeform) {
@@ -808,6 +832,24 @@ class Deformable {
     m_selfCollision = on; m_selfStiffness = stiffness; m_selfDepthCap = depthCap; m_selfMode = mode;
   }
   bool getSelfCollision() const { return m_selfCollision; }
+  // A rigid tool -- spheres, capsules, oriented boxes in the world frame -- against the tissue: penalty contact at the current state,
+  // ADDED to the external forces on the device (fb_fem_tool_contact; the reference has only the probe's axis-aligned box).  toolForce()
+  // and toolTorque() are what the tissue returned to the tool in the last such call, the torque about tool.origin: what a haptic device
+  // renders.  setContactFriction applies, with the tool's velocity and angular velocity as the other side's.
+  fb_fem_tool_contact_info collideTool(const fb_tool& tool, double stiffness, double depthCap = 0, int points = FB_TOOL_SURFACE_VERTICES) {
+    m_toolInfo = m_lpIntegrator->ToolContact(tool, stiffness, depthCap, points);
+    return m_toolInfo;
+  }
+  // every timestep() applies the tool behind gravity, the probe, the collision body and the self contact, just before it steps; the
+  // caller sets the tool again whenever it has moved.  clearTool: off again.  Never set: timestep() does what it always did.
+  void setTool(const fb_tool& tool, double stiffness, double depthCap = 0, int points = FB_TOOL_SURFACE_VERTICES) {
+    m_tool = tool; m_hasTool = true; m_toolStiffness = stiffness; m_toolDepthCap = depthCap; m_toolPoints = points;
+  }
+  void clearTool() { m_hasTool = false; }
+  bool hasTool() const { return m_hasTool; }
+  const fb_fem_tool_contact_info& lastToolContact() const { return m_toolInfo; }
+  vec3d toolForce() const { return vec3d(m_toolInfo.force_on_tool[0], m_toolInfo.force_on_tool[1], m_toolInfo.force_on_tool[2]); }
+  vec3d toolTorque() const { return vec3d(m_toolInfo.torque_on_tool[0], m_toolInfo.torque_on_tool[1], m_toolInfo.torque_on_tool[2]); }
   // Held and moved -- what the reference only flags (IAvatar::grip() sets m_isGripped, src/deformable/IScalpel.cpp:42-44, read at
   // AvatarRing.cpp:177; its integrator nails constrained DOFs to rest).  grip: the tool closes on `nodes` (ascending ids, e.g. pickVertices'),
   // which are held where they are.  moveGrip: they follow the tool, rotated by R (row-major) about pivot and shifted by t from where they
@@ -972,6 +1014,8 @@ class Deformable {
     m_boxCapacity = 64; m_lpIntegrator = nullptr; m_lpSurface = nullptr; m_hasFloor = false; m_floorY = 0.0; m_dof = 0; m_restVolume = -1.0;
     m_lpCollisionBody = nullptr; m_collisionStiffness = 0.0;
     m_selfCollision = false; m_selfStiffness = m_selfDepthCap = 0.0; m_selfMode = FB_SELF_CONTACT_OTHER_PARTS;
+    m_hasTool = false; m_toolStiffness = m_toolDepthCap = 0.0; m_toolPoints = FB_TOOL_SURFACE_VERTICES;
+    memset(&m_tool, 0, sizeof(m_tool)); memset(&m_toolInfo, 0, sizeof(m_toolInfo));
   }
   std::vector<double> m_rest;
   std::vector<int> m_elements;
@@ -984,6 +1028,11 @@ class Deformable {
   bool m_selfCollision;           // setSelfCollision
   double m_selfStiffness, m_selfDepthCap;
   int m_selfMode;
+  bool m_hasTool;                 // setTool
+  fb_tool m_tool;
+  double m_toolStiffness, m_toolDepthCap;
+  int m_toolPoints;
+  fb_fem_tool_contact_info m_toolInfo;  // the last collideTool
   std::vector<EmbeddedMesh*> m_vEmbedded;
   FOnApplyDeformations m_fOnDeform;
   U32 m_dof, m_ctCollided, m_ctTimeStep;

@@ -871,6 +871,71 @@ int fb_fem_self_contact_friction(fb_fem_t h, const fb_fem_self_contact_params* p
                                  fb_fem_self_contact_info* out, fb_fem_contact_friction_info* fout);
 int fb_fem_read_self_contact_friction(fb_fem_t h, double* normal_force, double* slip3, double* friction3);
 
+/* ---- Contact with a rigid tool, on the device ----
+ * What a rigid instrument does to the tissue: a tool made of up to FB_TOOL_MAX_SHAPES spheres, capsules and oriented boxes -- the shapes
+ * of fembrain_amd/erosion.py, with its inside tests -- pushes every point it holds out along the shape's normal, and the call hands back
+ * the force and the torque the tissue returns to the tool.  The reference has only the axis-aligned probe box (fb_fem_contact_move); the
+ * rule is this project's (tests/toolref.py restates it in numpy).  Unsharded handles only (FB_EINVAL otherwise); ids are
+ * the CALLER's, also on renumbered handles.  The call uses the current state and ADDS into the external force vector (set gravity or
+ * zero first), on the handle's stream.  A handle that never calls it allocates and launches nothing for it.  Every operation fp64, in
+ * the order written, no contraction; dot(u, v) = (u0 v0 + u1 v1) + u2 v2:
+ *  1. Points: FB_TOOL_SURFACE_VERTICES, fb_fem_surface's vertex_ids, ascending (the surface is built first where it is stale);
+ *     FB_TOOL_ALL_NODES, every node, ascending.  A point sits at p = x0 + q.
+ *  2. Per shape, whether it holds the point, the depth and the outward normal n:
+ *     sphere (a, r): u = p - a, l2 = dot(u, u); held iff l2 <= r * r; l = sqrt(l2), depth = r - l, n = u / l; l == 0 is held with
+ *       depth = r and is DEGENERATE (no normal);
+ *     capsule (a, b, r): d = b - a, dd = dot(d, d), t = dd > 0 ? min(max(dot(p - a, d) / dd, 0), 1) : 0, c = a + t * d (a multiply,
+ *       then an add); then the sphere rule about c;
+ *     box (a, half, R): u = p - a, l_i = dot(row i of R, u); held iff |l_i| <= half_i for i = 0, 1, 2; e_i = half_i - |l_i|, the axis
+ *       of the least e wins, the lowest i among equal ones; depth = e_i, n = row i of R, negated iff l_i < 0.  R is used as given.
+ *  3. Of the shapes that hold the point the greatest depth wins, the lowest shape index among equal ones.  A point held by no shape is
+ *     no contact.  A degenerate winner makes the contact degenerate: counted in n_contacts, contacts_by_shape and n_degenerate, it
+ *     pushes nothing and enters no sum, maximum or class.  Nothing is culled.  Contacts are ordered by ascending point.
+ *  4. Force: depth' = depth_cap > 0 ? min(depth, depth_cap) : depth, sd = stiffness * depth'.  Without fr, F_k = sd * n_k.  With fr:
+ *     r = p - origin, vt = velocity + omega x r with the cross product written (w1 r2 - w2 r1, w2 r0 - w0 r2, w0 r1 - w1 r0),
+ *     w_k = qvel[node][k] - vt_k, and from there the lines vn ... F_k of "Friction and damping of a contact" with this n and sd; the
+ *     classes are its classes.  With mu == 0 and damping == 0 the force vector gets the bits of the frictionless call wherever the
+ *     entry before the call is not -0: a record component that is -0 without fr (sd * n_k, n_k a negated zero of a box's row) is +0
+ *     from N * n_k - 0 * t_k, the records agree as numbers, and only -0 + (-0) against -0 + (+0) shows the sign in the vector.
+ *  5. +F is added to the node's entry of the external force vector, onto the value it had (the points are distinct nodes: no atomics,
+ *     the same bits from call to call).  The host forms, in record order over the contacts that are not degenerate, force_on_body =
+ *     sum F, force_on_tool = sum (-F), torque_on_tool = sum r x (-F) about origin (the cross product as above), max_depth (of depth'),
+ *     and with fr the classes and maxima as fb_fem_contact_friction_info defines them (all zero without fr).
+ * FB_EINVAL before anything is launched or written: a null tool or p; n_shapes outside 1 .. FB_TOOL_MAX_SHAPES; an unknown kind or
+ * `points`; a non-zero reserved; a radius or half extent that is negative or not finite; any other number of the tool that the rule
+ * reads (a; b of a capsule; R of a box; origin, velocity, omega) that is not finite; a box with |dot(R_i, R_j) - delta_ij| > 1e-9;
+ * a stiffness or depth_cap that is negative or not finite; what the friction calls refuse in fr.  FB_EINVAL with the force vector
+ * untouched: a position of a point that is not finite, and with fr a velocity of a point (the first kernel raises a flag that is read in
+ * the host wait for the number of contacts; forces are added after it).  A refused call leaves the records of the last call in place.
+ * fb_fem_read_tool_contact: per contact of the last adding call (n_contacts entries each, any pointer may be NULL) the node, the
+ * winning shape, depth before the cap, n, F; and N, t[3], -f[3] of the friction law (zero after a frictionless call or for a degenerate
+ * contact); fb_fem_num_tool_contacts is that number of entries, for a reader that did not make the call.  fb_fem_time_tool_contact: seconds of the three stages (points against shapes | compaction and the host wait | forces and
+ * the records' way back), means of `reps` runs; it adds no force and leaves the records alone. */
+#define FB_TOOL_SPHERE 0
+#define FB_TOOL_CAPSULE 1
+#define FB_TOOL_BOX 2
+#define FB_TOOL_MAX_SHAPES 16
+#define FB_TOOL_SURFACE_VERTICES 0
+#define FB_TOOL_ALL_NODES 1
+typedef struct fb_tool_shape { int kind, reserved; double a[3], b[3], size[3], R[9]; } fb_tool_shape;
+    /* sphere: centre a, radius size[0] | capsule: a, b, radius size[0] | box: centre a, half extents size, row i of R = axis i */
+typedef struct fb_tool { int n_shapes, reserved; fb_tool_shape shapes[FB_TOOL_MAX_SHAPES];
+                         double origin[3], velocity[3], omega[3]; } fb_tool;      /* world frame, at the moment of the call */
+typedef struct fb_fem_tool_contact_params { double stiffness, depth_cap; int points /* FB_TOOL_SURFACE_VERTICES | FB_TOOL_ALL_NODES */, reserved; } fb_fem_tool_contact_params;
+typedef struct fb_fem_tool_contact_info {
+  int n_points, n_contacts, n_degenerate, contacts_by_shape[FB_TOOL_MAX_SHAPES];
+  int n_sticking, n_sliding, n_separating;          /* 0 without friction */
+  double max_depth, max_slip_speed, max_normal_force, max_stick_rate;
+  double force_on_body[3], force_on_tool[3], torque_on_tool[3];
+} fb_fem_tool_contact_info;
+int fb_fem_tool_contact(fb_fem_t h, const fb_tool* tool, const fb_fem_tool_contact_params* p,
+                        const fb_fem_contact_friction_params* fr /* NULL: frictionless */, fb_fem_tool_contact_info* out /* may be NULL */);
+int fb_fem_num_tool_contacts(fb_fem_t h);   /* entries fb_fem_read_tool_contact writes: n_contacts of the last adding call (negative: FB_E*) */
+int fb_fem_read_tool_contact(fb_fem_t h, int* node, int* shape, double* depth, double* normal3, double* force3,
+                             double* normal_force, double* slip3, double* friction3);   /* any pointer NULL */
+int fb_fem_time_tool_contact(fb_fem_t h, const fb_tool* tool, const fb_fem_tool_contact_params* p,
+                             const fb_fem_contact_friction_params* fr, int reps, double seconds[3]);  /* adds no force */
+
 /* ---- Constrained motion: held nodes follow a tool, reaction forces on the device ----
  * A constrained DOF is otherwise nailed to q = 0 for life.  A MOTION SET is a subset of the handle's constrained DOFs, each with a
  * target displacement u_c: a grasper that drags tissue, a clamp that moves, a displacement-driven haptic device that is told what force
